@@ -21,6 +21,12 @@ Launch: `python bench.py --gpus 1` or, for N > 1,
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`
 Prints ONE JSON line on rank 0.  torch is used for plumbing only (synthetic data, device buffers,
 torch.distributed); every timed kernel is libmi355dr's hand-written HIP.
+
+A plain run sets up, warms up, times the steps and prints the headline line.  Everything else the bench measures or checks
+(planted-answer nDCG, PCIe-inclusive and one-query rates, block sizes, other k, N = 1 M, the MaxSim legs, power and bare-stream
+probes, the PMC traffic sub-run, CPU baselines and parity on a sample, the sharded-vs-one-GPU check) runs only with `--full`.
+`--dump-outputs DIR` writes what the last timed step returned (distances and row ids) as DIR/<name>.npy; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 
 from __future__ import annotations
@@ -44,8 +50,8 @@ from autorag_research_amd.synth import CHUNK_ROWS  # noqa: E402
 
 from bench_support import (HBM_PEAK_GBS, MFMA_BF16_PEAK_TF, MFMA_BF16_POWER_LIMITED_TF, MFMA_BF16_UBENCH_TF,  # noqa: E402
                            MFMA_I8_PEAK_TOPS, MFMA_I8_POWER_LIMITED_TOPS, MFMA_I8_UBENCH_TOPS, block_size_table,
-                           bare_stream_probe, cpu_shape_baselines, main_maxsim, other_k_line, pmc_fetch_subrun, maxsim_traffic, power_probe,
-                           replicated_leg, row_sharded_leg, run_maxsim, small_corpus_line)
+                           bare_stream_probe, cpu_shape_baselines, dump_outputs, main_maxsim, other_k_line, pmc_fetch_subrun,
+                           maxsim_traffic, power_probe, replicated_leg, row_sharded_leg, run_maxsim, small_corpus_line)
 
 
 class _HostHopDist:
@@ -124,9 +130,14 @@ def parse_args():
     ap.add_argument("--row-sharded-leg", action="store_true",
                     help="also measure the fully row-sharded layout (world x 1) after the main run and report it under "
                          "extra.row_sharded (only meaningful when the main layout is not already that one)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extras (planted-answer nDCG, PCIe-inclusive "
-                                                           "rate, BLAS / torch / B=1 CPU baselines)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed extras and the CPU baseline after the headline figure (off: a plain run times "
+                         "the steps and prints the line, nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed extras (planted-answer nDCG, "
+                                                           "PCIe-inclusive rate, BLAS / torch / B=1 CPU baselines)")
     ap.add_argument("--data", choices=["gaussian", "anisotropic"], default="gaussian",
                     help="gaussian = BASELINE headline; anisotropic = power-law spectrum + near-duplicate clusters (the offline "
                          "stand-in for bge-base on BEIR nq, config C2: use with --metric ip --k 100)")
@@ -140,7 +151,12 @@ def parse_args():
                     help="library option passed to mi355dr_set_option verbatim (developer A/B; repeatable)")
     ap.add_argument("--cpu-sample-rows", type=int, default=2_500_000)
     ap.add_argument("--cpu-sample-queries", type=int, default=3072, help="CPU baseline: queries timed (whole blocks of the pool)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run: the headline figure alone
+        args.no_extras = args.no_cpu_baseline = True
+    return args
 
 
 def main() -> None:
@@ -365,6 +381,9 @@ def main() -> None:
         tmax = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's [B,k] distances and global row ids (after the merge on row shards), as a caller gets them
+        dump_outputs(args.dump_outputs, {"distances": res[0].cpu().numpy(), "rows": res[1].cpu().numpy()})
 
     # ---- dominant-kernel accounting (k_screen), measured with HIP events on the launch stream
     all_launches = idx.stat("screen_launches")
@@ -393,7 +412,7 @@ def main() -> None:
     # HBM traffic of the dominant kernel: measured by a PMC sub-run of this very workload behind the timed region (below) or
     # absent -- nothing is replayed from an earlier round's profile (rocprofv3 cannot run inside the timed region)
     traffic = None
-    traffic_src = "not measured (run without --no-extras, or with --traffic, for the in-run rocprofv3 --pmc FETCH_SIZE sub-run)"
+    traffic_src = "not measured (run with --full, or with --traffic, for the in-run rocprofv3 --pmc FETCH_SIZE sub-run)"
     ubench = (MFMA_I8_UBENCH_TOPS["32x32x32"] if i8 else MFMA_BF16_UBENCH_TF)
     roof = {
         "bound": "mfma",

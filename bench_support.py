@@ -114,13 +114,15 @@ def cpu_shape_baselines(Cs: np.ndarray, Qs: np.ndarray, k: int, metric: str, n_t
     return out
 
 
-def run_maxsim(args, n_docs: int, tokens: str, nq: int, steps: int, warmup: int, cpu_sample_docs: int = 0, probe: bool = False) -> dict:
+def run_maxsim(args, n_docs: int, tokens: str, nq: int, steps: int, warmup: int, cpu_sample_docs: int = 0, probe: bool = False,
+               outputs: dict | None = None) -> dict:
     """MaxSim top-k (VectorChord `@#`) on a synthetic multi-vector store built ON THE DEVICE (token vectors generated in
     HBM, handed to the index by pointer: mi355dr_add_multivec_device).  `tokens` = "text" (ColBERT-like: U{32..180} vectors
     per doc) or "page" (ColPali-like: 1030 patch vectors per doc); d = 128, unit-norm vectors, seed 777.
     A step = one call with 16 queries x `nq` query vectors against every document: ONE bf16 MFMA screen pass over the bf16
     fragment copy serves all four groups of 4 (round 4; 8 queries in rounds 2-3), then per group the selection and the exact
-    fp32 MFMA kernel on the candidates; wall clock includes H2D of the queries and D2H of [16,k]."""
+    fp32 MFMA kernel on the candidates; wall clock includes H2D of the queries and D2H of [16,k].  `outputs` (a dict), when
+    given, receives the last timed step's distances and document ids."""
     import torch
 
     import autorag_research_amd as pkg
@@ -173,6 +175,8 @@ def run_maxsim(args, n_docs: int, tokens: str, nq: int, steps: int, warmup: int,
     el = time.perf_counter() - t0
     idx.set_option("profile", 0)
     assert (np.diff(res[0], axis=1) >= 0).all()
+    if outputs is not None:
+        outputs.update(distances=res[0], doc_ids=res[1])
     # (the counters of the TIMED steps: the power probe below runs more steps)
     screened, cands, fb = idx.stat("maxsim_screened"), idx.stat("maxsim_candidates"), idx.stat("maxsim_fallbacks")
     scr_n, scr_ns = idx.stat("maxsim_screen_launches"), idx.stat("maxsim_screen_ns")
@@ -386,10 +390,22 @@ def maxsim_traffic(roof: dict, tokens: str, docs: int) -> None:
         roof["traffic_source"] = f"not measured [live PMC sub-run: {note}]"
 
 
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: one .npy per array of the last timed step; float arrays keep their dtype, integer ids become float64
+    (exact below 2**53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+
+
 def main_maxsim(args) -> None:
     """Secondary workload as the whole bench line: `python bench.py --workload maxsim [--docs N] [--tokens text|page]`."""
+    last = {}
     r = run_maxsim(args, args.docs, args.tokens, 32 if args.tokens == "text" else 24, args.steps, args.warmup,
-                   0 if args.no_cpu_baseline else 20000, probe=not args.no_extras)
+                   0 if args.no_cpu_baseline else 20000, probe=not args.no_extras, outputs=last)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     out = {"metric": "queries/sec", "value": r["queries_per_s"], "unit": "queries/s", "n_gpus": 1, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "strong",
            "vs_baseline": None, "dtype": "f32", "data": "synthetic",

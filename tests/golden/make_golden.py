@@ -42,6 +42,8 @@ Fixtures written next to this file:
   ingest_golden.json       BaseIngestionService._embed_entities (orm/service/base_ingestion.py:326-495) over a fake Unit of
                            Work: NULL-content image chunks skipped, failed items remembered and the rest embedded, single and
                            multi-vector columns.
+  embedding_configs_golden.json  the reference's configs/embedding/colpali.yaml as loaded (keys and values), the file the
+                           package's mi355_colpali.yaml mirrors key for key.
   gqr_golden.npz / .json   Guided Query Refinement: outputs of GQRHybridRetrievalPipeline._optimize_query_embedding /
                            _optimize_query_multi_embedding / _optimize_in_score_space (pipelines/retrieval/
                            gqr_hybrid.py:306-362) on seeded pools, and of _retrieve_by_id (:472-489) over the fake
@@ -67,7 +69,7 @@ sys.dont_write_bytecode = True
 
 
 sys.path.insert(0, str(HERE))
-from ref_import import import_reference  # noqa: E402
+from ref_import import REFERENCE_ROOT, import_reference  # noqa: E402
 
 import_reference()
 
@@ -1070,6 +1072,13 @@ def make_ingest() -> dict:
     return out
 
 
+def make_embedding_configs() -> dict:
+    """The reference's embedding YAMLs the package's own configs mirror, loaded as data (no interpolation)."""
+    import yaml
+
+    return {"colpali": yaml.safe_load((Path(REFERENCE_ROOT) / "configs" / "embedding" / "colpali.yaml").read_text())}
+
+
 def main() -> None:
     (HERE / "metrics_golden.json").write_text(json.dumps(make_metrics(), indent=1))
     np.savez_compressed(HERE / "scores_golden.npz", **make_scores())
@@ -1084,6 +1093,7 @@ def main() -> None:
     np.savez_compressed(HERE / "embeddings_golden.npz", **make_embeddings())
     (HERE / "evaluation_golden.json").write_text(json.dumps(make_evaluation(), indent=1))
     (HERE / "ingest_golden.json").write_text(json.dumps(make_ingest(), indent=1))
+    (HERE / "embedding_configs_golden.json").write_text(json.dumps(make_embedding_configs(), indent=1))
     print("wrote", sorted(p.name for p in HERE.iterdir()))
 
 

@@ -2,8 +2,8 @@
 
 `import autorag_research` needs third-party modules this image does not have (tiktoken, hydra, langchain_core,
 pgvector, tenacity, ...).  `import_reference()` registers empty stand-in modules for them -- stand-ins for ABSENT
-DEPENDENCIES, nothing of the reference itself -- and puts /root/reference on sys.path.  Used by make_golden.py and by
-the build-container-only tests; nothing here runs on the GPU box (no /root/reference there).
+DEPENDENCIES, nothing of the reference itself -- and puts the reference tree (REFERENCE_ROOT) on sys.path.  Used by
+make_golden.py alone: the tests read the fixtures it wrote and never import the reference.
 """
 
 from __future__ import annotations

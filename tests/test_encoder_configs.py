@@ -180,10 +180,9 @@ def test_pali_yaml_configs_take_the_reference_keys(monkeypatch, fresh_loader):
 
     ours = yaml.safe_load((ROOT / "autorag_research_amd/configs/embedding/mi355_colpali.yaml").read_text())
     assert set(ours) == {"_target_", "model_name", "model_type", "device", "torch_dtype", "embed_batch_size"}
-    ref = Path("/root/reference/configs/embedding/colpali.yaml")
-    if ref.exists():   # build container: key for key the reference's file
-        theirs = yaml.safe_load(ref.read_text())
-        assert set(theirs) == set(ours) and all(ours[k] == theirs[k] for k in ("model_name", "model_type", "torch_dtype", "embed_batch_size"))
+    # key for key the reference's file (recorded by tests/golden/make_golden.py)
+    theirs = json.loads((ROOT / "tests/golden/embedding_configs_golden.json").read_text())["colpali"]
+    assert set(theirs) == set(ours) and all(ours[k] == theirs[k] for k in ("model_name", "model_type", "torch_dtype", "embed_batch_size"))
 
 
 def test_interpolation_and_target_resolution():
@@ -220,16 +219,49 @@ def test_the_reference_loader_is_preferred_when_it_has_the_config(tmp_path, monk
     assert len(E.load_embedding_model("mock").embed_query("x")) == 384 and calls == ["mi355_bge_base"]   # not there: the package's own
 
 
-@pytest.mark.skipif(not Path("/root/reference/autorag_research/embeddings/base.py").exists(),
-                    reason="reference tree only exists in the build container")
+# The reference's multi-vector bases as the package meets them (embeddings/base.py:37-137): pydantic models with the fields
+# `model_name` and `embed_batch_size`, abstract per-text methods, a batching default.  Stand-ins of that public shape only,
+# registered as `autorag_research.embeddings.base` before the package is imported.
+_REF_EMBEDDING_BASES = """
+import abc, sys, types
+from pydantic import BaseModel
+
+class MultiVectorBaseEmbedding(BaseModel, abc.ABC):
+    model_name: str = "unknown"
+    embed_batch_size: int = 10
+
+    @abc.abstractmethod
+    def embed_query(self, query): ...
+
+    @abc.abstractmethod
+    def embed_text(self, text): ...
+
+    def embed_documents(self, texts):
+        return [self.embed_text(t) for t in texts]
+
+    def embed_documents_batch(self, texts, show_progress=False):
+        n = self.embed_batch_size
+        return [v for i in range(0, len(texts), n) for v in self.embed_documents(texts[i:i + n])]
+
+class MultiVectorMultiModalEmbedding(MultiVectorBaseEmbedding):
+    @abc.abstractmethod
+    def embed_image(self, img_file_path): ...
+
+base = types.ModuleType("autorag_research.embeddings.base")
+base.MultiVectorBaseEmbedding, base.MultiVectorMultiModalEmbedding = MultiVectorBaseEmbedding, MultiVectorMultiModalEmbedding
+sys.modules.update({"autorag_research": types.ModuleType("autorag_research"),
+                    "autorag_research.embeddings": types.ModuleType("autorag_research.embeddings"),
+                    "autorag_research.embeddings.base": base})
+"""
+
+
 def test_multi_vector_wrappers_pass_the_reference_type_check():
     """`injection.load_embedding_model` accepts what a YAML instantiates only if `isinstance(model, (Embeddings,
-    MultiVectorBaseEmbedding))` (injection.py:134, 202-206): with the reference importable, the wrappers ARE subclasses of its
-    pydantic bases (a fresh process: the bases are chosen at import time)."""
+    MultiVectorBaseEmbedding))` (injection.py:134, 202-206): with the reference's bases importable (the stand-ins above), the
+    wrappers ARE subclasses of those pydantic bases (a fresh process: the bases are chosen at import time)."""
     code = (
-        "import sys, json; sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-        "from ref_import import import_reference\n"
-        "import_reference()\n"
+        "import sys, json; sys.path.insert(0, %r)\n"
+        + _REF_EMBEDDING_BASES +
         "import torch\n"
         "import autorag_research.embeddings.base as ref\n"
         "import autorag_research_amd.embeddings as E\n"
@@ -251,7 +283,7 @@ def test_multi_vector_wrappers_pass_the_reference_type_check():
         "       'q': len(late.embed_query('a b c')), 'docs_batch': len(late.embed_documents_batch(['a'] * 9)),\n"
         "       'img': len(col.embed_image(torch.zeros((3, 56, 56))))}\n"
         "print(json.dumps(out))\n"
-    ) % (str(ROOT), str(ROOT / "tests" / "golden"), str(ROOT / "tests"))
+    ) % str(ROOT)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT,
                        env={"PYTHONDONTWRITEBYTECODE": "1", "PATH": "/usr/bin:/bin"})
     assert r.returncode == 0, r.stderr[-3000:]

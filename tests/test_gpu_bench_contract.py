@@ -1,7 +1,8 @@
-"""GPU: `bench.py` keeps the driver's contract -- ONE JSON line, last on stdout, with the keys the driver reads, the
+"""GPU: `bench.py --full` keeps the driver's contract -- ONE JSON line, last on stdout, with the keys the driver reads, the
 `roofline` and `cpu_baseline` objects, and the bench's own parity verdicts true -- on a corpus small enough to run inside the
 suite (the driver runs the full-size line itself).  A second run takes the distributed code path with a world of one
-(process group on RCCL, packed all-gather + merge inside the timed loop, the sharded answer compared with one GPU's)."""
+(process group on RCCL, packed all-gather + merge inside the timed loop, the sharded answer compared with one GPU's).  A plain
+run (no `--full`) prints the headline line alone, and `--dump-outputs` writes the last timed step's answer."""
 
 import json
 import os
@@ -32,7 +33,8 @@ def _bench(*args, env=None):
 
 
 def test_default_shape_line_on_a_small_corpus(native_built):
-    d = _bench("--rows", "500000", "--steps", "4", "--warmup", "1", "--cpu-sample-rows", "250000", "--cpu-sample-queries", "1024")
+    d = _bench("--full", "--rows", "500000", "--steps", "4", "--warmup", "1", "--cpu-sample-rows", "250000", "--cpu-sample-queries",
+               "1024")
     assert TOP_KEYS <= set(d), TOP_KEYS - set(d)
     assert d["metric"] == "queries/sec" and d["unit"] == "queries/s" and d["higher_is_better"] is True
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and d["vs_baseline"] is None
@@ -71,7 +73,7 @@ def test_default_shape_line_on_a_small_corpus(native_built):
 
 
 def test_distributed_code_path_with_a_world_of_one(native_built):
-    d = _bench("--rows", "500000", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--force-dist",
+    d = _bench("--full", "--rows", "500000", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--force-dist",
                env={"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29541", "RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1"})
     assert d["n_gpus"] == 1 and d["config"]["layout"]["row_shards"] == 1
     assert d["extra"]["identical_to_one_gpu"] is True         # all-gather + merge of one shard == the plain search
@@ -83,7 +85,7 @@ def test_distributed_code_path_with_a_world_of_one(native_built):
 
 
 def test_distributed_code_path_through_the_library_communicator(native_built):
-    d = _bench("--rows", "500000", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--force-dist", "--comm", "lib",
+    d = _bench("--full", "--rows", "500000", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--force-dist", "--comm", "lib",
                env={"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29542", "RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1"})
     c = d["config"]["collective"]
     assert c["rccl_comm_count"] == 1 and c["ranks_in_all_gather"] == 1   # ncclCommCount, asked of RCCL itself
@@ -93,7 +95,8 @@ def test_distributed_code_path_through_the_library_communicator(native_built):
 def test_maxsim_leg_reports_the_mfma_roofline_from_the_timed_steps(native_built):
     """`--workload maxsim`: bound "mfma", algorithmic <= issued flops, both below the dense bf16 peak -- the counters are those of
     the TIMED steps (round 4: they were read behind the power probe's extra steps once and the issued rate came out at 4 PF)."""
-    d = _bench("--workload", "maxsim", "--tokens", "text", "--docs", "60000", "--steps", "6", "--warmup", "1", "--no-cpu-baseline")
+    d = _bench("--full", "--workload", "maxsim", "--tokens", "text", "--docs", "60000", "--steps", "6", "--warmup", "1",
+               "--no-cpu-baseline")
     assert d["metric"] == "queries/sec" and d["value"] > 0 and "workload" in d["config"]
     r = d["roofline"]
     # (round 6: a store of passages is screened over its granule-packed copy -- the line names the kernel and the copy it multiplied)
@@ -108,3 +111,25 @@ def test_maxsim_leg_reports_the_mfma_roofline_from_the_timed_steps(native_built)
     assert r0["kernel"].startswith("k_maxsim16_wg<16>") and r0["token_copy"].startswith("padded")
     assert r0["launches"] == 6 and r0["issued_tflops"] / r0["achieved"] > r["issued_tflops"] / r["achieved"] * 1.05
     assert d0["extra"]["candidates_per_query"] == d["extra"]["candidates_per_query"]
+
+
+def test_plain_line_and_dumped_outputs(native_built, tmp_path):
+    """Without `--full` the line is the headline alone (no CPU baseline, no untimed extras); `--steps` sets the timed steps;
+    `--dump-outputs` writes the last timed step's [B,k] distances and row ids, identical from run to run (seeded inputs)."""
+    runs = [_bench("--rows", "500000", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / name)) for name in "ab"]
+    for d in runs:
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"} <= set(d)
+        assert d["metric"] == "queries/sec" and d["unit"] == "queries/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["roofline"]["launches"] > 0 and d["extra"]["fallback_queries"] == 0
+        assert abs(d["value"] - d["config"]["queries_per_step"] / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+        assert not {"cpu_baseline", "cpu_baselines", "ndcg_at_10", "value_pcie_inclusive", "maxsim", "sustained"} & set(d)
+        assert "bare_stream" not in d["roofline"] and d["roofline"]["traffic"] is None
+    import numpy as np
+
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("distances", "rows")}
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in ("distances", "rows")}
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["distances.npy", "rows.npy"]
+    assert a["distances"].dtype == np.float64 and a["rows"].dtype == np.float64 and a["rows"].shape == a["distances"].shape == (1024, 10)
+    assert (np.diff(a["distances"], axis=1) >= 0).all() and (a["rows"] == np.round(a["rows"])).all()
+    assert a["rows"].min() >= 0 and a["rows"].max() < 500_000 and len(np.unique(a["rows"][0])) == 10
+    assert all(np.array_equal(a[n], b[n]) for n in a)

@@ -28,7 +28,7 @@ def test_bench_multi_rank_leg_runs_with_two_ranks_on_one_gpu(native_built, k):
         env.pop(var, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", port, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--rows", "1000000",
-           "--k", str(k), "--rehearse-one-gpu", "--no-cpu-baseline"]
+           "--k", str(k), "--rehearse-one-gpu", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -13,7 +13,6 @@ import sys
 from importlib.resources import files
 from pathlib import Path
 
-import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 YAMLS = {"mi355_vector_search", "mi355_image_vector_search", "mi355_heaven", "mi355_gqr_hybrid", "mi355_hybrid_rrf",
@@ -60,20 +59,27 @@ def test_registry_style_scan_finds_every_yaml():
     assert set(found) == YAMLS and set(found.values()) == {"retrieval"}
 
 
-@pytest.mark.skipif(not Path("/root/reference/autorag_research/plugin_registry.py").exists(),
-                    reason="reference tree only exists in the build container")
 def test_reference_registry_scans_this_package():
-    """The reference's own function over this package (build container only)."""
+    """The reference registry's `_scan_module_yamls` over this package, recorded by tests/golden/make_golden.py
+    (executor_golden.json: registry_scan), is what a scan of the package in a fresh process finds: the module loaded by name,
+    `importlib.resources.files` of it, YAMLs flat or one directory down (plugin_registry.py:90-120)."""
+    import json
+
+    recorded = json.loads((ROOT / "tests" / "golden" / "executor_golden.json").read_text())["registry_scan"]
+    assert sorted((r[0], r[1]) for r in recorded) == sorted((n, "retrieval") for n in YAMLS)
     code = (
-        "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-        "from ref_import import import_reference\n"
-        "import_reference()\n"
-        "from autorag_research import plugin_registry as pr\n"
-        "import autorag_research_amd as pkg\n"
-        "infos = pr._scan_module_yamls(pkg, 'mi355_vector_search', 'pipelines')\n"
-        "print(sorted((i.config_name, i.subcategory) for i in infos))\n"
-    ) % (str(ROOT), str(ROOT / "tests" / "golden"))
+        "import sys, importlib; sys.path.insert(0, %r)\n"
+        "from importlib.resources import files\n"
+        "pkg = importlib.import_module('autorag_research_amd')\n"
+        "found = []\n"
+        "for res in files(pkg).iterdir():\n"
+        "    if res.name.endswith('.yaml'):\n"
+        "        found.append((res.name[:-5], None))\n"
+        "    elif res.is_dir():\n"
+        "        found += [(s.name[:-5], res.name) for s in res.iterdir() if s.name.endswith('.yaml')]\n"
+        "print(sorted(found))\n"
+    ) % str(ROOT)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT,
                        env={"PYTHONDONTWRITEBYTECODE": "1", "PATH": "/usr/bin:/bin"})
     assert r.returncode == 0, r.stderr[-2000:]
-    assert r.stdout.strip() == str(sorted((n, "retrieval") for n in YAMLS))
+    assert r.stdout.strip() == str(sorted((r_[0], r_[1]) for r_ in recorded))

@@ -3,7 +3,7 @@
 #   bash tools/round_evidence.sh [section ...]      (no argument = the default set)
 # Sections (each writes gpurun_out/ev/<section>*):
 #   tests      pytest -m gpu + smoke()
-#   bench      the default bench line (what the driver runs) + the bf16-screen line
+#   bench      the full bench line (--full) + the bf16-screen line
 #   stats      rocprofv3 --kernel-trace --stats of the bench command
 #   traffic    PMC passes (separate, kernel-trace only) of the bench command: FETCH_SIZE, WRITE_SIZE, L2 hit, SQ busy / LDS
 #   timelines  one-step kernel timelines at N = 10 M and at the 8-way shard size
@@ -56,7 +56,7 @@ tests)
   timeout 1800 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; tail -2 $OUT/pytest_gpu.log
   python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log ;;
 bench)
-  python bench.py > $OUT/bench_default.log 2>&1; tail -1 $OUT/bench_default.log > $OUT/bench_default_line.json; cut -c1-400 $OUT/bench_default_line.json
+  python bench.py --full > $OUT/bench_default.log 2>&1; tail -1 $OUT/bench_default.log > $OUT/bench_default_line.json; cut -c1-400 $OUT/bench_default_line.json
   python bench.py --screen bf16 $BENCH_QUICK --traffic > $OUT/bench_bf16.log 2>&1; tail -1 $OUT/bench_bf16.log > $OUT/bench_bf16_line.json; cut -c1-200 $OUT/bench_bf16_line.json ;;
 stats)
   # the default command's steps / warm-up (10 / 2), without its untimed extras (they launch the same kernel on other workloads);
@@ -113,7 +113,7 @@ maxsim)
   for shape in text page; do
     docs=1000000; [ $shape = page ] && docs=100000
     ARGS="--workload maxsim --tokens $shape --docs $docs --warmup 2 --no-cpu-baseline"
-    python bench.py $ARGS --steps 63 > $OUT/maxsim_line_$shape.json 2> $OUT/maxsim_line_$shape.err; cut -c1-600 $OUT/maxsim_line_$shape.json
+    python bench.py $ARGS --full --steps 63 > $OUT/maxsim_line_$shape.json 2> $OUT/maxsim_line_$shape.err; cut -c1-600 $OUT/maxsim_line_$shape.json
     rm -rf $OUT/maxsim_st_$shape $OUT/maxsim_pmc_$shape
     MI355DR_BENCH_PMC=0 rocprofv3 --kernel-trace --stats -f csv -d $OUT/maxsim_st_$shape -o ms -- python bench.py $ARGS --steps 12 --no-extras > $OUT/maxsim_st_$shape.log 2>&1
     MI355DR_BENCH_PMC=0 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -f csv -d $OUT/maxsim_pmc_$shape -o sq -- python bench.py $ARGS --steps 6 --no-extras > $OUT/maxsim_pmc_$shape.log 2>&1
