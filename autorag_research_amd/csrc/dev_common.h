@@ -20,6 +20,8 @@ constexpr int kCandCapWide = 4096;  // ... of a pass whose prunes take the two-w
 constexpr int kSortMax = 4096;    // LDS sort capacity (>= kKMax + kCandCap, power of two)
 constexpr int kIrrCap = 1024;     // irregular (zero / non-finite / extreme-norm) rows the screen path tolerates
 constexpr uint64_t kKeyNaN = 0xFFFFFFFFFFFFFFFFull;
+// the general prune sorts the kept top-k and a whole candidate list together: its lists hold at most kCandCap slots
+static_assert(kSortMax >= kKMax + kCandCap, "the general prune's sort must hold k kept entries and a full candidate list");
 
 // status bits per query
 constexpr int kStOverflow = 1;   // candidate buffer overflowed in some chunk -> result must be recomputed

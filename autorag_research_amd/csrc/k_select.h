@@ -210,7 +210,15 @@ __device__ __forceinline__ void prune_body(const PruneArgs& a, char* smem) {
         return;
     }
     if (n_best + raw_cnt > SORT) {  // too many for this instantiation: left for the large one
-        if (SORT < kPruneBigSort) leave_for_general();
+        if (SORT < kPruneBigSort) {
+            leave_for_general();
+            return;
+        }
+        // the large one cannot hold them either (a list stride above kCandCap): not committed, flagged as an overflow
+        if (tid == 0) {
+            a.st.status[q] |= kStOverflow;
+            a.st.cnt[q] = 0;
+        }
         return;
     }
     const int n_new = raw_cnt;

@@ -214,8 +214,9 @@ constexpr double kSmallBlockBudget = 1.6;  // (the measured inflations are ~4 an
 // by the Gaussian tail ratio, ~6 measured over the round-5 pass at k = 100 -- budgeted as 10 with a quarter of the entries spare.
 constexpr double kInflationI8Wide = 10.0, kInflationBf16Wide = 4.0;
 inline bool wide_ok(const mi355dr_index* idx, int k) { return idx->prune_wide && k >= kWideKMin && k <= kWideKMax; }
-// the prunes of the search in progress take the two-wave form (the exact scan keeps the general form and its 2048-slot lists)
-inline bool wide_now(const mi355dr_index* idx) { return wide_ok(idx, idx->k_now) && idx->path != MI355DR_PATH_SCAN; }
+// the prunes of the search in progress take the two-wave form -- passes that screen only (enqueue_block sets the flag): the
+// exact scan keeps the general form and its <= 2048-slot lists, on path = scan and on an AUTO pass no screen can serve alike
+inline bool wide_now(const mi355dr_index* idx) { return idx->screening_now && wide_ok(idx, idx->k_now); }
 // candidate slots per query (= the lists' stride) of the search in progress
 inline int cap_now(const mi355dr_index* idx) { return !idx->cap_set && wide_now(idx) ? kCandCapWide : idx->cap; }
 inline double growth_budget(const mi355dr_index* idx, int k, bool i8) {
@@ -275,6 +276,8 @@ int launch_prune(mi355dr_index* idx, hipStream_t s, int nblocks, const int* qlis
         HIPCHECK(idx, hipGetLastError());
         return MI355DR_OK;
     }
+    // (its sort holds k kept entries and one whole list: kSortMax >= kKMax + kCandCap, dev_common.h)
+    if (pa.cap > kCandCap) return fail(idx, MI355DR_E_INTERNAL, "general-form prune on a list stride above kCandCap");
     const bool list_mode = qlist == nullptr;
     pa.skip_list = list_mode ? idx->prune_skip : nullptr;
     pa.skip_parity = list_mode ? (idx->prune_parity ^= 1) : 0;
@@ -701,6 +704,7 @@ int enqueue_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, 
     // (inner product rides the same cosine screens: thresholds become cos >= dot_k / (|q| cmax), see k_prune)
     const bool screen_possible = use_i8(idx) ? i8_available(idx) : idx->irr_n <= kIrrCap;
     const bool use_screen = idx->n > 0 && screen_possible && idx->path != MI355DR_PATH_SCAN;
+    idx->screening_now = use_screen;  // (before the plan and the first launch: every kernel of the pass sees one list stride)
     if (idx->path == MI355DR_PATH_SCREEN && !screen_possible && idx->n > 0)
         return fail(idx, MI355DR_E_UNSUPPORTED, "screen path unavailable (metric or too many irregular rows)");
     if (q_dev != idx->qdev)
@@ -745,7 +749,14 @@ int complete_block(mi355dr_index* idx, Pending& p) {
     p.active = false;
     HIPCHECK(idx, hipEventSynchronize(p.done));
     drain_events(idx);
-    if (!p.used_screen || p.status_host[kQBlockMax] == 0) return MI355DR_OK;
+    if (!p.used_screen) {
+        // the exact scan re-runs every chunk that overflowed (run_scan) and clears the flag of each: one left over is a lost chunk
+        for (int i = 0; i < p.B; ++i)
+            if (p.status_host[i] & kStOverflow)
+                return fail(idx, MI355DR_E_INTERNAL, "exact scan: query " + std::to_string(i) + " lost a candidate chunk");
+        return MI355DR_OK;
+    }
+    if (p.status_host[kQBlockMax] == 0) return MI355DR_OK;
     // some query overflowed its candidate buffer or has an irregular norm
     hipStream_t s = p.stream;
     const int B = p.B, k = p.k, level = p.level;

@@ -42,6 +42,32 @@ def corpus(rng, n, d, mode):
     return C
 
 
+def arrange(rng, C, Q, order, dirt, metric):
+    """row layouts the exact scan's chunk ladder is sensitive to, applied after the corpus mode:
+    order `ascending` / `descending`: every query leans towards one shared direction q0 (Q[0] is q0 itself) and the rows are
+    sorted by their score for q0 -- ascending, every row enters the running top-k and the scan's chunks overflow;
+    dirt `many`: more than 1024 irregular rows (no screen can serve the corpus: AUTO takes the exact scan), as a block at
+    the start of the corpus or scattered, all zero or a mix of zero / NaN / +-inf and a few extreme-norm rows."""
+    n, d = C.shape
+    if order != "as drawn":
+        q0 = rng.standard_normal(d).astype(np.float32)
+        Q = Q + 2.0 * q0[None, :] * (np.linalg.norm(Q, axis=1, keepdims=True) / np.linalg.norm(q0)).astype(np.float32)
+        Q[0] = q0
+        with np.errstate(all="ignore"):
+            s = C.astype(np.float64) @ q0.astype(np.float64)
+            if metric == "cosine":
+                s /= np.linalg.norm(C.astype(np.float64), axis=1)
+        C = C[np.argsort(s if order == "ascending" else -s, kind="stable")].copy()  # (NaN scores last)
+    if dirt == "many" and n >= 2100:
+        m = int(rng.integers(1025, min(n // 2, 3000) + 1))
+        pos = np.arange(m) if rng.random() < 0.5 else np.sort(rng.choice(n, size=m, replace=False))
+        values = (0.0,) if rng.random() < 0.3 else (0.0, np.nan, np.inf, -np.inf)
+        C[pos] = np.asarray(values, dtype=np.float32)[np.arange(m) % len(values)][:, None]
+        if len(values) > 1:  # (a few rows of finite distance: 0 for 1e-25, 1 for +-1e25)
+            C[rng.choice(pos, size=15, replace=False)] = rng.choice([1e-25, 1e25, -1e25], size=15).astype(np.float32)[:, None]
+    return C, Q
+
+
 def check_single(rng, case):
     n = int(rng.choice([1, 7, 300, 4000, 30000, 120000, 250000]))
     n = max(1, int(n * rng.uniform(0.5, 1.0)))
@@ -75,7 +101,12 @@ def check_single(rng, case):
     if rng.random() < 0.15:
         opts["prune_wide"] = 0
     row_offset = int(rng.choice([0, 0, 12345, 2**33]))
-    desc = f"single n={n} d={d} B={B} k={k} mode={mode} metric={metric} opts={opts} row_offset={row_offset}"
+    # (drawn after everything above: a case number keeps its shapes, mode and options)
+    order = str(rng.choice(["as drawn"] * 4 + ["ascending", "descending"]))
+    dirt = str(rng.choice(["as mode"] * 3 + ["many"]))
+    C, Q = arrange(rng, C, Q, order, dirt, metric)
+    desc = (f"single n={n} d={d} B={B} k={k} mode={mode} order={order} dirt={dirt} metric={metric} opts={opts} "
+            f"row_offset={row_offset}")
     import hashlib
     h_in = hashlib.sha1(C.tobytes() + Q.tobytes()).hexdigest()
     with pkg.Mi355Index(d, metric) as idx:
@@ -93,7 +124,7 @@ def check_single(rng, case):
             if opts.get("screen_dtype") == "i8" and "int8 screen unavailable" in str(e):
                 return desc + " (i8 unavailable: skipped)"
             raise
-        stats = {s: idx.stat(s) for s in ("fallback_queries", "retry_queries", "loose_rows", "screen_dtype_active")}
+        stats = {s: idx.stat(s) for s in ("fallback_queries", "retry_queries", "loose_rows", "irregular_rows", "screen_dtype_active")}
     rd, rr = cpu_ref.topk_search(C, Q, k, metric=metric)
     rr = np.where(rr >= 0, rr + row_offset, rr)
     ok = np.array_equal(rows, rr) and np.array_equal(np.isnan(dist), np.isnan(rd))
