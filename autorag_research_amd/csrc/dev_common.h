@@ -157,6 +157,24 @@ __device__ __forceinline__ float float_below(float x) {
 // a norm the bf16 screen can normalise safely
 __device__ __forceinline__ bool norm_is_regular(float n2) { return n2 >= 1e-30f && n2 <= 1e30f; }
 
+// ---- removed ("dead") rows (mi355dr_remove_rows; DESIGN.md "Mutable index") ----
+// A dead row keeps its slot and is marked in nrm2: a sum of squares is >= +0, +inf or NaN, never negative, so kDeadNrm2
+// is a value no stored row can have (and norm_is_regular rejects it: the shadow builders give the row the NaN / all-zero
+// images the screens never rank).  Where a (query, row) pair becomes an exact key, a dead row becomes the sorts' PADDING
+// entry -- (kKeyNaN, kRowNone) -- which orders behind every live row, irregular ones (NaN key, real row) included, and is
+// written out as "no result" (NaN / -1) by k_finalize.
+constexpr float kDeadNrm2 = -1.0f;
+constexpr int32_t kRowNone = 0x7FFFFFFF;
+__device__ __forceinline__ bool row_is_dead(float n2) { return n2 < 0.0f; }
+// exact key of a re-scored pair; `row` is replaced by kRowNone when the row is dead
+__device__ __forceinline__ uint64_t exact_key_of(int metric, float dot, float nq, float nc, int32_t& row) {
+    if (row_is_dead(nc)) {
+        row = kRowNone;
+        return kKeyNaN;
+    }
+    return dist_to_key(distance_from(metric, dot, nq, nc));
+}
+
 __device__ __forceinline__ int next_pow2(int x) {
     int p = 1;
     while (p < x) p <<= 1;

@@ -61,6 +61,9 @@ struct mi355dr_index {
     int32_t* irr8_rows = nullptr;  // [kIrrCap] irregular + loose rows
     int* irr8_count = nullptr;
     int irr8_n = 0;
+    // removed rows (mi355dr_remove_rows): slots that stay, marked in nrm2 (dev_common.h kDeadNrm2) and in neither list
+    int* dead_count = nullptr;
+    int64_t dead_n = 0;
 
     // per-search state (sized for one block of kQBlockMax queries)
     bool qstate_ready = false;

@@ -10,12 +10,15 @@ namespace mi355 {
 
 // grid: ceil(n/64) blocks of 64 threads (one wave, 64 rows)
 // n2max: running maximum of the regular |c|^2 (float bits; inner-product thresholds need the largest row norm)
+// ids != nullptr (mi355dr_update_rows): the n rows are ids[0 .. n) instead of row0 .. row0 + n -- the same chain, the same bits
 __global__ __launch_bounds__(64) void k_row_nrm2(const float* __restrict__ rows, int64_t row0, int64_t n, int d,
-                                                  float* __restrict__ nrm2, unsigned* __restrict__ n2max) {
+                                                  float* __restrict__ nrm2, unsigned* __restrict__ n2max,
+                                                  const int64_t* __restrict__ ids) {
     __shared__ float tile[kStageFloats];
     const int lane = threadIdx.x;
-    const int64_t i = row0 + (int64_t)blockIdx.x * kWave + lane;
-    const bool live = i < row0 + n;
+    const int64_t j = (int64_t)blockIdx.x * kWave + lane;
+    const bool live = j < n;
+    const int64_t i = ids ? (live ? ids[j] : 0) : row0 + j;
     const float* my_row = live ? rows + i * (int64_t)d : nullptr;
     float acc = 0.0f;
     for (int k0 = 0; k0 < d; k0 += kStageCols) {
@@ -42,14 +45,16 @@ __global__ __launch_bounds__(64) void k_row_nrm2(const float* __restrict__ rows,
 // non-negative float: unsigned max == float max) -- the corpus half of the bf16 screen bound.
 // absolute != 0 (inner-product metric): the shadow holds bf16_rn(c) itself -- the screen then estimates <q_hat, c> =
 // dot / |q| directly and no row norm enters the threshold (dev_common.h "inner product").
+// ids != nullptr (mi355dr_update_rows / _remove_rows): the n rows are ids[0 .. n), and nothing is recorded in irr_rows (the
+// caller rebuilds both side lists afterwards: k_rebuild_side_lists).  A removed row (nrm2 = kDeadNrm2) is not regular: NaN image.
 __global__ __launch_bounds__(256) void k_build_shadow(const float* __restrict__ rows, const float* __restrict__ nrm2,
                                                        int64_t row0, int64_t n, int d, int dpad,
                                                        uint16_t* __restrict__ shadow, int32_t* __restrict__ irr_rows,
                                                        int* __restrict__ irr_count, unsigned* __restrict__ res2_max,
-                                                       int absolute) {
+                                                       int absolute, const int64_t* __restrict__ ids) {
     __shared__ float sh[4];
-    const int64_t i = row0 + blockIdx.x;
-    if (i >= row0 + n) return;
+    if ((int64_t)blockIdx.x >= n) return;
+    const int64_t i = ids ? ids[blockIdx.x] : row0 + blockIdx.x;
     const float n2 = nrm2[i];
     const bool regular = norm_is_regular(n2);
     const float rc = regular ? (absolute ? 1.0f : 1.0f / sqrtf(n2)) : 0.0f;
@@ -81,7 +86,7 @@ __global__ __launch_bounds__(256) void k_build_shadow(const float* __restrict__ 
             const unsigned v = __float_as_uint((sh[0] + sh[1]) + (sh[2] + sh[3]));
             if (v > *(volatile unsigned*)res2_max) atomicMax(res2_max, v);
         }
-        else {
+        else if (ids == nullptr) {
             int slot = atomicAdd(irr_count, 1);
             if (slot < kIrrCap) irr_rows[slot] = (int32_t)i;
         }
@@ -109,16 +114,20 @@ __device__ __forceinline__ float block256_reduce(float v, bool is_max, float* sh
 // the residual norm |c_hat - S_g c8| measured per row, e_g = the largest.  A group is always rebuilt whole: when a later
 // add() lands in a partly filled group its old rows are requantised with the new step.  Loose rows are registered in
 // irr8_rows once -- only rows >= first_new (the rows this add() brought) are appended.
+// groups != nullptr (mi355dr_update_rows / _remove_rows): block b rebuilds group groups[b] -- the groups the call touched,
+// each listed once -- and the caller passes first_new = n_total: nothing is appended, it rebuilds the side lists afterwards.
+// A removed row (nrm2 = kDeadNrm2) is not regular, so it is "loose" here: out of the group's peak, all-zero image, flag 1.
 __global__ __launch_bounds__(256) void k_build_shadow8(const float* __restrict__ rows, const float* __restrict__ nrm2,
                                                         int64_t g0, int64_t n_total, int64_t first_new, int d, int dpad8,
                                                         int8_t* __restrict__ shadow8, uint8_t* __restrict__ flag8,
                                                         I8Group* __restrict__ grp, int32_t* __restrict__ irr8_rows,
-                                                        int* __restrict__ irr8_count, int absolute) {
+                                                        int* __restrict__ irr8_count, int absolute,
+                                                        const int64_t* __restrict__ groups) {
     __shared__ float s_peak[kI8GroupRows];
     __shared__ float s_err[kI8GroupRows];
     __shared__ float s_step;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t g = g0 + blockIdx.x;
+    const int64_t g = groups ? groups[blockIdx.x] : g0 + blockIdx.x;
     const int64_t row_g = g * kI8GroupRows;
     const float peak_limit = i8_row_peak_limit(d);
     for (int j = 0; j < 8; ++j) {

@@ -265,8 +265,9 @@ __global__ __launch_bounds__(WAVES * kWave) void k_prune_wide(PruneArgs a) {
             if (base + wave * kWave < nA) {  // wave-uniform
                 const float acc = staged_dot(tile, rp, qs, a.d, lane);
                 if (live) {
-                    SK[n_best + e] = dist_to_key(distance_from(a.metric, acc, nq, a.nrm2[row]));
-                    SR[n_best + e] = row;
+                    int32_t kept = row;  // (a dead row: the padding entry, dev_common.h)
+                    SK[n_best + e] = exact_key_of(a.metric, acc, nq, a.nrm2[row], kept);
+                    SR[n_best + e] = kept;
                 }
             }
         }
@@ -340,10 +341,12 @@ __global__ __launch_bounds__(WAVES * kWave) void k_prune_wide(PruneArgs a) {
                         uint64_t k64 = kKeyNaN;
                         bool pass = false;
                         if (live) {
-                            k64 = dist_to_key(distance_from(a.metric, acc, nq, a.nrm2[row]));
-                            // (a NaN distance only matters while fewer than k real ones are known: keep_x == 0)
-                            pass = keep_x == 0 ||
-                                   (k64 != kKeyNaN && f32_order_key(sim_of_dist(a.metric, key_to_dist(k64))) >= keep_x);
+                            const float nc = a.nrm2[row];
+                            k64 = dist_to_key(distance_from(a.metric, acc, nq, nc));
+                            // (a NaN distance only matters while fewer than k real ones are known: keep_x == 0; a dead row never)
+                            pass = !row_is_dead(nc) &&
+                                   (keep_x == 0 ||
+                                    (k64 != kKeyNaN && f32_order_key(sim_of_dist(a.metric, key_to_dist(k64))) >= keep_x));
                         }
                         const unsigned long long bal = __builtin_amdgcn_ballot_w64(pass);
                         int at = 0;

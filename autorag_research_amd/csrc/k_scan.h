@@ -181,8 +181,9 @@ __global__ __launch_bounds__(kScanThreads, 2) void k_scan(ScanArgs a) {
             const int64_t row = wrow0 + 32 * rb + (r & 3) + 8 * (r >> 2) + 4 * h;
             if (row >= a.row1) continue;
             const float dot = acc[rb][r];
-            const uint64_t key = dist_to_key(distance_from(a.metric, dot, qn, a.nrm2[row]));
-            if (key < tk || (key == tk && (int32_t)row < tr)) {
+            const float nc = a.nrm2[row];
+            const uint64_t key = dist_to_key(distance_from(a.metric, dot, qn, nc));
+            if (!row_is_dead(nc) && (key < tk || (key == tk && (int32_t)row < tr))) {
                 const int slot = atomicAdd(&a.st.cnt[q], 1);
                 if (slot < a.cap) {
                     a.cand_row[(int64_t)q * a.cap + slot] = (int32_t)row;
@@ -294,8 +295,9 @@ __global__ __launch_bounds__(kScanThreads, 2) void k_scan32(ScanArgs a, int64_t 
             const int64_t row = wrow0 + 32 * rb + (r & 3) + 8 * (r >> 2) + 4 * h;
             if (row >= a.row1) continue;
             const float dot = acc[rb][r];
-            const uint64_t key = dist_to_key(distance_from(a.metric, dot, qn, a.nrm2[row]));
-            if (key < tk || (key == tk && (int32_t)row < tr)) {
+            const float nc = a.nrm2[row];
+            const uint64_t key = dist_to_key(distance_from(a.metric, dot, qn, nc));
+            if (!row_is_dead(nc) && (key < tk || (key == tk && (int32_t)row < tr))) {
                 const int slot = atomicAdd(&a.st.cnt[q], 1);
                 if (slot < a.cap) {
                     a.cand_row[(int64_t)q * a.cap + slot] = (int32_t)row;
@@ -329,8 +331,9 @@ __global__ __launch_bounds__(64) void k_rescore_pairs(const float* __restrict__ 
         for (int k = 0; k < kn; ++k) acc = __builtin_fmaf(tc[k], tq[k], acc);
     }
     if (live) {
-        out_dot[p] = acc;
-        out_dist[p] = distance_from(metric, acc, qn[pair_q[p]], nrm2[pair_row[p]]);
+        const float nc = nrm2[pair_row[p]];  // (a removed row has no score: NaN, NaN)
+        out_dot[p] = row_is_dead(nc) ? __builtin_nanf("") : acc;
+        out_dist[p] = row_is_dead(nc) ? (double)__builtin_nanf("") : distance_from(metric, acc, qn[pair_q[p]], nc);
     }
 }
 

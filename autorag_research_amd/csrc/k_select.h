@@ -260,8 +260,9 @@ __device__ __forceinline__ void prune_body(const PruneArgs& a, char* smem) {
                     const float* rp = live ? a.rows + (int64_t)row * a.d : nullptr;
                     const float acc = staged_dot(tile, rp, qs, a.d, lane);
                     if (live) {
-                        SK[dst + e] = dist_to_key(distance_from(a.metric, acc, nq, a.nrm2[row]));
-                        SR[dst + e] = row;
+                        int32_t kept = row;  // (a dead row: the padding entry, dev_common.h)
+                        SK[dst + e] = exact_key_of(a.metric, acc, nq, a.nrm2[row], kept);
+                        SR[dst + e] = kept;
                     }
                 }
             };
@@ -484,9 +485,9 @@ __device__ __forceinline__ void prune_body(const PruneArgs& a, char* smem) {
                 float acc = 0.0f;
                 if (base + wave * kWave < e1) acc = staged_dot(tile, rp, qs, a.d, lane);  // wave-uniform condition
                 if (live) {
-                    const double dist = distance_from(a.metric, acc, nq, a.nrm2[row]);
-                    SK[dst + (e - e0)] = dist_to_key(dist);
-                    SR[dst + (e - e0)] = row;
+                    int32_t kept = row;  // (a dead row: the padding entry, dev_common.h)
+                    SK[dst + (e - e0)] = exact_key_of(a.metric, acc, nq, a.nrm2[row], kept);
+                    SR[dst + (e - e0)] = kept;
                 }
             }
         };
@@ -540,9 +541,8 @@ __device__ __forceinline__ void prune_body(const PruneArgs& a, char* smem) {
     } else {
         n_res = n_new;
         for (int i = tid; i < n_new; i += THREADS) {
-            const int32_t row = crow[i];
-            const double dist = distance_from(a.metric, cval[i], nq, a.nrm2[row]);
-            SK[n_best + i] = dist_to_key(dist);
+            int32_t row = crow[i];
+            SK[n_best + i] = exact_key_of(a.metric, cval[i], nq, a.nrm2[row], row);
             SR[n_best + i] = row;
         }
     }
@@ -600,7 +600,8 @@ __global__ __launch_bounds__(64) void k_finalize(QueryState st, int k, int64_t r
     const int q = blockIdx.x;
     const int n = st.best_n[q];
     for (int s = threadIdx.x; s < k; s += blockDim.x) {
-        if (s < n) {
+        // (a kept entry with row kRowNone is a removed row that filled a slot no live row claimed: "no result")
+        if (s < n && st.best_row[(int64_t)q * kKMax + s] != kRowNone) {
             out_dist[(int64_t)q * k + s] = key_to_dist(st.best_key[(int64_t)q * kKMax + s]);
             out_rows[(int64_t)q * k + s] = (int64_t)st.best_row[(int64_t)q * kKMax + s] + row_offset;
         } else {

@@ -14,6 +14,7 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "k_screen_stream.h"
 #include "k_select.h"
 #include "k_prune_wide.h"
+#include "k_update.h"
 
 using namespace mi355;
 
@@ -262,7 +263,8 @@ int launch_prune(mi355dr_index* idx, hipStream_t s, int nblocks, const int* qlis
     pa.exact = exact;
     // (flags exist only for loose rows, and every loose row is counted: a corpus without any -- the usual case -- spares each
     // candidate the dependent flag8[row] load, one memory round trip of the prune's latency chain)
-    pa.flag8 = (use_i8(idx) && idx->irr8_n > 0) ? idx->flag8 : nullptr;
+    // (a removed row carries the flag too -- its all-zero int8 image can pass a low threshold -- and is in no list: dead_n)
+    pa.flag8 = (use_i8(idx) && (idx->irr8_n > 0 || idx->dead_n > 0)) ? idx->flag8 : nullptr;
     pa.cscale = idx->metric == MI355DR_METRIC_IP ? idx->cmax : 1.0f;
     // int8 screen, cosine: candidates that survive the exact cut are screened once more on their bf16 shadow rows
     // (half the bytes of an fp32 row, a bound ~5x tighter) before the exact re-score
@@ -867,7 +869,7 @@ int check_search_args(mi355dr_index* idx, const void* q, int B, int k, const voi
 
 extern "C" {
 
-int mi355dr_version(void) { return 100; }
+int mi355dr_version(void) { return 101; }
 
 const char* mi355dr_last_error(const mi355dr_index* idx) {
     if (idx) return idx->err.c_str();
@@ -903,6 +905,8 @@ int mi355dr_create(mi355dr_index** out, int device_id, int dim, int metric) {
     if (e == hipSuccess) e = hipMalloc(&idx->irr8_rows, kIrrCap * sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc(&idx->irr8_count, sizeof(int));
     if (e == hipSuccess) e = hipMemset(idx->irr8_count, 0, sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&idx->dead_count, sizeof(int));
+    if (e == hipSuccess) e = hipMemset(idx->dead_count, 0, sizeof(int));
     if (e == hipSuccess) e = hipEventCreate(&idx->t0);
     if (e == hipSuccess) e = hipEventCreate(&idx->t1);
     if (e != hipSuccess) {
@@ -931,7 +935,7 @@ void mi355dr_destroy(mi355dr_index* idx) {
                     idx->rows, idx->shadow, idx->nrm2, idx->irr_rows, idx->irr_count, idx->st.qn, idx->st.qhat,
                     idx->st.thr, idx->st.cnt, idx->st.best_n, idx->st.best_key, idx->st.best_row, idx->st.thr_key,
                     idx->st.thr_row, idx->st.status, idx->qdev, idx->cand_row, idx->cand_val, idx->qlist_dev,
-                    idx->out_dist_dev, idx->out_rows_dev, idx->stat_dev, idx->prune_skip, idx->rq_progress, idx->park_thr};
+                    idx->out_dist_dev, idx->out_rows_dev, idx->stat_dev, idx->prune_skip, idx->rq_progress, idx->park_thr, idx->dead_count};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     multivec_destroy(idx);
@@ -980,11 +984,11 @@ static int add_rows_impl(mi355dr_index* idx, const float* rows, int64_t n, hipMe
     for (int64_t r0 = 0; r0 < n; r0 += kBuildSlice) {
         const int64_t m = std::min(kBuildSlice, n - r0), first = idx->n + r0;
         hipLaunchKernelGGL(k_row_nrm2, dim3((unsigned)((m + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows, first, m,
-                           idx->dim, idx->nrm2, idx->n2max_dev);
+                           idx->dim, idx->nrm2, idx->n2max_dev, (const int64_t*)nullptr);
         HIPCHECK(idx, hipGetLastError());
         hipLaunchKernelGGL(k_build_shadow, dim3((unsigned)m), dim3(256), 0, s, idx->rows, idx->nrm2, first, m, idx->dim,
                            idx->dpad, idx->shadow, idx->irr_rows, idx->irr_count, idx->bf16_res2_dev,
-                           idx->metric == MI355DR_METRIC_IP ? 1 : 0);
+                           idx->metric == MI355DR_METRIC_IP ? 1 : 0, (const int64_t*)nullptr);
         HIPCHECK(idx, hipGetLastError());
     }
     {   // int8 shadow: whole groups of 32 rows, from the (possibly partly filled) group the first new row falls into
@@ -993,7 +997,7 @@ static int add_rows_impl(mi355dr_index* idx, const float* rows, int64_t n, hipMe
             const int64_t m = std::min(kBuildSlice, g_hi - g0);
             hipLaunchKernelGGL(k_build_shadow8, dim3((unsigned)m), dim3(256), 0, s, idx->rows, idx->nrm2, g0, idx->n + n,
                                idx->n, idx->dim, idx->dpad8, idx->shadow8, idx->flag8, idx->grp8, idx->irr8_rows,
-                               idx->irr8_count, idx->metric == MI355DR_METRIC_IP ? 1 : 0);
+                               idx->irr8_count, idx->metric == MI355DR_METRIC_IP ? 1 : 0, (const int64_t*)nullptr);
             HIPCHECK(idx, hipGetLastError());
         }
     }
@@ -1021,7 +1025,114 @@ int mi355dr_add_rows_device(mi355dr_index* idx, const float* rows_dev, int64_t n
     return add_rows_impl(idx, rows_dev, n, hipMemcpyDeviceToDevice);
 }
 
+// ---- update / remove in place (DESIGN.md "Mutable index") ---------------------------------------------------------------
+namespace {
+struct DevBuf {  // scratch of one call, released on every way out
+    void* p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+constexpr int64_t kMutSlice = (int64_t)1 << 16;  // rows per staging upload and per-row launch
+
+// rows == nullptr: remove.  kind: where `rows` lives.  row_ids: host.
+int mutate_rows_impl(mi355dr_index* idx, const int64_t* row_ids, const float* rows, int64_t n, hipMemcpyKind kind, bool remove) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (n < 0) return fail(idx, MI355DR_E_INVALID, "negative row count");
+    if (n == 0) {  // (nothing to change, but the ordering promise holds: what is in flight is complete on return)
+        HIPCHECK(idx, hipSetDevice(idx->device));
+        return drain_pending(idx);
+    }
+    if (!row_ids || (!remove && !rows)) return fail(idx, MI355DR_E_INVALID, "null argument");
+    // every id inside the index and listed once -- checked before anything is touched
+    std::vector<int64_t> sorted(row_ids, row_ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.front() < 0 || sorted.back() >= idx->n) return fail(idx, MI355DR_E_INVALID, "row id out of range");
+    for (int64_t i = 1; i < n; ++i)
+        if (sorted[i] == sorted[i - 1]) return fail(idx, MI355DR_E_INVALID, "duplicated row id " + std::to_string(sorted[i]));
+    std::vector<int64_t> groups;  // the int8 groups the call touches, each once
+    for (int64_t r : sorted)
+        if (groups.empty() || groups.back() != r / kI8GroupRows) groups.push_back(r / kI8GroupRows);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_pending(idx));  // (a search in flight sees the index as it was)
+    hipStream_t s = idx->stream;
+    const int absolute = idx->metric == MI355DR_METRIC_IP ? 1 : 0;
+    DevBuf ids_dev, groups_dev, stage;
+    HIPCHECK(idx, hipMalloc(&ids_dev.p, (size_t)n * sizeof(int64_t)));
+    HIPCHECK(idx, hipMalloc(&groups_dev.p, groups.size() * sizeof(int64_t)));
+    HIPCHECK(idx, hipMemcpyAsync(ids_dev.p, row_ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIPCHECK(idx, hipMemcpyAsync(groups_dev.p, groups.data(), groups.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (!remove && kind == hipMemcpyHostToDevice)
+        HIPCHECK(idx, hipMalloc(&stage.p, (size_t)std::min(n, kMutSlice) * idx->dim * sizeof(float)));
+    for (int64_t r0 = 0; r0 < n; r0 += kMutSlice) {
+        const int64_t m = std::min(kMutSlice, n - r0);
+        const int64_t* ids = (const int64_t*)ids_dev.p + r0;
+        if (remove) {
+            hipLaunchKernelGGL(k_mark_dead, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, ids, m, idx->nrm2);
+            HIPCHECK(idx, hipGetLastError());
+        } else {
+            const float* src = rows + r0 * idx->dim;
+            if (stage.p) {
+                HIPCHECK(idx, hipMemcpyAsync(stage.p, src, (size_t)m * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
+                src = (const float*)stage.p;
+            }
+            const int vec4 = idx->dim % 4 == 0 && (uintptr_t)src % 16 == 0;
+            hipLaunchKernelGGL(k_update_rows, dim3((unsigned)m), dim3(256), 0, s, src, ids, m, idx->dim, vec4, idx->rows);
+            HIPCHECK(idx, hipGetLastError());
+            hipLaunchKernelGGL(k_row_nrm2, dim3((unsigned)((m + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows, (int64_t)0, m,
+                               idx->dim, idx->nrm2, idx->n2max_dev, ids);
+            HIPCHECK(idx, hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_build_shadow, dim3((unsigned)m), dim3(256), 0, s, idx->rows, idx->nrm2, (int64_t)0, m, idx->dim,
+                           idx->dpad, idx->shadow, idx->irr_rows, idx->irr_count, idx->bf16_res2_dev, absolute, ids);
+        HIPCHECK(idx, hipGetLastError());
+    }
+    constexpr int64_t kBuildSlice = (int64_t)1 << 22;
+    for (int64_t g0 = 0; g0 < (int64_t)groups.size(); g0 += kBuildSlice) {
+        const int64_t m = std::min<int64_t>(kBuildSlice, (int64_t)groups.size() - g0);
+        hipLaunchKernelGGL(k_build_shadow8, dim3((unsigned)m), dim3(256), 0, s, idx->rows, idx->nrm2, (int64_t)0, idx->n, idx->n,
+                           idx->dim, idx->dpad8, idx->shadow8, idx->flag8, idx->grp8, idx->irr8_rows, idx->irr8_count, absolute,
+                           (const int64_t*)groups_dev.p + g0);
+        HIPCHECK(idx, hipGetLastError());
+    }
+    // both side lists and the dead count anew, from the flags (a row may have entered or left either class)
+    HIPCHECK(idx, hipMemsetAsync(idx->irr_count, 0, sizeof(int), s));
+    HIPCHECK(idx, hipMemsetAsync(idx->irr8_count, 0, sizeof(int), s));
+    HIPCHECK(idx, hipMemsetAsync(idx->dead_count, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_rebuild_side_lists, dim3((unsigned)((idx->n + 255) / 256)), dim3(256), 0, s, idx->nrm2, idx->flag8,
+                       (int64_t)0, idx->n, idx->irr_rows, idx->irr_count, idx->irr8_rows, idx->irr8_count, idx->dead_count);
+    HIPCHECK(idx, hipGetLastError());
+    int irr = 0, irr8 = 0, dead = 0;
+    float res2 = 0.0f, n2max = 0.0f;
+    HIPCHECK(idx, hipMemcpyAsync(&irr, idx->irr_count, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(&irr8, idx->irr8_count, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(&dead, idx->dead_count, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(&res2, idx->bf16_res2_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(&n2max, idx->n2max_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    // the two running maxima only ever grow (the row that held one may be gone: a looser bound is still a bound)
+    idx->cmax = std::sqrt(n2max) * 1.000001f;
+    idx->bf16_ec = std::min(std::sqrt(res2) * 1.001f, 0.00390625f * 1.0001f * (absolute ? idx->cmax : 1.0f));
+    idx->irr_n = irr;
+    idx->irr8_n = irr8;
+    idx->dead_n = dead;
+    return MI355DR_OK;
+}
+}  // namespace
+
+int mi355dr_update_rows(mi355dr_index* idx, const int64_t* row_ids, const float* rows, int64_t n) {
+    return mutate_rows_impl(idx, row_ids, rows, n, hipMemcpyHostToDevice, false);
+}
+int mi355dr_update_rows_device(mi355dr_index* idx, const int64_t* row_ids, const float* rows_dev, int64_t n) {
+    return mutate_rows_impl(idx, row_ids, rows_dev, n, hipMemcpyDeviceToDevice, false);
+}
+int mi355dr_remove_rows(mi355dr_index* idx, const int64_t* row_ids, int64_t n) {
+    return mutate_rows_impl(idx, row_ids, nullptr, n, hipMemcpyHostToDevice, true);
+}
+
 int64_t mi355dr_size(const mi355dr_index* idx) { return idx ? idx->n : -1; }
+int64_t mi355dr_live_rows(const mi355dr_index* idx) { return idx ? idx->n - idx->dead_n : -1; }
 int mi355dr_dim(const mi355dr_index* idx) { return idx ? idx->dim : -1; }
 
 int mi355dr_get_rows(mi355dr_index* idx, int64_t row0, int64_t n, float* out) {
@@ -1318,6 +1429,7 @@ int mi355dr_get_stat(mi355dr_index* idx, const char* key, int64_t* out) {
     else if (k == "maxsim_packed_built") *out = idx->s_ms_packed_built;
     else if (k == "irregular_rows") *out = idx->irr_n;
     else if (k == "loose_rows") *out = idx->irr8_n;
+    else if (k == "dead_rows") *out = idx->dead_n;
     else if (k == "screen_dtype_active") *out = use_i8(idx) ? MI355DR_SCREEN_I8 : MI355DR_SCREEN_BF16;
     else if (k == "hbm_bytes_resident")
         *out = idx->cap_rows * ((int64_t)idx->dim * 4 + (int64_t)idx->dpad * 2 + (int64_t)idx->dpad8 + 5) +

@@ -69,6 +69,39 @@ class Mi355Index:
         """Append n rows already resident on this device (fp32, row-major, contiguous)."""
         check(self._h, self._lib.mi355dr_add_rows_device(self._h, ctypes.c_void_p(int(dev_ptr)), int(n)))
 
+    # ---- update / remove in place (row ids are stable; include/mi355dr.h "update / remove in place") ----
+    @staticmethod
+    def _row_ids(row_ids) -> np.ndarray:
+        ids = np.ascontiguousarray(row_ids, dtype=np.int64)
+        if ids.ndim != 1:
+            raise ValueError("row_ids must be one-dimensional")
+        return ids
+
+    def update_rows(self, row_ids, rows) -> None:
+        """Row row_ids[j] takes rows[j]: later searches see the index an `add` of the new vectors would have built.
+        Updating a removed row revives it.  Ids out of range or repeated: NativeError (MI355DR_E_INVALID), nothing changes."""
+        ids = self._row_ids(row_ids)
+        rows = f32c(rows)
+        if rows.ndim != 2 or rows.shape != (ids.shape[0], self.dim):
+            raise ValueError(f"rows must be [{ids.shape[0]}, {self.dim}], got {rows.shape}")
+        check(self._h, self._lib.mi355dr_update_rows(self._h, ptr(ids, ctypes.c_int64), ptr(rows, ctypes.c_float), ids.shape[0]))
+
+    def update_rows_device(self, row_ids, dev_ptr: int) -> None:
+        """The same with the new rows ([len(row_ids), dim] fp32, contiguous) already on this device; ids stay on the host."""
+        ids = self._row_ids(row_ids)
+        check(self._h, self._lib.mi355dr_update_rows_device(self._h, ptr(ids, ctypes.c_int64), ctypes.c_void_p(int(dev_ptr)),
+                                                            ids.shape[0]))
+
+    def remove_rows(self, row_ids) -> None:
+        """The rows are dead: never returned again by any path; their slots (and every other row's id) stay."""
+        ids = self._row_ids(row_ids)
+        check(self._h, self._lib.mi355dr_remove_rows(self._h, ptr(ids, ctypes.c_int64), ids.shape[0]))
+
+    @property
+    def live_rows(self) -> int:
+        """len(self) minus the removed rows."""
+        return int(self._lib.mi355dr_live_rows(self._h))
+
     def get_rows(self, row0: int, n: int) -> np.ndarray:
         out = np.empty((n, self.dim), dtype=np.float32)
         check(self._h, self._lib.mi355dr_get_rows(self._h, int(row0), int(n), ptr(out, ctypes.c_float)))

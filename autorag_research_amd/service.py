@@ -155,6 +155,9 @@ class _UnitIndex:
         self.device = device
         self.single_sharded: Any | None = None      # ShardedSearcher over this rank's rows (a _World is active)
         self.multi_sharded: Any | None = None
+        # False: `single` holds the NOT NULL rows compacted (how ensure_single builds it).  True (after a refresh): one slot
+        # per table position, NULL rows are removed slots -- single_rows is the identity and every later change is in place
+        self.slot_per_position = False
 
     def ensure_single_sharded(self, world: "_World") -> Any:
         """This rank's contiguous share of the NOT NULL rows behind a ShardedSearcher (global row ids = positions in the
@@ -225,6 +228,98 @@ class _UnitIndex:
                 ix.close()
         self.single = self.multi = self.single_sharded = self.multi_sharded = None
 
+    # ---- following the table ----
+    def _forget_maps(self) -> None:
+        """The key -> position and position -> row maps the service caches on the unit: stale once the table is replaced."""
+        self.__dict__.pop("_pos_of_id", None)
+        self.__dict__.pop("_row_of_pos", None)
+
+    def _build_slots(self, emb: np.ndarray) -> None:
+        """`single` with one slot per table position: NULL rows are added as placeholders and removed at once."""
+        null = np.isnan(emb).all(axis=1)
+        self.single = Mi355Index(emb.shape[1], "cosine", self.device)
+        self._append_slots(emb, null, 0)
+        self.single_rows = np.arange(emb.shape[0])
+        self.slot_per_position = True
+
+    def _append_slots(self, emb: np.ndarray, null: np.ndarray, first: int) -> None:
+        if emb.shape[0] == 0:
+            return
+        self.single.add(np.where(null[:, None], np.float32(0), emb) if null.any() else emb)
+        if null.any():
+            self.single.remove_rows(first + np.nonzero(null)[0])
+
+    def _rebuild(self, table: ChunkTable, why: str) -> str:
+        logger.info("refresh: full rebuild of the index (%s)", why)
+        self.close()
+        self.table = table
+        self.single_rows = self.multi_rows = None
+        self.slot_per_position = False
+        self._forget_maps()
+        return "rebuild"
+
+    def refresh(self, table: ChunkTable) -> str:
+        """Follow a newer export of the same table.  With the same primary keys in the same order (new keys only at the end)
+        the live single-vector index takes the difference alone -- what the reference's `UPDATE ... SET embedding`
+        (orm/service/base_ingestion.py:199-247) and `WHERE embedding IS NOT NULL` (orm/repository/base.py:409-415) make of it:
+
+            embedding changed -> update_rows        embedding became NULL -> remove_rows
+            NULL became a vector -> update_rows (the slot is revived)     new keys at the end -> add
+
+        Row mapping: an index that was never refreshed holds the NOT NULL rows compacted (`single_rows` = their table
+        positions).  The first refresh that has to change rows switches the unit to ONE SLOT PER TABLE POSITION, NULL rows
+        being removed slots (`single_rows` = the identity): a compacted index without NULL rows already has that form; one
+        built over NULL rows is laid out anew once (the only rebuild on this path), from then on every change is in place.
+        Slots stay in table order either way, so exact distance ties break as in a unit built fresh from `table`.
+
+        A changed key order, multi-vector data and row-sharded units (one process per GPU) fall back to the full rebuild
+        (close; the next search builds from `table`).  Returns "deferred" (nothing built yet), "unchanged", "incremental",
+        "relayout" or "rebuild"."""
+        old = self.table
+        if self.single is None and self.multi is None and self.single_sharded is None and self.multi_sharded is None:
+            self.table = table
+            self.single_rows = self.multi_rows = None
+            self._forget_maps()
+            return "deferred"
+        if self.multi is not None or self.multi_sharded is not None or table.mv_offsets is not None or old.mv_offsets is not None:
+            return self._rebuild(table, "multi-vector unit: in-place replace of token rows is not implemented")
+        if self.single_sharded is not None:
+            return self._rebuild(table, "row-sharded unit: global row ids are positions in the not-null order")
+        if self.single is None:
+            return self._rebuild(table, "no single-vector index to follow")
+        n_old = len(old.ids)
+        if len(table.ids) < n_old or list(table.ids[:n_old]) != list(old.ids):
+            return self._rebuild(table, "the primary keys or their order changed")
+        emb, was = table.embedding, old.embedding
+        if emb is None or was is None or emb.shape[1] != was.shape[1]:
+            return self._rebuild(table, "the embedding column changed shape")
+        emb = np.ascontiguousarray(emb, dtype=np.float32)
+        was = np.ascontiguousarray(was, dtype=np.float32)
+        null, was_null = np.isnan(emb).all(axis=1), np.isnan(was).all(axis=1)
+        head, head_null = emb[:n_old], null[:n_old]
+        differ = (head.view(np.uint32) != was.view(np.uint32)).any(axis=1)      # (bits: NaN-safe)
+        update = ~head_null & (was_null | differ)
+        remove = head_null & ~was_null
+        self._forget_maps()
+        if not (update.any() or remove.any() or len(table.ids) > n_old):
+            self.table = table
+            return "unchanged"
+        if not self.slot_per_position and was_null.any():
+            logger.info("refresh: the index was built over NULL rows; laying it out with one slot per table position")
+            self.single.close()
+            self.table = table
+            self._build_slots(emb)
+            return "relayout"
+        self.slot_per_position = True
+        if remove.any():
+            self.single.remove_rows(np.nonzero(remove)[0])
+        if update.any():
+            self.single.update_rows(np.nonzero(update)[0], head[update])
+        self._append_slots(emb[n_old:], null[n_old:], n_old)
+        self.table = table
+        self.single_rows = np.arange(len(table.ids))
+        return "incremental"
+
 
 def _is_store(obj: Any) -> bool:
     return all(hasattr(obj, a) for a in ("get_or_create_pipeline", "get_all_queries", "completed_query_ids", "chunks"))
@@ -285,6 +380,15 @@ class Mi355RetrievalService:
                 self._world.same_everywhere(f"table {unit!r}", _table_digest(table))
             self._units[unit] = _UnitIndex(table, self._device)
         return self._units[unit]
+
+    def refresh_unit(self, unit: str, table: ChunkTable) -> str:
+        """Hand a unit a newer export of its table: the live index takes the difference alone where it can
+        (`_UnitIndex.refresh`).  A unit nothing was built for yet reads the store's table at its first search, as before."""
+        if unit not in self._units:
+            return "deferred"
+        if self._world is not None:
+            self._world.same_everywhere(f"table {unit!r}", _table_digest(table))
+        return self._units[unit].refresh(table)
 
     def get_queries(self, query_ids: list) -> list:
         """The stored query rows (None = no such query).  One process per GPU: rank 0 reads them and every rank gets the same
@@ -459,8 +563,11 @@ class Mi355RetrievalService:
             u.ensure_single()
         inv = getattr(u, "_row_of_pos", None)
         if inv is None:
-            inv = u._row_of_pos = {int(p): r for r, p in enumerate(u.single_rows)}
-            u._pos_of_id = getattr(u, "_pos_of_id", None) or {pk: i for i, pk in enumerate(u.table.ids)}
+            # (a refreshed unit keeps a slot for a NULL embedding -- a removed row that still holds a vector: not a stored one)
+            stored = ~np.isnan(u.table.embedding).all(axis=1)
+            inv = u._row_of_pos = {int(p): r for r, p in enumerate(u.single_rows) if stored[p]}
+        if getattr(u, "_pos_of_id", None) is None:
+            u._pos_of_id = {pk: i for i, pk in enumerate(u.table.ids)}
         rows = [inv.get(u._pos_of_id.get(pk, -1), -1) for pk in doc_ids]
         return None if any(r < 0 for r in rows) else np.asarray(rows, dtype=np.int64)
 

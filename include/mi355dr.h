@@ -84,14 +84,38 @@ int mi355dr_reserve(mi355dr_index* idx, int64_t n_rows);
 int mi355dr_add_rows(mi355dr_index* idx, const float* rows, int64_t n);
 /* same, rows already resident on this index's device (e.g. an embedding model's output tensor) */
 int mi355dr_add_rows_device(mi355dr_index* idx, const float* rows_dev, int64_t n);
+/* stored slots, live or removed (row ids are stable: nothing is ever renumbered) */
 int64_t mi355dr_size(const mi355dr_index* idx);
 int mi355dr_dim(const mi355dr_index* idx);
+
+/* ---- update / remove in place ----
+ * The table this index mirrors is not append-only: re-embedding a chunk is a second UPDATE of the same row
+ * (orm/service/base_ingestion.py:199-247), and a row whose embedding became NULL -- or a deleted chunk -- leaves
+ * `WHERE embedding IS NOT NULL` at once (orm/repository/base.py:409-415).
+ *   update: row row_ids[j] takes rows[j]; every later search sees the index an add_rows of the new vector would have
+ *           built (norm bits, both shadows, the irregular / loose classes).  Updating a removed row revives it.
+ *   remove: the row is dead -- never returned by any path, metric or k.  Its slot stays (mi355dr_size counts it,
+ *           mi355dr_get_rows returns its last vector); when k exceeds the live rows the tail is NaN / -1.  A dead row is
+ *           not an irregular row (those are live and are returned last with NaN).  Removing a dead row is a no-op.
+ * row_ids: HOST [n], each in [0, size) and listed once per call -- otherwise MI355DR_E_INVALID and nothing changes.
+ * Each call first completes whatever search is in flight on the handle and is complete on return.  Cost: O(n) rows
+ * rewritten + the int8 groups (32 rows) they fall into rebuilt + one 5-byte-per-row pass over the index that recounts
+ * the side lists; the screens' two corpus-wide maxima (largest bf16 residual, largest norm) never shrink.
+ * A search takes its first threshold from the first rows of the index (16 k; 64 k at 33 <= k <= 128): when fewer than k of
+ * them are live -- the oldest rows all removed -- searches stay exact but fall back to slower paths; rebuild such an index.
+ * mi355dr_gqr_refine addresses rows directly and does not know removed rows: do not put them in a pool. */
+int mi355dr_update_rows(mi355dr_index* idx, const int64_t* row_ids, const float* rows, int64_t n); /* rows: host [n, dim] */
+/* the same with the new rows on this index's device ([n, dim] fp32); row_ids stay on the host */
+int mi355dr_update_rows_device(mi355dr_index* idx, const int64_t* row_ids, const float* rows_dev, int64_t n);
+int mi355dr_remove_rows(mi355dr_index* idx, const int64_t* row_ids, int64_t n);
+/* mi355dr_size minus the removed rows (stat "dead_rows") */
+int64_t mi355dr_live_rows(const mi355dr_index* idx);
 /* copy stored rows back (testing / cpu baseline): out host [n, dim] */
 int mi355dr_get_rows(mi355dr_index* idx, int64_t row0, int64_t n, float* out);
 
 /* ---- search (single-vector) ----
  * queries: [B, dim] fp32.  out_dist: [B, k] double, out_rows: [B, k] int64; slots beyond the
- * number of stored rows hold NaN / -1.  row_offset is added to every returned row (shards). */
+ * number of stored (live) rows hold NaN / -1.  row_offset is added to every returned row (shards). */
 int mi355dr_search(mi355dr_index* idx, const float* queries, int B, int k, double* out_dist, int64_t* out_rows);
 /* device-resident queries and outputs; stream = hipStream_t (NULL: the index's own stream).
  * Returns after the work is complete on that stream (it checks the device-side status word). */
