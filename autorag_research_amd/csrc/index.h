@@ -208,7 +208,58 @@ struct MultiVecView {
     int64_t n_docs;
 };
 bool multivec_view(const mi355dr_index* idx, MultiVecView* out);  // false: no store yet
-int multivec_col_perm(int j);  // position j of a stored token row holds original column multivec_col_perm(j)
+
+// Column order inside every group of 8 dims, for BOTH stored token rows and the staged query rows:
+// position j holds original column kPerm[j] = {0,4,2,6,1,5,3,7}[j].  A lane of the lower half (k-slot 0 of the
+// 32x32x2 MFMA) reads positions 0..3 = columns (0,4,2,6), a lane of the upper half positions 4..7 = (1,5,3,7),
+// so issuing the MFMAs on components x, z, y, w walks k = (0|1), (2|3), (4|5), (6|7): ascending, no lane swaps.
+__host__ __device__ inline int ms_perm(int j) {
+    constexpr int P[8] = {0, 4, 2, 6, 1, 5, 3, 7};
+    return (j & ~7) | P[j & 7];
+}
+
+// one query vector (d values) -> its row of a query image: the store's column order, zero-padded to dpad
+template <class T>
+inline void multivec_pack_query_row(const T* src, int d, int dpad, T* dst) {
+    for (int c = 0; c < dpad; ++c) {
+        const int oc = ms_perm(c);
+        dst[c] = oc < d ? src[oc] : T(0);
+    }
+}
+
+// Owner of one device allocation (Pinned: of one pinned host allocation), released on destruction.  Kernels and copies take the
+// raw pointer, `p`.  grow() gets the new block BEFORE it lets go of the old one: when it fails, the buffer is
+// what it was -- still valid, still its old size.  The old contents are not carried over.
+template <class T, bool Pinned = false>
+struct DevBuf {
+    T* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        bytes = 0;
+    }
+    hipError_t grow(size_t want) {  // at least `want` bytes
+        if (want <= bytes) return hipSuccess;
+        void* q = nullptr;
+        const hipError_t e = Pinned ? hipHostMalloc(&q, want) : hipMalloc(&q, want);
+        if (e != hipSuccess) return e;
+        release();
+        p = (T*)q;
+        bytes = want;
+        return hipSuccess;
+    }
+    void swap(DevBuf& o) {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+    }
+};
+template <class T>
+using HostBuf = DevBuf<T, true>;
 
 #define HIPCHECK(idx, expr)                                                                              \
     do {                                                                                                 \

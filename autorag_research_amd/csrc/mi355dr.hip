@@ -1027,12 +1027,6 @@ int mi355dr_add_rows_device(mi355dr_index* idx, const float* rows_dev, int64_t n
 
 // ---- update / remove in place (DESIGN.md "Mutable index") ---------------------------------------------------------------
 namespace {
-struct DevBuf {  // scratch of one call, released on every way out
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
 constexpr int64_t kMutSlice = (int64_t)1 << 16;  // rows per staging upload and per-row launch
 
 // rows == nullptr: remove.  kind: where `rows` lives.  row_ids: host.
@@ -1058,13 +1052,13 @@ int mutate_rows_impl(mi355dr_index* idx, const int64_t* row_ids, const float* ro
     CHECK(drain_pending(idx));  // (a search in flight sees the index as it was)
     hipStream_t s = idx->stream;
     const int absolute = idx->metric == MI355DR_METRIC_IP ? 1 : 0;
-    DevBuf ids_dev, groups_dev, stage;
-    HIPCHECK(idx, hipMalloc(&ids_dev.p, (size_t)n * sizeof(int64_t)));
-    HIPCHECK(idx, hipMalloc(&groups_dev.p, groups.size() * sizeof(int64_t)));
+    DevBuf<void> ids_dev, groups_dev, stage;  // scratch of one call, released on every way out
+    HIPCHECK(idx, ids_dev.grow((size_t)n * sizeof(int64_t)));
+    HIPCHECK(idx, groups_dev.grow(groups.size() * sizeof(int64_t)));
     HIPCHECK(idx, hipMemcpyAsync(ids_dev.p, row_ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIPCHECK(idx, hipMemcpyAsync(groups_dev.p, groups.data(), groups.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
     if (!remove && kind == hipMemcpyHostToDevice)
-        HIPCHECK(idx, hipMalloc(&stage.p, (size_t)std::min(n, kMutSlice) * idx->dim * sizeof(float)));
+        HIPCHECK(idx, stage.grow((size_t)std::min(n, kMutSlice) * idx->dim * sizeof(float)));
     for (int64_t r0 = 0; r0 < n; r0 += kMutSlice) {
         const int64_t m = std::min(kMutSlice, n - r0);
         const int64_t* ids = (const int64_t*)ids_dev.p + r0;
@@ -1591,26 +1585,22 @@ int mi355dr_debug_rescore(mi355dr_index* idx, const float* queries, int B, const
     hipStream_t s = idx->stream;
     HIPCHECK(idx, hipMemcpyAsync(idx->qdev, queries, (size_t)B * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
     CHECK(launch_prep(idx, s, B, (int)round_up(B, screen_tile(B)), idx->metric));
-    int32_t* pq = nullptr;
-    int64_t* pr = nullptr;
-    float* od = nullptr;
-    double* ods = nullptr;
-    HIPCHECK(idx, hipMalloc(&pq, n_pairs * sizeof(int32_t)));
-    HIPCHECK(idx, hipMalloc(&pr, n_pairs * sizeof(int64_t)));
-    HIPCHECK(idx, hipMalloc(&od, n_pairs * sizeof(float)));
-    HIPCHECK(idx, hipMalloc(&ods, n_pairs * sizeof(double)));
-    HIPCHECK(idx, hipMemcpyAsync(pq, pair_q, n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHECK(idx, hipMemcpyAsync(pr, pair_row, n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    DevBuf<int32_t> pq;
+    DevBuf<int64_t> pr;
+    DevBuf<float> od;
+    DevBuf<double> ods;
+    HIPCHECK(idx, pq.grow(n_pairs * sizeof(int32_t)));
+    HIPCHECK(idx, pr.grow(n_pairs * sizeof(int64_t)));
+    HIPCHECK(idx, od.grow(n_pairs * sizeof(float)));
+    HIPCHECK(idx, ods.grow(n_pairs * sizeof(double)));
+    HIPCHECK(idx, hipMemcpyAsync(pq.p, pair_q, n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHECK(idx, hipMemcpyAsync(pr.p, pair_row, n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_rescore_pairs, dim3((unsigned)((n_pairs + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows,
-                       idx->nrm2, idx->qdev, idx->st.qn, pq, pr, n_pairs, idx->dim, idx->metric, od, ods);
+                       idx->nrm2, idx->qdev, idx->st.qn, pq.p, pr.p, n_pairs, idx->dim, idx->metric, od.p, ods.p);
     HIPCHECK(idx, hipGetLastError());
-    HIPCHECK(idx, hipMemcpyAsync(out_dot, od, n_pairs * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIPCHECK(idx, hipMemcpyAsync(out_dist, ods, n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(out_dot, od.p, n_pairs * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(out_dist, ods.p, n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipStreamSynchronize(s));
-    (void)hipFree(pq);
-    (void)hipFree(pr);
-    (void)hipFree(od);
-    (void)hipFree(ods);
     return MI355DR_OK;
 }
 

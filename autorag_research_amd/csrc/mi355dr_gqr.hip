@@ -13,13 +13,6 @@ using namespace mi355;
 
 namespace {
 
-struct DevBuf {  // per-call scratch: pools are a few KB per query
-    void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 int check_params(mi355dr_index* idx, int B, int P, int n_steps, double lr, double temperature, double alpha) {
     if (B < 0 || P < 0) return fail(idx, MI355DR_E_INVALID, "gqr: negative sizes");
     if (P > kGqrPoolMax) return fail(idx, MI355DR_E_UNSUPPORTED, "gqr: more than 2048 candidates per query");
@@ -74,12 +67,12 @@ int mi355dr_gqr_refine(mi355dr_index* idx, const double* queries, int B, const i
     if (lds > 160 * 1024) return fail(idx, MI355DR_E_UNSUPPORTED, "gqr: dim + pool too large for one workgroup's LDS");
     HIPCHECK(idx, hipSetDevice(idx->device));
     hipStream_t s = idx->stream;
-    DevBuf q, c, cp, o;
+    DevBuf<void> q, c, cp, o;  // per-call scratch: pools are a few KB per query
     const size_t nq = (size_t)B * d * sizeof(double), nc = (size_t)B * P * sizeof(int32_t), np = (size_t)B * P * sizeof(double);
-    HIPCHECK(idx, hipMalloc(&q.p, nq));
-    HIPCHECK(idx, hipMalloc(&c.p, nc));
-    HIPCHECK(idx, hipMalloc(&cp.p, np));
-    HIPCHECK(idx, hipMalloc(&o.p, np));
+    HIPCHECK(idx, q.grow(nq));
+    HIPCHECK(idx, c.grow(nc));
+    HIPCHECK(idx, cp.grow(np));
+    HIPCHECK(idx, o.grow(np));
     HIPCHECK(idx, hipMemcpyAsync(q.p, queries, nq, hipMemcpyHostToDevice, s));
     HIPCHECK(idx, hipMemcpyAsync(c.p, local.data(), nc, hipMemcpyHostToDevice, s));
     HIPCHECK(idx, hipMemcpyAsync(cp.p, comp_dist, np, hipMemcpyHostToDevice, s));
@@ -112,12 +105,12 @@ int mi355dr_gqr_refine_scores(mi355dr_index* idx, const double* primary_scores, 
         if (counts[b] < 0 || counts[b] > P) return fail(idx, MI355DR_E_INVALID, "gqr: counts[b] must be in [0, P]");
     HIPCHECK(idx, hipSetDevice(idx->device));
     hipStream_t s = idx->stream;
-    DevBuf z, n, cp, o;
+    DevBuf<void> z, n, cp, o;
     const size_t np = (size_t)B * P * sizeof(double);
-    HIPCHECK(idx, hipMalloc(&z.p, np));
-    HIPCHECK(idx, hipMalloc(&n.p, (size_t)B * sizeof(int32_t)));
-    HIPCHECK(idx, hipMalloc(&cp.p, np));
-    HIPCHECK(idx, hipMalloc(&o.p, np));
+    HIPCHECK(idx, z.grow(np));
+    HIPCHECK(idx, n.grow((size_t)B * sizeof(int32_t)));
+    HIPCHECK(idx, cp.grow(np));
+    HIPCHECK(idx, o.grow(np));
     HIPCHECK(idx, hipMemcpyAsync(z.p, primary_scores, np, hipMemcpyHostToDevice, s));
     HIPCHECK(idx, hipMemcpyAsync(n.p, counts, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIPCHECK(idx, hipMemcpyAsync(cp.p, comp_dist, np, hipMemcpyHostToDevice, s));
@@ -163,22 +156,18 @@ int mi355dr_gqr_refine_maxsim(mi355dr_index* idx, const double* qtok, const int3
     if (lds > 160 * 1024) return fail(idx, MI355DR_E_UNSUPPORTED, "gqr: query matrix + pool too large for one workgroup's LDS");
     // the query matrix in the store's column order, zero-padded to dpad
     const int64_t nrow = q_offsets[B];
-    std::vector<double> qimg((size_t)nrow * dp, 0.0);
-    for (int64_t r = 0; r < nrow; ++r)
-        for (int c = 0; c < dp; ++c) {
-            const int oc = multivec_col_perm(c);
-            if (oc < d) qimg[(size_t)r * dp + c] = qtok[r * d + oc];
-        }
+    std::vector<double> qimg((size_t)nrow * dp);
+    for (int64_t r = 0; r < nrow; ++r) multivec_pack_query_row(qtok + r * d, d, dp, &qimg[(size_t)r * dp]);
     HIPCHECK(idx, hipSetDevice(idx->device));
     hipStream_t s = idx->stream;
-    DevBuf q, qo, c, cp, o, ws;
+    DevBuf<void> q, qo, c, cp, o, ws;
     const size_t np = (size_t)B * P * sizeof(double);
-    HIPCHECK(idx, hipMalloc(&q.p, qimg.size() * sizeof(double)));
-    HIPCHECK(idx, hipMalloc(&qo.p, (size_t)(B + 1) * sizeof(int32_t)));
-    HIPCHECK(idx, hipMalloc(&c.p, local.size() * sizeof(int32_t)));
-    HIPCHECK(idx, hipMalloc(&cp.p, np));
-    HIPCHECK(idx, hipMalloc(&o.p, np));
-    HIPCHECK(idx, hipMalloc(&ws.p, (size_t)B * P * nq_pad * sizeof(int32_t)));
+    HIPCHECK(idx, q.grow(qimg.size() * sizeof(double)));
+    HIPCHECK(idx, qo.grow((size_t)(B + 1) * sizeof(int32_t)));
+    HIPCHECK(idx, c.grow(local.size() * sizeof(int32_t)));
+    HIPCHECK(idx, cp.grow(np));
+    HIPCHECK(idx, o.grow(np));
+    HIPCHECK(idx, ws.grow((size_t)B * P * nq_pad * sizeof(int32_t)));
     HIPCHECK(idx, hipMemcpyAsync(q.p, qimg.data(), qimg.size() * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHECK(idx, hipMemcpyAsync(qo.p, q_offsets, (size_t)(B + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIPCHECK(idx, hipMemcpyAsync(c.p, local.data(), local.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));

@@ -86,40 +86,74 @@ def test_gpu_reranker_at_the_reference_models_shape(native_built, oracle):
     assert np.allclose(got, want, rtol=0, atol=2e-6) and got[3] == 0.0
 
 
-@pytest.mark.gpu
-def test_device_built_store_equals_host_built_store(native_built):
-    """mi355dr_add_multivec_device (kernel-built padded store, bf16 fragments, bound quantities) vs mi355dr_add_multivec:
-    the screened MaxSim search and the exact subset scoring return identical bits, appended in two batches."""
+_MS_STATS = ("maxsim_candidates", "maxsim_screened", "maxsim_fallbacks")
+
+
+def _host_and_device_built_stores_agree(d, lens, cut, rng):
+    """Two indexes over the same documents, appended in two batches (docs [0, cut) and the rest): `h` from host memory,
+    `g` from device memory.  The screened and the exact MaxSim search and the exact subset scoring return identical bits,
+    and the search statistics agree: the candidate count follows the screen bound, so it moves when one of the store's
+    bound maxima differs in its last bit."""
     import torch
 
     import autorag_research_amd as pkg
 
-    rng = np.random.default_rng(5)
-    d = 128
-    lens = rng.integers(0, 90, size=300)
-    lens[7] = 1030  # a ColPali-sized page
+    n = len(lens)
     tok = rng.standard_normal((int(lens.sum()), d)).astype(np.float32)
     tok /= np.linalg.norm(tok, axis=1, keepdims=True)
     off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     qt = rng.standard_normal((3 * 24, d)).astype(np.float32)
     qoff = np.array([0, 24, 48, 72], dtype=np.int32)
     h, g = pkg.Mi355Index(d), pkg.Mi355Index(d)
-    cut = 120
     h.add_multivec(tok[: off[cut]], off[: cut + 1])
     h.add_multivec(tok[off[cut]:], off[cut:] - off[cut])
     t = torch.from_numpy(tok).cuda()
     torch.cuda.synchronize()
     g.add_multivec_device(t.data_ptr(), off[: cut + 1])
     g.add_multivec_device(t[off[cut]:].data_ptr(), off[cut:] - off[cut])
-    assert h.n_docs() == g.n_docs() == 300
+    assert h.n_docs() == g.n_docs() == n
     for screen in (1, 0):
         h.set_option("maxsim_screen", screen)
         g.set_option("maxsim_screen", screen)
-        hd, hr = h.search_maxsim(qt, qoff, 10)
-        gd, gr = g.search_maxsim(qt, qoff, 10)
-        assert np.array_equal(hr, gr) and np.array_equal(hd.view(np.uint32), gd.view(np.uint32))
-    ids = np.tile(np.arange(300, dtype=np.int64), (3, 1))
+        for k in (10, 100):  # the pass-wide selection path and the per-query one
+            hd, hr = h.search_maxsim(qt, qoff, k)
+            gd, gr = g.search_maxsim(qt, qoff, k)
+            assert np.array_equal(hr, gr) and np.array_equal(hd.view(np.uint32), gd.view(np.uint32))
+            hs, gs = {s: h.stat(s) for s in _MS_STATS}, {s: g.stat(s) for s in _MS_STATS}
+            assert hs == gs
+    assert h.stat("maxsim_screened") > 0
+    m = min(n, 300)
+    ids = np.tile(np.arange(m, dtype=np.int64), (3, 1))
     a, b = h.maxsim_subset(qt, qoff, ids), g.maxsim_subset(qt, qoff, ids)
     assert np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a[~np.isnan(a)], b[~np.isnan(b)])
     h.close()
     g.close()
+
+
+@pytest.mark.gpu
+def test_device_built_store_equals_host_built_store(native_built):
+    """mi355dr_add_multivec_device (kernel-built padded store, bf16 fragments, bound quantities) vs mi355dr_add_multivec:
+    the screened MaxSim search and the exact subset scoring return identical bits, appended in two batches."""
+    rng = np.random.default_rng(5)
+    lens = rng.integers(0, 90, size=300)
+    lens[7] = 1030  # a ColPali-sized page
+    _host_and_device_built_stores_agree(128, lens, 120, rng)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["dim_not_multiple_of_16", "host_add_of_several_slices"])
+def test_device_built_store_equals_host_built_store_shapes(native_built, case):
+    """The same comparison (a) at a dim that is a multiple of neither 16 nor 8: both images end in zero padding; (b) with a
+    host add whose vectors exceed the staging slice of the host entry point (32 MiB of fp32 vectors: 65536 tokens at
+    d = 128), so that it is built in several slices -- here 1500 text-sized documents, ~159 000 tokens = 78 MiB in the
+    first batch alone -- while the device entry point builds each batch in one launch."""
+    rng = np.random.default_rng(11)
+    if case == "dim_not_multiple_of_16":
+        lens = rng.integers(0, 90, size=300)
+        lens[11] = 1030
+        _host_and_device_built_stores_agree(44, lens, 120, rng)
+    else:
+        lens = rng.integers(32, 181, size=1800)
+        lens[1700] = 1030
+        assert int(lens[:1500].sum()) * 128 * 4 > 2 * (32 << 20)
+        _host_and_device_built_stores_agree(128, lens, 1500, rng)
