@@ -15,22 +15,87 @@
 #include "mi355dr.h"
 
 namespace mi355 {
+// Owner of one device allocation (Pinned: of one pinned host allocation), released on destruction.  Kernels and copies take the
+// raw pointer, `p` (or the buffer itself: it converts).  grow() gets the new block BEFORE it lets go of the old one: when it
+// fails, the buffer is what it was -- still valid, still its old size.  The old contents are not carried over.
+template <class T, bool Pinned = false>
+struct DevBuf {
+    T* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        bytes = 0;
+    }
+    hipError_t grow(size_t want) {  // at least `want` bytes
+        if (want <= bytes) return hipSuccess;
+        void* q = nullptr;
+        const hipError_t e = Pinned ? hipHostMalloc(&q, want) : hipMalloc(&q, want);
+        if (e != hipSuccess) return e;
+        release();
+        p = (T*)q;
+        bytes = want;
+        return hipSuccess;
+    }
+    void swap(DevBuf& o) {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+    }
+    operator T*() const { return p; }
+};
+template <class T>
+using HostBuf = DevBuf<T, true>;
+
+// Owner of one HIP event, created on first use
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+
 struct EventPair {
     hipEvent_t a, b;
     int big;  // 1: the launch went to k_screen256 (the dominant kernel), 0: k_screen
+};
+// the timing pairs of option "profile": pooled (take_events) or behind a launch (drain_events), owned either way
+struct EventPairs {
+    std::vector<EventPair> v;
+    ~EventPairs() {
+        for (auto& p : v) {
+            (void)hipEventDestroy(p.a);
+            (void)hipEventDestroy(p.b);
+        }
+    }
 };
 struct MultiVecStore;  // mi355dr_maxsim.hip
 // one block between enqueue_block() and complete_block() (mi355dr.hip)
 struct Pending {
     bool active = false;
-    hipEvent_t done = nullptr;
-    int* status_host = nullptr;   // pinned [kQBlockMax + 1]: the block's per-query status words + their OR
+    Event done;
+    HostBuf<int> status_host;     // pinned [kQBlockMax + 1]: the block's per-query status words + their OR
     hipStream_t stream = nullptr;
     const float* q_dev = nullptr; // the caller's queries (valid until the wait: a fix-up gathers from them)
     int B = 0, k = 0, level = 0;
     double* out_dist = nullptr;
     int64_t* out_rows = nullptr;
     bool used_screen = false, was_i8 = false;
+};
+// buffers of the sub-block a search at retry level L re-screens (complete_block grows all four before it uses one)
+struct RetryBufs {
+    DevBuf<float> q;       // [kQBlockMax, dim] queries being re-screened / re-scanned
+    DevBuf<double> dist;   // [kQBlockMax, kKMax]
+    DevBuf<int64_t> rows;
+    DevBuf<int> map;       // [kQBlockMax] position of each sub-block query in its block
 };
 constexpr int kPendingRing = 4;
 }  // namespace mi355
@@ -40,44 +105,50 @@ struct mi355dr_index {
     hipStream_t stream = nullptr;
     std::mutex mu;
     std::string err;
+    mi355dr_index() = default;
+    // every member below that holds device memory, pinned memory or an event releases it itself; the stream goes first
+    ~mi355dr_index() {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 
     // corpus (single-vector)
     int64_t n = 0, cap_rows = 0;
-    float* rows = nullptr;
-    uint16_t* shadow = nullptr;
-    float* nrm2 = nullptr;
-    int32_t* irr_rows = nullptr;
-    int* irr_count = nullptr;
+    mi355::DevBuf<float> rows;
+    mi355::DevBuf<uint16_t> shadow;
+    mi355::DevBuf<float> nrm2;
+    mi355::DevBuf<int32_t> irr_rows;
+    mi355::DevBuf<int> irr_count;
     int irr_n = 0;
-    unsigned* n2max_dev = nullptr;  // largest regular |c|^2 (float bits)
+    mi355::DevBuf<unsigned> n2max_dev;  // largest regular |c|^2 (float bits)
     float cmax = 0.0f;              // its square root, inflated: inner-product thresholds
-    unsigned* bf16_res2_dev = nullptr;  // largest squared residual norm |c_hat - bf16(c_hat)|^2 over the rows (float bits)
+    mi355::DevBuf<unsigned> bf16_res2_dev;  // largest squared residual norm |c_hat - bf16(c_hat)|^2 over the rows (float bits)
     float bf16_ec = 0.00390625f;        // its square root, inflated: the corpus half of the bf16 screen bound
     // int8 screen: second shadow, one step for the whole corpus; rows it cannot hold are flagged and listed
     int dpad8 = 0;
-    int8_t* shadow8 = nullptr;     // [cap_rows, dpad8]
-    uint8_t* flag8 = nullptr;      // [cap_rows]
-    mi355::I8Group* grp8 = nullptr;  // [cap_rows / 32] int8 step + residual norm per group of 32 rows
-    int32_t* irr8_rows = nullptr;  // [kIrrCap] irregular + loose rows
-    int* irr8_count = nullptr;
+    mi355::DevBuf<int8_t> shadow8;     // [cap_rows, dpad8]
+    mi355::DevBuf<uint8_t> flag8;      // [cap_rows]
+    mi355::DevBuf<mi355::I8Group> grp8;  // [cap_rows / 32] int8 step + residual norm per group of 32 rows
+    mi355::DevBuf<int32_t> irr8_rows;  // [kIrrCap] irregular + loose rows
+    mi355::DevBuf<int> irr8_count;
     int irr8_n = 0;
     // removed rows (mi355dr_remove_rows): slots that stay, marked in nrm2 (dev_common.h kDeadNrm2) and in neither list
-    int* dead_count = nullptr;
+    mi355::DevBuf<int> dead_count;
     int64_t dead_n = 0;
 
     // per-search state (sized for one block of kQBlockMax queries)
     bool qstate_ready = false;
-    mi355::QueryState st{};
-    float* qdev = nullptr;       // [kQBlockMax, dim]
-    int32_t* cand_row = nullptr; // [kQBlockMax, cap]
-    float* cand_val = nullptr;
-    int* qlist_dev = nullptr;    // [kQBlockMax]
-    int* status_or_dev = nullptr;
-    int* status_host = nullptr;  // pinned [kQBlockMax + 1]
-    double* out_dist_dev = nullptr;  // [kQBlockMax, kKMax]
-    int64_t* out_rows_dev = nullptr;
-    unsigned long long* stat_dev = nullptr;  // [2*kQBlockMax]: per query (candidates, re-scored)
-    int* prune_skip = nullptr;   // [2 + 2*kQBlockMax] hand-over lists of k_prune (PruneArgs::skip_list)
+    mi355::QueryState st{};      // what the kernels take by value: views of st_mem, filled by ensure_qstate
+    mi355::DevBuf<void> st_mem[sizeof(mi355::QueryState) / sizeof(void*)];  // one owner per pointer of st, in its order
+    mi355::DevBuf<float> qdev;       // [kQBlockMax, dim]
+    mi355::DevBuf<int32_t> cand_row; // [kQBlockMax, cap]
+    mi355::DevBuf<float> cand_val;
+    mi355::DevBuf<int> qlist_dev;    // [2 * kQBlockMax] second half: overflow re-runs of the exact scan
+    int* status_or_dev = nullptr;    // = st.status + kQBlockMax
+    mi355::HostBuf<int> status_host;  // pinned [kQBlockMax + 1]
+    mi355::DevBuf<double> out_dist_dev;  // [kQBlockMax, kKMax]
+    mi355::DevBuf<int64_t> out_rows_dev;
+    mi355::DevBuf<unsigned long long> stat_dev;  // [2*kQBlockMax]: per query (candidates, re-scored)
+    mi355::DevBuf<int> prune_skip;   // [2 + 2*kQBlockMax] hand-over lists of k_prune (PruneArgs::skip_list)
     int prune_parity = 0;
 
     // options
@@ -88,11 +159,7 @@ struct mi355dr_index {
                                            // the wait doubles (16 ... 4096 blocks) every time that try overflows again
     int i8_demoted_k = INT_MAX;  // AUTO saw the int8 bound overflow on this corpus' score distribution at this k: bf16 from there up
     double i8_min_budget = 0.25;  // AUTO keeps the int8 screen while growth_budget(k, int8) stays above this (k <= 133)
-    // buffers of the sub-block a search at retry level L re-screens (one set per level: the nested call owns the next)
-    float* retry_q[3] = {nullptr, nullptr, nullptr};      // [kQBlockMax, dim] queries being re-screened / re-scanned
-    double* retry_dist[3] = {nullptr, nullptr, nullptr};  // [kQBlockMax, kKMax]
-    int64_t* retry_rows[3] = {nullptr, nullptr, nullptr};
-    int* retry_map[3] = {nullptr, nullptr, nullptr};      // [kQBlockMax] position of each sub-block query in its block
+    mi355::RetryBufs retry[3];  // one set per level: the nested call owns the next
     // blocks in flight: sequence numbers [seq_done, seq_next) live in pend[seq % kPendingRing]; sub_pend[level]: the
     // synchronous blocks of the fix-up levels
     mi355::Pending pend[mi355::kPendingRing];
@@ -155,13 +222,13 @@ struct mi355dr_index {
 
     // stats
     int64_t s_screen_launches = 0, s_screen_ns = 0, s_screen_rows = 0, s_fallback_queries = 0, s_chunks = 0,
-            s_passes = 0, s_candidates = 0, s_rescored = 0, s_starters = 0;
+            s_passes = 0, s_starters = 0;
     int64_t s_big_launches = 0, s_big_ns = 0, s_big_rows = 0;  // the k_screen256 share of the three above
     int screen_rq_split_tests = 1;  // k_screen_rq: a block test's maxima ride the MFMAs of the other row half (0: in one piece; d = 768 only, A/B; option "screen_rq_split_tests")
     int64_t debug_park = 0;     // diagnostic (option "debug_park_thresholds" = rows): k_screen_rq launches of at least that many rows run with every threshold at +inf -- what such a launch costs without hits; results are wrong while it is set
-    float* park_thr = nullptr;
+    mi355::DevBuf<float> park_thr;  // [kQBlockMax] +inf
     int screen_drift = 3;   // k_screen_rq: tiles a workgroup may run ahead of its slowest sibling (0 = no limiter; option "screen_drift")
-    int* rq_progress = nullptr;  // [kRqProgressWords] the limiter's progress words
+    mi355::DevBuf<int> rq_progress;  // [kRqProgressWords] the limiter's progress words
     int rq_epoch = 0;            // launch stamp of the last k_screen_rq launch (1 ... 4095)
     int64_t s_rq_launches = 0;  // of them: k_screen_rq launches (stat "screen_rq_launches")
     int64_t s_retry_queries = 0;  // queries whose candidate list overflowed and that were re-screened with the bf16 bound
@@ -172,9 +239,9 @@ struct mi355dr_index {
     int64_t s_ms_packed_blocks = 0;    // ... and the 32-token blocks of that copy (0: none built)
     int64_t s_ms_packed_built = 0;     // blocks k_ms_pack8 has written since the index was created (a store that grows is packed from its new granules on)
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
-    hipEvent_t ms_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<mi355::EventPair> ev_pool, ev_pending;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
+    mi355::Event ms_ev[4];
+    mi355::EventPairs ev_pool, ev_pending;
+    mi355::Event t0, t1;
 
     // RCCL communicator of a row-sharded index (mi355dr_comm.hip)
     void* comm = nullptr;
@@ -226,40 +293,6 @@ inline void multivec_pack_query_row(const T* src, int d, int dpad, T* dst) {
         dst[c] = oc < d ? src[oc] : T(0);
     }
 }
-
-// Owner of one device allocation (Pinned: of one pinned host allocation), released on destruction.  Kernels and copies take the
-// raw pointer, `p`.  grow() gets the new block BEFORE it lets go of the old one: when it fails, the buffer is
-// what it was -- still valid, still its old size.  The old contents are not carried over.
-template <class T, bool Pinned = false>
-struct DevBuf {
-    T* p = nullptr;
-    size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-        bytes = 0;
-    }
-    hipError_t grow(size_t want) {  // at least `want` bytes
-        if (want <= bytes) return hipSuccess;
-        void* q = nullptr;
-        const hipError_t e = Pinned ? hipHostMalloc(&q, want) : hipMalloc(&q, want);
-        if (e != hipSuccess) return e;
-        release();
-        p = (T*)q;
-        bytes = want;
-        return hipSuccess;
-    }
-    void swap(DevBuf& o) {
-        std::swap(p, o.p);
-        std::swap(bytes, o.bytes);
-    }
-};
-template <class T>
-using HostBuf = DevBuf<T, true>;
 
 #define HIPCHECK(idx, expr)                                                                              \
     do {                                                                                                 \

@@ -15,6 +15,7 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "k_select.h"
 #include "k_prune_wide.h"
 #include "k_update.h"
+#include "k_block.h"
 
 using namespace mi355;
 
@@ -41,55 +42,41 @@ int ensure_capacity(mi355dr_index* idx, int64_t want_rows) {
     if (want_rows <= idx->cap_rows) return MI355DR_OK;
     int64_t new_cap = std::max<int64_t>(want_rows, idx->cap_rows + idx->cap_rows / 2);
     new_cap = round_up(std::max<int64_t>(new_cap, kT2), kT2);  // whole 256-row screen tiles
-    float* rows = nullptr;
-    uint16_t* shadow = nullptr;
-    float* nrm2 = nullptr;
-    int8_t* shadow8 = nullptr;
-    uint8_t* flag8 = nullptr;
-    I8Group* grp8 = nullptr;
-    {   // all six or none: a failed allocation must not leak the ones before it
-        hipError_t e = hipMalloc(&rows, (size_t)new_cap * idx->dim * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&shadow, (size_t)new_cap * idx->dpad * sizeof(uint16_t));
-        if (e == hipSuccess) e = hipMalloc(&nrm2, (size_t)new_cap * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&shadow8, (size_t)new_cap * idx->dpad8);
-        if (e == hipSuccess) e = hipMalloc(&flag8, (size_t)new_cap);
-        if (e == hipSuccess) e = hipMalloc(&grp8, (size_t)(new_cap / kI8GroupRows) * sizeof(I8Group));
-        if (e != hipSuccess) {
-            for (void* p : {(void*)rows, (void*)shadow, (void*)nrm2, (void*)shadow8, (void*)flag8, (void*)grp8})
-                if (p) (void)hipFree(p);
-            HIPCHECK(idx, e);
-        }
-    }
-    HIPCHECK(idx, hipMemsetAsync(shadow, 0, (size_t)new_cap * idx->dpad * sizeof(uint16_t), idx->stream));
-    HIPCHECK(idx, hipMemsetAsync(shadow8, 0, (size_t)new_cap * idx->dpad8, idx->stream));
-    HIPCHECK(idx, hipMemsetAsync(flag8, 0, (size_t)new_cap, idx->stream));
-    HIPCHECK(idx, hipMemsetAsync(grp8, 0, (size_t)(new_cap / kI8GroupRows) * sizeof(I8Group), idx->stream));
+    // the new blocks live in local owners until the swap: a failure on the way leaves the index as it was and leaks nothing
+    DevBuf<float> rows, nrm2;
+    DevBuf<uint16_t> shadow;
+    DevBuf<int8_t> shadow8;
+    DevBuf<uint8_t> flag8;
+    DevBuf<I8Group> grp8;
+    const size_t row_b = (size_t)idx->dim * sizeof(float), sh_b = (size_t)idx->dpad * sizeof(uint16_t), sh8_b = (size_t)idx->dpad8;
+    const size_t grp_b = (size_t)(new_cap / kI8GroupRows) * sizeof(I8Group);
+    HIPCHECK(idx, rows.grow(new_cap * row_b));
+    HIPCHECK(idx, shadow.grow(new_cap * sh_b));
+    HIPCHECK(idx, nrm2.grow(new_cap * sizeof(float)));
+    HIPCHECK(idx, shadow8.grow(new_cap * sh8_b));
+    HIPCHECK(idx, flag8.grow(new_cap));
+    HIPCHECK(idx, grp8.grow(grp_b));
+    hipStream_t s = idx->stream;
+    HIPCHECK(idx, hipMemsetAsync(shadow, 0, new_cap * sh_b, s));
+    HIPCHECK(idx, hipMemsetAsync(shadow8, 0, new_cap * sh8_b, s));
+    HIPCHECK(idx, hipMemsetAsync(flag8, 0, new_cap, s));
+    HIPCHECK(idx, hipMemsetAsync(grp8, 0, grp_b, s));
     if (idx->n > 0) {
-        HIPCHECK(idx, hipMemcpyAsync(rows, idx->rows, (size_t)idx->n * idx->dim * sizeof(float),
-                                     hipMemcpyDeviceToDevice, idx->stream));
-        HIPCHECK(idx, hipMemcpyAsync(shadow, idx->shadow, (size_t)idx->n * idx->dpad * sizeof(uint16_t),
-                                     hipMemcpyDeviceToDevice, idx->stream));
-        HIPCHECK(idx, hipMemcpyAsync(nrm2, idx->nrm2, (size_t)idx->n * sizeof(float), hipMemcpyDeviceToDevice,
-                                     idx->stream));
-        HIPCHECK(idx, hipMemcpyAsync(shadow8, idx->shadow8, (size_t)idx->n * idx->dpad8, hipMemcpyDeviceToDevice,
-                                     idx->stream));
-        HIPCHECK(idx, hipMemcpyAsync(flag8, idx->flag8, (size_t)idx->n, hipMemcpyDeviceToDevice, idx->stream));
-        HIPCHECK(idx, hipMemcpyAsync(grp8, idx->grp8, (size_t)((idx->n + kI8GroupRows - 1) / kI8GroupRows) * sizeof(I8Group),
-                                     hipMemcpyDeviceToDevice, idx->stream));
+        const size_t n = idx->n, live_grp_b = (n + kI8GroupRows - 1) / kI8GroupRows * sizeof(I8Group);
+        HIPCHECK(idx, hipMemcpyAsync(rows, idx->rows, n * row_b, hipMemcpyDeviceToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(shadow, idx->shadow, n * sh_b, hipMemcpyDeviceToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(nrm2, idx->nrm2, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(shadow8, idx->shadow8, n * sh8_b, hipMemcpyDeviceToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(flag8, idx->flag8, n, hipMemcpyDeviceToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(grp8, idx->grp8, live_grp_b, hipMemcpyDeviceToDevice, s));
     }
-    HIPCHECK(idx, hipStreamSynchronize(idx->stream));
-    if (idx->rows) (void)hipFree(idx->rows);
-    if (idx->shadow) (void)hipFree(idx->shadow);
-    if (idx->nrm2) (void)hipFree(idx->nrm2);
-    if (idx->shadow8) (void)hipFree(idx->shadow8);
-    if (idx->flag8) (void)hipFree(idx->flag8);
-    if (idx->grp8) (void)hipFree(idx->grp8);
-    idx->shadow8 = shadow8;
-    idx->flag8 = flag8;
-    idx->grp8 = grp8;
-    idx->rows = rows;
-    idx->shadow = shadow;
-    idx->nrm2 = nrm2;
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    idx->rows.swap(rows);  // (the old blocks leave with the locals)
+    idx->shadow.swap(shadow);
+    idx->nrm2.swap(nrm2);
+    idx->shadow8.swap(shadow8);
+    idx->flag8.swap(flag8);
+    idx->grp8.swap(grp8);
     idx->cap_rows = new_cap;
     return MI355DR_OK;
 }
@@ -97,34 +84,41 @@ int ensure_capacity(mi355dr_index* idx, int64_t want_rows) {
 int ensure_qstate(mi355dr_index* idx) {
     if (idx->qstate_ready) return MI355DR_OK;
     const size_t B = kQBlockMax;
-    HIPCHECK(idx, hipMalloc(&idx->st.qn, B * sizeof(float)));
-    HIPCHECK(idx, hipMalloc(&idx->st.qhat, B * idx->dpad * sizeof(uint16_t)));
-    HIPCHECK(idx, hipMalloc(&idx->st.thr, B * sizeof(float)));
-    HIPCHECK(idx, hipMalloc(&idx->st.cnt, B * sizeof(int)));
-    HIPCHECK(idx, hipMalloc(&idx->st.best_n, B * sizeof(int)));
-    HIPCHECK(idx, hipMalloc(&idx->st.best_key, B * kKMax * sizeof(uint64_t)));
-    HIPCHECK(idx, hipMalloc(&idx->st.best_row, B * kKMax * sizeof(int32_t)));
-    HIPCHECK(idx, hipMalloc(&idx->st.thr_key, B * sizeof(uint64_t)));
-    HIPCHECK(idx, hipMalloc(&idx->st.thr_row, B * sizeof(int32_t)));
-    HIPCHECK(idx, hipMalloc(&idx->st.status, (B + 1) * sizeof(int)));  // [B]: the block's OR-ed status word
+    // a view of st gets its block from the owner at the same position; grow() keeps what an earlier, failed call already got
+    auto own = [&](auto*& view, size_t bytes) {
+        DevBuf<void>& mem = idx->st_mem[((char*)&view - (char*)&idx->st) / sizeof(void*)];
+        const hipError_t e = mem.grow(bytes);
+        view = static_cast<std::remove_reference_t<decltype(view)>>(mem.p);
+        return e;
+    };
+    HIPCHECK(idx, own(idx->st.qn, B * sizeof(float)));
+    HIPCHECK(idx, own(idx->st.qhat, B * idx->dpad * sizeof(uint16_t)));
+    HIPCHECK(idx, own(idx->st.thr, B * sizeof(float)));
+    HIPCHECK(idx, own(idx->st.cnt, B * sizeof(int)));
+    HIPCHECK(idx, own(idx->st.best_n, B * sizeof(int)));
+    HIPCHECK(idx, own(idx->st.best_key, B * kKMax * sizeof(uint64_t)));
+    HIPCHECK(idx, own(idx->st.best_row, B * kKMax * sizeof(int32_t)));
+    HIPCHECK(idx, own(idx->st.thr_key, B * sizeof(uint64_t)));
+    HIPCHECK(idx, own(idx->st.thr_row, B * sizeof(int32_t)));
+    HIPCHECK(idx, own(idx->st.status, (B + 1) * sizeof(int)));  // [B]: the block's OR-ed status word
     idx->status_or_dev = idx->st.status + B;
-    HIPCHECK(idx, hipMalloc(&idx->st.E, B * sizeof(float)));
-    HIPCHECK(idx, hipMalloc(&idx->st.E16, B * sizeof(float)));
-    HIPCHECK(idx, hipMalloc(&idx->st.sc, B * sizeof(float)));
-    HIPCHECK(idx, hipMalloc(&idx->st.kq, B * sizeof(float)));
-    HIPCHECK(idx, hipMalloc(&idx->rq_progress, kRqProgressWords * sizeof(int)));
+    HIPCHECK(idx, own(idx->st.E, B * sizeof(float)));
+    HIPCHECK(idx, own(idx->st.E16, B * sizeof(float)));
+    HIPCHECK(idx, own(idx->st.sc, B * sizeof(float)));
+    HIPCHECK(idx, own(idx->st.kq, B * sizeof(float)));
+    HIPCHECK(idx, idx->rq_progress.grow(kRqProgressWords * sizeof(int)));
     HIPCHECK(idx, hipMemset(idx->rq_progress, 0, kRqProgressWords * sizeof(int)));
-    HIPCHECK(idx, hipMalloc(&idx->st.qhat8, B * idx->dpad8));
-    HIPCHECK(idx, hipMalloc(&idx->st.carry, B * sizeof(int)));
-    HIPCHECK(idx, hipMalloc(&idx->qdev, B * idx->dim * sizeof(float)));
-    HIPCHECK(idx, hipMalloc(&idx->cand_row, B * kCandCapWide * sizeof(int32_t)));
-    HIPCHECK(idx, hipMalloc(&idx->cand_val, B * kCandCapWide * sizeof(float)));
-    HIPCHECK(idx, hipMalloc(&idx->qlist_dev, 2 * B * sizeof(int)));  // second half: overflow re-runs
-    HIPCHECK(idx, hipHostMalloc(&idx->status_host, (B + 1) * sizeof(int)));
-    HIPCHECK(idx, hipMalloc(&idx->out_dist_dev, B * kKMax * sizeof(double)));
-    HIPCHECK(idx, hipMalloc(&idx->out_rows_dev, B * kKMax * sizeof(int64_t)));
-    HIPCHECK(idx, hipMalloc(&idx->prune_skip, (2 + 2 * B) * sizeof(int)));
-    HIPCHECK(idx, hipMalloc(&idx->stat_dev, 2 * B * sizeof(unsigned long long)));
+    HIPCHECK(idx, own(idx->st.qhat8, B * idx->dpad8));
+    HIPCHECK(idx, own(idx->st.carry, B * sizeof(int)));
+    HIPCHECK(idx, idx->qdev.grow(B * idx->dim * sizeof(float)));
+    HIPCHECK(idx, idx->cand_row.grow(B * kCandCapWide * sizeof(int32_t)));
+    HIPCHECK(idx, idx->cand_val.grow(B * kCandCapWide * sizeof(float)));
+    HIPCHECK(idx, idx->qlist_dev.grow(2 * B * sizeof(int)));  // second half: overflow re-runs
+    HIPCHECK(idx, idx->status_host.grow((B + 1) * sizeof(int)));
+    HIPCHECK(idx, idx->out_dist_dev.grow(B * kKMax * sizeof(double)));
+    HIPCHECK(idx, idx->out_rows_dev.grow(B * kKMax * sizeof(int64_t)));
+    HIPCHECK(idx, idx->prune_skip.grow((2 + 2 * B) * sizeof(int)));
+    HIPCHECK(idx, idx->stat_dev.grow(2 * B * sizeof(unsigned long long)));
     HIPCHECK(idx, hipMemsetAsync(idx->stat_dev, 0, 2 * B * sizeof(unsigned long long), idx->stream));
     // the prune / scan kernels use more than the default 64 KiB of dynamic LDS
     if (prune_lds_bytes(idx->dim, kPruneBigThreads, kPruneBigSort, 0) > 160 * 1024 || scan_lds_bytes(idx->dim, 1) > 160 * 1024)
@@ -164,7 +158,7 @@ int ensure_qstate(mi355dr_index* idx) {
     HIPCHECK(idx, hipFuncSetAttribute((const void*)k_screen_rq<6, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, rq_lds(6)));
     HIPCHECK(idx, hipFuncSetAttribute((const void*)k_merge_topk, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       kSortMax * 12));
-    idx->qstate_ready = true;
+    idx->qstate_ready = true;  // (behind the last step that can fail)
     return MI355DR_OK;
 }
 
@@ -176,9 +170,9 @@ inline float screen_bound(int d) {
 }
 
 EventPair take_events(mi355dr_index* idx) {
-    if (!idx->ev_pool.empty()) {
-        EventPair p = idx->ev_pool.back();
-        idx->ev_pool.pop_back();
+    if (!idx->ev_pool.v.empty()) {
+        EventPair p = idx->ev_pool.v.back();
+        idx->ev_pool.v.pop_back();
         return p;
     }
     EventPair p{};
@@ -189,7 +183,7 @@ EventPair take_events(mi355dr_index* idx) {
 
 void drain_events(mi355dr_index* idx) {  // the pairs whose launch has finished (a later block's may still be in flight)
     std::vector<EventPair> keep;
-    for (auto& p : idx->ev_pending) {
+    for (auto& p : idx->ev_pending.v) {
         if (hipEventQuery(p.b) == hipErrorNotReady) {
             keep.push_back(p);
             continue;
@@ -199,9 +193,9 @@ void drain_events(mi355dr_index* idx) {  // the pairs whose launch has finished 
             idx->s_screen_ns += (int64_t)(ms * 1e6);
             if (p.big) idx->s_big_ns += (int64_t)(ms * 1e6);
         }
-        idx->ev_pool.push_back(p);
+        idx->ev_pool.v.push_back(p);
     }
-    idx->ev_pending.swap(keep);
+    idx->ev_pending.v.swap(keep);
 }
 
 // Candidates a chunk appends per query ~ k * (chunk / rows seen before) * inflation, where the inflation is how much
@@ -309,11 +303,6 @@ inline int screen_tile(int B) { return B > kTileN ? kT2 : kTileM; }
 constexpr int kRetryLevels = 2;  // re-screens of an overflowed query (bf16, growth/2, then growth 0.25) before the exact scan
 
 // launch one screen pass over rows [r0, r_end) (r0 a multiple of the tile edge)
-__global__ void k_set_counts(int* cnt, int n, int v) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) cnt[i] = v;
-}
-
 int launch_screen(mi355dr_index* idx, hipStream_t s, int B, int64_t r0, int64_t r_end, int cap, int emit_mode) {
     const bool emit_all = emit_mode != 0;  // (both special epilogues live in k_screen)
     // the emit-all first chunk always goes through the 128x128 kernel (k_screen256 has no emit-all epilogue)
@@ -352,7 +341,7 @@ int launch_screen(mi355dr_index* idx, hipStream_t s, int B, int64_t r0, int64_t 
         if (idx->debug_park > 0 && r_end - r0 >= idx->debug_park) {  // (diagnostic: thresholds at +inf for a launch of at least that many rows -- its cost without a single hit; results are WRONG)
             if (!idx->park_thr) {
                 std::vector<float> inf(kQBlockMax, INFINITY);
-                HIPCHECK(idx, hipMalloc(&idx->park_thr, kQBlockMax * sizeof(float)));
+                HIPCHECK(idx, idx->park_thr.grow(kQBlockMax * sizeof(float)));
                 HIPCHECK(idx, hipMemcpy(idx->park_thr, inf.data(), kQBlockMax * sizeof(float), hipMemcpyHostToDevice));
             }
             sa.thr = idx->park_thr;
@@ -521,7 +510,7 @@ int run_screen(mi355dr_index* idx, hipStream_t s, int B, int k, const PassPlan& 
         if (idx->profile) {
             HIPCHECK(idx, hipEventRecord(ev.b, s));
             ev.big = big ? 1 : 0;
-            idx->ev_pending.push_back(ev);
+            idx->ev_pending.v.push_back(ev);
         }
         idx->s_screen_launches++;
         idx->s_screen_rows += rows;
@@ -574,18 +563,6 @@ int run_screen(mi355dr_index* idx, hipStream_t s, int B, int k, const PassPlan& 
     }
     idx->s_passes++;
     return MI355DR_OK;
-}
-
-__global__ void k_reset_queries(QueryState st, const int* qlist, int nq) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nq) return;
-    const int q = qlist[i];
-    st.cnt[q] = 0;
-    st.carry[q] = 0;
-    st.best_n[q] = 0;
-    st.thr_key[q] = kKeyNaN;
-    st.thr_row[q] = 0x7FFFFFFF;
-    st.status[q] &= ~kStOverflow;
 }
 
 // exact scan of rows [r0,r1) for the <= kScanQ queries in qlist_dev[off..off+nq), then exact prune
@@ -662,20 +639,6 @@ int run_scan(mi355dr_index* idx, hipStream_t s, const std::vector<int>& qs, int 
     return MI355DR_OK;
 }
 
-// rows `map[j]` of src -> row j of dst (d floats each)
-__global__ void k_gather_queries(const float* src, const int* map, int d, float* dst) {
-    const int j = blockIdx.x;
-    for (int c = threadIdx.x; c < d; c += blockDim.x) dst[(int64_t)j * d + c] = src[(int64_t)map[j] * d + c];
-}
-// result j of the re-screened sub-block -> slot map[j] of the block's outputs
-__global__ void k_scatter_results(const double* sd, const int64_t* sr, const int* map, int k, double* od, int64_t* orow) {
-    const int j = blockIdx.x;
-    for (int i = threadIdx.x; i < k; i += blockDim.x) {
-        od[(int64_t)map[j] * k + i] = sd[(int64_t)j * k + i];
-        orow[(int64_t)map[j] * k + i] = sr[(int64_t)j * k + i];
-    }
-}
-
 // ---- a block in flight -------------------------------------------------------------------------------------------------
 // Round 3: a block no longer ends with a host synchronisation.  enqueue_block() puts the whole pass on the stream -- prepare,
 // starter, chunks, finalize, a copy of the per-query status words into the block's own pinned buffer, an event -- and returns;
@@ -687,8 +650,8 @@ __global__ void k_scatter_results(const double* sd, const int64_t* sr, const int
 // single: blocks follow each other in stream order, and a fix-up (enqueued behind whatever is in flight) gathers its
 // queries from the CALLER's buffer, which therefore stays valid until the wait.
 int pending_alloc(mi355dr_index* idx, Pending& p) {
-    if (!p.status_host) HIPCHECK(idx, hipHostMalloc(&p.status_host, (kQBlockMax + 1) * sizeof(int)));
-    if (!p.done) HIPCHECK(idx, hipEventCreateWithFlags(&p.done, hipEventDisableTiming));
+    HIPCHECK(idx, p.status_host.grow((kQBlockMax + 1) * sizeof(int)));
+    HIPCHECK(idx, p.done.create(hipEventDisableTiming));
     return MI355DR_OK;
 }
 
@@ -779,16 +742,14 @@ int complete_block(mi355dr_index* idx, Pending& p) {
     }
     const int n_sub = (int)sub.size(), n_retry = n_sub - n_todo;
     if (n_sub == 0) return MI355DR_OK;
-    if (!idx->retry_q[level]) {
-        HIPCHECK(idx, hipMalloc(&idx->retry_q[level], (size_t)kQBlockMax * idx->dim * sizeof(float)));
-        HIPCHECK(idx, hipMalloc(&idx->retry_dist[level], (size_t)kQBlockMax * kKMax * sizeof(double)));
-        HIPCHECK(idx, hipMalloc(&idx->retry_rows[level], (size_t)kQBlockMax * kKMax * sizeof(int64_t)));
-        HIPCHECK(idx, hipMalloc(&idx->retry_map[level], (size_t)kQBlockMax * sizeof(int)));
-    }
+    RetryBufs& rb = idx->retry[level];  // all four or no fix-up: a level whose set is incomplete asks again for what is missing
+    HIPCHECK(idx, rb.q.grow((size_t)kQBlockMax * idx->dim * sizeof(float)));
+    HIPCHECK(idx, rb.dist.grow((size_t)kQBlockMax * kKMax * sizeof(double)));
+    HIPCHECK(idx, rb.rows.grow((size_t)kQBlockMax * kKMax * sizeof(int64_t)));
+    HIPCHECK(idx, rb.map.grow((size_t)kQBlockMax * sizeof(int)));
     // both sub-blocks' queries are gathered from the caller's buffer BEFORE either runs (a nested search overwrites qdev)
-    HIPCHECK(idx, hipMemcpyAsync(idx->retry_map[level], sub.data(), n_sub * sizeof(int), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_gather_queries, dim3(n_sub), dim3(128), 0, s, p.q_dev, idx->retry_map[level], idx->dim,
-                       idx->retry_q[level]);
+    HIPCHECK(idx, hipMemcpyAsync(rb.map, sub.data(), n_sub * sizeof(int), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_gather_queries, dim3(n_sub), dim3(128), 0, s, p.q_dev, rb.map, idx->dim, rb.q);
     HIPCHECK(idx, hipGetLastError());
     HIPCHECK(idx, hipStreamSynchronize(s));  // `sub` (pageable) was read by the copy
     const int saved_level = idx->retry_level, saved_path = idx->path;
@@ -796,7 +757,7 @@ int complete_block(mi355dr_index* idx, Pending& p) {
     if (n_todo > 0) {  // guaranteed exact path
         idx->retry_level = level + 1;  // (buffers of the next level; the scan itself never re-screens)
         idx->path = MI355DR_PATH_SCAN;
-        rc = search_block(idx, s, idx->retry_q[level], n_todo, k, idx->retry_dist[level], idx->retry_rows[level]);
+        rc = search_block(idx, s, rb.q, n_todo, k, rb.dist, rb.rows);
         idx->path = saved_path;
         idx->retry_level = saved_level;
         CHECK(rc);
@@ -816,13 +777,12 @@ int complete_block(mi355dr_index* idx, Pending& p) {
             idx->i8_probation = idx->i8_backoff;
         }
         idx->retry_level = level + 1;
-        rc = search_block(idx, s, idx->retry_q[level] + (size_t)n_todo * idx->dim, n_retry, k,
-                          idx->retry_dist[level] + (size_t)n_todo * k, idx->retry_rows[level] + (size_t)n_todo * k);
+        rc = search_block(idx, s, rb.q + (size_t)n_todo * idx->dim, n_retry, k,
+                          rb.dist + (size_t)n_todo * k, rb.rows + (size_t)n_todo * k);
         idx->retry_level = saved_level;
         CHECK(rc);
     }
-    hipLaunchKernelGGL(k_scatter_results, dim3(n_sub), dim3(128), 0, s, idx->retry_dist[level], idx->retry_rows[level],
-                       idx->retry_map[level], k, p.out_dist, p.out_rows);
+    hipLaunchKernelGGL(k_scatter_results, dim3(n_sub), dim3(128), 0, s, rb.dist, rb.rows, rb.map, k, p.out_dist, p.out_rows);
     HIPCHECK(idx, hipGetLastError());
     HIPCHECK(idx, hipStreamSynchronize(s));
     return MI355DR_OK;
@@ -830,15 +790,16 @@ int complete_block(mi355dr_index* idx, Pending& p) {
 
 // blocks still in flight (mi355dr_search_device_async) are finished before anything that is not the next block on the same
 // stream touches the per-search state or the corpus buffers
-int drain_pending(mi355dr_index* idx) {
+int complete_until(mi355dr_index* idx, int64_t seq) {  // finish the blocks below sequence number `seq`; the first error, if any
     int rc = MI355DR_OK;
-    while (idx->seq_done < idx->seq_next) {
+    while (idx->seq_done < seq) {
         const int r = complete_block(idx, idx->pend[idx->seq_done % kPendingRing]);
         if (rc == MI355DR_OK) rc = r;
         idx->seq_done++;
     }
     return rc;
 }
+int drain_pending(mi355dr_index* idx) { return complete_until(idx, idx->seq_next); }
 
 // one block of B <= kQBlockMax device-resident queries -> device outputs [B,k], complete on return
 int search_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, int k, double* out_dist_dev,
@@ -856,6 +817,30 @@ inline size_t merge_lds(int world, int k) {
     return np * 12;
 }
 inline int merge_threads(int world, int k) { return (int64_t)world * k <= 128 ? 64 : 256; }
+
+// rank r's [B, k] distances / rows start r * stride entries behind dist_all / rows_all; asynchronous on the stream
+int launch_merge(mi355dr_index* idx, const double* dist_all, const int64_t* rows_all, int64_t stride, int world, int B, int k,
+                 double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
+    if (world <= 0 || B < 0 || k <= 0) return fail(idx, MI355DR_E_INVALID, "bad merge shape");
+    if ((int64_t)world * k > kSortMax) return fail(idx, MI355DR_E_UNSUPPORTED, "world*k exceeds 4096");
+    if (B == 0) return MI355DR_OK;
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(ensure_qstate(idx));
+    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
+    hipLaunchKernelGGL(k_merge_topk, dim3(B), dim3(merge_threads(world, k)), merge_lds(world, k), s, dist_all, rows_all, stride,
+                       world, B, k, out_dist_dev, out_rows_dev);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+// the debug entry points' start: blocks in flight finished, the B queries uploaded and prepared (`metric`: k_prep_queries)
+int upload_and_prep(mi355dr_index* idx, const float* queries, int B, int metric) {
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_pending(idx));
+    CHECK(ensure_qstate(idx));
+    HIPCHECK(idx, hipMemcpyAsync(idx->qdev, queries, (size_t)B * idx->dim * sizeof(float), hipMemcpyHostToDevice, idx->stream));
+    return launch_prep(idx, idx->stream, B, (int)round_up(B, screen_tile(B)), metric);
+}
 
 int check_search_args(mi355dr_index* idx, const void* q, int B, int k, const void* od, const void* orow) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
@@ -895,23 +880,22 @@ int mi355dr_create(mi355dr_index** out, int device_id, int dim, int metric) {
     idx->metric = metric;
     hipError_t e = hipSetDevice(device_id);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&idx->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&idx->irr_rows, kIrrCap * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&idx->irr_count, sizeof(int));
-    if (e == hipSuccess) e = hipMemset(idx->irr_count, 0, sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&idx->n2max_dev, sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemset(idx->n2max_dev, 0, sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc(&idx->bf16_res2_dev, sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemset(idx->bf16_res2_dev, 0, sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc(&idx->irr8_rows, kIrrCap * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&idx->irr8_count, sizeof(int));
-    if (e == hipSuccess) e = hipMemset(idx->irr8_count, 0, sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&idx->dead_count, sizeof(int));
-    if (e == hipSuccess) e = hipMemset(idx->dead_count, 0, sizeof(int));
-    if (e == hipSuccess) e = hipEventCreate(&idx->t0);
-    if (e == hipSuccess) e = hipEventCreate(&idx->t1);
+    auto zeroed = [&](auto& word) {  // one 4-byte counter or running maximum, starting at 0
+        if (e == hipSuccess) e = word.grow(4);
+        if (e == hipSuccess) e = hipMemset(word, 0, 4);
+    };
+    if (e == hipSuccess) e = idx->irr_rows.grow(kIrrCap * sizeof(int32_t));
+    zeroed(idx->irr_count);
+    zeroed(idx->n2max_dev);
+    zeroed(idx->bf16_res2_dev);
+    if (e == hipSuccess) e = idx->irr8_rows.grow(kIrrCap * sizeof(int32_t));
+    zeroed(idx->irr8_count);
+    zeroed(idx->dead_count);
+    if (e == hipSuccess) e = idx->t0.create();
+    if (e == hipSuccess) e = idx->t1.create();
     if (e != hipSuccess) {
         std::string m = std::string("device setup failed: ") + hipGetErrorString(e);
-        delete idx;
+        delete idx;  // (its members and its destructor release whatever the steps before the failure created)
         return fail(nullptr, MI355DR_E_HIP, m);
     }
     *out = idx;
@@ -923,38 +907,9 @@ void mi355dr_destroy(mi355dr_index* idx) {
     (void)hipSetDevice(idx->device);
     (void)drain_pending(idx);
     if (idx->stream) (void)hipStreamSynchronize(idx->stream);
-    for (Pending* pp : {&idx->pend[0], &idx->pend[1], &idx->pend[2], &idx->pend[3], &idx->sub_pend[0], &idx->sub_pend[1],
-                        &idx->sub_pend[2], &idx->sub_pend[3]}) {
-        if (pp->done) (void)hipEventDestroy(pp->done);
-        if (pp->status_host) (void)hipHostFree(pp->status_host);
-    }
-    void* ptrs[] = {idx->retry_q[2], idx->retry_dist[2], idx->retry_rows[2], idx->retry_map[2],
-                    idx->n2max_dev, idx->bf16_res2_dev, idx->retry_q[0], idx->retry_dist[0], idx->retry_rows[0], idx->retry_map[0], idx->retry_q[1],
-                    idx->retry_dist[1], idx->retry_rows[1], idx->retry_map[1], idx->shadow8, idx->flag8, idx->grp8, idx->irr8_rows, idx->irr8_count, idx->st.E, idx->st.E16, idx->st.sc, idx->st.kq,
-                    idx->st.qhat8, idx->st.carry,
-                    idx->rows, idx->shadow, idx->nrm2, idx->irr_rows, idx->irr_count, idx->st.qn, idx->st.qhat,
-                    idx->st.thr, idx->st.cnt, idx->st.best_n, idx->st.best_key, idx->st.best_row, idx->st.thr_key,
-                    idx->st.thr_row, idx->st.status, idx->qdev, idx->cand_row, idx->cand_val, idx->qlist_dev,
-                    idx->out_dist_dev, idx->out_rows_dev, idx->stat_dev, idx->prune_skip, idx->rq_progress, idx->park_thr, idx->dead_count};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     multivec_destroy(idx);
     comm_destroy(idx);
-    if (idx->status_host) (void)hipHostFree(idx->status_host);
-    for (auto& p : idx->ev_pool) {
-        (void)hipEventDestroy(p.a);
-        (void)hipEventDestroy(p.b);
-    }
-    for (auto& p : idx->ev_pending) {
-        (void)hipEventDestroy(p.a);
-        (void)hipEventDestroy(p.b);
-    }
-    for (hipEvent_t e : idx->ms_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (idx->t0) (void)hipEventDestroy(idx->t0);
-    if (idx->t1) (void)hipEventDestroy(idx->t1);
-    if (idx->stream) (void)hipStreamDestroy(idx->stream);
-    delete idx;
+    delete idx;  // every buffer and event goes with its owner, the stream with the handle's destructor (index.h)
 }
 
 int mi355dr_reserve(mi355dr_index* idx, int64_t n_rows) {
@@ -966,6 +921,64 @@ int mi355dr_reserve(mi355dr_index* idx, int64_t n_rows) {
     CHECK(drain_pending(idx));
     return ensure_capacity(idx, n_rows);
 }
+
+// ---- the derived data of stored rows: built and published the same way by add, update and remove ------------------------
+namespace {
+// the per-row build kernels run one workgroup per row: a grid is kept below 2^22 rows (gridDim.x * blockDim.x < 2^32)
+constexpr int64_t kBuildSlice = (int64_t)1 << 22;
+
+// |c|^2 (with_nrm2) and the bf16 image of n rows: [first, first + n), or ids[0 .. n) (device) when ids != nullptr
+int build_rows(mi355dr_index* idx, hipStream_t s, int64_t first, int64_t n, const int64_t* ids, bool with_nrm2) {
+    for (int64_t r0 = 0; r0 < n; r0 += kBuildSlice) {
+        const int64_t m = std::min(kBuildSlice, n - r0), row0 = ids ? 0 : first + r0;
+        const int64_t* slice = ids ? ids + r0 : nullptr;
+        if (with_nrm2) {
+            hipLaunchKernelGGL(k_row_nrm2, dim3((unsigned)((m + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows, row0, m,
+                               idx->dim, idx->nrm2, idx->n2max_dev, slice);
+            HIPCHECK(idx, hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_build_shadow, dim3((unsigned)m), dim3(256), 0, s, idx->rows, idx->nrm2, row0, m, idx->dim,
+                           idx->dpad, idx->shadow, idx->irr_rows, idx->irr_count, idx->bf16_res2_dev,
+                           idx->metric == MI355DR_METRIC_IP ? 1 : 0, slice);
+        HIPCHECK(idx, hipGetLastError());
+    }
+    return MI355DR_OK;
+}
+
+// the int8 image of n whole groups of 32 rows: [g_first, g_first + n), or groups[0 .. n) (device) when groups != nullptr
+// (n_total, first_new: k_build_shadow8 -- loose rows from first_new on are appended to their side list)
+int build_groups(mi355dr_index* idx, hipStream_t s, int64_t g_first, int64_t n, const int64_t* groups, int64_t n_total,
+                 int64_t first_new) {
+    for (int64_t g0 = 0; g0 < n; g0 += kBuildSlice) {
+        const int64_t m = std::min(kBuildSlice, n - g0);
+        hipLaunchKernelGGL(k_build_shadow8, dim3((unsigned)m), dim3(256), 0, s, idx->rows, idx->nrm2, groups ? 0 : g_first + g0,
+                           n_total, first_new, idx->dim, idx->dpad8, idx->shadow8, idx->flag8, idx->grp8, idx->irr8_rows,
+                           idx->irr8_count, idx->metric == MI355DR_METRIC_IP ? 1 : 0, groups ? groups + g0 : nullptr);
+        HIPCHECK(idx, hipGetLastError());
+    }
+    return MI355DR_OK;
+}
+
+// what the build kernels counted and measured becomes the host's view of the corpus; the call's one synchronisation
+int commit_corpus(mi355dr_index* idx, hipStream_t s, bool mutated) {
+    int irr = 0, irr8 = 0, dead = 0;
+    float res2 = 0.0f, n2max = 0.0f;
+    HIPCHECK(idx, hipMemcpyAsync(&irr, idx->irr_count, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(&irr8, idx->irr8_count, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (mutated) HIPCHECK(idx, hipMemcpyAsync(&dead, idx->dead_count, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(&res2, idx->bf16_res2_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(&n2max, idx->n2max_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    // the two running maxima only ever grow (the row that held one may be gone: a looser bound is still a bound)
+    idx->cmax = std::sqrt(n2max) * 1.000001f;
+    // (a-priori cap: 2^-8 |c_hat|; inner product: the shadow holds the rows themselves, residuals in their units)
+    idx->bf16_ec = std::min(std::sqrt(res2) * 1.001f, 0.00390625f * 1.0001f * (idx->metric == MI355DR_METRIC_IP ? idx->cmax : 1.0f));
+    idx->irr_n = irr;
+    idx->irr8_n = irr8;
+    if (mutated) idx->dead_n = dead;
+    return MI355DR_OK;
+}
+}  // namespace
 
 static int add_rows_impl(mi355dr_index* idx, const float* rows, int64_t n, hipMemcpyKind kind) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
@@ -979,41 +992,11 @@ static int add_rows_impl(mi355dr_index* idx, const float* rows, int64_t n, hipMe
     CHECK(ensure_capacity(idx, idx->n + n));
     hipStream_t s = idx->stream;
     HIPCHECK(idx, hipMemcpyAsync(idx->rows + idx->n * idx->dim, rows, (size_t)n * idx->dim * sizeof(float), kind, s));
-    // the per-row build kernels run one workgroup per row: a grid is kept below 2^22 rows (gridDim.x * blockDim.x < 2^32)
-    constexpr int64_t kBuildSlice = (int64_t)1 << 22;
-    for (int64_t r0 = 0; r0 < n; r0 += kBuildSlice) {
-        const int64_t m = std::min(kBuildSlice, n - r0), first = idx->n + r0;
-        hipLaunchKernelGGL(k_row_nrm2, dim3((unsigned)((m + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows, first, m,
-                           idx->dim, idx->nrm2, idx->n2max_dev, (const int64_t*)nullptr);
-        HIPCHECK(idx, hipGetLastError());
-        hipLaunchKernelGGL(k_build_shadow, dim3((unsigned)m), dim3(256), 0, s, idx->rows, idx->nrm2, first, m, idx->dim,
-                           idx->dpad, idx->shadow, idx->irr_rows, idx->irr_count, idx->bf16_res2_dev,
-                           idx->metric == MI355DR_METRIC_IP ? 1 : 0, (const int64_t*)nullptr);
-        HIPCHECK(idx, hipGetLastError());
-    }
-    {   // int8 shadow: whole groups of 32 rows, from the (possibly partly filled) group the first new row falls into
-        const int64_t g_lo = idx->n / kI8GroupRows, g_hi = (idx->n + n + kI8GroupRows - 1) / kI8GroupRows;
-        for (int64_t g0 = g_lo; g0 < g_hi; g0 += kBuildSlice) {
-            const int64_t m = std::min(kBuildSlice, g_hi - g0);
-            hipLaunchKernelGGL(k_build_shadow8, dim3((unsigned)m), dim3(256), 0, s, idx->rows, idx->nrm2, g0, idx->n + n,
-                               idx->n, idx->dim, idx->dpad8, idx->shadow8, idx->flag8, idx->grp8, idx->irr8_rows,
-                               idx->irr8_count, idx->metric == MI355DR_METRIC_IP ? 1 : 0, (const int64_t*)nullptr);
-            HIPCHECK(idx, hipGetLastError());
-        }
-    }
-    int irr = 0, irr8 = 0;
-    HIPCHECK(idx, hipMemcpyAsync(&irr, idx->irr_count, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHECK(idx, hipMemcpyAsync(&irr8, idx->irr8_count, sizeof(int), hipMemcpyDeviceToHost, s));
-    float res2 = 0.0f;
-    HIPCHECK(idx, hipMemcpyAsync(&res2, idx->bf16_res2_dev, sizeof(float), hipMemcpyDeviceToHost, s));
-    HIPCHECK(idx, hipStreamSynchronize(s));
-    float n2max = 0.0f;
-    HIPCHECK(idx, hipMemcpy(&n2max, idx->n2max_dev, sizeof(float), hipMemcpyDeviceToHost));
-    idx->cmax = std::sqrt(n2max) * 1.000001f;
-    // (a-priori cap: 2^-8 |c_hat|; inner product: the shadow holds the rows themselves, residuals in their units)
-    idx->bf16_ec = std::min(std::sqrt(res2) * 1.001f, 0.00390625f * 1.0001f * (idx->metric == MI355DR_METRIC_IP ? idx->cmax : 1.0f));
-    idx->irr_n = irr;
-    idx->irr8_n = irr8;
+    CHECK(build_rows(idx, s, idx->n, n, nullptr, /*with_nrm2=*/true));
+    // int8 shadow: whole groups of 32 rows, from the (possibly partly filled) group the first new row falls into
+    const int64_t g_lo = idx->n / kI8GroupRows, g_hi = (idx->n + n + kI8GroupRows - 1) / kI8GroupRows;
+    CHECK(build_groups(idx, s, g_lo, g_hi - g_lo, nullptr, idx->n + n, idx->n));
+    CHECK(commit_corpus(idx, s, /*mutated=*/false));
     idx->n += n;
     return MI355DR_OK;
 }
@@ -1051,7 +1034,6 @@ int mutate_rows_impl(mi355dr_index* idx, const int64_t* row_ids, const float* ro
     HIPCHECK(idx, hipSetDevice(idx->device));
     CHECK(drain_pending(idx));  // (a search in flight sees the index as it was)
     hipStream_t s = idx->stream;
-    const int absolute = idx->metric == MI355DR_METRIC_IP ? 1 : 0;
     DevBuf<void> ids_dev, groups_dev, stage;  // scratch of one call, released on every way out
     HIPCHECK(idx, ids_dev.grow((size_t)n * sizeof(int64_t)));
     HIPCHECK(idx, groups_dev.grow(groups.size() * sizeof(int64_t)));
@@ -1074,22 +1056,10 @@ int mutate_rows_impl(mi355dr_index* idx, const int64_t* row_ids, const float* ro
             const int vec4 = idx->dim % 4 == 0 && (uintptr_t)src % 16 == 0;
             hipLaunchKernelGGL(k_update_rows, dim3((unsigned)m), dim3(256), 0, s, src, ids, m, idx->dim, vec4, idx->rows);
             HIPCHECK(idx, hipGetLastError());
-            hipLaunchKernelGGL(k_row_nrm2, dim3((unsigned)((m + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows, (int64_t)0, m,
-                               idx->dim, idx->nrm2, idx->n2max_dev, ids);
-            HIPCHECK(idx, hipGetLastError());
         }
-        hipLaunchKernelGGL(k_build_shadow, dim3((unsigned)m), dim3(256), 0, s, idx->rows, idx->nrm2, (int64_t)0, m, idx->dim,
-                           idx->dpad, idx->shadow, idx->irr_rows, idx->irr_count, idx->bf16_res2_dev, absolute, ids);
-        HIPCHECK(idx, hipGetLastError());
+        CHECK(build_rows(idx, s, 0, m, ids, /*with_nrm2=*/!remove));
     }
-    constexpr int64_t kBuildSlice = (int64_t)1 << 22;
-    for (int64_t g0 = 0; g0 < (int64_t)groups.size(); g0 += kBuildSlice) {
-        const int64_t m = std::min<int64_t>(kBuildSlice, (int64_t)groups.size() - g0);
-        hipLaunchKernelGGL(k_build_shadow8, dim3((unsigned)m), dim3(256), 0, s, idx->rows, idx->nrm2, (int64_t)0, idx->n, idx->n,
-                           idx->dim, idx->dpad8, idx->shadow8, idx->flag8, idx->grp8, idx->irr8_rows, idx->irr8_count, absolute,
-                           (const int64_t*)groups_dev.p + g0);
-        HIPCHECK(idx, hipGetLastError());
-    }
+    CHECK(build_groups(idx, s, 0, (int64_t)groups.size(), (const int64_t*)groups_dev.p, idx->n, idx->n));
     // both side lists and the dead count anew, from the flags (a row may have entered or left either class)
     HIPCHECK(idx, hipMemsetAsync(idx->irr_count, 0, sizeof(int), s));
     HIPCHECK(idx, hipMemsetAsync(idx->irr8_count, 0, sizeof(int), s));
@@ -1097,21 +1067,7 @@ int mutate_rows_impl(mi355dr_index* idx, const int64_t* row_ids, const float* ro
     hipLaunchKernelGGL(k_rebuild_side_lists, dim3((unsigned)((idx->n + 255) / 256)), dim3(256), 0, s, idx->nrm2, idx->flag8,
                        (int64_t)0, idx->n, idx->irr_rows, idx->irr_count, idx->irr8_rows, idx->irr8_count, idx->dead_count);
     HIPCHECK(idx, hipGetLastError());
-    int irr = 0, irr8 = 0, dead = 0;
-    float res2 = 0.0f, n2max = 0.0f;
-    HIPCHECK(idx, hipMemcpyAsync(&irr, idx->irr_count, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHECK(idx, hipMemcpyAsync(&irr8, idx->irr8_count, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHECK(idx, hipMemcpyAsync(&dead, idx->dead_count, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHECK(idx, hipMemcpyAsync(&res2, idx->bf16_res2_dev, sizeof(float), hipMemcpyDeviceToHost, s));
-    HIPCHECK(idx, hipMemcpyAsync(&n2max, idx->n2max_dev, sizeof(float), hipMemcpyDeviceToHost, s));
-    HIPCHECK(idx, hipStreamSynchronize(s));
-    // the two running maxima only ever grow (the row that held one may be gone: a looser bound is still a bound)
-    idx->cmax = std::sqrt(n2max) * 1.000001f;
-    idx->bf16_ec = std::min(std::sqrt(res2) * 1.001f, 0.00390625f * 1.0001f * (absolute ? idx->cmax : 1.0f));
-    idx->irr_n = irr;
-    idx->irr8_n = irr8;
-    idx->dead_n = dead;
-    return MI355DR_OK;
+    return commit_corpus(idx, s, /*mutated=*/true);
 }
 }  // namespace
 
@@ -1168,10 +1124,7 @@ static int search_device_async_locked(mi355dr_index* idx, const float* queries_d
     if (idx->seq_done < idx->seq_next && idx->pend[(idx->seq_next - 1) % kPendingRing].stream != s) CHECK(drain_pending(idx));
     for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
         const int nb = std::min(kQBlockMax, B - b0);
-        if (idx->seq_next - idx->seq_done >= kPendingRing) {  // the ring is full: finish the oldest block
-            CHECK(complete_block(idx, idx->pend[idx->seq_done % kPendingRing]));
-            idx->seq_done++;
-        }
+        if (idx->seq_next - idx->seq_done >= kPendingRing) CHECK(complete_until(idx, idx->seq_done + 1));  // the ring is full: finish the oldest block
         Pending& p = idx->pend[idx->seq_next % kPendingRing];
         CHECK(enqueue_block(idx, s, queries_dev + (int64_t)b0 * idx->dim, nb, k, out_dist_dev + (int64_t)b0 * k,
                             out_rows_dev + (int64_t)b0 * k, p));
@@ -1196,13 +1149,7 @@ int mi355dr_search_wait(mi355dr_index* idx, int64_t ticket) {
     std::lock_guard<std::mutex> g(idx->mu);
     if (ticket < 0 || ticket > idx->seq_next) return fail(idx, MI355DR_E_INVALID, "unknown ticket");
     HIPCHECK(idx, hipSetDevice(idx->device));
-    int rc = MI355DR_OK;
-    while (idx->seq_done < ticket) {
-        const int r = complete_block(idx, idx->pend[idx->seq_done % kPendingRing]);
-        if (rc == MI355DR_OK) rc = r;
-        idx->seq_done++;
-    }
-    return rc;
+    return complete_until(idx, ticket);
 }
 
 int mi355dr_search_device(mi355dr_index* idx, const float* queries_dev, int B, int k, double* out_dist_dev,
@@ -1220,16 +1167,7 @@ int mi355dr_merge_topk_device(mi355dr_index* idx, const double* dist_all_dev, co
                               int B, int k, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
-    if (world <= 0 || B < 0 || k <= 0) return fail(idx, MI355DR_E_INVALID, "bad merge shape");
-    if ((int64_t)world * k > kSortMax) return fail(idx, MI355DR_E_UNSUPPORTED, "world*k exceeds 4096");
-    if (B == 0) return MI355DR_OK;
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(ensure_qstate(idx));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
-    hipLaunchKernelGGL(k_merge_topk, dim3(B), dim3(merge_threads(world, k)), merge_lds(world, k), s, dist_all_dev, rows_all_dev,
-                       (int64_t)B * k, world, B, k, out_dist_dev, out_rows_dev);
-    HIPCHECK(idx, hipGetLastError());
-    return MI355DR_OK;  // asynchronous on `s`
+    return launch_merge(idx, dist_all_dev, rows_all_dev, (int64_t)B * k, world, B, k, out_dist_dev, out_rows_dev, stream);
 }
 
 int mi355dr_pack_topk_device(mi355dr_index* idx, const double* dist_dev, const int64_t* rows_dev, int B, int k,
@@ -1251,18 +1189,126 @@ int mi355dr_merge_topk_packed_device(mi355dr_index* idx, const int64_t* packed_a
                                      double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
-    if (world <= 0 || B < 0 || k <= 0) return fail(idx, MI355DR_E_INVALID, "bad merge shape");
-    if ((int64_t)world * k > kSortMax) return fail(idx, MI355DR_E_UNSUPPORTED, "world*k exceeds 4096");
-    if (B == 0) return MI355DR_OK;
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(ensure_qstate(idx));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
     const int64_t plane = (int64_t)B * k;
-    hipLaunchKernelGGL(k_merge_topk, dim3(B), dim3(merge_threads(world, k)), merge_lds(world, k), s, (const double*)packed_all_dev,
-                       packed_all_dev + plane, 2 * plane, world, B, k, out_dist_dev, out_rows_dev);
-    HIPCHECK(idx, hipGetLastError());
-    return MI355DR_OK;  // asynchronous on `s`
+    return launch_merge(idx, (const double*)packed_all_dev, packed_all_dev + plane, 2 * plane, world, B, k, out_dist_dev, out_rows_dev, stream);
 }
+
+// ---- options and stats: one table row each --------------------------------------------------------------------------------
+namespace {
+using Index = mi355dr_index;
+
+// where an option's value goes: an int, an int64, a switch (an int that holds value != 0) or a double that holds value / 100
+struct Field {
+    int Index::*i = nullptr;
+    int64_t Index::*l = nullptr;
+    double Index::*x100 = nullptr;
+    bool is_switch = false;
+    constexpr Field(int Index::*p, bool is_switch = false) : i(p), is_switch(is_switch) {}
+    constexpr Field(int64_t Index::*p) : l(p) {}
+    constexpr Field(double Index::*p) : x100(p) {}
+    void set(Index* idx, int64_t v) const {
+        if (i) idx->*i = is_switch ? v != 0 : (int)v;
+        else if (l) idx->*l = v;
+        else idx->*x100 = (double)v / 100.0;
+    }
+};
+constexpr bool kSwitch = true;
+
+struct Option {
+    const char* key;
+    Field field;
+    int64_t lo = INT64_MIN, hi = INT64_MAX;  // accepted: lo <= value <= hi ...
+    void (*then)(Index*) = nullptr;          // what else a successful set does
+    int64_t gap_lo = 0, gap_hi = 0;          // ... but not gap_lo < value < gap_hi
+};
+const Option kOptions[] = {
+    {"path", &Index::path, 0, 2},
+    {"screen_dtype", &Index::screen_dtype, 0, 2, [](Index* x) {  // (setting the option again re-arms AUTO)
+         x->i8_demoted_k = INT_MAX;
+         x->i8_backoff = x->i8_probation = 0;
+     }},
+    {"i8_min_budget_x100", &Index::i8_min_budget, 1, 1000},
+    {"maxsim_screen", {&Index::maxsim_screen, kSwitch}},
+    {"maxsim_coop", &Index::maxsim_coop, -1, 1},  // -1: by document length
+    {"maxsim_persistent", {&Index::maxsim_persistent, kSwitch}},
+    {"maxsim_wg", &Index::maxsim_wg, -1, 2},  // -1: by document length
+    {"maxsim_tighten", {&Index::maxsim_tighten, kSwitch}},
+    {"maxsim_aligned", {&Index::maxsim_aligned, kSwitch}},
+    {"maxsim_wg_min", &Index::maxsim_wg_min, 8, 9},
+    {"maxsim_wg_pipe", {&Index::maxsim_wg_pipe, kSwitch}},
+    {"maxsim_pack8", &Index::maxsim_pack8, -1, 1},  // -1: when it pays
+    {"maxsim_wg_bps", &Index::maxsim_wg_bps, 2, 4, nullptr, 2, 4},  // 2 or 4
+    {"maxsim_pass_groups", &Index::maxsim_pass_groups, 1, 4},
+    {"row_offset", &Index::row_offset},
+    {"profile", {&Index::profile, kSwitch}},
+    // (an explicit first chunk means the emit-all ladder: no starter)
+    {"chunk0_rows", &Index::chunk0_rows, 1, INT64_MAX, [](Index* x) { x->chunk0_set = 1; }},
+    {"starter", {&Index::starter, kSwitch}},
+    {"prune_companion", {&Index::prune_companion, kSwitch}},
+    {"scan_dma", {&Index::scan_dma, kSwitch}},
+    {"defer_round_b", {&Index::defer_round_b, kSwitch}},
+    {"chunk_growth", &Index::chunk_growth, 1, INT64_MAX, [](Index* x) { x->chunk_growth_set = 1; }},
+    {"screen_stream", {&Index::screen_stream, kSwitch}},
+    {"screen_rq", {&Index::screen_rq, kSwitch}},
+    {"debug_park_thresholds", &Index::debug_park},
+    {"screen_rq_split_tests", {&Index::screen_rq_split_tests, kSwitch}},
+    {"screen_drift", &Index::screen_drift, 0, 1024},  // tiles
+    {"small_chunk_rows", &Index::small_chunk_rows, 0},
+    {"round_a", &Index::round_a, 0, 64},
+    {"prefilter16", {&Index::prefilter16, kSwitch}},
+    {"cand_cap", &Index::cap, 16, kCandCap, [](Index* x) { x->cap_set = 1; }},
+    {"prune_wide", {&Index::prune_wide, kSwitch}},
+    {"screen_flush_sync", {&Index::screen_flush_sync, kSwitch}},
+    {"screen_flush_lanes", &Index::screen_flush_lanes, 1, 64},
+    {"screen_flush_alone", &Index::screen_flush_alone, 8, 60},
+    {"wide_inflation_x10", &Index::wide_inflation_x10, 20, 400},
+    {"chunk_taper_x100", &Index::chunk_taper_x100, 0, 300, nullptr, 0, 100},  // 0 (auto) or 100 ... 300
+    {"starter_rows_wide", &Index::starter_rows_wide, 4096, 262144},
+};
+
+struct Stat {
+    const char* key;
+    int64_t Index::*counter;                   // a host counter, which mi355dr_reset_stats zeroes if `reset` ...
+    bool reset;
+    int64_t (*value)(const Index*) = nullptr;  // ... or a value worked out when it is asked for
+};
+const Stat kStats[] = {
+    {"screen_launches", &Index::s_screen_launches, true},
+    {"screen_ns", &Index::s_screen_ns, true},
+    {"screen_rows", &Index::s_screen_rows, true},
+    {"screen256_launches", &Index::s_big_launches, true},
+    {"screen_rq_launches", &Index::s_rq_launches, true},
+    {"screen256_ns", &Index::s_big_ns, true},
+    {"screen256_rows", &Index::s_big_rows, true},
+    {"fallback_queries", &Index::s_fallback_queries, true},
+    {"chunks", &Index::s_chunks, true},
+    {"passes", &Index::s_passes, true},
+    {"starters", &Index::s_starters, true},
+    {"retry_queries", &Index::s_retry_queries, true},
+    {"maxsim_screened", &Index::s_ms_screened, true},
+    {"maxsim_candidates", &Index::s_ms_candidates, true},
+    {"maxsim_fallbacks", &Index::s_ms_fallbacks, true},
+    {"maxsim_screen_ns", &Index::s_ms_screen_ns, true},
+    {"maxsim_pack_ns", &Index::s_ms_pack_ns, true},
+    {"maxsim_screen_launches", &Index::s_ms_screen_launches, true},
+    {"maxsim_exact_ns", &Index::s_ms_exact_ns, true},
+    {"maxsim_exact_launches", &Index::s_ms_exact_launches, true},
+    {"maxsim_screen_cols", &Index::s_ms_screen_cols, true},
+    {"maxsim_packed_launches", &Index::s_ms_packed_launches, true},
+    {"maxsim_packed_blocks", &Index::s_ms_packed_blocks, false},  // (the packed copy's size and its build history: state, not activity)
+    {"maxsim_packed_built", &Index::s_ms_packed_built, false},
+    {"i8_demoted", nullptr, false, [](const Index* x) -> int64_t { return x->i8_demoted_k != INT_MAX ? 1 : 0; }},
+    {"i8_demoted_k", nullptr, false, [](const Index* x) -> int64_t { return x->i8_demoted_k == INT_MAX ? 0 : x->i8_demoted_k; }},
+    {"irregular_rows", nullptr, false, [](const Index* x) -> int64_t { return x->irr_n; }},
+    {"loose_rows", nullptr, false, [](const Index* x) -> int64_t { return x->irr8_n; }},
+    {"dead_rows", nullptr, false, [](const Index* x) -> int64_t { return x->dead_n; }},
+    {"screen_dtype_active", nullptr, false, [](const Index* x) -> int64_t { return use_i8(x) ? MI355DR_SCREEN_I8 : MI355DR_SCREEN_BF16; }},
+    {"hbm_bytes_resident", nullptr, false, [](const Index* x) -> int64_t {
+         return x->cap_rows * ((int64_t)x->dim * 4 + (int64_t)x->dpad * 2 + (int64_t)x->dpad8 + 5) +
+                x->cap_rows / kI8GroupRows * (int64_t)sizeof(I8Group);
+     }},
+};
+}  // namespace
 
 int mi355dr_set_option(mi355dr_index* idx, const char* key, int64_t value) {
     if (!idx || !key) return fail(idx, MI355DR_E_INVALID, "null argument");
@@ -1271,119 +1317,26 @@ int mi355dr_set_option(mi355dr_index* idx, const char* key, int64_t value) {
         HIPCHECK(idx, hipSetDevice(idx->device));
         CHECK(drain_pending(idx));
     }
-    const std::string k(key);
-    if (k == "path") {
-        if (value < 0 || value > 2) return fail(idx, MI355DR_E_INVALID, "path must be 0,1,2");
-        idx->path = (int)value;
-    } else if (k == "screen_dtype") {
-        if (value < 0 || value > 2) return fail(idx, MI355DR_E_INVALID, "screen_dtype must be 0,1,2");
-        idx->screen_dtype = (int)value;
-        idx->i8_demoted_k = INT_MAX;  // (setting the option again re-arms AUTO)
-        idx->i8_backoff = idx->i8_probation = 0;
-    } else if (k == "i8_min_budget_x100") {
-        if (value < 1 || value > 1000) return fail(idx, MI355DR_E_INVALID, "i8_min_budget_x100 must be in 1..1000");
-        idx->i8_min_budget = (double)value / 100.0;
-    } else if (k == "maxsim_screen") {
-        idx->maxsim_screen = value != 0;
-    } else if (k == "maxsim_coop") {
-        if (value < -1 || value > 1) return fail(idx, MI355DR_E_INVALID, "maxsim_coop must be -1 (by document length), 0 or 1");
-        idx->maxsim_coop = (int)value;
-    } else if (k == "maxsim_persistent") {
-        idx->maxsim_persistent = value != 0;
-    } else if (k == "maxsim_wg") {
-        if (value < -1 || value > 2) return fail(idx, MI355DR_E_INVALID, "maxsim_wg must be -1 (by document length), 0, 1 or 2");
-        idx->maxsim_wg = (int)value;
-    } else if (k == "maxsim_tighten") {
-        idx->maxsim_tighten = value != 0;
-    } else if (k == "maxsim_aligned") {
-        idx->maxsim_aligned = value != 0;
-    } else if (k == "maxsim_wg_min") {
-        if (value < 8 || value > 9) return fail(idx, MI355DR_E_INVALID, "maxsim_wg_min must be 8 or 9");
-        idx->maxsim_wg_min = (int)value;
-    } else if (k == "maxsim_wg_pipe") {
-        idx->maxsim_wg_pipe = value != 0;
-    } else if (k == "maxsim_pack8") {
-        if (value < -1 || value > 1) return fail(idx, MI355DR_E_INVALID, "maxsim_pack8 must be -1 (when it pays), 0 or 1");
-        idx->maxsim_pack8 = (int)value;
-    } else if (k == "maxsim_wg_bps") {
-        if (value != 2 && value != 4) return fail(idx, MI355DR_E_INVALID, "maxsim_wg_bps must be 2 or 4");
-        idx->maxsim_wg_bps = (int)value;
-    } else if (k == "maxsim_pass_groups") {
-        if (value < 1 || value > 4) return fail(idx, MI355DR_E_INVALID, "maxsim_pass_groups must be in 1..4");
-        idx->maxsim_pass_groups = (int)value;
-    } else if (k == "row_offset") {
-        idx->row_offset = value;
-    } else if (k == "profile") {
-        idx->profile = value != 0;
-    } else if (k == "chunk0_rows") {
-        if (value < 1) return fail(idx, MI355DR_E_INVALID, "chunk0_rows must be >= 1");
-        idx->chunk0_rows = value;
-        idx->chunk0_set = 1;  // (an explicit first chunk means the emit-all ladder: no starter)
-    } else if (k == "starter") {
-        idx->starter = value != 0;
-    } else if (k == "prune_companion") {
-        idx->prune_companion = value != 0;
-    } else if (k == "scan_dma") {
-        idx->scan_dma = value != 0;
-    } else if (k == "defer_round_b") {
-        idx->defer_round_b = value != 0;
-    } else if (k == "chunk_growth") {
-        if (value < 1) return fail(idx, MI355DR_E_INVALID, "chunk_growth must be >= 1");
-        idx->chunk_growth = value;
-        idx->chunk_growth_set = 1;
-    } else if (k == "screen_stream") {
-        idx->screen_stream = value != 0;
-    } else if (k == "screen_rq") {
-        idx->screen_rq = value != 0;
-    } else if (k == "debug_park_thresholds") {
-        idx->debug_park = value;
-    } else if (k == "screen_rq_split_tests") {
-        idx->screen_rq_split_tests = value != 0;
-    } else if (k == "screen_drift") {
-        if (value < 0 || value > 1024) return fail(idx, MI355DR_E_INVALID, "screen_drift: 0 ... 1024 tiles");
-        idx->screen_drift = (int)value;
-    } else if (k == "small_chunk_rows") {
-        if (value < 0) return fail(idx, MI355DR_E_INVALID, "small_chunk_rows must be >= 0");
-        idx->small_chunk_rows = value;
-    } else if (k == "round_a") {
-        if (value < 0 || value > 64) return fail(idx, MI355DR_E_INVALID, "round_a must be in [0,64]");
-        idx->round_a = (int)value;
-    } else if (k == "prefilter16") {
-        idx->prefilter16 = value != 0;
-    } else if (k == "cand_cap") {
-        if (value < 16 || value > kCandCap) return fail(idx, MI355DR_E_INVALID, "cand_cap must be in [16,2048]");
-        idx->cap = (int)value;
-        idx->cap_set = 1;
-    } else if (k == "prune_wide") {
-        idx->prune_wide = value != 0;
-    } else if (k == "screen_flush_sync") {
-        idx->screen_flush_sync = value != 0;
-    } else if (k == "screen_flush_lanes") {
-        if (value < 1 || value > 64) return fail(idx, MI355DR_E_INVALID, "screen_flush_lanes must be in [1, 64]");
-        idx->screen_flush_lanes = (int)value;
-    } else if (k == "screen_flush_alone") {
-        if (value < 8 || value > 60) return fail(idx, MI355DR_E_INVALID, "screen_flush_alone must be in [8, 60]");
-        idx->screen_flush_alone = (int)value;
-    } else if (k == "wide_inflation_x10") {
-        if (value < 20 || value > 400) return fail(idx, MI355DR_E_INVALID, "wide_inflation_x10 must be in [20, 400]");
-        idx->wide_inflation_x10 = (int)value;
-    } else if (k == "chunk_taper_x100") {
-        if (value != 0 && (value < 100 || value > 300)) return fail(idx, MI355DR_E_INVALID, "chunk_taper_x100 must be 0 (auto) or in [100, 300]");
-        idx->chunk_taper_x100 = (int)value;
-    } else if (k == "starter_rows_wide") {
-        if (value < 4096 || value > 262144) return fail(idx, MI355DR_E_INVALID, "starter_rows_wide must be in [4096, 262144]");
-        idx->starter_rows_wide = value;
-    } else {
-        return fail(idx, MI355DR_E_INVALID, "unknown option: " + k);
+    for (const Option& o : kOptions) {
+        if (strcmp(o.key, key) != 0) continue;
+        if (value < o.lo || value > o.hi || (value > o.gap_lo && value < o.gap_hi)) {
+            std::string range = o.hi == INT64_MAX ? " must be >= " + std::to_string(o.lo)
+                                                  : " must be in [" + std::to_string(o.lo) + ", " + std::to_string(o.hi) + "]";
+            if (o.gap_lo < o.gap_hi) range += ", not between " + std::to_string(o.gap_lo) + " and " + std::to_string(o.gap_hi);
+            return fail(idx, MI355DR_E_INVALID, o.key + range);
+        }
+        o.field.set(idx, value);
+        if (o.then) o.then(idx);
+        return MI355DR_OK;
     }
-    return MI355DR_OK;
+    return fail(idx, MI355DR_E_INVALID, std::string("unknown option: ") + key);
 }
 
 int mi355dr_get_stat(mi355dr_index* idx, const char* key, int64_t* out) {
     if (!idx || !key || !out) return fail(idx, MI355DR_E_INVALID, "null argument");
     std::lock_guard<std::mutex> g(idx->mu);
     const std::string k(key);
-    if (k == "candidates" || k == "rescored") {
+    if (k == "candidates" || k == "rescored") {  // the two counters the prunes keep on the device, per query
         unsigned long long v[2] = {0, 0};
         if (idx->stat_dev) {
             std::vector<unsigned long long> per(2 * kQBlockMax);
@@ -1395,50 +1348,21 @@ int mi355dr_get_stat(mi355dr_index* idx, const char* key, int64_t* out) {
             }
         }
         *out = (int64_t)(k == "candidates" ? v[0] : v[1]);
-    } else if (k == "screen_launches") *out = idx->s_screen_launches;
-    else if (k == "screen_ns") *out = idx->s_screen_ns;
-    else if (k == "screen_rows") *out = idx->s_screen_rows;
-    else if (k == "screen256_launches") *out = idx->s_big_launches;
-    else if (k == "screen_rq_launches") *out = idx->s_rq_launches;
-    else if (k == "screen256_ns") *out = idx->s_big_ns;
-    else if (k == "screen256_rows") *out = idx->s_big_rows;
-    else if (k == "fallback_queries") *out = idx->s_fallback_queries;
-    else if (k == "chunks") *out = idx->s_chunks;
-    else if (k == "passes") *out = idx->s_passes;
-    else if (k == "starters") *out = idx->s_starters;
-    else if (k == "retry_queries") *out = idx->s_retry_queries;
-    else if (k == "i8_demoted") *out = idx->i8_demoted_k != INT_MAX ? 1 : 0;
-    else if (k == "i8_demoted_k") *out = idx->i8_demoted_k == INT_MAX ? 0 : idx->i8_demoted_k;
-    else if (k == "maxsim_screened") *out = idx->s_ms_screened;
-    else if (k == "maxsim_candidates") *out = idx->s_ms_candidates;
-    else if (k == "maxsim_fallbacks") *out = idx->s_ms_fallbacks;
-    else if (k == "maxsim_screen_ns") *out = idx->s_ms_screen_ns;
-    else if (k == "maxsim_pack_ns") *out = idx->s_ms_pack_ns;
-    else if (k == "maxsim_screen_launches") *out = idx->s_ms_screen_launches;
-    else if (k == "maxsim_exact_ns") *out = idx->s_ms_exact_ns;
-    else if (k == "maxsim_exact_launches") *out = idx->s_ms_exact_launches;
-    else if (k == "maxsim_screen_cols") *out = idx->s_ms_screen_cols;
-    else if (k == "maxsim_packed_launches") *out = idx->s_ms_packed_launches;
-    else if (k == "maxsim_packed_blocks") *out = idx->s_ms_packed_blocks;
-    else if (k == "maxsim_packed_built") *out = idx->s_ms_packed_built;
-    else if (k == "irregular_rows") *out = idx->irr_n;
-    else if (k == "loose_rows") *out = idx->irr8_n;
-    else if (k == "dead_rows") *out = idx->dead_n;
-    else if (k == "screen_dtype_active") *out = use_i8(idx) ? MI355DR_SCREEN_I8 : MI355DR_SCREEN_BF16;
-    else if (k == "hbm_bytes_resident")
-        *out = idx->cap_rows * ((int64_t)idx->dim * 4 + (int64_t)idx->dpad * 2 + (int64_t)idx->dpad8 + 5) +
-               idx->cap_rows / kI8GroupRows * (int64_t)sizeof(I8Group);
-    else return fail(idx, MI355DR_E_INVALID, "unknown stat: " + k);
-    return MI355DR_OK;
+        return MI355DR_OK;
+    }
+    for (const Stat& st : kStats) {
+        if (k != st.key) continue;
+        *out = st.counter ? idx->*st.counter : st.value(idx);
+        return MI355DR_OK;
+    }
+    return fail(idx, MI355DR_E_INVALID, "unknown stat: " + k);
 }
 
 int mi355dr_reset_stats(mi355dr_index* idx) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
-    idx->s_screen_launches = idx->s_screen_ns = idx->s_screen_rows = idx->s_fallback_queries = idx->s_chunks =
-        idx->s_passes = idx->s_rq_launches = idx->s_big_launches = idx->s_big_ns = idx->s_big_rows = idx->s_starters = 0;
-    idx->s_ms_screened = idx->s_ms_candidates = idx->s_ms_fallbacks = idx->s_retry_queries = 0;
-    idx->s_ms_screen_ns = idx->s_ms_screen_launches = idx->s_ms_exact_ns = idx->s_ms_exact_launches = idx->s_ms_screen_cols = idx->s_ms_pack_ns = idx->s_ms_packed_launches = 0;
+    for (const Stat& st : kStats)
+        if (st.reset) idx->*st.counter = 0;
     if (idx->stat_dev) {
         HIPCHECK(idx, hipSetDevice(idx->device));
         HIPCHECK(idx, hipMemset(idx->stat_dev, 0, 2 * kQBlockMax * sizeof(unsigned long long)));
@@ -1500,13 +1424,8 @@ int mi355dr_debug_screen_dense(mi355dr_index* idx, const float* queries, int B, 
     if (B <= 0 || B > kQBlockMax || n <= 0 || n > kCandCap || row0 < 0 || row0 % screen_tile(B) != 0 || row0 + n > idx->n)
         return fail(idx, MI355DR_E_INVALID,
                     "debug_screen_dense: need 1<=B<=1024, 1<=n<=2048, row0 a multiple of the tile (128; 256 if B>128)");
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
-    CHECK(ensure_qstate(idx));
+    CHECK(upload_and_prep(idx, queries, B, /*metric=*/2));  // test hook: thresholds at -inf for every query
     hipStream_t s = idx->stream;
-    HIPCHECK(idx, hipMemcpyAsync(idx->qdev, queries, (size_t)B * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
-    const int Bpad = (int)round_up(B, screen_tile(B));
-    CHECK(launch_prep(idx, s, B, Bpad, /*metric=*/2));  // test hook: thresholds at -inf for every query
     CHECK(launch_screen(idx, s, B, row0, row0 + n, kCandCap, /*emit_mode=*/0));
     std::vector<int> cnt(B);
     std::vector<int32_t> crow((size_t)B * kCandCap);
@@ -1532,12 +1451,8 @@ int mi355dr_debug_screen_bound(mi355dr_index* idx, const float* queries, int B, 
     if (!idx || !queries || !out_E) return fail(idx, MI355DR_E_INVALID, "null argument");
     std::lock_guard<std::mutex> g(idx->mu);
     if (B <= 0 || B > kQBlockMax) return fail(idx, MI355DR_E_INVALID, "need 1<=B<=1024");
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
-    CHECK(ensure_qstate(idx));
+    CHECK(upload_and_prep(idx, queries, B, idx->metric));
     hipStream_t s = idx->stream;
-    HIPCHECK(idx, hipMemcpyAsync(idx->qdev, queries, (size_t)B * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
-    CHECK(launch_prep(idx, s, B, (int)round_up(B, screen_tile(B)), idx->metric));
     HIPCHECK(idx, hipMemcpyAsync(out_E, idx->st.E, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipStreamSynchronize(s));
     return MI355DR_OK;
@@ -1551,12 +1466,8 @@ int mi355dr_debug_i8_state(mi355dr_index* idx, const float* queries, int B, floa
     if (g0 < 0 || n_groups < 0 || (g0 + n_groups) * kI8GroupRows > idx->cap_rows)
         return fail(idx, MI355DR_E_INVALID, "group range outside the index");
     if (!use_i8(idx)) return fail(idx, MI355DR_E_UNSUPPORTED, "the int8 screen is not active");
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
-    CHECK(ensure_qstate(idx));
+    CHECK(upload_and_prep(idx, queries, B, idx->metric));
     hipStream_t s = idx->stream;
-    HIPCHECK(idx, hipMemcpyAsync(idx->qdev, queries, (size_t)B * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
-    CHECK(launch_prep(idx, s, B, (int)round_up(B, screen_tile(B)), idx->metric));
     HIPCHECK(idx, hipMemcpyAsync(out_sq, idx->st.sc, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipMemcpyAsync(out_kq, idx->st.kq, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, s));
     std::vector<I8Group> gr((size_t)n_groups);
@@ -1579,12 +1490,8 @@ int mi355dr_debug_rescore(mi355dr_index* idx, const float* queries, int B, const
     for (int64_t i = 0; i < n_pairs; ++i)
         if (pair_q[i] < 0 || pair_q[i] >= B || pair_row[i] < 0 || pair_row[i] >= idx->n)
             return fail(idx, MI355DR_E_INVALID, "pair out of range");
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
-    CHECK(ensure_qstate(idx));
+    CHECK(upload_and_prep(idx, queries, B, idx->metric));
     hipStream_t s = idx->stream;
-    HIPCHECK(idx, hipMemcpyAsync(idx->qdev, queries, (size_t)B * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
-    CHECK(launch_prep(idx, s, B, (int)round_up(B, screen_tile(B)), idx->metric));
     DevBuf<int32_t> pq;
     DevBuf<int64_t> pr;
     DevBuf<float> od;

@@ -671,7 +671,7 @@ int ms_launch_screen(const MsSearch& c, const MsPass& p) {
                                  hipMemcpyHostToDevice, s));
     if (idx->profile) {
         for (auto& e : idx->ms_ev)
-            if (!e) HIPCHECK(idx, hipEventCreate(&e));
+            HIPCHECK(idx, e.create());
         HIPCHECK(idx, hipEventRecord(idx->ms_ev[0], s));
     }
     if (nkk == 8) {  // dims <= 128: the compile-time-unrolled forms, only as many column blocks as the pass has

@@ -686,3 +686,136 @@ def test_two_wave_prune_on_adversarial_row_orders(pkg, oracle, k, order):
                 # ~1 460 copies of the best row tie at the k-th place: round B re-scores them by the hundred and every one passes the
                 # buffer's filter (equal images), so the 512-entry exact buffer is re-selected several times per prune
                 assert idx.stat("rescored") / B > 1000, idx.stat("rescored") / B
+
+
+def _same(dist, rows, rd, rr):
+    assert np.array_equal(rows, rr)
+    ok = ~np.isnan(rd)
+    assert np.array_equal(np.isnan(dist), np.isnan(rd)) and np.array_equal(dist[ok].view(np.uint64), rd[ok].view(np.uint64))
+
+
+@pytest.mark.parametrize("metric", ["cosine", "ip"])
+@pytest.mark.parametrize("d", [44, 64])
+def test_growth_across_capacity_boundaries(pkg, oracle, d, metric):
+    """Three adds that regrow the corpus buffers twice (capacity 512 -> 768 -> 2048 rows): the rows, both shadows, the norms, the
+    int8 flags and the group records of the rows stored before are carried into the new blocks -- also the partly filled int8
+    group at the seam (300 = 9 groups of 32 + 12 rows), which the next add completes and requantises.  After every step both
+    screens answer as the oracle does over the rows added so far."""
+    rng = np.random.default_rng(4400 + d)
+    C = rng.standard_normal((2000, d)).astype(np.float32)
+    C *= rng.uniform(0.05, 20.0, size=(2000, 1)).astype(np.float32)
+    Q = rng.standard_normal((5, d)).astype(np.float32)
+    resident = []
+    with pkg.Mi355Index(d, metric) as idx:
+        for n in (300, 700, 2000):
+            idx.add(C[len(idx):n])
+            assert len(idx) == n
+            resident.append(idx.stat("hbm_bytes_resident"))   # (proportional to the capacity)
+            for screen in SCREENS:
+                idx.set_option("screen_dtype", screen)
+                _check(idx, oracle, C[:n], Q, 10, metric)
+        assert idx.stat("fallback_queries") == 0 and idx.stat("passes") >= 6   # the screens answered, not the exact scan
+    assert resident[1] * 512 == resident[0] * 768 and resident[2] * 512 == resident[0] * 2048
+
+
+# option: (default, the first value below and above what it accepts).  Switches (stored as value != 0) and the two options
+# that take any value have no such values.
+OPTIONS = {
+    "path": (0, [-1, 3]), "screen_dtype": (0, [-1, 3]), "i8_min_budget_x100": (25, [0, 1001]), "maxsim_screen": (1, []),
+    "maxsim_coop": (-1, [-2, 2]), "maxsim_persistent": (0, []), "maxsim_wg": (-1, [-2, 3]), "maxsim_tighten": (1, []),
+    "maxsim_aligned": (1, []), "maxsim_wg_min": (8, [7, 10]), "maxsim_wg_pipe": (1, []), "maxsim_pack8": (-1, [-2, 2]),
+    "maxsim_wg_bps": (4, [1, 3, 5]), "maxsim_pass_groups": (4, [0, 5]), "row_offset": (0, []), "profile": (0, []),
+    "chunk0_rows": (1024, [0]), "starter": (1, []), "prune_companion": (1, []), "scan_dma": (1, []), "defer_round_b": (1, []),
+    "chunk_growth": (3, [0]), "screen_stream": (1, []), "screen_rq": (1, []), "debug_park_thresholds": (0, []),
+    "screen_rq_split_tests": (1, []), "screen_drift": (3, [-1, 1025]), "small_chunk_rows": (16384, [-1]),
+    "round_a": (0, [-1, 65]), "prefilter16": (0, []), "cand_cap": (2048, [15, 2049]), "prune_wide": (1, []),
+    "screen_flush_sync": (1, []), "screen_flush_lanes": (48, [0, 65]), "screen_flush_alone": (40, [7, 61]),
+    "wide_inflation_x10": (100, [19, 401]), "chunk_taper_x100": (0, [-1, 1, 50, 99, 301]),
+    "starter_rows_wide": (65536, [4095, 262145]),
+}
+STATS = ["candidates", "rescored", "screen_launches", "screen_ns", "screen_rows", "screen256_launches", "screen_rq_launches",
+         "screen256_ns", "screen256_rows", "fallback_queries", "chunks", "passes", "starters", "retry_queries", "i8_demoted",
+         "i8_demoted_k", "maxsim_screened", "maxsim_candidates", "maxsim_fallbacks", "maxsim_screen_ns", "maxsim_pack_ns",
+         "maxsim_screen_launches", "maxsim_exact_ns", "maxsim_exact_launches", "maxsim_screen_cols", "maxsim_packed_launches",
+         "maxsim_packed_blocks", "maxsim_packed_built", "irregular_rows", "loose_rows", "dead_rows", "screen_dtype_active",
+         "hbm_bytes_resident"]
+E_INVALID = -1
+
+
+def test_option_and_stat_surface(pkg, oracle):
+    """Every option takes its default and refuses the first value outside its range with MI355DR_E_INVALID, in a text that names
+    the option; unknown keys are refused; every stat reads; reset_stats zeroes the activity counters and leaves the row classes."""
+    def refused(call, *args, names=None):
+        with pytest.raises(pkg.NativeError) as e:
+            call(*args)
+        assert e.value.code == E_INVALID and (names is None or names in str(e.value)), e.value
+
+    rng = np.random.default_rng(45)
+    n, d = 6000, 64
+    C = rng.standard_normal((n, d)).astype(np.float32)
+    C[7] = 0.0        # an irregular row (and with it a loose one)
+    C[100, 3] = 50.0  # a loose row: one component holds all of it
+    Q = rng.standard_normal((9, d)).astype(np.float32)
+    with pkg.Mi355Index(d) as idx:
+        for key, (default, bad) in OPTIONS.items():
+            for v in bad:
+                refused(idx.set_option, key, v, names=key)
+            idx.set_option(key, default)
+        refused(idx.set_option, "no_such_option", 1, names="no_such_option")
+        refused(idx.stat, "no_such_stat", names="no_such_stat")
+    live = np.setdiff1d(np.arange(n), [11, 12, 13])
+    rd, rr = oracle.topk_search(C[live], Q, 10)
+    with pkg.Mi355Index(d) as idx:   # (a fresh index: setting chunk0_rows / chunk_growth / cand_cap pins the schedule)
+        idx.add(C)
+        idx.remove_rows([11, 12, 13])
+        idx.set_option("cand_cap", 16)   # every list overflows: re-screens, then the exact scan
+        _same(*idx.search(Q, 10), rd, np.where(rr >= 0, live[np.maximum(rr, 0)], -1))
+        before = {key: idx.stat(key) for key in STATS}
+        for key in ("passes", "chunks", "screen_launches", "candidates", "retry_queries"):
+            assert before[key] > 0, key
+        assert (before["irregular_rows"], before["loose_rows"], before["dead_rows"]) == (1, 2, 3)
+        idx.reset_stats()
+        after = {key: idx.stat(key) for key in STATS}
+        kept = ["irregular_rows", "loose_rows", "dead_rows", "maxsim_packed_blocks", "maxsim_packed_built", "i8_demoted",
+                "i8_demoted_k", "screen_dtype_active", "hbm_bytes_resident"]
+        for key in STATS:
+            assert after[key] == (before[key] if key in kept else 0), key
+
+
+def test_create_use_destroy_cycles(pkg, oracle):
+    """Eight indexes created, used and destroyed in one process while another index lives on: every cycle touches each buffer
+    and event the handle creates on demand -- the per-search state, the re-screen levels' buffers and the exact scan behind them
+    (a 16-slot candidate list), the profile events, an asynchronous block, a remove and a debug call -- and the index that
+    lived across all of them still answers as the oracle does."""
+    rng = np.random.default_rng(46)
+    n, d, k = 6000, 64, 10
+    C = rng.standard_normal((n, d)).astype(np.float32)
+    Q = rng.standard_normal((20, d)).astype(np.float32)
+    dead = np.array([5, 64, 4000])
+    live = np.setdiff1d(np.arange(n), dead)
+    rd, rr = oracle.topk_search(C, Q, k)
+    ld, lr = oracle.topk_search(C[live], Q, k)
+    lr = np.where(lr >= 0, live[np.maximum(lr, 0)], -1)
+    with pkg.Mi355Index(d) as keeper:
+        keeper.add(C)
+        _same(*keeper.search(Q, k), rd, rr)
+        for _ in range(8):
+            with pkg.Mi355Index(d) as idx:
+                idx.add(C)
+                idx.set_option("profile", 1)
+                idx.set_option("cand_cap", 16)
+                _same(*idx.search(Q, k), rd, rr)
+                assert idx.stat("retry_queries") > 0 and idx.stat("fallback_queries") > 0 and idx.stat("screen_ns") > 0
+                pq, od, orr = idx.dev_alloc(Q.nbytes), idx.dev_alloc(len(Q) * k * 8), idx.dev_alloc(len(Q) * k * 8)
+                idx.dev_upload(pq, Q)
+                idx.search_wait(idx.search_device_async(pq, len(Q), k, od, orr))
+                gd, gr = np.empty((len(Q), k)), np.empty((len(Q), k), dtype=np.int64)
+                idx.dev_download(od, gd)
+                idx.dev_download(orr, gr)
+                _same(gd, gr, rd, rr)
+                idx.remove_rows(dead)
+                _same(*idx.search(Q, k), ld, lr)
+                assert np.isfinite(idx.debug_screen_bound(Q)).all()
+                for p in (pq, od, orr):
+                    idx.dev_free(p)
+        _same(*keeper.search(Q, k), rd, rr)
