@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "mi355dr_update_rows", "mi355dr_update_rows_device", "mi355dr_remove_rows", "mi355dr_live_rows",
     "mi355dr_search", "mi355dr_search_device", "mi355dr_search_device_async", "mi355dr_search_wait", "mi355dr_add_multivec", "mi355dr_size_multivec",
     "mi355dr_search_maxsim", "mi355dr_search_maxsim_device", "mi355dr_maxsim_subset", "mi355dr_maxsim_subset_ex", "mi355dr_add_multivec_device", "mi355dr_gqr_refine", "mi355dr_gqr_refine_maxsim",
+    "mi355dr_set_multivec", "mi355dr_set_multivec_device", "mi355dr_live_multivec",
     "mi355dr_gqr_refine_scores", "mi355dr_merge_topk_device", "mi355dr_pack_topk_device",
     "mi355dr_merge_topk_packed_device", "mi355dr_comm_unique_id", "mi355dr_comm_init", "mi355dr_comm_world", "mi355dr_comm_count", "mi355dr_comm_init_custom",
     "mi355dr_search_sharded_device", "mi355dr_set_option", "mi355dr_get_stat",
@@ -136,6 +137,12 @@ def load() -> ctypes.CDLL:
     L.mi355dr_maxsim_subset_ex.argtypes = [vp, f32p, i32p, c_int, i64p, c_int, c_int, f32p]
     L.mi355dr_add_multivec_device.restype = c_int
     L.mi355dr_add_multivec_device.argtypes = [vp, vp, i64p, i64]
+    L.mi355dr_set_multivec.restype = c_int
+    L.mi355dr_set_multivec.argtypes = [vp, i64p, f32p, i64p, i64]
+    L.mi355dr_set_multivec_device.restype = c_int
+    L.mi355dr_set_multivec_device.argtypes = [vp, i64p, vp, i64p, i64]
+    L.mi355dr_live_multivec.restype = i64
+    L.mi355dr_live_multivec.argtypes = [vp]
     c_double = ctypes.c_double
     L.mi355dr_gqr_refine.restype = c_int
     L.mi355dr_gqr_refine.argtypes = [vp, f64p, c_int, i64p, c_int, f64p, c_int, c_double, c_double, c_double, f64p]

@@ -238,6 +238,8 @@ struct mi355dr_index {
     int64_t s_ms_packed_launches = 0;  // screen launches that took the granule-packed copy (k_maxsim_wg8.h)
     int64_t s_ms_packed_blocks = 0;    // ... and the 32-token blocks of that copy (0: none built)
     int64_t s_ms_packed_built = 0;     // blocks k_ms_pack8 has written since the index was created (a store that grows is packed from its new granules on)
+    int64_t s_ms_set_docs = 0;         // documents rewritten by mi355dr_set_multivec ...
+    int64_t s_ms_moved_blocks = 0;     // ... and the blocks its relayouts copied (k_ms_relayout; the in-place path moves none)
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
     mi355::EventPairs ev_pool, ev_pending;
@@ -265,6 +267,7 @@ namespace mi355 {
 
 int fail(mi355dr_index* idx, int code, const std::string& msg);  // mi355dr.hip
 void multivec_destroy(mi355dr_index* idx);                       // mi355dr_maxsim.hip
+int64_t multivec_bytes(const mi355dr_index* idx);                // mi355dr_maxsim.hip: stat "hbm_bytes_resident"
 void comm_destroy(mi355dr_index* idx);                           // mi355dr_comm.hip
 // read-only view of the multi-vector store for kernels outside mi355dr_maxsim.hip (GQR refinement)
 struct MultiVecView {

@@ -854,7 +854,7 @@ int check_search_args(mi355dr_index* idx, const void* q, int B, int k, const voi
 
 extern "C" {
 
-int mi355dr_version(void) { return 101; }
+int mi355dr_version(void) { return 102; }
 
 const char* mi355dr_last_error(const mi355dr_index* idx) {
     if (idx) return idx->err.c_str();
@@ -1297,6 +1297,8 @@ const Stat kStats[] = {
     {"maxsim_packed_launches", &Index::s_ms_packed_launches, true},
     {"maxsim_packed_blocks", &Index::s_ms_packed_blocks, false},  // (the packed copy's size and its build history: state, not activity)
     {"maxsim_packed_built", &Index::s_ms_packed_built, false},
+    {"maxsim_set_docs", &Index::s_ms_set_docs, true},
+    {"maxsim_moved_blocks", &Index::s_ms_moved_blocks, true},
     {"i8_demoted", nullptr, false, [](const Index* x) -> int64_t { return x->i8_demoted_k != INT_MAX ? 1 : 0; }},
     {"i8_demoted_k", nullptr, false, [](const Index* x) -> int64_t { return x->i8_demoted_k == INT_MAX ? 0 : x->i8_demoted_k; }},
     {"irregular_rows", nullptr, false, [](const Index* x) -> int64_t { return x->irr_n; }},
@@ -1305,7 +1307,7 @@ const Stat kStats[] = {
     {"screen_dtype_active", nullptr, false, [](const Index* x) -> int64_t { return use_i8(x) ? MI355DR_SCREEN_I8 : MI355DR_SCREEN_BF16; }},
     {"hbm_bytes_resident", nullptr, false, [](const Index* x) -> int64_t {
          return x->cap_rows * ((int64_t)x->dim * 4 + (int64_t)x->dpad * 2 + (int64_t)x->dpad8 + 5) +
-                x->cap_rows / kI8GroupRows * (int64_t)sizeof(I8Group);
+                x->cap_rows / kI8GroupRows * (int64_t)sizeof(I8Group) + multivec_bytes(x);
      }},
 };
 }  // namespace

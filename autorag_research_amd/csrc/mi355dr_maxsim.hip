@@ -57,7 +57,9 @@ struct MultiVecStore {
     DevBuf<int64_t> blk_off;       // [cap_docs+1] first block of each doc (device)
     std::vector<int64_t> blk_off_host;
     std::vector<int32_t> tok_cnt_host;  // [n_docs] token vectors of each doc (the padded copies do not keep it)
+    int64_t n_live = 0;                 // docs that have vectors (a removed doc is a doc without: mi355dr_set_multivec)
     // the granule-packed bf16 copy of k_maxsim_wg8.h: a second shadow, built on first use (ms_pack8_ensure), stale after an add
+    // (extended by the next pass that takes it) and after a set (pack_docs = -1: packed whole)
     DevBuf<uint4> tok16p;          // [pack_cap_blocks * nkk * 64]
     DevBuf<int64_t> goff;          // [pack_cap_docs + 1] first 8-token granule of each doc (device)
     int64_t pack_docs = -1;        // n_docs the copy was built (or judged) for; -1: never
@@ -96,6 +98,13 @@ bool multivec_view(const mi355dr_index* idx, MultiVecView* out) {
     out->dpad = m->dpad;
     out->n_docs = m->n_docs;
     return true;
+}
+
+// device bytes of the store's images, offset table and granule-packed copy as they are allocated now (the buffers' own sizes: a
+// relayout's swap, a regrow and a released packed copy are all reflected)
+int64_t multivec_bytes(const mi355dr_index* idx) {
+    const MultiVecStore* m = idx->mv;
+    return m ? (int64_t)(m->tok.bytes + m->tok16.bytes + m->blk_off.bytes + m->tok16p.bytes + m->goff.bytes) : 0;
 }
 
 void multivec_destroy(mi355dr_index* idx) {
@@ -152,9 +161,111 @@ int ms_reserve(mi355dr_index* idx, MultiVecStore* m, int64_t want_blocks, int64_
     return MI355DR_OK;
 }
 
-// A host add stages its vectors on the device in slices of whole documents of at most this many bytes (a longer document goes
-// alone) and builds slice by slice: the device memory an add needs beyond the store does not grow with the call.
+// A host payload is staged on the device in slices of whole documents of at most this many bytes (a longer document goes
+// alone) and built slice by slice: the device memory a call needs beyond the store does not grow with the call.
 constexpr size_t kMsAddSliceBytes = (size_t)32 << 20;
+
+// The documents of one call whose images are to be written: the ONE slice loop behind add and set.
+struct MsBuild {
+    const float* vecs;        // [.., dim] on the host, or (on_device) on the index's GPU, read in place
+    const int64_t* offsets;   // [n + 1]: document j owns rows offsets[j] .. offsets[j + 1] of vecs
+    int64_t n;
+    bool on_device;
+    int64_t blk_base;         // add: the documents' blocks follow each other from this block on (k_ms_build) ...
+    const int64_t* doc_dst0;  // ... set: [n] the first destination block of every document (k_ms_build_at); nullptr for an add
+    float* tok;               // the images that are written into
+    uint16_t* tok16;
+};
+
+// k_ms_build(_at) per slice of whole docs [i0, i1): a device payload is one slice read in place, a host payload's slices are
+// staged.  Every buffer is allocated before the first block is written (an allocation that fails has changed no image), and the
+// call is complete on return: st = the three maxima of the built tokens (double bit patterns) and (int) their not-finite flag.
+int ms_build_docs(mi355dr_index* idx, const MultiVecStore* m, const MsBuild& j, unsigned long long st[4]) {
+    const int d = idx->dim;
+    const int64_t* offsets = j.offsets;
+    hipStream_t s = idx->stream;
+    auto blocks_of = [&](int64_t i) { return (offsets[i + 1] - offsets[i] + kMsBlkRows - 1) / kMsBlkRows; };
+    const int64_t slice_rows = j.on_device ? INT64_MAX : std::max<int64_t>(1, (int64_t)(kMsAddSliceBytes / ((size_t)d * sizeof(float))));
+    std::vector<int64_t> ends;  // i1 of every slice
+    size_t max_bytes = 0, max_docs = 0, max_blocks = 0;
+    for (int64_t i0 = 0, i1; i0 < j.n; i0 = i1) {
+        int64_t rows = 0, blocks = 0;  // (a doc without vectors counts as one row: the tables of a slice are bounded like its vectors)
+        for (i1 = i0; i1 < j.n && (i1 == i0 || rows + std::max<int64_t>(offsets[i1 + 1] - offsets[i1], 1) <= slice_rows); ++i1) {
+            rows += std::max<int64_t>(offsets[i1 + 1] - offsets[i1], 1);
+            blocks += blocks_of(i1);
+        }
+        ends.push_back(i1);
+        if (blocks == 0) continue;
+        max_bytes = std::max(max_bytes, (size_t)(offsets[i1] - offsets[i0]) * d * sizeof(float));
+        max_docs = std::max(max_docs, (size_t)(i1 - i0));
+        max_blocks = std::max(max_blocks, (size_t)blocks);
+    }
+    DevBuf<float> stage;
+    DevBuf<int64_t> tok0_dev, T_dev, blk0_dev, dst0_dev;
+    DevBuf<int32_t> blk_doc_dev;
+    DevBuf<unsigned long long> stats;  // [3] the maxima of the build kernels, then (int) their not-finite flag
+    HIPCHECK(idx, stats.grow(4 * sizeof(unsigned long long)));
+    if (!j.on_device) HIPCHECK(idx, stage.grow(max_bytes));
+    HIPCHECK(idx, tok0_dev.grow(max_docs * sizeof(int64_t)));
+    HIPCHECK(idx, T_dev.grow(max_docs * sizeof(int64_t)));
+    HIPCHECK(idx, blk0_dev.grow(max_docs * sizeof(int64_t)));
+    if (j.doc_dst0) HIPCHECK(idx, dst0_dev.grow(max_docs * sizeof(int64_t)));
+    HIPCHECK(idx, blk_doc_dev.grow(max_blocks * sizeof(int32_t)));
+    HIPCHECK(idx, hipMemsetAsync(stats.p, 0, stats.bytes, s));
+    std::vector<int64_t> tok0, T, blk0;  // of the slice's docs: first token in `src`, tokens, first block in the slice
+    std::vector<int32_t> blk_doc;        // of the slice's blocks: doc in the slice
+    int64_t blk_base = j.blk_base, i0 = 0;
+    for (const int64_t i1 : ends) {
+        tok0.clear(), T.clear(), blk0.clear(), blk_doc.clear();
+        const int64_t t_base = j.on_device ? 0 : offsets[i0];
+        for (int64_t i = i0; i < i1; ++i) {
+            tok0.push_back(offsets[i] - t_base);
+            T.push_back(offsets[i + 1] - offsets[i]);
+            blk0.push_back((int64_t)blk_doc.size());
+            blk_doc.insert(blk_doc.end(), (size_t)blocks_of(i), (int32_t)(i - i0));
+        }
+        const int64_t first = i0;
+        i0 = i1;
+        if (blk_doc.empty()) continue;
+        const float* src = j.vecs;
+        if (!j.on_device) {
+            const size_t bytes = (size_t)(offsets[i1] - offsets[first]) * d * sizeof(float);
+            HIPCHECK(idx, hipMemcpyAsync(stage.p, j.vecs + offsets[first] * d, bytes, hipMemcpyHostToDevice, s));
+            src = stage.p;
+        }
+        const size_t nd = (size_t)(i1 - first) * sizeof(int64_t);
+        HIPCHECK(idx, hipMemcpyAsync(tok0_dev.p, tok0.data(), nd, hipMemcpyHostToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(T_dev.p, T.data(), nd, hipMemcpyHostToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(blk0_dev.p, blk0.data(), nd, hipMemcpyHostToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(blk_doc_dev.p, blk_doc.data(), blk_doc.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (j.doc_dst0) {
+            HIPCHECK(idx, hipMemcpyAsync(dst0_dev.p, j.doc_dst0 + first, nd, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_ms_build_at, dim3((unsigned)blk_doc.size()), dim3(64), 0, s, src, tok0_dev.p, T_dev.p, blk_doc_dev.p,
+                               blk0_dev.p, dst0_dev.p, d, m->dpad, m->nkk, j.tok, j.tok16, stats.p, (int*)(stats.p + 3));
+        } else {
+            hipLaunchKernelGGL(k_ms_build, dim3((unsigned)blk_doc.size()), dim3(64), 0, s, src, tok0_dev.p, T_dev.p, blk_doc_dev.p,
+                               blk0_dev.p, d, m->dpad, m->nkk, blk_base, j.tok, j.tok16, stats.p, (int*)(stats.p + 3));
+        }
+        HIPCHECK(idx, hipGetLastError());
+        HIPCHECK(idx, hipStreamSynchronize(s));  // (the host tables and the staging buffer are rewritten for the next slice)
+        blk_base += (int64_t)blk_doc.size();
+    }
+    HIPCHECK(idx, hipMemcpyAsync(st, stats.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    return MI355DR_OK;
+}
+
+// the bound quantities only ever move in the conservative direction: the maxima grow, `finite` turns false
+void ms_commit_bounds(MultiVecStore* m, const unsigned long long st[4]) {
+    double v[3];
+    memcpy(v, st, sizeof(v));
+    int nf;
+    memcpy(&nf, &st[3], sizeof(nf));
+    m->tok_norm_max = std::max(m->tok_norm_max, v[0]);
+    m->tok16_norm_max = std::max(m->tok16_norm_max, v[1]);
+    m->tok_res_max = std::max(m->tok_res_max, v[2]);
+    if (nf) m->finite = false;
+}
 
 // vecs: [offsets[n_docs], dim] on the host, or (on_device) on the index's GPU.  All or nothing: room for the whole call is
 // reserved first (what is stored is carried over, the device offset table included), the images of the new blocks and the new
@@ -177,7 +288,6 @@ int ms_add(mi355dr_index* idx, const float* vecs, const int64_t* offsets, int64_
     }
     MultiVecStore* m = idx->mv;
     if (m->n_docs + n_docs >= ((int64_t)1 << 31)) return fail(idx, MI355DR_E_UNSUPPORTED, "too many docs");
-    const int d = idx->dim;
     auto blocks_of = [&](int64_t i) { return (offsets[i + 1] - offsets[i] + kMsBlkRows - 1) / kMsBlkRows; };
     // the table with the new docs' block offsets, built on the side
     std::vector<int64_t> table(m->blk_off_host);
@@ -186,69 +296,153 @@ int ms_add(mi355dr_index* idx, const float* vecs, const int64_t* offsets, int64_
     for (int64_t i = 0; i < n_docs; ++i) table.push_back(m->n_blocks + (new_blocks += blocks_of(i)));
     CHECK(ms_reserve(idx, m, m->n_blocks + new_blocks, m->n_docs + n_docs));
     hipStream_t s = idx->stream;
-    DevBuf<float> stage;
-    DevBuf<int64_t> tok0_dev, T_dev, blk0_dev;
-    DevBuf<int32_t> blk_doc_dev;
-    DevBuf<unsigned long long> stats;  // [3] the maxima of k_ms_build, then (int) its not-finite flag
-    HIPCHECK(idx, stats.grow(4 * sizeof(unsigned long long)));
-    HIPCHECK(idx, hipMemsetAsync(stats.p, 0, stats.bytes, s));
-    // k_ms_build per slice of whole docs [i0, i1): a device add is one slice read in place, a host add's slices are staged
-    const int64_t slice_rows = on_device ? INT64_MAX : std::max<int64_t>(1, (int64_t)(kMsAddSliceBytes / ((size_t)d * sizeof(float))));
-    std::vector<int64_t> tok0, T, blk0;  // of the slice's docs: first token in `src`, tokens, first block in the slice
-    std::vector<int32_t> blk_doc;        // of the slice's blocks: doc in the slice
-    int64_t blk_base = m->n_blocks;
-    for (int64_t i0 = 0, i1; i0 < n_docs; i0 = i1) {
-        tok0.clear(), T.clear(), blk0.clear(), blk_doc.clear();
-        const int64_t t_base = on_device ? 0 : offsets[i0];
-        int64_t rows = 0;  // (a doc without vectors counts as one: the tables of a slice are bounded like its vectors)
-        for (i1 = i0; i1 < n_docs && (i1 == i0 || rows + std::max<int64_t>(offsets[i1 + 1] - offsets[i1], 1) <= slice_rows); ++i1) {
-            rows += std::max<int64_t>(offsets[i1 + 1] - offsets[i1], 1);
-            tok0.push_back(offsets[i1] - t_base);
-            T.push_back(offsets[i1 + 1] - offsets[i1]);
-            blk0.push_back((int64_t)blk_doc.size());
-            blk_doc.insert(blk_doc.end(), (size_t)blocks_of(i1), (int32_t)(i1 - i0));
-        }
-        if (blk_doc.empty()) continue;
-        const float* src = vecs;
-        if (!on_device) {
-            const size_t bytes = (size_t)(offsets[i1] - offsets[i0]) * d * sizeof(float);
-            if (bytes > stage.bytes) stage.release();  // (its contents are dead: the old block does not add to the peak)
-            HIPCHECK(idx, stage.grow(bytes));
-            HIPCHECK(idx, hipMemcpyAsync(stage.p, vecs + offsets[i0] * d, bytes, hipMemcpyHostToDevice, s));
-            src = stage.p;
-        }
-        const size_t nd = (size_t)(i1 - i0) * sizeof(int64_t);
-        HIPCHECK(idx, tok0_dev.grow(nd));
-        HIPCHECK(idx, T_dev.grow(nd));
-        HIPCHECK(idx, blk0_dev.grow(nd));
-        HIPCHECK(idx, blk_doc_dev.grow(blk_doc.size() * sizeof(int32_t)));
-        HIPCHECK(idx, hipMemcpyAsync(tok0_dev.p, tok0.data(), nd, hipMemcpyHostToDevice, s));
-        HIPCHECK(idx, hipMemcpyAsync(T_dev.p, T.data(), nd, hipMemcpyHostToDevice, s));
-        HIPCHECK(idx, hipMemcpyAsync(blk0_dev.p, blk0.data(), nd, hipMemcpyHostToDevice, s));
-        HIPCHECK(idx, hipMemcpyAsync(blk_doc_dev.p, blk_doc.data(), blk_doc.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_ms_build, dim3((unsigned)blk_doc.size()), dim3(64), 0, s, src, tok0_dev.p, T_dev.p, blk_doc_dev.p,
-                           blk0_dev.p, d, m->dpad, m->nkk, blk_base, m->tok.p, (uint16_t*)m->tok16.p, stats.p, (int*)(stats.p + 3));
-        HIPCHECK(idx, hipGetLastError());
-        HIPCHECK(idx, hipStreamSynchronize(s));  // (the host tables and the staging buffer are rewritten for the next slice)
-        blk_base += (int64_t)blk_doc.size();
-    }
     unsigned long long st[4] = {0, 0, 0, 0};
-    HIPCHECK(idx, hipMemcpyAsync(st, stats.p, sizeof(st), hipMemcpyDeviceToHost, s));
+    CHECK(ms_build_docs(idx, m, MsBuild{vecs, offsets, n_docs, on_device, m->n_blocks, nullptr, m->tok.p, (uint16_t*)m->tok16.p}, st));
     HIPCHECK(idx, hipMemcpyAsync(m->blk_off.p, table.data(), table.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIPCHECK(idx, hipStreamSynchronize(s));
     // ---- commit (nothing below fails; until here a search saw the store as it was: entries past n_docs / n_blocks are not read)
-    double v[3];
-    memcpy(v, st, sizeof(v));
-    int nf;
-    memcpy(&nf, &st[3], sizeof(nf));
     m->blk_off_host.swap(table);
-    m->tok_norm_max = std::max(m->tok_norm_max, v[0]);
-    m->tok16_norm_max = std::max(m->tok16_norm_max, v[1]);
-    m->tok_res_max = std::max(m->tok_res_max, v[2]);
-    if (nf) m->finite = false;
-    for (int64_t i = 0; i < n_docs; ++i) m->tok_cnt_host.push_back((int32_t)(offsets[i + 1] - offsets[i]));
+    ms_commit_bounds(m, st);
+    for (int64_t i = 0; i < n_docs; ++i) {
+        m->tok_cnt_host.push_back((int32_t)(offsets[i + 1] - offsets[i]));
+        m->n_live += offsets[i + 1] > offsets[i] ? 1 : 0;
+    }
     m->n_blocks += new_blocks;
     m->n_docs += n_docs;
+    return MI355DR_OK;
+}
+
+// A set makes the granule-packed copy (tok16p, goff) stale as a whole: its incremental branch knows appended documents only, so
+// the next pass that takes it packs it anew (pack_docs = -1) and none reads it before (pack_use).  The stat "maxsim_packed_blocks"
+// reads 0 (none built for these contents) until ms_pack8_ensure has packed again -- if it decides not to, it stays 0.  `release`:
+// the copy's memory goes too.
+void ms_pack8_stale(mi355dr_index* idx, MultiVecStore* m, bool release) {
+    m->pack_docs = -1;
+    m->pack_use = false;
+    m->pack_blocks = 0;
+    idx->s_ms_packed_blocks = 0;
+    if (!release) return;
+    m->tok16p.release();
+    m->pack_cap_blocks = 0;
+}
+
+// ---- replace / remove documents in place (mi355dr_set_multivec) ----
+// Document doc_ids[j] takes the vectors offsets[j] .. offsets[j + 1] (none: the document is removed -- a document without vectors,
+// the state every reader already skips).  Two write paths, chosen per call:
+//   in place   no touched document changes its block count: its blocks of the live images are rewritten (k_ms_build_at), nothing
+//              else is read or written.  O(touched blocks).
+//   relayout   some block count changes, so everything behind it shifts: a new cumulative table on the host, FRESH tok / tok16
+//              buffers (ms_reserve's capacity policy), the untouched documents' blocks moved by k_ms_relayout (one run per maximal
+//              stretch of untouched documents), the touched documents' blocks built from the new vectors, the buffers and the
+//              device table swapped at the commit.  One device pass over the store; peak = one extra copy of both images until
+//              the call returns.
+// All or nothing: arguments are checked before anything is touched, every allocation is made before the first write, and
+// n_blocks, both offset tables, the token counts, the maxima and (relayout) the buffers change at a commit that cannot fail.  The
+// in-place path writes the touched blocks of the live images before that commit: what can still fail then is a copy or a launch
+// on the stream (MI355DR_E_HIP, a broken device), never an allocation.
+int ms_set(mi355dr_index* idx, const int64_t* doc_ids, const float* vecs, const int64_t* offsets, int64_t n, bool on_device) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (n < 0 || (n > 0 && (!doc_ids || !offsets))) return fail(idx, MI355DR_E_INVALID, "bad set_multivec arguments");
+    if (n == 0) return MI355DR_OK;
+    MultiVecStore* m = idx->mv;
+    if (!m || m->n_docs == 0) return fail(idx, MI355DR_E_INVALID, "set_multivec: the index has no multi-vector store");
+    for (int64_t j = 0; j < n; ++j)
+        if (offsets[j + 1] < offsets[j]) return fail(idx, MI355DR_E_INVALID, "offsets must be non-decreasing");
+    if (offsets[n] > offsets[0] && !vecs) return fail(idx, MI355DR_E_INVALID, "null vectors");
+    std::vector<int64_t> order((size_t)n);  // the call's documents by ascending id
+    for (int64_t j = 0; j < n; ++j) {
+        if (doc_ids[j] < 0 || doc_ids[j] >= m->n_docs)
+            return fail(idx, MI355DR_E_INVALID, "set_multivec: document id " + std::to_string(doc_ids[j]) + " out of range");
+        if (offsets[j + 1] - offsets[j] > INT32_MAX) return fail(idx, MI355DR_E_UNSUPPORTED, "too many vectors in one document");
+        order[j] = j;
+    }
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return doc_ids[a] < doc_ids[b]; });
+    for (int64_t r = 1; r < n; ++r)
+        if (doc_ids[order[r]] == doc_ids[order[r - 1]])
+            return fail(idx, MI355DR_E_INVALID, "set_multivec: document id " + std::to_string(doc_ids[order[r]]) + " listed twice");
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    hipStream_t s = idx->stream;
+    const std::vector<int64_t>& old = m->blk_off_host;
+    auto blocks_of = [&](int64_t j) { return (offsets[j + 1] - offsets[j] + kMsBlkRows - 1) / kMsBlkRows; };
+    bool in_place = true;
+    for (int64_t j = 0; j < n && in_place; ++j) in_place = blocks_of(j) == old[doc_ids[j] + 1] - old[doc_ids[j]];
+    std::vector<int64_t> dst0((size_t)n);  // first destination block of every document of the call
+    std::vector<int64_t> table;            // relayout: the new cumulative table
+    DevBuf<float> tok_new;
+    DevBuf<uint4> tok16_new;
+    DevBuf<int64_t> blk_off_new;
+    int64_t cap_new = m->cap_blocks, moved = 0;
+    float* tok_dst = m->tok.p;
+    uint4* tok16_dst = m->tok16.p;
+    if (in_place) {
+        for (int64_t j = 0; j < n; ++j) dst0[j] = old[doc_ids[j]];
+        // (stale before the first block of the live images is rewritten: a copy or launch that fails half-way leaves no pass
+        // reading a packed copy that no longer matches them)
+        ms_pack8_stale(idx, m, false);
+    } else {
+        // the new table and the runs: documents [prev, t) in front of every touched document t, and those behind the last one
+        table.resize(old.size());
+        std::vector<MsRun> runs;
+        int64_t prev = 0;
+        table[0] = 0;
+        auto run_to = [&](int64_t t) {  // untouched documents [prev, t): table entries, one run
+            const int64_t shift = table[prev] - old[prev];
+            for (int64_t i = prev; i < t; ++i) table[i + 1] = old[i + 1] + shift;
+            if (old[t] > old[prev]) runs.push_back(MsRun{table[prev], old[prev], old[t] - old[prev]});
+            moved += old[t] - old[prev];
+        };
+        for (int64_t r = 0; r < n; ++r) {
+            const int64_t j = order[r], t = doc_ids[j];
+            run_to(t);
+            dst0[j] = table[t];
+            table[t + 1] = table[t] + blocks_of(j);
+            prev = t + 1;
+        }
+        run_to(m->n_docs);
+        const int64_t nb = table[m->n_docs];
+        if (nb > cap_new) cap_new = std::max<int64_t>(nb, m->cap_blocks + m->cap_blocks / 2);
+        cap_new = std::max<int64_t>(cap_new, 1);
+        // (the granule-packed copy is stale whatever becomes of this call's images and is packed whole after it: an optional
+        // shadow, it goes before the fresh buffers come and never adds to the peak; a call that fails from here on has cost a repack)
+        ms_pack8_stale(idx, m, true);
+        HIPCHECK(idx, tok_new.grow((size_t)cap_new * kMsBlkRows * m->dpad * sizeof(float)));
+        HIPCHECK(idx, tok16_new.grow((size_t)cap_new * m->nkk * 64 * sizeof(uint4)));
+        HIPCHECK(idx, blk_off_new.grow((size_t)(m->cap_docs + 1) * sizeof(int64_t)));
+        tok_dst = tok_new.p;
+        tok16_dst = tok16_new.p;
+        DevBuf<MsRun> runs_dev;
+        if (!runs.empty()) {
+            HIPCHECK(idx, runs_dev.grow(runs.size() * sizeof(MsRun)));
+            HIPCHECK(idx, hipMemcpyAsync(runs_dev.p, runs.data(), runs.size() * sizeof(MsRun), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_ms_relayout, dim3((unsigned)((nb + kMsRelayoutWaves - 1) / kMsRelayoutWaves)), dim3(64 * kMsRelayoutWaves),
+                               0, s, (const uint4*)m->tok.p, (const uint4*)m->tok16.p, runs_dev.p, (int)runs.size(), nb, m->dpad / 8,
+                               m->nkk, (uint4*)tok_new.p, tok16_new.p);
+            HIPCHECK(idx, hipGetLastError());
+        }
+        HIPCHECK(idx, hipMemcpyAsync(blk_off_new.p, table.data(), table.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        HIPCHECK(idx, hipStreamSynchronize(s));  // (`runs` and its device copy end with this scope)
+    }
+    unsigned long long st[4] = {0, 0, 0, 0};
+    CHECK(ms_build_docs(idx, m, MsBuild{vecs, offsets, n, on_device, 0, dst0.data(), tok_dst, (uint16_t*)tok16_dst}, st));
+    // ---- commit (nothing below fails)
+    if (!in_place) {
+        m->tok.swap(tok_new);  // (the old images are released when this call returns)
+        m->tok16.swap(tok16_new);
+        m->blk_off.swap(blk_off_new);
+        m->blk_off_host.swap(table);
+        m->cap_blocks = cap_new;
+        m->n_blocks = m->blk_off_host[m->n_docs];
+    }
+    ms_commit_bounds(m, st);
+    for (int64_t j = 0; j < n; ++j) {
+        int32_t& cnt = m->tok_cnt_host[doc_ids[j]];
+        const int32_t T = (int32_t)(offsets[j + 1] - offsets[j]);
+        m->n_live += (T > 0 ? 1 : 0) - (cnt > 0 ? 1 : 0);
+        cnt = T;
+    }
+    idx->s_ms_set_docs += n;
+    idx->s_ms_moved_blocks += moved;
     return MI355DR_OK;
 }
 
@@ -1017,7 +1211,17 @@ int mi355dr_add_multivec_device(mi355dr_index* idx, const float* vecs_dev, const
     return ms_add(idx, vecs_dev, offsets, n_docs, true);
 }
 
+int mi355dr_set_multivec(mi355dr_index* idx, const int64_t* doc_ids, const float* vecs, const int64_t* offsets, int64_t n) {
+    return ms_set(idx, doc_ids, vecs, offsets, n, false);
+}
+
+int mi355dr_set_multivec_device(mi355dr_index* idx, const int64_t* doc_ids, const float* vecs_dev, const int64_t* offsets, int64_t n) {
+    return ms_set(idx, doc_ids, vecs_dev, offsets, n, true);
+}
+
 int64_t mi355dr_size_multivec(const mi355dr_index* idx) { return idx && idx->mv ? idx->mv->n_docs : 0; }
+
+int64_t mi355dr_live_multivec(const mi355dr_index* idx) { return idx && idx->mv ? idx->mv->n_live : 0; }
 
 int mi355dr_search_maxsim(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, int k,
                           float* out_dist, int64_t* out_rows) {

@@ -241,6 +241,42 @@ class Mi355Index:
     def n_docs(self) -> int:
         return int(self._lib.mi355dr_size_multivec(self._h))
 
+    # ---- replace / remove documents in place (document ids are stable; include/mi355dr.h "update / remove in place (multi-vector)") ----
+    @staticmethod
+    def _doc_ids_offsets(doc_ids, offsets) -> tuple[np.ndarray, np.ndarray]:
+        ids = np.ascontiguousarray(doc_ids, dtype=np.int64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if ids.ndim != 1 or offsets.ndim != 1 or offsets.shape[0] != ids.shape[0] + 1:
+            raise ValueError("doc_ids must be [n] and offsets [n + 1]")
+        return ids, offsets
+
+    def set_multivec(self, doc_ids, vecs, offsets) -> None:
+        """Document doc_ids[j] takes vecs[offsets[j]:offsets[j + 1]]: later searches see the store an `add_multivec` of the
+        current contents would have built.  No vectors removes the document, vectors revive a removed one.  Ids out of range
+        or repeated, decreasing offsets: NativeError (MI355DR_E_INVALID), nothing changes."""
+        ids, offsets = self._doc_ids_offsets(doc_ids, offsets)
+        vecs = f32c(vecs).reshape(-1, self.dim)
+        if offsets[0] != 0 or offsets[-1] != vecs.shape[0]:
+            raise ValueError("offsets must start at 0 and end at vecs.shape[0]")
+        check(self._h, self._lib.mi355dr_set_multivec(self._h, ptr(ids, ctypes.c_int64), ptr(vecs, ctypes.c_float),
+                                                      ptr(offsets, ctypes.c_int64), ids.shape[0]))
+
+    def set_multivec_device(self, doc_ids, vecs_ptr: int, offsets) -> None:
+        """The same with the new vectors ([offsets[-1], dim] fp32, contiguous) already on this device; ids and offsets stay
+        on the host."""
+        ids, offsets = self._doc_ids_offsets(doc_ids, offsets)
+        check(self._h, self._lib.mi355dr_set_multivec_device(self._h, ptr(ids, ctypes.c_int64), ctypes.c_void_p(int(vecs_ptr)),
+                                                             ptr(offsets, ctypes.c_int64), ids.shape[0]))
+
+    def remove_multivec(self, doc_ids) -> None:
+        """The documents lose their vectors: never returned again by any search; their ids (and every other document's) stay."""
+        ids = np.ascontiguousarray(doc_ids, dtype=np.int64)
+        self.set_multivec(ids, np.zeros((0, self.dim), np.float32), np.zeros(ids.shape[0] + 1, np.int64))
+
+    def live_docs(self) -> int:
+        """n_docs() minus the documents without vectors."""
+        return int(self._lib.mi355dr_live_multivec(self._h))
+
     def search_maxsim(self, qtok, q_offsets, k: int) -> tuple[np.ndarray, np.ndarray]:
         """MaxSim top-k.  Returns (distance float32 [B,k] = -sum_i max_j <q_i,d_j>, doc rows int64 [B,k])."""
         qtok = f32c(qtok)

@@ -260,65 +260,145 @@ class _UnitIndex:
 
     def refresh(self, table: ChunkTable) -> str:
         """Follow a newer export of the same table.  With the same primary keys in the same order (new keys only at the end)
-        the live single-vector index takes the difference alone -- what the reference's `UPDATE ... SET embedding`
+        the live indexes take the difference alone.  The single-vector index -- what the reference's `UPDATE ... SET embedding`
         (orm/service/base_ingestion.py:199-247) and `WHERE embedding IS NOT NULL` (orm/repository/base.py:409-415) make of it:
 
             embedding changed -> update_rows        embedding became NULL -> remove_rows
             NULL became a vector -> update_rows (the slot is revived)     new keys at the end -> add
 
-        Row mapping: an index that was never refreshed holds the NOT NULL rows compacted (`single_rows` = their table
-        positions).  The first refresh that has to change rows switches the unit to ONE SLOT PER TABLE POSITION, NULL rows
+        The multi-vector index (`set_multi_vector_embedding(s_batch)`, orm/repository/base.py:428-485, and `embeddings IS NOT
+        NULL`, :487-535), when it is built and both exports carry the column with the same width:
+
+            token count or token bits changed, vectors lost, vectors regained -> ONE set_multivec (no vectors = removed)
+            new keys at the end -> ONE add_multivec
+
+        A unit with both indexes built takes both differences; one that has only the multi-vector index built takes that one (the
+        single-vector index is built from `table` when it is first asked for, `single_rows` is forgotten, and a change of the
+        embedding column alone is still "incremental": "unchanged" means neither column changed).
+
+        Row mapping: a single-vector index that was never refreshed holds the NOT NULL rows compacted (`single_rows` = their
+        table positions).  The first refresh that has to change rows switches the unit to ONE SLOT PER TABLE POSITION, NULL rows
         being removed slots (`single_rows` = the identity): a compacted index without NULL rows already has that form; one
         built over NULL rows is laid out anew once (the only rebuild on this path), from then on every change is in place.
-        Slots stay in table order either way, so exact distance ties break as in a unit built fresh from `table`.
+        Slots stay in table order either way, so exact distance ties break as in a unit built fresh from `table`.  The
+        multi-vector index always has one document per table position (`multi_rows` = the identity).
 
-        A changed key order, multi-vector data and row-sharded units (one process per GPU) fall back to the full rebuild
-        (close; the next search builds from `table`).  Returns "deferred" (nothing built yet), "unchanged", "incremental",
-        "relayout" or "rebuild"."""
+        A changed key order, a changed width, a multi-vector column that appears or disappears (or one no index was built
+        for) and row-sharded units (one process per GPU) fall back to the full rebuild (close; the next search builds from
+        `table`).  Returns "deferred" (nothing built yet), "unchanged" (neither column changed), "incremental", "relayout" or
+        "rebuild"."""
         old = self.table
         if self.single is None and self.multi is None and self.single_sharded is None and self.multi_sharded is None:
             self.table = table
             self.single_rows = self.multi_rows = None
             self._forget_maps()
             return "deferred"
-        if self.multi is not None or self.multi_sharded is not None or table.mv_offsets is not None or old.mv_offsets is not None:
-            return self._rebuild(table, "multi-vector unit: in-place replace of token rows is not implemented")
+        if table.mv_offsets is not None or old.mv_offsets is not None or self.multi is not None or self.multi_sharded is not None:
+            if self.multi_sharded is not None or self.single_sharded is not None:
+                return self._rebuild(table, "multi-vector unit: row-sharded stores are not followed in place")
+            if self.multi is None or table.mv_offsets is None or old.mv_offsets is None:
+                return self._rebuild(table, "multi-vector unit: the column appeared or disappeared, or no index was built for it")
         if self.single_sharded is not None:
             return self._rebuild(table, "row-sharded unit: global row ids are positions in the not-null order")
-        if self.single is None:
-            return self._rebuild(table, "no single-vector index to follow")
         n_old = len(old.ids)
         if len(table.ids) < n_old or list(table.ids[:n_old]) != list(old.ids):
             return self._rebuild(table, "the primary keys or their order changed")
-        emb, was = table.embedding, old.embedding
-        if emb is None or was is None or emb.shape[1] != was.shape[1]:
-            return self._rebuild(table, "the embedding column changed shape")
-        emb = np.ascontiguousarray(emb, dtype=np.float32)
-        was = np.ascontiguousarray(was, dtype=np.float32)
+        # ---- what each built index has to do (nothing is touched before both differences are known to be applicable)
+        single_plan = multi_plan = None
+        if self.single is not None:
+            emb, was = table.embedding, old.embedding
+            if emb is None or was is None or emb.shape[1] != was.shape[1]:
+                return self._rebuild(table, "the embedding column changed shape")
+            single_plan = self._single_difference(np.ascontiguousarray(emb, dtype=np.float32),
+                                                  np.ascontiguousarray(was, dtype=np.float32), n_old)
+        if self.multi is not None:
+            if table.mv_tokens is None or old.mv_tokens is None or table.mv_tokens.shape[1] != old.mv_tokens.shape[1]:
+                return self._rebuild(table, "the multi-vector column changed width")
+            multi_plan = self._multi_difference(table, old, n_old)
+        self._forget_maps()
+        appended = len(table.ids) > n_old
+        single_changes = single_plan is not None and (single_plan["update"].any() or single_plan["remove"].any() or appended)
+        multi_changes = multi_plan is not None and (multi_plan["changed"].size > 0 or appended)
+        if self.single is None:
+            # no single-vector index to follow: it is built from `table` when first asked for, and positions cached from the
+            # old table's NULL pattern (`single_positions`) do not outlive that table
+            self.single_rows = None
+            if not multi_changes and not self._same_bits(table.embedding, old.embedding):
+                self.table = table
+                return "incremental"                                             # ("unchanged" means neither column changed)
+        if not (single_changes or multi_changes):
+            self.table = table
+            return "unchanged"
+        outcome = "incremental"
+        if single_changes:
+            outcome = self._apply_single(single_plan, n_old)
+        if multi_changes:
+            self._apply_multi(table, multi_plan, n_old)
+        self.table = table
+        if self.multi is not None:
+            self.multi_rows = np.arange(len(table.ids))
+        return outcome
+
+    @staticmethod
+    def _same_bits(a: np.ndarray | None, b: np.ndarray | None) -> bool:
+        if a is None or b is None:
+            return a is None and b is None
+        a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+        return a.shape == b.shape and bool((a.view(np.uint32) == b.view(np.uint32)).all())      # (bits: NaN-safe)
+
+    @staticmethod
+    def _single_difference(emb: np.ndarray, was: np.ndarray, n_old: int) -> dict[str, Any]:
         null, was_null = np.isnan(emb).all(axis=1), np.isnan(was).all(axis=1)
         head, head_null = emb[:n_old], null[:n_old]
         differ = (head.view(np.uint32) != was.view(np.uint32)).any(axis=1)      # (bits: NaN-safe)
-        update = ~head_null & (was_null | differ)
-        remove = head_null & ~was_null
-        self._forget_maps()
-        if not (update.any() or remove.any() or len(table.ids) > n_old):
-            self.table = table
-            return "unchanged"
-        if not self.slot_per_position and was_null.any():
+        return {"emb": emb, "null": null, "was_null": was_null, "update": ~head_null & (was_null | differ),
+                "remove": head_null & ~was_null}
+
+    def _apply_single(self, plan: dict[str, Any], n_old: int) -> str:
+        emb, null = plan["emb"], plan["null"]
+        if not self.slot_per_position and plan["was_null"].any():
             logger.info("refresh: the index was built over NULL rows; laying it out with one slot per table position")
             self.single.close()
-            self.table = table
             self._build_slots(emb)
             return "relayout"
         self.slot_per_position = True
-        if remove.any():
-            self.single.remove_rows(np.nonzero(remove)[0])
-        if update.any():
-            self.single.update_rows(np.nonzero(update)[0], head[update])
+        if plan["remove"].any():
+            self.single.remove_rows(np.nonzero(plan["remove"])[0])
+        if plan["update"].any():
+            self.single.update_rows(np.nonzero(plan["update"])[0], emb[:n_old][plan["update"]])
         self._append_slots(emb[n_old:], null[n_old:], n_old)
-        self.table = table
-        self.single_rows = np.arange(len(table.ids))
-        return "incremental"
+        self.single_rows = np.arange(emb.shape[0])        # (only here and in _build_slots: an index this call did not touch keeps
+        return "incremental"                              # its rows -> positions map, compacted or not)
+
+    @staticmethod
+    def _multi_difference(table: ChunkTable, old: ChunkTable, n_old: int) -> dict[str, Any]:
+        """Positions < n_old whose documents differ between the two exports: another token count (losing or regaining every
+        vector included) or, at the same count, other token bits."""
+        off = np.ascontiguousarray(table.mv_offsets, dtype=np.int64)
+        was_off = np.ascontiguousarray(old.mv_offsets, dtype=np.int64)
+        tok = np.ascontiguousarray(table.mv_tokens, dtype=np.float32)
+        was_tok = np.ascontiguousarray(old.mv_tokens, dtype=np.float32)
+        lens, was_lens = np.diff(off[:n_old + 1]), np.diff(was_off)
+        changed = lens != was_lens
+        same = np.nonzero(~changed & (lens > 0))[0]
+        if same.size:
+            n = lens[same]
+            first = np.cumsum(n) - n                                             # of each such document in the gathered rows
+            within = np.arange(int(n.sum())) - np.repeat(first, n)
+            rows, was_rows = np.repeat(off[same], n) + within, np.repeat(was_off[same], n) + within
+            differ = (tok[rows].view(np.uint32) != was_tok[was_rows].view(np.uint32)).any(axis=1)   # (bits: NaN-safe)
+            changed[same[np.logical_or.reduceat(differ, first)]] = True
+        return {"off": off, "tok": tok, "changed": np.nonzero(changed)[0]}
+
+    def _apply_multi(self, table: ChunkTable, plan: dict[str, Any], n_old: int) -> None:
+        off, tok, ids = plan["off"], plan["tok"], plan["changed"]
+        if ids.size:
+            lens = off[ids + 1] - off[ids]
+            parts = [tok[off[i]:off[i + 1]] for i in ids]
+            self.multi.set_multivec(ids, np.concatenate(parts, axis=0) if parts else tok[:0],
+                                    np.concatenate([[0], np.cumsum(lens)]).astype(np.int64))
+        if len(table.ids) > n_old:
+            self.multi.add_multivec(tok[off[n_old]:off[-1]], off[n_old:] - off[n_old])
 
 
 def _is_store(obj: Any) -> bool:

@@ -140,7 +140,41 @@ int mi355dr_add_multivec(mi355dr_index* idx, const float* vecs, const int64_t* o
 /* the same from DEVICE memory (an encoder's output never leaves HBM: embeddings/colpali.py:168-245 `embed_image(s)` /
  * `embed_documents` -> [T,128] patch / token tensors): vecs_dev = device [sum_T, dim], offsets = HOST [n_docs+1] */
 int mi355dr_add_multivec_device(mi355dr_index* idx, const float* vecs_dev, const int64_t* offsets, int64_t n_docs);
+/* documents stored, with or without vectors (document ids are stable: nothing is ever renumbered) */
 int64_t mi355dr_size_multivec(const mi355dr_index* idx);
+
+/* ---- update / remove in place (multi-vector) ----
+ * The multi-vector column is not append-only either: BaseVectorRepository.set_multi_vector_embedding(s_batch)
+ * (orm/repository/base.py:428-485) is an UPDATE of an existing row, and a row whose `embeddings` became NULL -- or a deleted
+ * chunk -- leaves maxsim_search at once (:487-535, `embeddings IS NOT NULL`).
+ *   set: document doc_ids[j] takes the vectors offsets[j] .. offsets[j+1] of vecs (the layout of mi355dr_add_multivec).  No
+ *        vectors removes the document: it becomes a document without vectors -- skipped by every search, NaN in
+ *        mi355dr_maxsim_subset, refused by mi355dr_gqr_refine_maxsim -- and a later set with vectors revives it.  Ids stay and
+ *        mi355dr_size_multivec is unchanged.  Afterwards every entry point that reads the store (mi355dr_search_maxsim / _device,
+ *        mi355dr_maxsim_subset / _ex, mi355dr_gqr_refine_maxsim) answers as a fresh store built by mi355dr_add_multivec from the
+ *        current contents would, bit for bit in distances and ids.
+ * doc_ids: HOST [n], each in [0, size_multivec) and listed once per call; offsets: HOST [n+1], non-decreasing -- otherwise
+ * MI355DR_E_INVALID and nothing changes; a failed allocation returns MI355DR_E_NOMEM and nothing changes.  The call runs under
+ * the handle's mutex and is complete on return.  A host payload is staged in slices of 32 MiB, like an add's.
+ * Layout and cost: documents own consecutive 32-token blocks of one stream, so the call takes one of two paths.
+ *   in place  no listed document changes its block count ceil(T/32) (re-embedding: same tokenizer, same token count; pages
+ *             with a fixed patch count): only the listed documents' blocks of the fp32 and bf16 images are rewritten.
+ *             O(listed blocks).
+ *   relayout  some block count changes (every removal, any shorter or longer document): the cumulative block table is laid
+ *             out anew, FRESH image buffers are allocated (capacity as before, more if the new total needs it), one kernel
+ *             moves the blocks of the documents that were not listed, the listed ones are built from the new vectors, and
+ *             the buffers are swapped at the end.  One device pass over the store; PEAK MEMORY: one extra copy of the two
+ *             images (6 bytes per stored value) for the duration of the call.
+ * What never shrinks: the three maxima of the screen bound (largest token norm, largest bf16-rounded token norm, largest bf16
+ * residual) and the "not finite" flag move in the conservative direction only, as the single-vector maxima do -- candidate
+ * counts may differ from a fresh store's, results may not; nor does the capacity.  The granule-packed copy (option
+ * "maxsim_pack8") is stale after any set and is packed anew, whole, by the next pass that takes it. */
+int mi355dr_set_multivec(mi355dr_index* idx, const int64_t* doc_ids, const float* vecs, const int64_t* offsets, int64_t n); /* vecs: host */
+/* the same with the new vectors on this index's device ([.., dim] fp32, read in place); doc_ids and offsets stay on the host */
+int mi355dr_set_multivec_device(mi355dr_index* idx, const int64_t* doc_ids, const float* vecs_dev, const int64_t* offsets, int64_t n);
+/* documents that have vectors: mi355dr_size_multivec minus the removed and the empty ones */
+int64_t mi355dr_live_multivec(const mi355dr_index* idx);
+
 /* qtok: host [sum_nq, dim], q_offsets: [B+1].  out_dist: [B,k] fp32 (= -sum_i max_j <q_i,d_j>). */
 int mi355dr_search_maxsim(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, int k,
                           float* out_dist, int64_t* out_rows);
@@ -275,8 +309,10 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
  *          "maxsim_fallbacks" (queries re-run by the exact full scan), "maxsim_screen_launches" / "maxsim_screen_ns" /
  *          "maxsim_exact_launches" / "maxsim_exact_ns" (profile=1), "maxsim_packed_launches" / "maxsim_packed_blocks" / "maxsim_packed_built" (screen launches over the
  *          granule-packed copy / its 32-token blocks / blocks written into it so far: a store that grows is packed from its new granules on), "maxsim_screen_cols" (query columns the screen launches
- *          multiplied every token by),
- *          "hbm_bytes_resident". */
+ *          multiplied every token by), "maxsim_set_docs" (documents rewritten by mi355dr_set_multivec) / "maxsim_moved_blocks"
+ *          (32-token blocks its relayouts copied; 0 on the in-place path),
+ *          "hbm_bytes_resident" (the single-vector corpus with its shadows at its capacity + the multi-vector store's two
+ *          images, offset table and granule-packed copy as allocated now). */
 int mi355dr_set_option(mi355dr_index* idx, const char* key, int64_t value);
 int mi355dr_get_stat(mi355dr_index* idx, const char* key, int64_t* out);
 int mi355dr_reset_stats(mi355dr_index* idx);
