@@ -65,7 +65,7 @@ struct Event {
 
 struct EventPair {
     hipEvent_t a, b;
-    int big;  // 1: the launch went to k_screen256 (the dominant kernel), 0: k_screen
+    int big;  // 1: the launch went to k_screen256c or k_screen_rq (the dominant kernel), 0: k_screen
 };
 // the timing pairs of option "profile": pooled (take_events) or behind a launch (drain_events), owned either way
 struct EventPairs {
@@ -223,7 +223,7 @@ struct mi355dr_index {
     // stats
     int64_t s_screen_launches = 0, s_screen_ns = 0, s_screen_rows = 0, s_fallback_queries = 0, s_chunks = 0,
             s_passes = 0, s_starters = 0;
-    int64_t s_big_launches = 0, s_big_ns = 0, s_big_rows = 0;  // the k_screen256 share of the three above
+    int64_t s_big_launches = 0, s_big_ns = 0, s_big_rows = 0;  // the k_screen256c / k_screen_rq share of the three above
     int screen_rq_split_tests = 1;  // k_screen_rq: a block test's maxima ride the MFMAs of the other row half (0: in one piece; d = 768 only, A/B; option "screen_rq_split_tests")
     int64_t debug_park = 0;     // diagnostic (option "debug_park_thresholds" = rows): k_screen_rq launches of at least that many rows run with every threshold at +inf -- what such a launch costs without hits; results are wrong while it is set
     mi355::DevBuf<float> park_thr;  // [kQBlockMax] +inf

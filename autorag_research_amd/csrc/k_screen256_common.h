@@ -8,13 +8,14 @@
 //  * Persistent: the grid is 8 XCDs x L workgroups (one per CU, the ring fills the LDS); a workgroup keeps its query tile and
 //    walks corpus tiles ctl, ctl + 8 L / n_qtiles, ...  Workgroups that run together on an XCD are the query tiles of
 //    neighbouring corpus tiles, so the shadow is fetched from HBM once per pass and re-read from that XCD's L2.
-//  * Hits go to a per-wave LDS queue (k_screen.h: screen_queue_hits) that is flushed to the global candidate lists when it
+//  * Hits go to a per-wave LDS queue (screen_hits.h: screen_queue_hits) that is flushed to the global candidate lists when it
 //    fills up and when the workgroup is done: the epilogue never touches the vector-memory counter while DMA is in flight.
 // (The first, second and fourth forms of the kernel that were built on this geometry -- docs/LAB_NOTES_r1_r3.md 4.1, 4.1b,
 // 4.1c -- are in the history only.  Round 5: k_screen_rq.h keeps the QUERY operand in registers and serves int8 shadows of at
 // most 768 B per row; k_screen256c stays for the bf16 shadow and wider rows.  A/B harness: tools/screen_ab.hip.)
 #pragma once
-#include "k_screen.h"
+#include "screen_common.h"
+#include "screen_hits.h"  // kWaveQueueCap: the per-wave queues are part of the LDS carve
 
 namespace mi355 {
 

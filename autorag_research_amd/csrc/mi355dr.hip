@@ -4,6 +4,7 @@
 #include "index.h"
 #include "k_prep.h"
 #include "k_scan.h"
+#include "screen_common.h"
 #include "k_screen.h"
 #include "k_screen256c.h"
 #include "k_screen_rq.h"
@@ -305,9 +306,9 @@ constexpr int kRetryLevels = 2;  // re-screens of an overflowed query (bf16, gro
 // launch one screen pass over rows [r0, r_end) (r0 a multiple of the tile edge)
 int launch_screen(mi355dr_index* idx, hipStream_t s, int B, int64_t r0, int64_t r_end, int cap, int emit_mode) {
     const bool emit_all = emit_mode != 0;  // (both special epilogues live in k_screen)
-    // the emit-all first chunk always goes through the 128x128 kernel (k_screen256 has no emit-all epilogue)
+    // the emit-all first chunk always goes through the 128x128 kernel (k_screen256c and k_screen_rq have no emit-all epilogue)
     // ... and so do chunks of a few thousand rows: their thresholds are still so low that a good part of the tile is a
-    // hit, which the per-lane global append of k_screen handles better than k_screen256's small per-wave queues
+    // hit, which the per-lane global append of k_screen handles better than the small per-wave queues of k_screen256c and k_screen_rq
     const int tile = (emit_all || r_end - r0 <= idx->small_chunk_rows) ? kTileM : screen_tile(B);
     const bool i8 = use_i8(idx);
     ScreenArgs2 sa{};

@@ -3,7 +3,7 @@
 The screen kernels keep LDS-DMA loads (global_load_lds) of later K-steps in flight while the current step's
 operands are read from LDS and multiplied.  That only holds if the compiler's waitcnt insertion does not put a
 full `s_waitcnt vmcnt(0)` in front of the ds_reads -- which it does, silently and at a 2x cost, when the LDS reads
-are typed differently (see the NOTE in csrc/k_screen.h).  This test pins the property on the generated ISA.
+are typed differently (see the NOTE at the fragment reads of csrc/k_screen.h).  This test pins the property on the generated ISA.
 """
 
 import subprocess
@@ -293,7 +293,12 @@ def test_the_product_kernels_carry_no_timing_builds():
     """the screens' ablation forms (template parameter ABL: no fragment reads / tests / barrier / LDS-DMA, ...)
     live in tools/k_screen_rq_abl.h / tools/k_screen256c_abl.h for tools/screen_ab.hip; the library's headers carry the kernels
     alone, and the packed MaxSim copy (measured slower in round 4) is gone."""
-    for h in ("k_screen_rq.h", "k_screen256c.h", "k_screen256_common.h", "k_prune_wide.h"):
+    for h in ("k_screen_rq.h", "k_screen256c.h", "k_screen256_common.h", "k_prune_wide.h", "k_screen.h", "screen_common.h",
+              "screen_hits.h"):
         assert "ABL" not in (CSRC / h).read_text(), h
+    # ... nor the hit paths' A/B forms (template parameter MODE): those live in tools/screen_hits_abl.h
+    for h in ("k_screen.h", "screen_common.h", "screen_hits.h"):
+        assert "MODE" not in (CSRC / h).read_text(), h
+    assert (ROOT / "tools" / "screen_hits_abl.h").exists()
     assert not (CSRC / "k_maxsim_wgp.h").exists()
     assert (ROOT / "tools" / "k_screen_rq_abl.h").exists() and "ABL" in (ROOT / "tools" / "k_screen_rq_abl.h").read_text()

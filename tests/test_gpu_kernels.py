@@ -190,3 +190,57 @@ def test_int8_screen_values_and_bound(pkg, d, B):
             # ... and not a vacuous one: it never overshoots by more than the whole two-sided bound
             assert (t - cos <= E[:, None] + 2.0 * kq[:, None] * eg[None, :] + 1e-6).all()
             assert np.abs(t - kq[:, None] * eg[None, :] - cos).max() > 0.05 * (E.min() + eg.min())
+
+
+@pytest.fixture(scope="module")
+def hit_burst(oracle):
+    """A corpus in which 600 consecutive rows are near-duplicates of ONE direction and the first 16 queries (one wave's query
+    columns in both large kernels) look along it: every 128-row tile inside the burst gives such a wave a hit in every lane.
+    Returns (C, Q, k, the oracle's distances and rows); the oracle's lists have no tie at position k, so equality is unambiguous."""
+    rng = np.random.default_rng(20260)
+    n, d, B, k, m, r0 = 40_000, 64, 130, 10, 600, 20_096   # 130 queries: the least that selects the 256-wide kernels, plus a little
+    C = rng.standard_normal((n, d)).astype(np.float32)
+    Q = rng.standard_normal((B, d)).astype(np.float32)
+    v = rng.standard_normal(d).astype(np.float32)
+    v /= np.linalg.norm(v)
+    noise = rng.standard_normal((m, d)).astype(np.float32)
+    noise -= (noise @ v)[:, None] * v[None, :]
+    noise /= np.linalg.norm(noise, axis=1, keepdims=True)
+    amp = np.sqrt(1.0 / np.linspace(0.999, 0.95, m) ** 2 - 1.0).astype(np.float32)   # cosines to v spread over [0.95, 0.999]
+    C[r0:r0 + m] = v[None, :] + amp[:, None] * noise
+    Q[:16] = v[None, :] + 0.05 * rng.standard_normal((16, d)).astype(np.float32)
+    dist, rows = oracle.topk_search(C, Q, k + 1, metric="cosine")
+    assert (dist[:, k - 1] < dist[:, k]).all()
+    assert (rows[:16, :k] >= r0).all() and (rows[:16, :k] < r0 + m).all()
+    return C, Q, k, dist[:, :k], rows[:, :k]
+
+
+@pytest.mark.parametrize("rq", [1, 0])
+def test_hit_burst_reaches_the_rare_branches_of_the_queues(pkg, hit_burst, rq):
+    """The rare branches of the two queued hit paths (csrc/screen_hits.h), on a burst of near-duplicate rows.  One K-step of int8
+    (d = 64); small_chunk_rows = 0 hands every chunk behind the starter to the large kernel.  Inside the burst a 32 x 32 block
+    brings the wave that owns queries 0..15 a hit in 16 x 2 lanes.
+    screen_rq = 1 (k_screen_rq): 32 entries per block, 128 per tile against a hit-lane queue of kLaneQueueCap = 64 -- the third
+      block of a tile does not fit, the queue is expanded inside the loop (lane_queue_flush_small); nothing is flagged.
+    screen_rq = 0 (k_screen256c): 16 queries x 128 rows = 2048 entries per tile against kWaveQueueCap = 320 -- the queue fills up,
+      the 16 queries are flagged and re-screened by the host.
+    Either way the result is the oracle's, bit for bit, and no query pays the exact scan."""
+    C, Q, k, exp_dist, exp_rows = hit_burst
+    with pkg.Mi355Index(C.shape[1]) as idx:
+        idx.set_option("screen_dtype", "i8")
+        idx.set_option("path", "screen")
+        idx.set_option("small_chunk_rows", 0)
+        idx.set_option("screen_rq", rq)
+        idx.add(C)
+        idx.reset_stats()
+        dist, rows = idx.search(Q, k)
+        stats = {s: idx.stat(s) for s in ("screen256_launches", "screen_rq_launches", "retry_queries", "fallback_queries")}
+    print(f"screen_rq={rq}: {stats}")
+    assert np.array_equal(rows, exp_rows)
+    assert np.array_equal(dist.view(np.uint64), exp_dist.view(np.uint64))
+    assert stats["screen256_launches"] > 0 and (stats["screen_rq_launches"] > 0) == (rq == 1)
+    assert stats["fallback_queries"] == 0
+    if rq == 1:
+        assert stats["retry_queries"] == 0   # (the lists hold the burst: what screen_rq = 0 re-screens is the full queue's doing)
+    else:
+        assert stats["retry_queries"] >= 16

@@ -28,6 +28,7 @@
 // LDS: the ring of 8 half-tile slots (2 parities x A0 B0 B1 A1), the per-wave candidate queues, 1 KiB of records.
 #pragma once
 #include "k_screen256_common.h"
+#include "screen_hits_abl.h"  // (tools/: screen_test_block_cold, ABL bit 12)
 
 namespace mi355 {
 
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(512, 2) void k_screen256c(ScreenArgs2 a) {
     const int q0 = qt * kT2;
     const int64_t row_bytes = a.row_bytes;
 
-    // ---- DMA sources (as in k_screen256): this wave stages local rows [16*wave + 8u, +8) of every half-tile
+    // ---- DMA sources: this wave stages local rows [16*wave + 8u, +8) of every half-tile
     unsigned voffA[2], voffB[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {

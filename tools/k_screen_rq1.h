@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256, 1) void k_screen_rq1(ScreenArgs2 a) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0..3
     const unsigned lq = lds_addr(smem + rq_que_off(KS) + wave * kLaneQueueBytes);
-    int lq_n = 0, lq_ovf = 0;
+    int lq_n = 0;
 
     const int b = blockIdx.x;
     const int xcd = b & 7;
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256, 1) void k_screen_rq1(ScreenArgs2 a) {
             const int rbase__ = (ROW0) + 32 * (RB) + 4 * (lane_e >> 5);                               \
             I8Blk blk__{1.0f, 0.0f};                                                                  \
             if constexpr (I8) blk__ = I8Blk{rec_s[RB] * scq[H], rec_e[RB] * kqq[H]};                  \
-            screen_test_block_lq_max<I8, 0>(a, a.status, row_end, acc[RB][H], tg, q__, rbase__, th[H], blk__, lq, lq_n, lq_ovf); \
+            screen_test_block_lq_max<I8>(a, row_end, acc[RB][H], tg, q__, rbase__, th[H], blk__, lq, lq_n); \
         }                                                                                             \
     } while (0)
 #define R1_MICRO(M, TT, ZERO, SB, SBN, TEST, TB, TH)                                                  \

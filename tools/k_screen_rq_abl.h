@@ -23,7 +23,7 @@
 //     k_screen256c, so that a finished tile's blocks are tested UNDER MFMAs of the other row half (both waves of a SIMD
 //     reach a tile's end together: tests behind the last MFMA would idle the matrix pipe).  Row fragments are read three
 //     micro-steps ahead under counted lgkmcnt.
-//   * Hits: a per-wave queue of HIT LANES (k_screen.h: screen_test_block_lq) -- five LDS stores per lane and no call in the hot
+//   * Hits: a per-wave queue of HIT LANES (screen_hits.h: screen_test_block_lq) -- five LDS stores per lane and no call in the hot
 //     loop, expanded into candidates 64 entries at a time --; same persistent XCD-aware walk as k_screen256c (the query
 //     tiles of one row tile run on one XCD: the shadow comes from HBM once), same int8 row-group records by one small LDS-DMA
 //     piece per tile.
@@ -35,6 +35,7 @@
 // L2 -> LDS bytes no longer moved), zeros -26 % (4.3 POP/s = 0.86 of the int8 peak: in cycles the staging no longer shows).
 #pragma once
 #include "k_screen256_common.h"
+#include "screen_hits_abl.h"  // (tools/: the A/B forms of the hit path, ABL bits 8, 9)
 
 namespace mi355 {
 
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(512, 2) void k_screen_rq(ScreenArgs2 a) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned lq = lds_addr(smem + rq_que_off(KS) + wave * kLaneQueueBytes);  // this wave's queue of hit lanes (k_screen.h)
+    const unsigned lq = lds_addr(smem + rq_que_off(KS) + wave * kLaneQueueBytes);  // this wave's queue of hit lanes (screen_hits.h)
     int lq_n = 0, lq_ovf = 0;                                                       // entries in it; "a block did not fit" (wave-uniform)
 
     const int b = blockIdx.x;
@@ -243,9 +244,9 @@ __global__ __launch_bounds__(512, 2) void k_screen_rq(ScreenArgs2 a) {
                 blk__ = I8Blk{rec_m[RB], rec_e[RB]};                                                  \
             }                                                                                         \
             if constexpr ((ABL & 8192) != 0)                                                          \
-                screen_test_block_lq<I8, (ABL >> 8) & 3>(a, a.status, row_end, acc[RB], q__, rbase__, th, blk__, lq, lq_n, lq_ovf); \
+                screen_test_block_lq_abl<I8, (ABL >> 8) & 3>(a, row_end, acc[RB], q__, rbase__, th, blk__, lq, lq_n, lq_ovf); \
             else                                                                                      \
-                screen_test_block_lq_max<I8, (ABL >> 8) & 3>(a, a.status, row_end, acc[RB], tg, q__, rbase__, th, blk__, lq, lq_n, lq_ovf); \
+                screen_test_block_lq_max_abl<I8, (ABL >> 8) & 3>(a, row_end, acc[RB], tg, q__, rbase__, th, blk__, lq, lq_n, lq_ovf); \
         }                                                                                             \
     } while (0)
 #define RQ_MICRO(M, TT, ZERO, SB, SBN)                                                                \
