@@ -21,7 +21,7 @@ _lib: ctypes.CDLL | None = None
 ABI_SYMBOLS = [
     "mi355dr_create", "mi355dr_destroy", "mi355dr_last_error", "mi355dr_version", "mi355dr_reserve",
     "mi355dr_add_rows", "mi355dr_add_rows_device", "mi355dr_size", "mi355dr_dim", "mi355dr_get_rows",
-    "mi355dr_update_rows", "mi355dr_update_rows_device", "mi355dr_remove_rows", "mi355dr_live_rows",
+    "mi355dr_update_rows", "mi355dr_update_rows_device", "mi355dr_remove_rows", "mi355dr_live_rows", "mi355dr_compact",
     "mi355dr_search", "mi355dr_search_device", "mi355dr_search_device_async", "mi355dr_search_wait", "mi355dr_add_multivec", "mi355dr_size_multivec",
     "mi355dr_search_maxsim", "mi355dr_search_maxsim_device", "mi355dr_maxsim_subset", "mi355dr_maxsim_subset_ex", "mi355dr_add_multivec_device", "mi355dr_gqr_refine", "mi355dr_gqr_refine_maxsim",
     "mi355dr_set_multivec", "mi355dr_set_multivec_device", "mi355dr_live_multivec",
@@ -107,6 +107,8 @@ def load() -> ctypes.CDLL:
     L.mi355dr_update_rows_device.argtypes = [vp, i64p, vp, i64]
     L.mi355dr_remove_rows.restype = c_int
     L.mi355dr_remove_rows.argtypes = [vp, i64p, i64]
+    L.mi355dr_compact.restype = c_int
+    L.mi355dr_compact.argtypes = [vp, i64p]
     L.mi355dr_live_rows.restype = i64
     L.mi355dr_live_rows.argtypes = [vp]
     L.mi355dr_size.restype = i64

@@ -165,7 +165,7 @@ __device__ __forceinline__ bool norm_is_regular(float n2) { return n2 >= 1e-30f 
 // written out as "no result" (NaN / -1) by k_finalize.
 constexpr float kDeadNrm2 = -1.0f;
 constexpr int32_t kRowNone = 0x7FFFFFFF;
-__device__ __forceinline__ bool row_is_dead(float n2) { return n2 < 0.0f; }
+__host__ __device__ __forceinline__ bool row_is_dead(float n2) { return n2 < 0.0f; }
 // exact key of a re-scored pair; `row` is replaced by kRowNone when the row is dead
 __device__ __forceinline__ uint64_t exact_key_of(int metric, float dot, float nq, float nc, int32_t& row) {
     if (row_is_dead(nc)) {

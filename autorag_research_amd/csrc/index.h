@@ -218,6 +218,7 @@ struct mi355dr_index {
     // pass schedule: ratio of chunk i = (geometric mean) x taper^((n-1)/2 - i) -- early chunks (cheap hits, loose bound) larger,
     // late chunks (expensive hits) smaller; 100 = uniform ratios (option "chunk_taper_x100")
     int chunk_taper_x100 = 0;   // 0 = auto: 120 for passes of the two-wave prune (measured -1 % at k = 100), 100 otherwise (k = 10: no gain)
+    int64_t compact_slice_rows = 65536;  // mi355dr_compact: destination rows per slice of its staging buffer (option "compact_slice_rows", 32 ... 2^22)
     int64_t starter_rows_wide = 65536;  // the starter's sample at 33 <= k <= 128 (option "starter_rows_wide", tuning: 4096 ... 262144)
 
     // stats
@@ -240,6 +241,8 @@ struct mi355dr_index {
     int64_t s_ms_packed_built = 0;     // blocks k_ms_pack8 has written since the index was created (a store that grows is packed from its new granules on)
     int64_t s_ms_set_docs = 0;         // documents rewritten by mi355dr_set_multivec ...
     int64_t s_ms_moved_blocks = 0;     // ... and the blocks its relayouts copied (k_ms_relayout; the in-place path moves none)
+    int64_t s_compactions = 0;         // mi355dr_compact calls that moved rows ...
+    int64_t s_compact_moved_rows = 0;  // ... and the rows they copied (k_compact_gather)
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
     mi355::EventPairs ev_pool, ev_pending;

@@ -16,6 +16,7 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "k_select.h"
 #include "k_prune_wide.h"
 #include "k_update.h"
+#include "k_compact.h"
 #include "k_block.h"
 
 using namespace mi355;
@@ -1082,6 +1083,99 @@ int mi355dr_remove_rows(mi355dr_index* idx, const int64_t* row_ids, int64_t n) {
     return mutate_rows_impl(idx, row_ids, nullptr, n, hipMemcpyHostToDevice, true);
 }
 
+// ---- compaction (DESIGN.md "Compaction") --------------------------------------------------------------------------------
+int mi355dr_compact(mi355dr_index* idx, int64_t* new_of_old) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_pending(idx));  // (a search in flight sees the index as it was, under the old ids)
+    const int64_t n_old = idx->n;
+    if (idx->dead_n == 0) {  // nothing to drop: nothing is read, moved or rebuilt
+        if (new_of_old)
+            for (int64_t r = 0; r < n_old; ++r) new_of_old[r] = r;
+        return MI355DR_OK;
+    }
+    hipStream_t s = idx->stream;
+    // the dead rows from nrm2; src_of_dst for the destinations from the first dead slot on (rows in front of it stay)
+    std::vector<float> n2;
+    std::vector<int32_t> src_of_dst;
+    int64_t first_dead = n_old;
+    try {
+        n2.resize((size_t)n_old);
+        HIPCHECK(idx, hipMemcpyAsync(n2.data(), idx->nrm2, (size_t)n_old * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipStreamSynchronize(s));
+        for (int64_t r = 0; r < n_old; ++r)
+            if (row_is_dead(n2[(size_t)r])) {
+                first_dead = r;
+                break;
+            }
+        src_of_dst.reserve((size_t)(n_old - first_dead));
+        for (int64_t r = first_dead; r < n_old; ++r)
+            if (!row_is_dead(n2[(size_t)r])) src_of_dst.push_back((int32_t)r);
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, "compact: out of host memory for the row maps");
+    }
+    const int64_t n_moved = (int64_t)src_of_dst.size(), n_new = first_dead + n_moved;
+    const int64_t slice = std::min(idx->compact_slice_rows, n_moved);
+    const size_t row_b = (size_t)idx->dim * sizeof(float);
+    // every allocation of the call, before the first byte of the index is written
+    DevBuf<int32_t> map_dev;
+    DevBuf<float> stage;  // [slice, dim] rows, then [slice] nrm2
+    // (src_of_dst is pageable: HIP stages such a copy before the call returns, as for the id lists of mutate_rows_impl, and
+    // commit_corpus synchronises the stream before the vector goes)
+    if (n_moved > 0) {
+        HIPCHECK(idx, map_dev.grow((size_t)n_moved * sizeof(int32_t)));
+        HIPCHECK(idx, stage.grow((size_t)slice * (row_b + sizeof(float))));
+        HIPCHECK(idx, hipMemcpyAsync(map_dev.p, src_of_dst.data(), (size_t)n_moved * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    float* stage_n2 = stage.p + slice * idx->dim;
+    const int vec4 = idx->dim % 4 == 0 && (uintptr_t)idx->rows.p % 16 == 0 && (uintptr_t)stage.p % 16 == 0;
+    for (int64_t j0 = 0; j0 < n_moved; j0 += slice) {  // ascending slices of destination rows first_dead + [j0, j0 + m)
+        const int64_t m = std::min(slice, n_moved - j0), dst0 = first_dead + j0;
+        hipLaunchKernelGGL(k_compact_gather, dim3((unsigned)((m + kCompactWaves - 1) / kCompactWaves)), dim3(64 * kCompactWaves),
+                           0, s, idx->rows, idx->nrm2, map_dev.p + j0, m, idx->dim, vec4, stage.p, stage_n2);
+        HIPCHECK(idx, hipGetLastError());
+        HIPCHECK(idx, hipMemcpyAsync(idx->rows + dst0 * idx->dim, stage.p, (size_t)m * row_b, hipMemcpyDeviceToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(idx->nrm2 + dst0, stage_n2, (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    // the slots behind the new end, up to the end of the last 256-row tile the old index reached, become capacity that was
+    // never used (ensure_capacity: all-zero images, flags and group records) -- screens read whole tiles and whole groups
+    const int64_t tail_end = std::min(round_up(n_old, kT2), idx->cap_rows), tail = tail_end - n_new;
+    const int64_t g_tail = (n_new + kI8GroupRows - 1) / kI8GroupRows, g_end = tail_end / kI8GroupRows;
+    if (tail > 0) {
+        HIPCHECK(idx, hipMemsetAsync(idx->nrm2 + n_new, 0, (size_t)tail * sizeof(float), s));
+        HIPCHECK(idx, hipMemsetAsync(idx->shadow + n_new * idx->dpad, 0, (size_t)tail * idx->dpad * sizeof(uint16_t), s));
+        HIPCHECK(idx, hipMemsetAsync(idx->shadow8 + n_new * idx->dpad8, 0, (size_t)tail * idx->dpad8, s));
+        HIPCHECK(idx, hipMemsetAsync(idx->flag8 + n_new, 0, (size_t)tail, s));
+    }
+    if (g_end > g_tail) HIPCHECK(idx, hipMemsetAsync(idx->grp8 + g_tail, 0, (size_t)(g_end - g_tail) * sizeof(I8Group), s));
+    // derived data of the moved rows, by the builders add_rows uses (nrm2 came with the rows: the bits of their add)
+    CHECK(build_rows(idx, s, first_dead, n_moved, nullptr, /*with_nrm2=*/false));
+    const int64_t g_lo = first_dead / kI8GroupRows;  // group membership shifts from here on: whole groups, as an append rebuilds them
+    CHECK(build_groups(idx, s, g_lo, g_tail - g_lo, nullptr, n_new, n_new));
+    HIPCHECK(idx, hipMemsetAsync(idx->irr_count, 0, sizeof(int), s));
+    HIPCHECK(idx, hipMemsetAsync(idx->irr8_count, 0, sizeof(int), s));
+    HIPCHECK(idx, hipMemsetAsync(idx->dead_count, 0, sizeof(int), s));
+    if (n_new > 0) {
+        hipLaunchKernelGGL(k_rebuild_side_lists, dim3((unsigned)((n_new + 255) / 256)), dim3(256), 0, s, idx->nrm2, idx->flag8,
+                           (int64_t)0, n_new, idx->irr_rows, idx->irr_count, idx->irr8_rows, idx->irr8_count, idx->dead_count);
+        HIPCHECK(idx, hipGetLastError());
+    }
+    CHECK(commit_corpus(idx, s, /*mutated=*/true));
+    idx->n = n_new;
+    // AUTO's demotion of the int8 screen was a verdict on the old layout (a dead head overflows every int8 list): re-armed, as
+    // setting "screen_dtype" does
+    idx->i8_demoted_k = INT_MAX;
+    idx->i8_backoff = idx->i8_probation = 0;
+    idx->s_compactions += n_moved > 0;  // (a call that only dropped a dead tail moved nothing)
+    idx->s_compact_moved_rows += n_moved;
+    if (new_of_old) {
+        int64_t next = 0;
+        for (int64_t r = 0; r < n_old; ++r) new_of_old[r] = row_is_dead(n2[(size_t)r]) ? -1 : next++;
+    }
+    return MI355DR_OK;
+}
+
 int64_t mi355dr_size(const mi355dr_index* idx) { return idx ? idx->n : -1; }
 int64_t mi355dr_live_rows(const mi355dr_index* idx) { return idx ? idx->n - idx->dead_n : -1; }
 int mi355dr_dim(const mi355dr_index* idx) { return idx ? idx->dim : -1; }
@@ -1265,6 +1359,7 @@ const Option kOptions[] = {
     {"wide_inflation_x10", &Index::wide_inflation_x10, 20, 400},
     {"chunk_taper_x100", &Index::chunk_taper_x100, 0, 300, nullptr, 0, 100},  // 0 (auto) or 100 ... 300
     {"starter_rows_wide", &Index::starter_rows_wide, 4096, 262144},
+    {"compact_slice_rows", &Index::compact_slice_rows, 32, (int64_t)1 << 22},  // destination rows per staged slice of mi355dr_compact
 };
 
 struct Stat {
@@ -1300,6 +1395,8 @@ const Stat kStats[] = {
     {"maxsim_packed_built", &Index::s_ms_packed_built, false},
     {"maxsim_set_docs", &Index::s_ms_set_docs, true},
     {"maxsim_moved_blocks", &Index::s_ms_moved_blocks, true},
+    {"compactions", &Index::s_compactions, true},
+    {"compact_moved_rows", &Index::s_compact_moved_rows, true},
     {"i8_demoted", nullptr, false, [](const Index* x) -> int64_t { return x->i8_demoted_k != INT_MAX ? 1 : 0; }},
     {"i8_demoted_k", nullptr, false, [](const Index* x) -> int64_t { return x->i8_demoted_k == INT_MAX ? 0 : x->i8_demoted_k; }},
     {"irregular_rows", nullptr, false, [](const Index* x) -> int64_t { return x->irr_n; }},

@@ -97,6 +97,16 @@ class Mi355Index:
         ids = self._row_ids(row_ids)
         check(self._h, self._lib.mi355dr_remove_rows(self._h, ptr(ids, ctypes.c_int64), ids.shape[0]))
 
+    def compact(self) -> np.ndarray:
+        """Drop the removed rows: the live rows keep their order and become rows 0 .. live_rows-1, and the index answers
+        like one built fresh by one `add` of them.  Returns new_of_old (int64 [len(self) before the call]): the new id of
+        every old row, -1 for a removed one.  Pools for gqr_refine and any row -> key map of the caller follow this map."""
+        if not self._h:
+            raise ValueError("compact() on a closed index")
+        new_of_old = np.empty(len(self), dtype=np.int64)
+        check(self._h, self._lib.mi355dr_compact(self._h, ptr(new_of_old, ctypes.c_int64)))
+        return new_of_old
+
     @property
     def live_rows(self) -> int:
         """len(self) minus the removed rows."""

@@ -146,7 +146,7 @@ def _table_digest(table: ChunkTable) -> str:
 class _UnitIndex:
     """GPU index of one table (chunk / image_chunk): row <-> primary-key mapping + the native handle."""
 
-    def __init__(self, table: ChunkTable, device: int):
+    def __init__(self, table: ChunkTable, device: int, compact_dead_fraction: float | None = None):
         self.table = table
         self.single: Mi355Index | None = None
         self.multi: Mi355Index | None = None
@@ -158,6 +158,11 @@ class _UnitIndex:
         # False: `single` holds the NOT NULL rows compacted (how ensure_single builds it).  True (after a refresh): one slot
         # per table position, NULL rows are removed slots -- single_rows is the identity and every later change is in place
         self.slot_per_position = False
+        # True (after compact_single): `single` holds slots for a SUBSET of the table positions, in table order -- single_rows is
+        # strictly increasing, positions that were NULL at the compaction have no slot, and refresh works through that map
+        self.compacted = False
+        # refresh compacts by itself once dead / size reaches this fraction, or the head of the index is dead (None: never)
+        self.compact_dead_fraction = compact_dead_fraction
 
     def ensure_single_sharded(self, world: "_World") -> Any:
         """This rank's contiguous share of the NOT NULL rows behind a ShardedSearcher (global row ids = positions in the
@@ -241,6 +246,7 @@ class _UnitIndex:
         self._append_slots(emb, null, 0)
         self.single_rows = np.arange(emb.shape[0])
         self.slot_per_position = True
+        self.compacted = False
 
     def _append_slots(self, emb: np.ndarray, null: np.ndarray, first: int) -> None:
         if emb.shape[0] == 0:
@@ -255,8 +261,42 @@ class _UnitIndex:
         self.table = table
         self.single_rows = self.multi_rows = None
         self.slot_per_position = False
+        self.compacted = False
         self._forget_maps()
         return "rebuild"
+
+    # ---- compaction (Mi355Index.compact: the removed slots are squeezed out in place, the live rows keep their order) ----
+    def compact_single(self) -> bool:
+        """Drop the removed slots of the single-vector index.  Acts when that index is built, the unit is not row-sharded and
+        the index has dead rows; True when it acted.  Afterwards the unit holds slots for the NOT NULL positions only, still
+        in table order (`single_rows` strictly increasing), and `refresh` keeps following the table in place through that
+        map.  Exact distance ties break as in a unit built fresh from the table."""
+        if self.single is None or self.single_sharded is not None or len(self.single) == self.single.live_rows:
+            return False
+        new_of_old = np.asarray(self.single.compact())
+        self.single_rows = np.asarray(self.single_rows)[new_of_old >= 0]
+        self._forget_maps()
+        self.compacted = True
+        self.slot_per_position = False
+        return True
+
+    _HEAD_SLOTS, _HEAD_LIVE = 65536, 1024   # the dead-head condition: fewer than _HEAD_LIVE of the first _HEAD_SLOTS slots live
+
+    def _wants_compaction(self, null: np.ndarray) -> bool:
+        """The policy of `compact_dead_fraction`, from the NULL pattern of the table just applied (a slot is live exactly
+        when its position is NOT NULL).  Dead head: a search pass takes its first threshold from the first slots of the
+        index (DESIGN "Known cliff").  A table with fewer than 1024 live rows in its head meets that condition with any dead
+        row: at that size a compaction costs less than the fallbacks it avoids."""
+        if self.compact_dead_fraction is None:
+            return False
+        size = len(self.single)
+        dead = size - self.single.live_rows
+        if dead == 0:
+            return False
+        if dead >= self.compact_dead_fraction * size:
+            return True
+        head = np.asarray(self.single_rows)[:min(size, self._HEAD_SLOTS)]
+        return int((~null[head]).sum()) < self._HEAD_LIVE
 
     def refresh(self, table: ChunkTable) -> str:
         """Follow a newer export of the same table.  With the same primary keys in the same order (new keys only at the end)
@@ -285,8 +325,11 @@ class _UnitIndex:
 
         A changed key order, a changed width, a multi-vector column that appears or disappears (or one no index was built
         for) and row-sharded units (one process per GPU) fall back to the full rebuild (close; the next search builds from
-        `table`).  Returns "deferred" (nothing built yet), "unchanged" (neither column changed), "incremental", "relayout" or
-        "rebuild"."""
+        `table`).  Returns "deferred" (nothing built yet), "unchanged" (neither column changed), "incremental", "relayout",
+        "rebuild" or -- only with `compact_dead_fraction` set -- "compacted": the difference was applied in place and the
+        removed slots were then squeezed out (`compact_single`).  A compacted unit keeps following in place: changed rows, rows
+        that become NULL and new keys go through its row <-> position maps; only a NULL position that lost its slot to a
+        compaction and regains a vector is a "relayout"."""
         old = self.table
         if self.single is None and self.multi is None and self.single_sharded is None and self.multi_sharded is None:
             self.table = table
@@ -332,6 +375,8 @@ class _UnitIndex:
         outcome = "incremental"
         if single_changes:
             outcome = self._apply_single(single_plan, n_old)
+            if outcome == "incremental" and self._wants_compaction(single_plan["null"]) and self.compact_single():
+                outcome = "compacted"
         if multi_changes:
             self._apply_multi(table, multi_plan, n_old)
         self.table = table
@@ -356,6 +401,8 @@ class _UnitIndex:
 
     def _apply_single(self, plan: dict[str, Any], n_old: int) -> str:
         emb, null = plan["emb"], plan["null"]
+        if self.compacted:
+            return self._apply_single_compacted(plan, n_old)
         if not self.slot_per_position and plan["was_null"].any():
             logger.info("refresh: the index was built over NULL rows; laying it out with one slot per table position")
             self.single.close()
@@ -369,6 +416,28 @@ class _UnitIndex:
         self._append_slots(emb[n_old:], null[n_old:], n_old)
         self.single_rows = np.arange(emb.shape[0])        # (only here and in _build_slots: an index this call did not touch keeps
         return "incremental"                              # its rows -> positions map, compacted or not)
+
+    def _apply_single_compacted(self, plan: dict[str, Any], n_old: int) -> str:
+        """The same difference for a compacted unit, through single_rows (row -> position) and its inverse (position -> row,
+        -1: no slot).  Only a NULL position whose slot was squeezed out and that regains a vector cannot be served in place
+        -- its slot would have to lie between two others to keep table order -- and takes the one-slot-per-position layout."""
+        emb, null = plan["emb"], plan["null"]
+        row_of_pos = np.full(n_old, -1, dtype=np.int64)
+        row_of_pos[self.single_rows] = np.arange(self.single_rows.shape[0])
+        update, remove = np.nonzero(plan["update"])[0], np.nonzero(plan["remove"])[0]
+        if (row_of_pos[update] < 0).any():
+            logger.info("refresh: a NULL row without a slot in the compacted index regained a vector; laying it out with one "
+                        "slot per table position")
+            self.single.close()
+            self._build_slots(emb)
+            return "relayout"
+        if remove.size:
+            self.single.remove_rows(row_of_pos[remove])
+        if update.size:
+            self.single.update_rows(row_of_pos[update], emb[update])
+        self._append_slots(emb[n_old:], null[n_old:], len(self.single))
+        self.single_rows = np.concatenate([self.single_rows, np.arange(n_old, emb.shape[0])])
+        return "incremental"
 
     @staticmethod
     def _multi_difference(table: ChunkTable, old: ChunkTable, n_old: int) -> dict[str, Any]:
@@ -415,8 +484,12 @@ class Mi355RetrievalService:
       that needs the `autorag_research` package importable, which it is wherever the Executor runs.
     """
 
-    def __init__(self, session_factory: Callable[[], Any], schema: Any | None = None, device: int = 0):
+    def __init__(self, session_factory: Callable[[], Any], schema: Any | None = None, device: int = 0,
+                 compact_dead_fraction: float | None = None):
         self.session_factory = session_factory
+        # None: units never compact by themselves (compact_unit still does); else `_UnitIndex.refresh` compacts the single-vector
+        # index once that share of its slots is dead, or its head is
+        self._compact_dead_fraction = compact_dead_fraction
         self._schema = schema
         # one process per GPU under torch.distributed: this rank's GPU, row-sharded units, rank 0 reads ids / writes results
         self._world = _World.detect()
@@ -458,7 +531,7 @@ class Mi355RetrievalService:
                 # every rank exported the table by itself: global row ids are positions in the export order, so the ranks
                 # must have seen the SAME keys in the SAME order with the same NULL pattern before any of them shards it
                 self._world.same_everywhere(f"table {unit!r}", _table_digest(table))
-            self._units[unit] = _UnitIndex(table, self._device)
+            self._units[unit] = _UnitIndex(table, self._device, self._compact_dead_fraction)
         return self._units[unit]
 
     def refresh_unit(self, unit: str, table: ChunkTable) -> str:
@@ -469,6 +542,11 @@ class Mi355RetrievalService:
         if self._world is not None:
             self._world.same_everywhere(f"table {unit!r}", _table_digest(table))
         return self._units[unit].refresh(table)
+
+    def compact_unit(self, unit: str) -> bool:
+        """Squeeze the removed slots out of a unit's single-vector index now (`_UnitIndex.compact_single`); False when there
+        was nothing to do: no such unit or index yet, a row-sharded unit, or no removed slot."""
+        return unit in self._units and self._units[unit].compact_single()
 
     def get_queries(self, query_ids: list) -> list:
         """The stored query rows (None = no such query).  One process per GPU: rank 0 reads them and every rank gets the same

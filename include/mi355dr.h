@@ -84,7 +84,7 @@ int mi355dr_reserve(mi355dr_index* idx, int64_t n_rows);
 int mi355dr_add_rows(mi355dr_index* idx, const float* rows, int64_t n);
 /* same, rows already resident on this index's device (e.g. an embedding model's output tensor) */
 int mi355dr_add_rows_device(mi355dr_index* idx, const float* rows_dev, int64_t n);
-/* stored slots, live or removed (row ids are stable: nothing is ever renumbered) */
+/* stored slots, live or removed (row ids are stable: only mi355dr_compact renumbers, and says how) */
 int64_t mi355dr_size(const mi355dr_index* idx);
 int mi355dr_dim(const mi355dr_index* idx);
 
@@ -102,7 +102,7 @@ int mi355dr_dim(const mi355dr_index* idx);
  * rewritten + the int8 groups (32 rows) they fall into rebuilt + one 5-byte-per-row pass over the index that recounts
  * the side lists; the screens' two corpus-wide maxima (largest bf16 residual, largest norm) never shrink.
  * A search takes its first threshold from the first rows of the index (16 k; 64 k at 33 <= k <= 128): when fewer than k of
- * them are live -- the oldest rows all removed -- searches stay exact but fall back to slower paths; rebuild such an index.
+ * them are live -- the oldest rows all removed -- searches stay exact but fall back to slower paths; compact (or rebuild) such an index.
  * mi355dr_gqr_refine addresses rows directly and does not know removed rows: do not put them in a pool. */
 int mi355dr_update_rows(mi355dr_index* idx, const int64_t* row_ids, const float* rows, int64_t n); /* rows: host [n, dim] */
 /* the same with the new rows on this index's device ([n, dim] fp32); row_ids stay on the host */
@@ -110,6 +110,26 @@ int mi355dr_update_rows_device(mi355dr_index* idx, const int64_t* row_ids, const
 int mi355dr_remove_rows(mi355dr_index* idx, const int64_t* row_ids, int64_t n);
 /* mi355dr_size minus the removed rows (stat "dead_rows") */
 int64_t mi355dr_live_rows(const mi355dr_index* idx);
+/* ---- compaction ----
+ * Drop every removed row: the live rows keep their relative order and become rows 0 .. live-1.
+ * new_of_old: HOST [mi355dr_size() before the call] or NULL; entry r = the new id of old row r, -1 for a removed row.
+ * The call runs under the handle's mutex, first completes whatever search is in flight (its outputs carry the OLD ids) and is
+ * complete on return.  With no removed row it changes nothing, moves nothing and returns the identity map.  Afterwards
+ * mi355dr_size == mi355dr_live_rows == the old live count, stat "dead_rows" is 0, and every reader -- mi355dr_get_rows, the
+ * searches on every path, metric and screen_dtype, the stats "irregular_rows" / "loose_rows", the debug entry points --
+ * answers like an index built fresh by ONE mi355dr_add_rows of the live rows in their order; exact distance ties break by
+ * the new ids.  Live irregular and loose rows stay live, are listed under their new ids and are still returned last with NaN.
+ * Capacity does not shrink: the freed tail is room for later adds (stat "hbm_bytes_resident" is unchanged).  The screens' two
+ * monotone maxima (largest bf16 residual, largest norm) keep their values, as after a remove: candidate counts may differ
+ * from a fresh index's, results do not.  AUTO's demotion of the int8 screen (option "screen_dtype") was a verdict on the old
+ * layout -- a dead head overflows every int8 list -- and is re-armed, as setting that option does.
+ * Works in place through a staging buffer of option "compact_slice_rows" rows (default 65536); every allocation happens
+ * before the first byte of the index is written: MI355DR_E_NOMEM means nothing has changed.  A later failure can only be a
+ * device error; the handle is then unusable and must be destroyed (DESIGN.md "Compaction").
+ * Stats: "compactions" (calls that moved rows), "compact_moved_rows".
+ * The map is local to this handle: option "row_offset" and the communicator are not touched -- a row-sharded caller owns the
+ * renumbering across its shards.  Pools for mi355dr_gqr_refine must be rebuilt from the map.  The multi-vector store is untouched. */
+int mi355dr_compact(mi355dr_index* idx, int64_t* new_of_old);
 /* copy stored rows back (testing / cpu baseline): out host [n, dim] */
 int mi355dr_get_rows(mi355dr_index* idx, int64_t row0, int64_t n, float* out);
 
