@@ -160,8 +160,7 @@ class Mi355HyDERetrievalPipeline(Mi355BaseRetrievalPipeline):
 
         # generation + embedding: rank-local work that samples and may fail -> rank 0 alone, one broadcast of (live, vectors);
         # the retries above issue no collective
-        world = getattr(self._service, "_world", None)
-        live, vecs = world.from_root(generate_and_embed) if world is not None else generate_and_embed()
+        live, vecs = self._service.from_root(generate_and_embed)
         out: list[list[dict] | None] = [None] * len(query_ids)
         if not live:
             return out

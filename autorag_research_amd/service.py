@@ -19,7 +19,7 @@ import asyncio
 import logging
 import os
 from collections.abc import Awaitable, Callable
-from typing import Any, Literal
+from typing import Any, Literal, NamedTuple
 
 import numpy as np
 
@@ -74,12 +74,17 @@ class _World:
         """`make()` on rank 0, its (picklable) value on every rank.  An exception raised by `make()` on rank 0 travels the
         same way and is re-raised on EVERY rank: rank 0 always reaches the broadcast, so the other ranks never block on a
         collective that rank 0 left through an exception (a database error in `get_or_create_pipeline` / `next_page`)."""
-        box: list[Any] = [None]
+        outcome = None
         if self.rank == 0:
             try:
-                box[0] = (True, make())
-            except Exception as e:  # noqa: BLE001 - re-raised below, on every rank
-                box[0] = (False, self._portable(e))
+                outcome = (True, make())
+            except Exception as e:  # noqa: BLE001 - re-raised by share_outcome, on every rank
+                outcome = (False, self._portable(e))
+        return self.share_outcome(outcome)
+
+    def share_outcome(self, outcome: tuple[bool, Any] | None) -> Any:
+        """Rank 0's `(True, value)` or `(False, portable exception)` on every rank: the value returned, the exception raised."""
+        box: list[Any] = [outcome]
         self.dist.broadcast_object_list(box, src=0, group=self.group)
         ok, value = box[0]
         if not ok:
@@ -143,6 +148,20 @@ def _table_digest(table: ChunkTable) -> str:
     return h.hexdigest()
 
 
+class _SinglePlan(NamedTuple):  # what a newer export asks of the single-vector index (_UnitIndex._single_difference)
+    emb: np.ndarray         # the new column, float32
+    null: np.ndarray        # [n_new] bool: NULL in the new export
+    was_null: np.ndarray    # [n_old] bool: NULL in the old one
+    update: np.ndarray      # [n_old] bool: holds a vector now that differs from the old one (a revived NULL included)
+    remove: np.ndarray      # [n_old] bool: became NULL
+
+
+class _MultiPlan(NamedTuple):   # ... and of the multi-vector store (_UnitIndex._multi_difference)
+    off: np.ndarray         # the new offsets, int64
+    tok: np.ndarray         # the new token rows, float32
+    changed: np.ndarray     # positions < n_old whose documents differ
+
+
 class _UnitIndex:
     """GPU index of one table (chunk / image_chunk): row <-> primary-key mapping + the native handle."""
 
@@ -150,39 +169,52 @@ class _UnitIndex:
         self.table = table
         self.single: Mi355Index | None = None
         self.multi: Mi355Index | None = None
-        self.single_rows: np.ndarray | None = None  # index row -> table position (NULL embeddings skipped)
+        # THE layout of the single-vector index: index row -> table position, strictly increasing.  Every NOT NULL position
+        # has a slot; a NULL position has a removed slot or none
+        self.single_rows: np.ndarray | None = None
         self.multi_rows: np.ndarray | None = None
         self.device = device
         self.single_sharded: Any | None = None      # ShardedSearcher over this rank's rows (a _World is active)
         self.multi_sharded: Any | None = None
-        # False: `single` holds the NOT NULL rows compacted (how ensure_single builds it).  True (after a refresh): one slot
-        # per table position, NULL rows are removed slots -- single_rows is the identity and every later change is in place
-        self.slot_per_position = False
-        # True (after compact_single): `single` holds slots for a SUBSET of the table positions, in table order -- single_rows is
-        # strictly increasing, positions that were NULL at the compaction have no slot, and refresh works through that map
+        # True (after compact_single): the positions that were NULL at the compaction have no slot ON PURPOSE and refresh works
+        # through the map.  False with such positions missing: built over NULL rows and never laid out (`_apply_single`)
         self.compacted = False
         # refresh compacts by itself once dead / size reaches this fraction, or the head of the index is dead (None: never)
         self.compact_dead_fraction = compact_dead_fraction
+        self._pos_of_id = self._stored_row_of_pos = None   # (dict) caches of pos_of_id() / stored_row_of_pos(): see _forget_maps
 
-    def ensure_single_sharded(self, world: "_World") -> Any:
-        """This rank's contiguous share of the NOT NULL rows behind a ShardedSearcher (global row ids = positions in the
-        table's not-null order, the same ids the unsharded index uses)."""
+    def _not_null_positions(self) -> np.ndarray:
+        emb = self.table.embedding
+        if emb is None:
+            raise ValueError("table has no single-vector embeddings")
+        return np.nonzero(~np.isnan(emb).all(axis=1))[0]  # WHERE embedding IS NOT NULL
+
+    def single_positions(self) -> np.ndarray:
+        """`single_rows`, without building an index: a unit nothing was laid out for has the NOT NULL rows in table order."""
+        if self.single_rows is None:
+            self.single_rows = self._not_null_positions()
+        return self.single_rows
+
+    def single_searcher(self, world: "_World | None") -> Any:
+        """The local index -- or, under a world, this rank's contiguous share of the NOT NULL rows behind a ShardedSearcher
+        (global row ids = positions in the table's not-null order, the same ids the unsharded index uses)."""
+        if world is None:
+            return self.ensure_single()
         if self.single_sharded is None:
             from .sharded import ShardedSearcher, shard_bounds  # noqa: PLC0415
 
-            emb = self.table.embedding
-            if emb is None:
-                raise ValueError("table has no single-vector embeddings")
-            not_null = ~np.isnan(emb).all(axis=1)
-            self.single_rows = np.nonzero(not_null)[0]
-            lo, hi = shard_bounds(int(self.single_rows.shape[0]), world.size, world.rank)
+            rows, emb = self.single_positions(), self.table.embedding
+            lo, hi = shard_bounds(int(rows.shape[0]), world.size, world.rank)
             s = ShardedSearcher(emb.shape[1], "cosine", self.device, index_factory=Mi355Index, group=world.group)
-            s.add_local(emb[self.single_rows[lo:hi]], lo)
+            s.add_local(emb[rows[lo:hi]], lo)
             self.single_sharded = s
         return self.single_sharded
 
-    def ensure_multi_sharded(self, world: "_World") -> Any:
-        """Multi-vector table: docs cut by cumulative TOKEN count (the MaxSim pass streams token rows: SURVEY 8(e))."""
+    def multi_searcher(self, world: "_World | None") -> Any:
+        """Multi-vector table: under a world the docs are cut by cumulative TOKEN count (the MaxSim pass streams token rows:
+        SURVEY 8(e))."""
+        if world is None:
+            return self.ensure_multi()
         if self.multi_sharded is None:
             from .sharded import ShardedSearcher, shard_bounds_by_tokens  # noqa: PLC0415
 
@@ -196,25 +228,11 @@ class _UnitIndex:
             self.multi_rows = np.arange(off.shape[0] - 1)
         return self.multi_sharded
 
-    def single_positions(self) -> np.ndarray:
-        """index row -> table position for the single-vector column (`WHERE embedding IS NOT NULL` order), without building
-        an index (one process per GPU: no rank holds the whole table on its GPU)."""
-        if self.single_rows is None:
-            emb = self.table.embedding
-            if emb is None:
-                raise ValueError("table has no single-vector embeddings")
-            self.single_rows = np.nonzero(~np.isnan(emb).all(axis=1))[0]
-        return self.single_rows
-
     def ensure_single(self) -> Mi355Index:
         if self.single is None:
-            emb = self.table.embedding
-            if emb is None:
-                raise ValueError("table has no single-vector embeddings")
-            not_null = ~np.isnan(emb).all(axis=1)  # WHERE embedding IS NOT NULL
-            self.single_rows = np.nonzero(not_null)[0]
+            rows, emb = self.single_positions(), self.table.embedding
             self.single = Mi355Index(emb.shape[1], "cosine", self.device)
-            self.single.add(emb[not_null] if not not_null.all() else emb)
+            self.single.add(emb if rows.shape[0] == emb.shape[0] else emb[rows])
         return self.single
 
     def ensure_multi(self) -> Mi355Index:
@@ -232,21 +250,54 @@ class _UnitIndex:
             if ix is not None:
                 ix.close()
         self.single = self.multi = self.single_sharded = self.multi_sharded = None
+        self._start_over(self.table)
+
+    # ---- primary key -> table position -> index row (the GQR pools and the candidate scorer name chunks by key) ----
+    def pos_of_id(self) -> dict:
+        if self._pos_of_id is None:
+            self._pos_of_id = {pk: i for i, pk in enumerate(self.table.ids)}
+        return self._pos_of_id
+
+    def stored_row_of_pos(self) -> dict:
+        """table position -> index row, for the positions whose embedding is STORED.  Not `_slot_of_pos`: a refreshed unit
+        keeps a slot for a NULL embedding -- a removed row that still holds a vector -- and that is not a stored one."""
+        if self._stored_row_of_pos is None:
+            stored = self._not_null_positions()
+            self._stored_row_of_pos = dict(zip(stored.tolist(), self._slot_of_pos()[stored].tolist()))
+        return self._stored_row_of_pos
+
+    def _slot_of_pos(self) -> np.ndarray:
+        """table position -> index row for EVERY position that has a slot, live or removed (-1: no slot): what a refresh
+        addresses -- updating a removed slot is how a NULL is revived."""
+        rows, slot = self.single_positions(), np.full(len(self.table.ids), -1, dtype=np.int64)
+        slot[rows] = np.arange(rows.shape[0])
+        return slot
+
+    def _forget_maps(self) -> None:   # (the caches of pos_of_id / stored_row_of_pos: stale once the table or the layout changes)
+        self._pos_of_id = self._stored_row_of_pos = None
+
+    @property
+    def slot_per_position(self) -> bool:
+        """There is a slot for every table position (NULL rows are removed slots, `single_rows` is the identity)."""
+        return self.single_rows is not None and self.single_rows.shape[0] == len(self.table.ids)
 
     # ---- following the table ----
-    def _forget_maps(self) -> None:
-        """The key -> position and position -> row maps the service caches on the unit: stale once the table is replaced."""
-        self.__dict__.pop("_pos_of_id", None)
-        self.__dict__.pop("_row_of_pos", None)
+    def _start_over(self, table: ChunkTable) -> None:
+        """Take `table` and forget everything derived from the old one: the row maps, the key maps, the layout flag."""
+        self.table = table
+        self.single_rows = self.multi_rows = None
+        self.compacted = False
+        self._forget_maps()
 
-    def _build_slots(self, emb: np.ndarray) -> None:
-        """`single` with one slot per table position: NULL rows are added as placeholders and removed at once."""
-        null = np.isnan(emb).all(axis=1)
+    def _relayout(self, emb: np.ndarray, null: np.ndarray, why: str) -> str:
+        """`single` anew with one slot per table position: NULL rows are added as placeholders and removed at once."""
+        logger.info("refresh: %s; laying it out with one slot per table position", why)
+        self.single.close()
         self.single = Mi355Index(emb.shape[1], "cosine", self.device)
         self._append_slots(emb, null, 0)
         self.single_rows = np.arange(emb.shape[0])
-        self.slot_per_position = True
         self.compacted = False
+        return "relayout"
 
     def _append_slots(self, emb: np.ndarray, null: np.ndarray, first: int) -> None:
         if emb.shape[0] == 0:
@@ -258,11 +309,7 @@ class _UnitIndex:
     def _rebuild(self, table: ChunkTable, why: str) -> str:
         logger.info("refresh: full rebuild of the index (%s)", why)
         self.close()
-        self.table = table
-        self.single_rows = self.multi_rows = None
-        self.slot_per_position = False
-        self.compacted = False
-        self._forget_maps()
+        self._start_over(table)
         return "rebuild"
 
     # ---- compaction (Mi355Index.compact: the removed slots are squeezed out in place, the live rows keep their order) ----
@@ -277,7 +324,6 @@ class _UnitIndex:
         self.single_rows = np.asarray(self.single_rows)[new_of_old >= 0]
         self._forget_maps()
         self.compacted = True
-        self.slot_per_position = False
         return True
 
     _HEAD_SLOTS, _HEAD_LIVE = 65536, 1024   # the dead-head condition: fewer than _HEAD_LIVE of the first _HEAD_SLOTS slots live
@@ -312,29 +358,22 @@ class _UnitIndex:
             token count or token bits changed, vectors lost, vectors regained -> ONE set_multivec (no vectors = removed)
             new keys at the end -> ONE add_multivec
 
-        A unit with both indexes built takes both differences; one that has only the multi-vector index built takes that one (the
-        single-vector index is built from `table` when it is first asked for, `single_rows` is forgotten, and a change of the
-        embedding column alone is still "incremental": "unchanged" means neither column changed).
+        A unit with both indexes built takes both differences; one with only the multi-vector index built takes that one (the
+        single-vector index is built from `table` when first asked for, and "unchanged" means neither column changed).
 
-        Row mapping: a single-vector index that was never refreshed holds the NOT NULL rows compacted (`single_rows` = their
-        table positions).  The first refresh that has to change rows switches the unit to ONE SLOT PER TABLE POSITION, NULL rows
-        being removed slots (`single_rows` = the identity): a compacted index without NULL rows already has that form; one
-        built over NULL rows is laid out anew once (the only rebuild on this path), from then on every change is in place.
-        Slots stay in table order either way, so exact distance ties break as in a unit built fresh from `table`.  The
-        multi-vector index always has one document per table position (`multi_rows` = the identity).
+        Row mapping: `single_rows` is the layout and the difference is applied through it (`_apply_single`): a row that
+        becomes NULL keeps its slot, removed; new keys get slots at the end.  An index built over NULL rows is laid out anew
+        ONCE -- one slot per table position, NULL rows being removed slots -- at the first refresh that changes the column (the
+        only rebuild on this path).  Slots stay in table order throughout, so exact distance ties break as in a unit built
+        fresh from `table`.  The multi-vector index always has one document per table position (`multi_rows` = the identity).
 
         A changed key order, a changed width, a multi-vector column that appears or disappears (or one no index was built
         for) and row-sharded units (one process per GPU) fall back to the full rebuild (close; the next search builds from
-        `table`).  Returns "deferred" (nothing built yet), "unchanged" (neither column changed), "incremental", "relayout",
-        "rebuild" or -- only with `compact_dead_fraction` set -- "compacted": the difference was applied in place and the
-        removed slots were then squeezed out (`compact_single`).  A compacted unit keeps following in place: changed rows, rows
-        that become NULL and new keys go through its row <-> position maps; only a NULL position that lost its slot to a
-        compaction and regains a vector is a "relayout"."""
+        `table`).  Returns "deferred" (nothing built yet), "unchanged", "incremental", "relayout", "rebuild" or -- only with
+        `compact_dead_fraction` set -- "compacted": applied in place, the removed slots then squeezed out (`compact_single`)."""
         old = self.table
         if self.single is None and self.multi is None and self.single_sharded is None and self.multi_sharded is None:
-            self.table = table
-            self.single_rows = self.multi_rows = None
-            self._forget_maps()
+            self._start_over(table)
             return "deferred"
         if table.mv_offsets is not None or old.mv_offsets is not None or self.multi is not None or self.multi_sharded is not None:
             if self.multi_sharded is not None or self.single_sharded is not None:
@@ -360,8 +399,8 @@ class _UnitIndex:
             multi_plan = self._multi_difference(table, old, n_old)
         self._forget_maps()
         appended = len(table.ids) > n_old
-        single_changes = single_plan is not None and (single_plan["update"].any() or single_plan["remove"].any() or appended)
-        multi_changes = multi_plan is not None and (multi_plan["changed"].size > 0 or appended)
+        single_changes = single_plan is not None and (single_plan.update.any() or single_plan.remove.any() or appended)
+        multi_changes = multi_plan is not None and (multi_plan.changed.size > 0 or appended)
         if self.single is None:
             # no single-vector index to follow: it is built from `table` when first asked for, and positions cached from the
             # old table's NULL pattern (`single_positions`) do not outlive that table
@@ -375,7 +414,7 @@ class _UnitIndex:
         outcome = "incremental"
         if single_changes:
             outcome = self._apply_single(single_plan, n_old)
-            if outcome == "incremental" and self._wants_compaction(single_plan["null"]) and self.compact_single():
+            if outcome == "incremental" and self._wants_compaction(single_plan.null) and self.compact_single():
                 outcome = "compacted"
         if multi_changes:
             self._apply_multi(table, multi_plan, n_old)
@@ -392,55 +431,35 @@ class _UnitIndex:
         return a.shape == b.shape and bool((a.view(np.uint32) == b.view(np.uint32)).all())      # (bits: NaN-safe)
 
     @staticmethod
-    def _single_difference(emb: np.ndarray, was: np.ndarray, n_old: int) -> dict[str, Any]:
+    def _single_difference(emb: np.ndarray, was: np.ndarray, n_old: int) -> _SinglePlan:
         null, was_null = np.isnan(emb).all(axis=1), np.isnan(was).all(axis=1)
         head, head_null = emb[:n_old], null[:n_old]
         differ = (head.view(np.uint32) != was.view(np.uint32)).any(axis=1)      # (bits: NaN-safe)
-        return {"emb": emb, "null": null, "was_null": was_null, "update": ~head_null & (was_null | differ),
-                "remove": head_null & ~was_null}
+        return _SinglePlan(emb=emb, null=null, was_null=was_null, update=~head_null & (was_null | differ),
+                           remove=head_null & ~was_null)
 
-    def _apply_single(self, plan: dict[str, Any], n_old: int) -> str:
-        emb, null = plan["emb"], plan["null"]
-        if self.compacted:
-            return self._apply_single_compacted(plan, n_old)
-        if not self.slot_per_position and plan["was_null"].any():
-            logger.info("refresh: the index was built over NULL rows; laying it out with one slot per table position")
-            self.single.close()
-            self._build_slots(emb)
-            return "relayout"
-        self.slot_per_position = True
-        if plan["remove"].any():
-            self.single.remove_rows(np.nonzero(plan["remove"])[0])
-        if plan["update"].any():
-            self.single.update_rows(np.nonzero(plan["update"])[0], emb[:n_old][plan["update"]])
-        self._append_slots(emb[n_old:], null[n_old:], n_old)
-        self.single_rows = np.arange(emb.shape[0])        # (only here and in _build_slots: an index this call did not touch keeps
-        return "incremental"                              # its rows -> positions map, compacted or not)
-
-    def _apply_single_compacted(self, plan: dict[str, Any], n_old: int) -> str:
-        """The same difference for a compacted unit, through single_rows (row -> position) and its inverse (position -> row,
-        -1: no slot).  Only a NULL position whose slot was squeezed out and that regains a vector cannot be served in place
-        -- its slot would have to lie between two others to keep table order -- and takes the one-slot-per-position layout."""
-        emb, null = plan["emb"], plan["null"]
-        row_of_pos = np.full(n_old, -1, dtype=np.int64)
-        row_of_pos[self.single_rows] = np.arange(self.single_rows.shape[0])
-        update, remove = np.nonzero(plan["update"])[0], np.nonzero(plan["remove"])[0]
-        if (row_of_pos[update] < 0).any():
-            logger.info("refresh: a NULL row without a slot in the compacted index regained a vector; laying it out with one "
-                        "slot per table position")
-            self.single.close()
-            self._build_slots(emb)
-            return "relayout"
+    def _apply_single(self, plan: _SinglePlan, n_old: int) -> str:
+        """Apply the difference through `single_rows` and its inverse (`_slot_of_pos`; `self.table` is still the old table
+        here).  An index this call does not touch keeps its layout."""
+        emb, null = plan.emb, plan.null
+        slot = self._slot_of_pos()
+        update, remove = np.nonzero(plan.update)[0], np.nonzero(plan.remove)[0]
+        if not self.compacted and self.single_rows.shape[0] < n_old:
+            # KEPT ON PURPOSE (the routine below could serve this unit in place wherever no NULL row regains a vector): a unit
+            # built over NULL rows and never compacted lays itself out at the first change of the column, whatever the change
+            return self._relayout(emb, null, "the index was built over NULL rows")
+        if (slot[update] < 0).any():   # (its slot would have to lie between two others to keep table order)
+            return self._relayout(emb, null, "a NULL row without a slot in the compacted index regained a vector")
         if remove.size:
-            self.single.remove_rows(row_of_pos[remove])
+            self.single.remove_rows(slot[remove])
         if update.size:
-            self.single.update_rows(row_of_pos[update], emb[update])
+            self.single.update_rows(slot[update], emb[update])
         self._append_slots(emb[n_old:], null[n_old:], len(self.single))
         self.single_rows = np.concatenate([self.single_rows, np.arange(n_old, emb.shape[0])])
         return "incremental"
 
     @staticmethod
-    def _multi_difference(table: ChunkTable, old: ChunkTable, n_old: int) -> dict[str, Any]:
+    def _multi_difference(table: ChunkTable, old: ChunkTable, n_old: int) -> _MultiPlan:
         """Positions < n_old whose documents differ between the two exports: another token count (losing or regaining every
         vector included) or, at the same count, other token bits."""
         off = np.ascontiguousarray(table.mv_offsets, dtype=np.int64)
@@ -457,10 +476,10 @@ class _UnitIndex:
             rows, was_rows = np.repeat(off[same], n) + within, np.repeat(was_off[same], n) + within
             differ = (tok[rows].view(np.uint32) != was_tok[was_rows].view(np.uint32)).any(axis=1)   # (bits: NaN-safe)
             changed[same[np.logical_or.reduceat(differ, first)]] = True
-        return {"off": off, "tok": tok, "changed": np.nonzero(changed)[0]}
+        return _MultiPlan(off=off, tok=tok, changed=np.nonzero(changed)[0])
 
-    def _apply_multi(self, table: ChunkTable, plan: dict[str, Any], n_old: int) -> None:
-        off, tok, ids = plan["off"], plan["tok"], plan["changed"]
+    def _apply_multi(self, table: ChunkTable, plan: _MultiPlan, n_old: int) -> None:
+        off, tok, ids = plan.off, plan.tok, plan.changed
         if ids.size:
             lens = off[ids + 1] - off[ids]
             parts = [tok[off[i]:off[i + 1]] for i in ids]
@@ -493,11 +512,10 @@ class Mi355RetrievalService:
         self._schema = schema
         # one process per GPU under torch.distributed: this rank's GPU, row-sharded units, rank 0 reads ids / writes results
         self._world = _World.detect()
-        if self._world is not None and "LOCAL_RANK" in os.environ:
-            device = int(os.environ["LOCAL_RANK"])
-        self._device = device
         if self._world is not None:
+            device = int(os.environ.get("LOCAL_RANK", device))
             self._world.bind_device(device)
+        self._device = device
         self._units: dict[str, _UnitIndex] = {}
         self._uow_store: UowStore | None = None
         probe = session_factory()
@@ -517,20 +535,42 @@ class Mi355RetrievalService:
     def _store(self) -> Any:
         return self._uow_store if self._uow_store is not None else self.session_factory()
 
+    def from_root(self, make: Callable[[], Any]) -> Any:
+        """`make()` -- under a _World on rank 0 only, its value (or its exception) on every rank (`_World.from_root`).  This,
+        `on_root`, `agree` and `_same_table_everywhere` are the only places that ask "one process per GPU, or not"."""
+        return make() if self._world is None else self._world.from_root(make)
+
+    async def on_root(self, make: Callable[[], Awaitable[Any]]) -> Any:
+        """`await make()`, shared the same way: an embedding-model call is a rank-local step that may fail or differ."""
+        if self._world is None:
+            return await make()
+        outcome = None
+        if self._world.rank == 0:
+            try:
+                outcome = (True, await make())
+            except Exception as e:  # noqa: BLE001 - re-raised by share_outcome, on every rank
+                outcome = (False, _World._portable(e))
+        return self._world.share_outcome(outcome)
+
+    def agree(self, ok: bool) -> bool:
+        """True iff `ok` on every rank (`_World.agree`); `ok` itself in a single process."""
+        return ok if self._world is None else self._world.agree(ok)
+
+    def _same_table_everywhere(self, unit: str, table: ChunkTable) -> None:
+        """Every rank exported the table by itself: global row ids are positions in the export order, so the ranks must have
+        seen the SAME keys in the SAME order with the same NULL pattern before any of them shards or follows it."""
+        if self._world is not None:
+            self._world.same_everywhere(f"table {unit!r}", _table_digest(table))
+
     def delete_pipeline_results(self, pipeline_id) -> int:
         """Reference RetrievalPipelineService.delete_pipeline_results (:359-372): the Executor's health-check cleanup."""
-        if self._world is not None:
-            return self._world.from_root(lambda: self._store().delete_pipeline_results(pipeline_id))
-        return self._store().delete_pipeline_results(pipeline_id)
+        return self.from_root(lambda: self._store().delete_pipeline_results(pipeline_id))
 
     def _unit(self, unit: str) -> _UnitIndex:
         if unit not in self._units:
             store = self._store()
             table = store.image_chunks if unit == "image_chunk" else store.chunks
-            if self._world is not None:
-                # every rank exported the table by itself: global row ids are positions in the export order, so the ranks
-                # must have seen the SAME keys in the SAME order with the same NULL pattern before any of them shards it
-                self._world.same_everywhere(f"table {unit!r}", _table_digest(table))
+            self._same_table_everywhere(unit, table)
             self._units[unit] = _UnitIndex(table, self._device, self._compact_dead_fraction)
         return self._units[unit]
 
@@ -539,8 +579,7 @@ class Mi355RetrievalService:
         (`_UnitIndex.refresh`).  A unit nothing was built for yet reads the store's table at its first search, as before."""
         if unit not in self._units:
             return "deferred"
-        if self._world is not None:
-            self._world.same_everywhere(f"table {unit!r}", _table_digest(table))
+        self._same_table_everywhere(unit, table)
         return self._units[unit].refresh(table)
 
     def compact_unit(self, unit: str) -> bool:
@@ -552,25 +591,7 @@ class Mi355RetrievalService:
         """The stored query rows (None = no such query).  One process per GPU: rank 0 reads them and every rank gets the same
         rows -- a transient database error then happens once, on rank 0, and reaches every rank as the same exception instead
         of sending one rank down the retry path while the others wait in the block's collective."""
-        read = lambda: [self._store().get_query(q) for q in query_ids]  # noqa: E731
-        return self._world.from_root(read) if self._world is not None else read()
-
-    async def on_root(self, make: Callable[[], Awaitable[Any]]) -> Any:
-        """`await make()` -- under a _World on rank 0 only, its value (or its exception) on every rank: an embedding-model
-        call in `_retrieve_by_text` is a rank-local step that may fail or differ between ranks."""
-        if self._world is None:
-            return await make()
-        box: list[Any] = [None]
-        if self._world.rank == 0:
-            try:
-                box[0] = (True, await make())
-            except Exception as e:  # noqa: BLE001
-                box[0] = (False, _World._portable(e))
-        self._world.dist.broadcast_object_list(box, src=0, group=self._world.group)
-        ok, value = box[0]
-        if not ok:
-            raise value
-        return value
+        return self.from_root(lambda: [self._store().get_query(q) for q in query_ids])
 
     def close(self) -> None:
         for u in self._units.values():
@@ -581,14 +602,11 @@ class Mi355RetrievalService:
             self._scratch = None
 
     def get_or_create_pipeline(self, name: str, config: dict[str, Any]) -> tuple[int, bool]:
-        if self._world is not None:  # one row in the pipeline table, created by rank 0
-            return tuple(self._world.from_root(lambda: tuple(self._store().get_or_create_pipeline(name, config))))
-        return self._store().get_or_create_pipeline(name, config)
+        # (one process per GPU: one row in the pipeline table, created by rank 0)
+        return self.from_root(lambda: tuple(self._store().get_or_create_pipeline(name, config)))
 
     def find_query_by_text(self, query_text: str):
-        if self._world is not None:
-            return self._world.from_root(lambda: self._store().find_query_by_text(query_text))
-        return self._store().find_query_by_text(query_text)
+        return self.from_root(lambda: self._store().find_query_by_text(query_text))
 
     def _make_retrieval_result(self, table: ChunkTable, pos: int, score: float, with_content: bool) -> dict[str, Any]:
         return {"doc_id": table.ids[pos], "score": score, "content": table.contents[pos] if with_content else None}
@@ -635,10 +653,8 @@ class Mi355RetrievalService:
 
     def _single_block(self, Q: np.ndarray, top_k: int, unit: str) -> list[list[dict]]:
         u = self._unit(unit)
-        if self._world is not None:  # every rank: local top-k of its rows, all-gather, merge -> the same global lists
-            dist, rows = u.ensure_single_sharded(self._world).search(Q, top_k)
-        else:
-            dist, rows = u.ensure_single().search(Q, top_k)
+        # (one process per GPU, every rank: local top-k of its rows, all-gather, merge -> the same global lists)
+        dist, rows = u.single_searcher(self._world).search(Q, top_k)
         # reference: score = 1 - distance (retrieval_pipeline.py:522-524) in Python float arithmetic = IEEE double
         return self._results_from_block(u.table, u.single_rows, rows, 1.0 - dist, unit == "chunk")
 
@@ -649,7 +665,7 @@ class Mi355RetrievalService:
 
     def maxsim_search_by_embeddings(self, query_vectors: list, top_k: int, unit: str = "chunk") -> list[list[dict]]:
         u = self._unit(unit)
-        ix = u.ensure_multi_sharded(self._world) if self._world is not None else u.ensure_multi()
+        ix = u.multi_searcher(self._world)
         dim = u.table.mv_tokens.shape[1]
         mats = [np.asarray(qv, dtype=np.float32).reshape(-1, dim) for qv in query_vectors]
         lens = [m.shape[0] for m in mats]
@@ -672,10 +688,7 @@ class Mi355RetrievalService:
         `_score_candidates`, heaven.py:244-266).  Ids unknown to the table or without multi-vector embeddings are left
         out (as `_fetch_candidate_multi_embeddings` does, heaven.py:224-241); no query vectors -> every score 0.0."""
         u = self._unit(unit)
-        pos = getattr(u, "_pos_of_id", None)
-        if pos is None:
-            pos = u._pos_of_id = {pk: i for i, pk in enumerate(u.table.ids)}
-        off = u.table.mv_offsets
+        pos, off = u.pos_of_id(), u.table.mv_offsets
         known = [(pk, pos[pk]) for pk in doc_ids if pk in pos and off is not None and off[pos[pk] + 1] > off[pos[pk]]]
         if not known:
             return {}
@@ -683,10 +696,9 @@ class Mi355RetrievalService:
         if q.size == 0:
             return {pk: 0.0 for pk, _ in known}
         # one process per GPU: the token-sharded store -- every rank scores the candidates it owns, one all-gather of [1, m] fp32
-        ix = u.ensure_multi_sharded(self._world) if self._world is not None else u.ensure_multi()
         q = q.reshape(-1, u.table.mv_tokens.shape[1])
         rows = np.array([[p for _, p in known]], dtype=np.int64)
-        dist = ix.maxsim_subset(q, np.array([0, q.shape[0]], dtype=np.int32), rows)[0]
+        dist = u.multi_searcher(self._world).maxsim_subset(q, np.array([0, q.shape[0]], dtype=np.int32), rows)[0]
         return {pk: -float(dv) / q.shape[0] for (pk, _), dv in zip(known, dist) if dv == dv}
 
     # ---- Guided Query Refinement support (reference retrieval_pipeline.py:573-641 + gqr_hybrid.py:306-362) ----
@@ -715,18 +727,10 @@ class Mi355RetrievalService:
         u = self._unit("chunk")
         if u.table.embedding is None:
             return None
-        if self._world is not None:
-            u.single_positions()   # (the mapping only: the rows themselves are staged per page, see gqr_refine_single)
-        else:
+        if self._world is None:    # (one process per GPU: the mapping only -- the rows are staged per page, see gqr_refine_single)
             u.ensure_single()
-        inv = getattr(u, "_row_of_pos", None)
-        if inv is None:
-            # (a refreshed unit keeps a slot for a NULL embedding -- a removed row that still holds a vector: not a stored one)
-            stored = ~np.isnan(u.table.embedding).all(axis=1)
-            inv = u._row_of_pos = {int(p): r for r, p in enumerate(u.single_rows) if stored[p]}
-        if getattr(u, "_pos_of_id", None) is None:
-            u._pos_of_id = {pk: i for i, pk in enumerate(u.table.ids)}
-        rows = [inv.get(u._pos_of_id.get(pk, -1), -1) for pk in doc_ids]
+        pos, row = u.pos_of_id(), u.stored_row_of_pos()
+        rows = [row.get(pos.get(pk, -1), -1) for pk in doc_ids]
         return None if any(r < 0 for r in rows) else np.asarray(rows, dtype=np.int64)
 
     def chunk_rows_multi(self, doc_ids: list) -> np.ndarray | None:
@@ -737,9 +741,7 @@ class Mi355RetrievalService:
             return None
         if self._world is None:
             u.ensure_multi()
-        if getattr(u, "_pos_of_id", None) is None:
-            u._pos_of_id = {pk: i for i, pk in enumerate(u.table.ids)}
-        pos = [u._pos_of_id.get(pk, -1) for pk in doc_ids]
+        pos = [u.pos_of_id().get(pk, -1) for pk in doc_ids]
         if any(p < 0 or off[p + 1] <= off[p] for p in pos):
             return None
         return np.asarray(pos, dtype=np.int64)
@@ -809,15 +811,12 @@ class Mi355RetrievalService:
         """
         store = self._store()
         result_id_key = "image_chunk_id" if unit == "image_chunk" else "chunk_id"
-        read_unit = lambda: store.pipeline_config(pipeline_id).get("retrieval_unit", "chunk")  # noqa: E731
-        configured = self._world.from_root(read_unit) if self._world is not None else read_unit()
+        configured = self.from_root(lambda: store.pipeline_config(pipeline_id).get("retrieval_unit", "chunk"))
         if configured == "mixed":
             raise ValueError(f"Pipeline {pipeline_id!r} is configured for mixed results, which cannot be persisted directly.")
         if configured != unit:
             raise ValueError(f"Pipeline {pipeline_id!r} is configured for {configured} results; "
                              f"refusing to persist {unit} results into the same pipeline identity.")
-
-        world = self._world
 
         async def one(qid) -> list[dict] | None:
             assert retrieval_func is not None
@@ -830,7 +829,7 @@ class Mi355RetrievalService:
                     err = e
                 # one process per GPU: an attempt counts only if it succeeded on EVERY rank -- all ranks then retry (or give
                 # the query up) together, and their sequences of collective searches stay aligned
-                if (err is None) if world is None else world.agree(err is None):
+                if self.agree(err is None):
                     return res
                 if attempt + 1 >= max(1, max_retries):
                     logger.error(f"Retrieval failed for query {qid} after {max_retries} attempts", exc_info=err)
@@ -848,8 +847,8 @@ class Mi355RetrievalService:
 
             return list(await asyncio.gather(*[guarded(q) for q in qids]))
 
-        writer = world is None or world.rank == 0  # one process per GPU: rank 0 reads the page's ids and persists
-        if world is not None:
+        writer = self._world is None or self._world.rank == 0  # one process per GPU: rank 0 reads the page's ids and persists
+        if self._world is not None:
             max_concurrency = 1  # the per-query fallback is a sequence of collective searches: the same order on every rank
 
         def next_page(eff: int, offset: int):
@@ -867,7 +866,7 @@ class Mi355RetrievalService:
             if query_limit is not None and total_queries >= query_limit:
                 break
             eff = min(batch_size, query_limit - total_queries) if query_limit is not None else batch_size
-            n_page, qids = world.from_root(lambda: next_page(eff, offset)) if world is not None else next_page(eff, offset)
+            n_page, qids = self.from_root(lambda: next_page(eff, offset))
             if n_page == 0:
                 break
             if not qids:
@@ -884,7 +883,7 @@ class Mi355RetrievalService:
                 # rank-local HIP / out-of-memory error, while its peers are already inside the block's all-gather leaves them
                 # blocked there -- what ends that is the process group's own timeout (`init_process_group(timeout=...)`,
                 # torchrun's failure detection), not this code; INTEGRATION.md "one process per GPU" says so.)
-                if not ((block_err is None) if world is None else world.agree(block_err is None)):
+                if not self.agree(block_err is None):
                     # one bad query (missing / malformed embedding, too many query vectors for a block, an embedding-batch
                     # error) must not abort the run: the page falls back to the reference's per-query path, where retries,
                     # backoff and `failed_queries` apply to that query alone (retrieval_pipeline.py:222-236)

@@ -9,100 +9,14 @@ import pytest
 
 from autorag_research_amd import service as svc
 from autorag_research_amd.store import ChunkTable
-
-D, K = 16, 12
-
-
-class MutableOracleIndex:
-    """add / update_rows / remove_rows / search with Mi355Index's semantics: stable row ids, removed rows never returned,
-    answered by oracle.topk_search over the compacted live rows."""
-
-    created = 0
-
-    def __init__(self, dim, metric="cosine", device=0):
-        from oracle import cpu_ref
-
-        self._o, self.dim, self.metric = cpu_ref, dim, metric
-        self._rows = np.zeros((0, dim), np.float32)
-        self._live = np.zeros(0, bool)
-        self.calls = []
-        self.closed = False
-        MutableOracleIndex.created += 1
-
-    def __len__(self):
-        return self._rows.shape[0]
-
-    @property
-    def live_rows(self):
-        return int(self._live.sum())
-
-    def add(self, rows):
-        rows = np.ascontiguousarray(rows, dtype=np.float32)
-        self.calls.append(("add", rows.shape[0]))
-        self._rows = np.concatenate([self._rows, rows])
-        self._live = np.concatenate([self._live, np.ones(rows.shape[0], bool)])
-
-    def _ids(self, row_ids):
-        ids = np.asarray(row_ids, dtype=np.int64)
-        assert ids.ndim == 1 and np.unique(ids).shape[0] == ids.shape[0] and (ids >= 0).all() and (ids < len(self)).all()
-        return ids
-
-    def update_rows(self, row_ids, rows):
-        ids = self._ids(row_ids)
-        self.calls.append(("update", sorted(ids.tolist())))
-        self._rows[ids] = np.asarray(rows, dtype=np.float32).reshape(ids.shape[0], self.dim)
-        self._live[ids] = True
-
-    def remove_rows(self, row_ids):
-        ids = self._ids(row_ids)
-        self.calls.append(("remove", sorted(ids.tolist())))
-        self._live[ids] = False
-
-    def search(self, queries, k):
-        live = np.nonzero(self._live)[0]
-        d, r = self._o.topk_search(self._rows[live], np.ascontiguousarray(queries, dtype=np.float32), k, metric=self.metric)
-        return d, np.where(r >= 0, live[np.maximum(r, 0)], -1)
-
-    def close(self):
-        self.closed = True
+from helpers import UNIT_D as D, MutableOracleIndex, unit_answers as answers, unit_base as base, unit_built as built
+from helpers import unit_fresh as fresh, unit_table as table
 
 
 @pytest.fixture(autouse=True)
 def stand_in(monkeypatch, oracle):
     monkeypatch.setattr(svc, "Mi355Index", MutableOracleIndex)
     MutableOracleIndex.created = 0
-
-
-def table(ids, emb):
-    return ChunkTable(ids=list(ids), contents=[f"text {pk}" for pk in ids], embedding=np.array(emb, dtype=np.float32))
-
-
-def base(n=60, nulls=()):
-    rng = np.random.default_rng(5)
-    emb = rng.standard_normal((n, D)).astype(np.float32)
-    emb[list(nulls)] = np.nan
-    return table([f"pk{i:03d}" for i in range(n)], emb), rng.standard_normal((9, D)).astype(np.float32)
-
-
-def answers(unit, Q, k=K):
-    """[(primary key, distance bits)] per query, through the unit's row -> table position mapping"""
-    dist, rows = unit.ensure_single().search(Q, k)
-    out = []
-    for dr, rr in zip(dist, rows):
-        out.append([(unit.table.ids[unit.single_rows[r]], np.float64(x).view(np.uint64)) for x, r in zip(dr, rr) if r >= 0])
-    return out
-
-
-def fresh(t, Q, k=K):
-    u = svc._UnitIndex(t, 0)
-    return answers(u, Q, k)
-
-
-def built(t, Q):
-    u = svc._UnitIndex(t, 0)
-    answers(u, Q)              # builds the index
-    u.single.calls.clear()
-    return u
 
 
 def test_changed_embeddings_are_updated_in_place():

@@ -1,116 +1,26 @@
 """CPU: compaction of a unit's single-vector index (`service._UnitIndex.compact_single`, the `compact_dead_fraction` policy of
 `refresh`, `Mi355RetrievalService.compact_unit`).
 
-The index is the stand-in of tests/test_unit_refresh.py over numpy and the CPU oracle, with a `compact()` of Mi355Index's
+The index is the stand-in of tests/helpers.py over numpy and the CPU oracle, with a `compact()` of Mi355Index's
 semantics that records its call: every case must answer like a unit built fresh from the table -- the same (primary key,
 distance bits) lists -- and must issue only the calls the difference needs."""
+
+import functools
 
 import numpy as np
 import pytest
 
 from autorag_research_amd import service as svc
-from autorag_research_amd.store import ChunkTable
+from helpers import UNIT_D as D, MutableOracleIndex, unit_answers as answers, unit_base, unit_built as built
+from helpers import unit_fresh as fresh, unit_table as table
 
-D, K = 16, 12
-
-
-class MutableOracleIndex:
-    """add / update_rows / remove_rows / search with Mi355Index's semantics (the stand-in of tests/test_unit_refresh.py):
-    stable row ids, removed rows never returned, answered by oracle.topk_search over the live rows."""
-
-    created = 0
-
-    def __init__(self, dim, metric="cosine", device=0):
-        from oracle import cpu_ref
-
-        self._o, self.dim, self.metric = cpu_ref, dim, metric
-        self._rows = np.zeros((0, dim), np.float32)
-        self._live = np.zeros(0, bool)
-        self.calls = []
-        self.closed = False
-        MutableOracleIndex.created += 1
-
-    def __len__(self):
-        return self._rows.shape[0]
-
-    @property
-    def live_rows(self):
-        return int(self._live.sum())
-
-    def add(self, rows):
-        rows = np.ascontiguousarray(rows, dtype=np.float32)
-        self.calls.append(("add", rows.shape[0]))
-        self._rows = np.concatenate([self._rows, rows])
-        self._live = np.concatenate([self._live, np.ones(rows.shape[0], bool)])
-
-    def _ids(self, row_ids):
-        ids = np.asarray(row_ids, dtype=np.int64)
-        assert ids.ndim == 1 and np.unique(ids).shape[0] == ids.shape[0] and (ids >= 0).all() and (ids < len(self)).all()
-        return ids
-
-    def update_rows(self, row_ids, rows):
-        ids = self._ids(row_ids)
-        self.calls.append(("update", sorted(ids.tolist())))
-        self._rows[ids] = np.asarray(rows, dtype=np.float32).reshape(ids.shape[0], self.dim)
-        self._live[ids] = True
-
-    def remove_rows(self, row_ids):
-        ids = self._ids(row_ids)
-        self.calls.append(("remove", sorted(ids.tolist())))
-        self._live[ids] = False
-
-    def search(self, queries, k):
-        live = np.nonzero(self._live)[0]
-        d, r = self._o.topk_search(self._rows[live], np.ascontiguousarray(queries, dtype=np.float32), k, metric=self.metric)
-        return d, np.where(r >= 0, live[np.maximum(r, 0)], -1)
-
-    def close(self):
-        self.closed = True
-
-
-class CompactingOracleIndex(MutableOracleIndex):
-    """... and compact(): the live rows keep their order and become rows 0 .. live-1; returns new_of_old (-1: removed)"""
-
-    def compact(self):
-        self.calls.append(("compact",))
-        new_of_old = np.where(self._live, np.cumsum(self._live) - 1, -1).astype(np.int64)
-        self._rows = self._rows[self._live]
-        self._live = np.ones(self._rows.shape[0], bool)
-        return new_of_old
+base = functools.partial(unit_base, key="pk{:05d}")
 
 
 @pytest.fixture(autouse=True)
 def stand_in(monkeypatch, oracle):
-    monkeypatch.setattr(svc, "Mi355Index", CompactingOracleIndex)
+    monkeypatch.setattr(svc, "Mi355Index", MutableOracleIndex)
     MutableOracleIndex.created = 0
-
-
-def table(ids, emb):
-    return ChunkTable(ids=list(ids), contents=[f"text {pk}" for pk in ids], embedding=np.array(emb, dtype=np.float32))
-
-
-def base(n=60, nulls=(), d=D):
-    rng = np.random.default_rng(5)
-    emb = rng.standard_normal((n, d)).astype(np.float32)
-    emb[list(nulls)] = np.nan
-    return table([f"pk{i:05d}" for i in range(n)], emb), rng.standard_normal((9, d)).astype(np.float32)
-
-
-def answers(unit, Q, k=K):
-    dist, rows = unit.ensure_single().search(Q, k)
-    return [[(unit.table.ids[unit.single_rows[r]], np.float64(x).view(np.uint64)) for x, r in zip(dr, rr) if r >= 0]
-            for dr, rr in zip(dist, rows)]
-
-
-def fresh(t, Q, k=K):
-    return answers(svc._UnitIndex(t, 0), Q, k)
-
-
-def built(t, Q, **kw):
-    u = svc._UnitIndex(t, 0, **kw)
-    answers(u, Q)
-    u.single.calls.clear()
-    return u
 
 
 def with_nulls(t, nulls):

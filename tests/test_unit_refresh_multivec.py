@@ -10,132 +10,14 @@ import pytest
 
 from autorag_research_amd import service as svc
 from autorag_research_amd.store import ChunkTable, InMemoryStore
-
-D, K = 16, 12
-
-
-class MutableOracleStore:
-    """add_multivec / set_multivec / search_maxsim with Mi355Index's semantics: stable document ids, a document without vectors
-    is never returned, answered by oracle.maxsim_topk over the current contents.  The single-vector half (`add`, `update_rows`,
-    `remove_rows`, `search`) is there for units that have both indexes built."""
-
-    created = 0
-
-    def __init__(self, dim, metric="cosine", device=0):
-        from oracle import cpu_ref
-
-        self._o, self.dim, self.metric = cpu_ref, dim, metric
-        self._docs = []                                   # [T_i, dim] per document
-        self._rows = np.zeros((0, dim), np.float32)
-        self._live = np.zeros(0, bool)
-        self.calls = []
-        self.closed = False
-        MutableOracleStore.created += 1
-
-    # ---- multi-vector ----
-    def n_docs(self):
-        return len(self._docs)
-
-    def live_docs(self):
-        return sum(1 for t in self._docs if t.shape[0] > 0)
-
-    @staticmethod
-    def _split(vecs, offsets, dim):
-        vecs = np.ascontiguousarray(vecs, dtype=np.float32).reshape(-1, dim)
-        offsets = np.asarray(offsets, dtype=np.int64)
-        assert offsets[0] == 0 and offsets[-1] == vecs.shape[0] and (np.diff(offsets) >= 0).all()
-        return [vecs[offsets[i]:offsets[i + 1]].copy() for i in range(offsets.shape[0] - 1)]
-
-    def add_multivec(self, vecs, offsets):
-        docs = self._split(vecs, offsets, self.dim)
-        self.calls.append(("add_multivec", len(docs)))
-        self._docs += docs
-
-    def set_multivec(self, doc_ids, vecs, offsets):
-        ids = np.asarray(doc_ids, dtype=np.int64)
-        assert ids.ndim == 1 and np.unique(ids).shape[0] == ids.shape[0] and (ids >= 0).all() and (ids < len(self._docs)).all()
-        docs = self._split(vecs, offsets, self.dim)
-        assert len(docs) == ids.shape[0]
-        self.calls.append(("set_multivec", ids.tolist(), [t.shape[0] for t in docs]))
-        for i, t in zip(ids.tolist(), docs):
-            self._docs[i] = t
-
-    def search_maxsim(self, qtok, q_offsets, k):
-        tok = np.concatenate(self._docs, axis=0) if self._docs else np.zeros((0, self.dim), np.float32)
-        off = np.concatenate([[0], np.cumsum([t.shape[0] for t in self._docs])]).astype(np.int64)
-        return self._o.maxsim_topk(tok, off, qtok, q_offsets, k)
-
-    # ---- single-vector ----
-    def __len__(self):
-        return self._rows.shape[0]
-
-    def add(self, rows):
-        rows = np.ascontiguousarray(rows, dtype=np.float32)
-        self.calls.append(("add", rows.shape[0]))
-        self._rows = np.concatenate([self._rows, rows])
-        self._live = np.concatenate([self._live, np.ones(rows.shape[0], bool)])
-
-    def update_rows(self, row_ids, rows):
-        ids = np.asarray(row_ids, dtype=np.int64)
-        self.calls.append(("update", sorted(ids.tolist())))
-        self._rows[ids] = np.asarray(rows, dtype=np.float32).reshape(ids.shape[0], self.dim)
-        self._live[ids] = True
-
-    def remove_rows(self, row_ids):
-        ids = np.asarray(row_ids, dtype=np.int64)
-        self.calls.append(("remove", sorted(ids.tolist())))
-        self._live[ids] = False
-
-    def search(self, queries, k):
-        live = np.nonzero(self._live)[0]
-        d, r = self._o.topk_search(self._rows[live], np.ascontiguousarray(queries, dtype=np.float32), k, metric=self.metric)
-        return d, np.where(r >= 0, live[np.maximum(r, 0)], -1)
-
-    def close(self):
-        self.closed = True
+from helpers import UNIT_D as D, UNIT_K as K, MutableOracleStore, mv_answers as answers, mv_base as base, mv_built as built
+from helpers import mv_fresh as fresh, mv_table as table
 
 
 @pytest.fixture(autouse=True)
 def stand_in(monkeypatch, oracle):
     monkeypatch.setattr(svc, "Mi355Index", MutableOracleStore)
     MutableOracleStore.created = 0
-
-
-def table(ids, docs, emb=None, dim=D):
-    """docs: one [T, dim] array per key (T = 0: the key has no multi-vector embedding)"""
-    lens = [t.shape[0] for t in docs]
-    tok = np.concatenate(docs, axis=0).astype(np.float32) if docs else np.zeros((0, dim), np.float32)
-    return ChunkTable(ids=list(ids), contents=[f"text {pk}" for pk in ids], embedding=emb, mv_tokens=tok.reshape(-1, dim),
-                      mv_offsets=np.concatenate([[0], np.cumsum(lens)]).astype(np.int64))
-
-
-def base(n=40, empties=(7, 20), with_single=False):
-    rng = np.random.default_rng(15)
-    docs = [rng.standard_normal((int(t), D)).astype(np.float32) for t in rng.integers(1, 70, size=n)]
-    for i in empties:
-        docs[i] = docs[i][:0]
-    emb = rng.standard_normal((n, D)).astype(np.float32) if with_single else None
-    ids = [f"pk{i:03d}" for i in range(n)]
-    qs = [rng.standard_normal((t, D)).astype(np.float32) for t in (5, 32, 1, 9)]
-    return ids, docs, emb, (np.concatenate(qs), np.concatenate([[0], np.cumsum([q.shape[0] for q in qs])]).astype(np.int32))
-
-
-def answers(unit, Q, k=K):
-    """[(primary key, distance bits)] per query, through the unit's document -> table position mapping"""
-    dist, rows = unit.ensure_multi().search_maxsim(Q[0], Q[1], k)
-    return [[(unit.table.ids[unit.multi_rows[r]], np.float32(x).view(np.uint32)) for x, r in zip(dr, rr) if r >= 0]
-            for dr, rr in zip(dist, rows)]
-
-
-def fresh(t, Q, k=K):
-    return answers(svc._UnitIndex(t, 0), Q, k)
-
-
-def built(t, Q):
-    u = svc._UnitIndex(t, 0)
-    answers(u, Q)              # builds the store
-    u.multi.calls.clear()
-    return u
 
 
 def test_changed_lost_revived_and_appended_documents_are_applied_in_place():
