@@ -299,7 +299,7 @@ __global__ __launch_bounds__(kGqrThreads) void k_gqr_multi(GqrMultiArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     best[r] = -__builtin_inf();
-                    barg[r] = 0x7FFFFFFF;
+                    barg[r] = (int)r0;  // a real row even if no product ever compares greater (NaN): the gradient pass reads it
                 }
                 for (int64_t t0 = r0; t0 < r1; t0 += 32) {  // docs own whole 32-row blocks: two 16-token tiles at a time
                     const float* ta = a.tok + (t0 + col) * dp;

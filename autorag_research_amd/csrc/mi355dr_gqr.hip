@@ -4,6 +4,7 @@
 // PostgreSQL (autorag_research/pipelines/retrieval/gqr_hybrid.py:306-362 driven by `_run_gqr`, :415-470): here the
 // candidate vectors never leave HBM -- the caller names them by row id -- and a block of queries is refined in one
 // launch, one workgroup per query.
+#include <cmath>
 #include <vector>
 
 #include "index.h"
@@ -156,6 +157,9 @@ int mi355dr_gqr_refine_maxsim(mi355dr_index* idx, const double* qtok, const int3
     if (lds > 160 * 1024) return fail(idx, MI355DR_E_UNSUPPORTED, "gqr: query matrix + pool too large for one workgroup's LDS");
     // the query matrix in the store's column order, zero-padded to dpad
     const int64_t nrow = q_offsets[B];
+    // a NaN product never compares greater, so the kernel's argmax would name no token of the doc
+    for (int64_t e = 0; e < nrow * d; ++e)
+        if (!std::isfinite(qtok[e])) return fail(idx, MI355DR_E_INVALID, "gqr: query vectors must be finite");
     std::vector<double> qimg((size_t)nrow * dp);
     for (int64_t r = 0; r < nrow; ++r) multivec_pack_query_row(qtok + r * d, d, dp, &qimg[(size_t)r * dp]);
     HIPCHECK(idx, hipSetDevice(idx->device));

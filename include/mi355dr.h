@@ -228,8 +228,9 @@ int mi355dr_maxsim_subset_ex(mi355dr_index* idx, const float* qtok, const int32_
  * (P <= 2048); comp_dist: host [B, P] complementary distribution (gqr_hybrid.py:436); out_scores: host [B, P], NaN at
  * padding.  n_steps > 0, learning_rate > 0, temperature > 0, 0 <= mixture_alpha <= 1 (:202-216), else MI355DR_E_INVALID.
  *   mi355dr_gqr_refine         queries: host [B, dim] float64; candidates = single-vector rows; out = refined cosine
- *   mi355dr_gqr_refine_maxsim  qtok: host [sum_nq, dim] float64, q_offsets [B+1] (every query >= 1 vector); candidates =
- *                              multi-vector docs (each must have vectors); out = refined mean-of-max late-interaction score
+ *   mi355dr_gqr_refine_maxsim  qtok: host [sum_nq, dim] float64, finite (else MI355DR_E_INVALID), q_offsets [B+1] (every
+ *                              query >= 1 vector); candidates = multi-vector docs (each must have vectors); out = refined
+ *                              mean-of-max late-interaction score
  *   mi355dr_gqr_refine_scores  no vectors: primary_scores host [B, P] float64 are the variables, counts[b] live entries */
 int mi355dr_gqr_refine(mi355dr_index* idx, const double* queries, int B, const int64_t* cand_rows, int P,
                        const double* comp_dist, int n_steps, double learning_rate, double temperature,
