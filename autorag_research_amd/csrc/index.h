@@ -149,6 +149,7 @@ struct mi355dr_index {
     mi355::DevBuf<int64_t> out_rows_dev;
     mi355::DevBuf<unsigned long long> stat_dev;  // [2*kQBlockMax]: per query (candidates, re-scored)
     mi355::DevBuf<int> prune_skip;   // [2 + 2*kQBlockMax] hand-over lists of k_prune (PruneArgs::skip_list)
+    mi355::DevBuf<int32_t> subset_ids;  // the listed rows of the mi355dr_search_subset call in progress: local, ascending, unique
     int prune_parity = 0;
 
     // options
@@ -243,6 +244,9 @@ struct mi355dr_index {
     int64_t s_ms_moved_blocks = 0;     // ... and the blocks its relayouts copied (k_ms_relayout; the in-place path moves none)
     int64_t s_compactions = 0;         // mi355dr_compact calls that moved rows ...
     int64_t s_compact_moved_rows = 0;  // ... and the rows they copied (k_compact_gather)
+    int64_t s_subset_searches = 0;       // mi355dr_search_subset / _device calls ...
+    int64_t s_subset_rows_scored = 0;    // ... the (query, listed row) pairs their gathered scans scored ...
+    int64_t s_subset_rerun_queries = 0;  // ... and the queries whose list overflowed in a chunk that was then re-run in list-sized pieces
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
     mi355::EventPairs ev_pool, ev_pending;

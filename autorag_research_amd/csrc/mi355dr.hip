@@ -4,6 +4,8 @@
 #include "index.h"
 #include "k_prep.h"
 #include "k_scan.h"
+#include "k_scan_ids.h"
+#include "subset_ids.h"
 #include "screen_common.h"
 #include "k_screen.h"
 #include "k_screen256c.h"
@@ -140,6 +142,8 @@ int ensure_qstate(mi355dr_index* idx) {
                                           (int)scan_lds_bytes(idx->dim, per)));
     }
     HIPCHECK(idx, hipFuncSetAttribute((const void*)k_scan32, hipFuncAttributeMaxDynamicSharedMemorySize, kScan32Lds));
+    HIPCHECK(idx, hipFuncSetAttribute((const void*)k_scan_ids, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)scan_ids_lds_bytes(idx->dim, kScanQ)));
     HIPCHECK(idx, hipFuncSetAttribute((const void*)k_screen<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kScreenLds));
     HIPCHECK(idx, hipFuncSetAttribute((const void*)k_screen<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kScreenLds));
     {
@@ -638,6 +642,95 @@ int run_scan(mi355dr_index* idx, hipStream_t s, const std::vector<int>& qs, int 
         }
     }
     idx->s_fallback_queries += nq_all;
+    return MI355DR_OK;
+}
+
+// ---- the gathered scan (mi355dr_search_subset) ------------------------------------------------------
+// exact scan of list positions [p0, p1) of idx->subset_ids for the <= kScanQ queries in qlist_dev[off..off+nq), then exact prune
+int scan_ids_range(mi355dr_index* idx, hipStream_t s, int off, int nq, int k, int64_t p0, int64_t p1) {
+    ScanIdsArgs ia{};
+    ia.ids = idx->subset_ids;
+    ia.s.rows = idx->rows;
+    ia.s.nrm2 = idx->nrm2;
+    ia.s.q = idx->qdev;
+    ia.s.st = idx->st;
+    ia.s.cand_row = idx->cand_row;
+    ia.s.cand_val = idx->cand_val;
+    ia.s.qlist = idx->qlist_dev + off;
+    ia.s.nq = nq;
+    ia.s.cap = cap_now(idx);
+    ia.s.d = idx->dim;
+    ia.s.metric = idx->metric;
+    ia.s.row0 = p0;
+    ia.s.row1 = p1;
+    const int64_t grid = (p1 - p0 + kScanThreads - 1) / kScanThreads;
+    hipLaunchKernelGGL(k_scan_ids, dim3((unsigned)grid), dim3(kScanThreads), scan_ids_lds_bytes(idx->dim, nq), s, ia);
+    HIPCHECK(idx, hipGetLastError());
+    return launch_prune(idx, s, nq, idx->qlist_dev + off, k, /*exact=*/1);
+}
+
+// run_scan's schedule over the m list POSITIONS instead of the index's rows, for the B prepared queries of the block: groups
+// of kScanQ queries, the chunk0_rows / x63 ladder, a chunk larger than the list re-run in list-sized pieces for the queries
+// it overflowed.  (The list is sorted: positions are in row order, and a sorted corpus is as adversarial here as there.)
+int run_scan_ids(mi355dr_index* idx, hipStream_t s, int B, int k, int64_t m) {
+    std::vector<int> qs(B);
+    for (int i = 0; i < B; ++i) qs[i] = i;
+    HIPCHECK(idx, hipMemcpyAsync(idx->qlist_dev, qs.data(), qs.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_reset_queries, dim3((B + 255) / 256), dim3(256), 0, s, idx->st, idx->qlist_dev, B);
+    HIPCHECK(idx, hipGetLastError());
+    const int cap = cap_now(idx);
+    for (int off = 0; off < B; off += kScanQ) {
+        const int nq = std::min(kScanQ, B - off);
+        int64_t done = 0;
+        int64_t chunk = std::min<int64_t>(idx->chunk0_rows, cap);
+        while (done < m) {
+            const int64_t end = std::min<int64_t>(m, done + chunk);
+            CHECK(scan_ids_range(idx, s, off, nq, k, done, end));
+            if (end - done > cap) {  // only a chunk larger than the buffer can overflow
+                HIPCHECK(idx, hipMemcpyAsync(idx->status_host, idx->st.status, kQBlockMax * sizeof(int), hipMemcpyDeviceToHost, s));
+                HIPCHECK(idx, hipStreamSynchronize(s));
+                std::vector<int> redo;
+                for (int j = 0; j < nq; ++j)
+                    if (idx->status_host[off + j] & kStOverflow) redo.push_back(off + j);
+                if (!redo.empty()) {
+                    // the overflowed queries alone, in buffer-sized pieces (cannot overflow); the others committed the chunk
+                    const int roff = kQBlockMax;  // (the tail of qlist_dev)
+                    HIPCHECK(idx, hipMemcpyAsync(idx->qlist_dev + roff, redo.data(), redo.size() * sizeof(int), hipMemcpyHostToDevice, s));
+                    for (int q : redo) idx->status_host[q] &= ~kStOverflow;  // (the prune did not commit the failed chunk: the kept list stands)
+                    for (int q : redo)
+                        HIPCHECK(idx, hipMemcpyAsync(idx->st.status + q, idx->status_host + q, sizeof(int), hipMemcpyHostToDevice, s));
+                    for (int64_t p = done; p < end; p += cap)
+                        CHECK(scan_ids_range(idx, s, roff, (int)redo.size(), k, p, std::min<int64_t>(end, p + cap)));
+                    HIPCHECK(idx, hipStreamSynchronize(s));  // `redo` (pageable) was read by the copy
+                    idx->s_subset_rerun_queries += (int64_t)redo.size();
+                }
+            }
+            done = end;
+            chunk = std::max<int64_t>(chunk, done * (idx->chunk_growth_set ? idx->chunk_growth : 63));
+        }
+    }
+    HIPCHECK(idx, hipStreamSynchronize(s));  // `qs` (pageable) was read by the copy
+    return MI355DR_OK;
+}
+
+// one block of B <= kQBlockMax device-resident queries against the m uploaded ids -> device outputs [B,k], complete on return
+int subset_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, int k, int64_t m, double* out_dist_dev,
+                 int64_t* out_rows_dev) {
+    idx->k_now = k;
+    idx->screening_now = false;  // (before the first launch: every kernel of the pass sees the exact path's list stride)
+    if (q_dev != idx->qdev)
+        HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q_dev, (size_t)B * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+    CHECK(launch_prep(idx, s, B, (int)round_up(B, screen_tile(B)), idx->metric));
+    if (m > 0) CHECK(run_scan_ids(idx, s, B, k, m));
+    hipLaunchKernelGGL(k_finalize, dim3(B), dim3(64), 0, s, idx->st, k, idx->row_offset, out_dist_dev, out_rows_dev,
+                       idx->status_or_dev);
+    HIPCHECK(idx, hipGetLastError());
+    HIPCHECK(idx, hipMemcpyAsync(idx->status_host, idx->st.status, (size_t)kQBlockMax * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    // the scan re-runs every chunk that overflowed and clears the flag of each (complete_block, !used_screen): one left over is a lost chunk
+    for (int i = 0; i < B; ++i)
+        if (idx->status_host[i] & kStOverflow)
+            return fail(idx, MI355DR_E_INTERNAL, "subset scan: query " + std::to_string(i) + " lost a candidate chunk");
     return MI355DR_OK;
 }
 
@@ -1258,6 +1351,125 @@ int mi355dr_search_device(mi355dr_index* idx, const float* queries_dev, int B, i
     return drain_pending(idx);
 }
 
+// ---- search within a listed subset of rows (DESIGN.md section 4.5 "Gathered scan") -------------------------------------
+namespace {
+// the caller's global ids -> idx->subset_ids (local rows, ascending, unique); *m_out = how many.  Nothing of the index or of
+// the per-search state has been touched when this fails.
+int subset_upload_ids(mi355dr_index* idx, hipStream_t s, const int64_t* row_ids, int64_t m, int64_t* m_out) {
+    std::vector<int32_t> ids;
+    try {
+        subset_prepare_ids(row_ids, m, idx->row_offset, idx->n, ids);
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, "search_subset: out of host memory for the row list");
+    }
+    *m_out = (int64_t)ids.size();
+    if (ids.empty()) return MI355DR_OK;
+    HIPCHECK(idx, idx->subset_ids.grow(ids.size() * sizeof(int32_t)));
+    HIPCHECK(idx, hipMemcpyAsync(idx->subset_ids, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHECK(idx, hipStreamSynchronize(s));  // (`ids` is pageable and leaves with this frame)
+    return MI355DR_OK;
+}
+
+// host == true: queries / outputs are host buffers staged through the index's own; else device buffers used in place
+int search_subset_impl(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* row_ids, int64_t m,
+                       double* out_dist, int64_t* out_rows, hipStream_t s, bool host) {
+    CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
+    if (m < 0 || (m > 0 && !row_ids)) return fail(idx, MI355DR_E_INVALID, "search_subset: m must be >= 0 and row_ids not null");
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_pending(idx));
+    if (B == 0) return MI355DR_OK;
+    if (!s) s = idx->stream;
+    int64_t m_valid = 0;
+    CHECK(subset_upload_ids(idx, s, row_ids, m, &m_valid));
+    CHECK(ensure_qstate(idx));
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        const float* q = queries + (int64_t)b0 * idx->dim;
+        double* od = out_dist + (int64_t)b0 * k;
+        int64_t* orow = out_rows + (int64_t)b0 * k;
+        if (host) {
+            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q, (size_t)nb * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
+            CHECK(subset_block(idx, s, idx->qdev, nb, k, m_valid, idx->out_dist_dev, idx->out_rows_dev));
+            HIPCHECK(idx, hipMemcpyAsync(od, idx->out_dist_dev, (size_t)nb * k * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHECK(idx, hipMemcpyAsync(orow, idx->out_rows_dev, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            HIPCHECK(idx, hipStreamSynchronize(s));
+        } else {
+            CHECK(subset_block(idx, s, q, nb, k, m_valid, od, orow));
+        }
+    }
+    idx->s_subset_searches++;
+    idx->s_subset_rows_scored += m_valid * B;
+    return MI355DR_OK;
+}
+}  // namespace
+
+int mi355dr_search_subset(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* row_ids, int64_t m,
+                          double* out_dist, int64_t* out_rows) {
+    return search_subset_impl(idx, queries, B, k, row_ids, m, out_dist, out_rows, nullptr, /*host=*/true);
+}
+
+int mi355dr_search_subset_device(mi355dr_index* idx, const float* queries_dev, int B, int k, const int64_t* row_ids, int64_t m,
+                                 double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
+    return search_subset_impl(idx, queries_dev, B, k, row_ids, m, out_dist_dev, out_rows_dev, (hipStream_t)stream, /*host=*/false);
+}
+
+int mi355dr_score_subset(mi355dr_index* idx, const float* queries, int B, const int64_t* row_ids, int m, double* out_dist) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    if (B < 0 || m < 0) return fail(idx, MI355DR_E_INVALID, "score_subset: B and m must be >= 0");
+    if (B > 0 && (!queries || (m > 0 && (!row_ids || !out_dist)))) return fail(idx, MI355DR_E_INVALID, "null buffer");
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_pending(idx));
+    const int64_t total = (int64_t)B * m;
+    for (int64_t i = 0; i < total; ++i) out_dist[i] = NAN;
+    if (total == 0) return MI355DR_OK;
+    hipStream_t s = idx->stream;
+    std::vector<int32_t> pq;
+    std::vector<int64_t> pr, where;  // where: the pair's slot in out_dist
+    std::vector<double> got;
+    DevBuf<int32_t> pq_dev;
+    DevBuf<int64_t> pr_dev;
+    DevBuf<float> dot_dev;
+    DevBuf<double> dist_dev;
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        try {  // pairs for the ids inside this index only: k_rescore_pairs does not range-check
+            pq.clear();
+            pr.clear();
+            where.clear();
+            for (int b = 0; b < nb; ++b)
+                for (int j = 0; j < m; ++j) {
+                    const int64_t at = (int64_t)(b0 + b) * m + j, r = subset_local_row(row_ids[at], idx->row_offset, idx->n);
+                    if (r < 0) continue;
+                    pq.push_back(b);
+                    pr.push_back(r);
+                    where.push_back(at);
+                }
+            got.resize(pq.size());
+        } catch (const std::bad_alloc&) {
+            return fail(idx, MI355DR_E_NOMEM, "score_subset: out of host memory for the pair list");
+        }
+        const int64_t n_pairs = (int64_t)pq.size();
+        if (n_pairs == 0) continue;
+        HIPCHECK(idx, pq_dev.grow(n_pairs * sizeof(int32_t)));
+        HIPCHECK(idx, pr_dev.grow(n_pairs * sizeof(int64_t)));
+        HIPCHECK(idx, dot_dev.grow(n_pairs * sizeof(float)));
+        HIPCHECK(idx, dist_dev.grow(n_pairs * sizeof(double)));
+        CHECK(upload_and_prep(idx, queries + (int64_t)b0 * idx->dim, nb, idx->metric));
+        HIPCHECK(idx, hipMemcpyAsync(pq_dev.p, pq.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(pr_dev.p, pr.data(), n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_rescore_pairs, dim3((unsigned)((n_pairs + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows,
+                           idx->nrm2, idx->qdev, idx->st.qn, pq_dev.p, pr_dev.p, n_pairs, idx->dim, idx->metric, dot_dev.p,
+                           dist_dev.p);
+        HIPCHECK(idx, hipGetLastError());
+        HIPCHECK(idx, hipMemcpyAsync(got.data(), dist_dev.p, n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipStreamSynchronize(s));
+        for (int64_t i = 0; i < n_pairs; ++i) out_dist[where[i]] = got[i];  // (a removed row, an undefined distance: the kernel's NaN)
+    }
+    return MI355DR_OK;
+}
+
 int mi355dr_merge_topk_device(mi355dr_index* idx, const double* dist_all_dev, const int64_t* rows_all_dev, int world,
                               int B, int k, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
@@ -1395,6 +1607,9 @@ const Stat kStats[] = {
     {"maxsim_packed_built", &Index::s_ms_packed_built, false},
     {"maxsim_set_docs", &Index::s_ms_set_docs, true},
     {"maxsim_moved_blocks", &Index::s_ms_moved_blocks, true},
+    {"subset_searches", &Index::s_subset_searches, true},
+    {"subset_rows_scored", &Index::s_subset_rows_scored, true},
+    {"subset_rerun_queries", &Index::s_subset_rerun_queries, true},
     {"compactions", &Index::s_compactions, true},
     {"compact_moved_rows", &Index::s_compact_moved_rows, true},
     {"i8_demoted", nullptr, false, [](const Index* x) -> int64_t { return x->i8_demoted_k != INT_MAX ? 1 : 0; }},

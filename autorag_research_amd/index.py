@@ -159,6 +159,49 @@ class Mi355Index:
         """Complete every block up to `ticket` (waits, then recomputes the rare queries the screen flagged)."""
         check(self._h, self._lib.mi355dr_search_wait(self._h, int(ticket)))
 
+    # ---- search within a listed subset of rows (include/mi355dr.h "search within a listed subset of rows") ----
+    def search_subset(self, queries, k: int, row_ids) -> tuple[np.ndarray, np.ndarray]:
+        """Exact top-k among the listed rows only: `search` with `AND id = ANY(row_ids)`.  row_ids: global rows as the
+        searches return them, one list for all queries, in any order; ids outside the index (-1 padding included) and
+        removed rows are skipped, an id listed twice counts once.  Same distances, order and NaN / -1 tail as `search`."""
+        q = f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [B, {self.dim}], got {q.shape}")
+        ids = self._row_ids(row_ids)
+        B = q.shape[0]
+        dist = np.empty((B, k), dtype=np.float64)
+        rows = np.empty((B, k), dtype=np.int64)
+        check(self._h, self._lib.mi355dr_search_subset(self._h, ptr(q, ctypes.c_float), B, int(k), ptr(ids, ctypes.c_int64),
+                                                       ids.shape[0], ptr(dist, ctypes.c_double), ptr(rows, ctypes.c_int64)))
+        return dist, rows
+
+    def search_subset_device(self, q_ptr: int, B: int, k: int, row_ids, out_dist_ptr: int, out_rows_ptr: int,
+                             stream: int | None = None) -> None:
+        """The same with queries and outputs in device memory (the list stays on the host); complete on return."""
+        ids = self._row_ids(row_ids)
+        check(self._h, self._lib.mi355dr_search_subset_device(
+            self._h, ctypes.c_void_p(int(q_ptr)), int(B), int(k), ptr(ids, ctypes.c_int64), ids.shape[0],
+            ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
+            ctypes.c_void_p(int(stream) if stream else None)))
+
+    def score_subset(self, queries, row_ids) -> np.ndarray:
+        """Exact distance of each query to its own list of rows: row_ids [B, m] (global) -> float64 [B, m]; NaN for ids
+        outside the index, removed rows and undefined distances."""
+        q = f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        ids = np.ascontiguousarray(row_ids, dtype=np.int64)
+        if ids.ndim == 1:
+            ids = ids[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim or ids.ndim != 2 or ids.shape[0] != q.shape[0]:
+            raise ValueError(f"queries must be [B, {self.dim}] and row_ids [B, m]")
+        out = np.empty(ids.shape, dtype=np.float64)
+        check(self._h, self._lib.mi355dr_score_subset(self._h, ptr(q, ctypes.c_float), q.shape[0], ptr(ids, ctypes.c_int64),
+                                                      ids.shape[1], ptr(out, ctypes.c_double)))
+        return out
+
     def merge_topk_device(self, dist_all_ptr: int, rows_all_ptr: int, world: int, B: int, k: int, out_dist_ptr: int,
                           out_rows_ptr: int, stream: int | None = None) -> None:
         check(self._h, self._lib.mi355dr_merge_topk_device(

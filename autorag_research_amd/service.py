@@ -613,8 +613,11 @@ class Mi355RetrievalService:
 
     # ---- the hot path ----
     def vector_search(self, query_ids: list[int | str], top_k: int = 10,
-                      search_mode: Literal["single", "multi"] = "single", unit: str = "chunk") -> list[list[dict]]:
-        """Top-k for every query id, scored as one block.  Raises ValueError exactly like the reference."""
+                      search_mode: Literal["single", "multi"] = "single", unit: str = "chunk",
+                      within: list | None = None) -> list[list[dict]]:
+        """Top-k for every query id, scored as one block.  Raises ValueError exactly like the reference.
+        `within` (not in the reference's signature; None = today's behaviour): primary keys the search is restricted to --
+        the statement with `AND id = ANY(:within)`.  Keys unknown to the table or without a stored embedding are left out."""
         queries = []
         for qid, q in zip(query_ids, self.get_queries(list(query_ids)), strict=True):
             if q is None:
@@ -629,9 +632,9 @@ class Mi355RetrievalService:
         if not queries:
             return []
         if search_mode == "multi":
-            return self.maxsim_search_by_embeddings([q.embeddings for q in queries], top_k, unit)
+            return self.maxsim_search_by_embeddings([q.embeddings for q in queries], top_k, unit, within=within)
         Q = np.stack([q.embedding for q in queries]).astype(np.float32, copy=False)
-        return self._single_block(Q, top_k, unit)
+        return self._single_block(Q, top_k, unit, within)
 
     @staticmethod
     def _results_from_block(table: ChunkTable, pos_of_row: np.ndarray, rows: np.ndarray, scores: np.ndarray,
@@ -651,19 +654,48 @@ class Mi355RetrievalService:
         return [[{"doc_id": ids[p], "score": s, "content": None} for p, s in zip(pr[:n], sr[:n])]
                 for pr, sr, n in zip(pos, sc, n_valid)]
 
-    def _single_block(self, Q: np.ndarray, top_k: int, unit: str) -> list[list[dict]]:
+    @staticmethod
+    def _single_rows_of(u: _UnitIndex, doc_ids: list) -> tuple[list, np.ndarray]:
+        """(the keys of `doc_ids` that have a stored single-vector embedding, each once in first-seen order; their index rows)"""
+        if u.table.embedding is None:
+            return [], np.zeros(0, dtype=np.int64)
+        pos, row = u.pos_of_id(), u.stored_row_of_pos()
+        known = {pk: row[pos[pk]] for pk in doc_ids if pk in pos and pos[pk] in row}
+        return list(known), np.fromiter(known.values(), dtype=np.int64, count=len(known))
+
+    def _single_block(self, Q: np.ndarray, top_k: int, unit: str, within: list | None = None) -> list[list[dict]]:
         u = self._unit(unit)
         # (one process per GPU, every rank: local top-k of its rows, all-gather, merge -> the same global lists)
-        dist, rows = u.single_searcher(self._world).search(Q, top_k)
+        searcher = u.single_searcher(self._world)
+        if within is None:
+            dist, rows = searcher.search(Q, top_k)
+        else:   # ... among the listed rows: every rank passes the whole list, the library keeps what falls in its shard
+            dist, rows = searcher.search_subset(Q, top_k, self._single_rows_of(u, within)[1])
         # reference: score = 1 - distance (retrieval_pipeline.py:522-524) in Python float arithmetic = IEEE double
         return self._results_from_block(u.table, u.single_rows, rows, 1.0 - dist, unit == "chunk")
 
-    def vector_search_by_embedding(self, embedding: list[float], top_k: int = 10, unit: str = "chunk") -> list[dict]:
+    def vector_search_by_embedding(self, embedding: list[float], top_k: int = 10, unit: str = "chunk",
+                                   within: list | None = None) -> list[dict]:
         if len(embedding) == 0:  # reference: `if not query_vector: return []` (base.py:403-404)
             return []
-        return self._single_block(np.asarray(embedding, dtype=np.float32)[None, :], top_k, unit)[0]
+        return self._single_block(np.asarray(embedding, dtype=np.float32)[None, :], top_k, unit, within)[0]
 
-    def maxsim_search_by_embeddings(self, query_vectors: list, top_k: int, unit: str = "chunk") -> list[list[dict]]:
+    def score_candidates(self, embedding: list[float], doc_ids: list, unit: str = "chunk") -> dict:
+        """Dense score of explicit candidates: {doc_id: 1.0 - cosine distance}, the score `vector_search_by_embedding` gives
+        the same chunk (Python float arithmetic).  Ids unknown to the table or without a stored embedding are left out (as
+        `maxsim_score_candidates` does); no embedding -> {}."""
+        if len(embedding) == 0:
+            return {}
+        u = self._unit(unit)
+        searcher = u.single_searcher(self._world)
+        known, rows = self._single_rows_of(u, doc_ids)
+        if not known:
+            return {}
+        dist = searcher.score_subset(np.asarray(embedding, dtype=np.float32)[None, :], rows[None, :])[0]
+        return {pk: 1.0 - float(dv) for pk, dv in zip(known, dist)}
+
+    def maxsim_search_by_embeddings(self, query_vectors: list, top_k: int, unit: str = "chunk",
+                                    within: list | None = None) -> list[list[dict]]:
         u = self._unit(unit)
         ix = u.multi_searcher(self._world)
         dim = u.table.mv_tokens.shape[1]
@@ -675,13 +707,33 @@ class Mi355RetrievalService:
             return out
         qtok = np.concatenate([mats[i] for i in live], axis=0)
         qoff = np.concatenate([[0], np.cumsum([lens[i] for i in live])]).astype(np.int32)
-        dist, rows = ix.search_maxsim(qtok, qoff, top_k)
+        if within is None:
+            dist, rows = ix.search_maxsim(qtok, qoff, top_k)
+        else:
+            dist, rows = self._maxsim_within(u, ix, qtok, qoff, top_k, within)
         # reference: score = -distance / n_query_vectors (retrieval_pipeline.py:511-514): float(f32) negated, divided
         n_q = np.maximum(1, np.asarray([lens[i] for i in live], dtype=np.int64))[:, None]
         scores = -dist.astype(np.float64) / n_q
         for i, res in zip(live, self._results_from_block(u.table, u.multi_rows, rows, scores, unit == "chunk")):
             out[i] = res
         return out
+
+    @staticmethod
+    def _maxsim_within(u: _UnitIndex, ix: Any, qtok: np.ndarray, qoff: np.ndarray, top_k: int, within: list):
+        """`search_maxsim` among the listed keys: every query scores the same candidates exactly (maxsim_subset -- under a
+        _World each rank the documents it owns, one all-gather) and the host orders them by (distance, document)."""
+        pos, off = u.pos_of_id(), u.table.mv_offsets
+        docs = np.array(sorted({pos[pk] for pk in within if pk in pos and off[pos[pk] + 1] > off[pos[pk]]}), dtype=np.int64)
+        B = qoff.shape[0] - 1
+        dist = np.full((B, top_k), np.nan, dtype=np.float32)
+        rows = np.full((B, top_k), -1, dtype=np.int64)
+        if docs.size:
+            scored = np.asarray(ix.maxsim_subset(qtok, qoff, np.tile(docs, (B, 1))), dtype=np.float32)
+            for b in range(B):
+                live = np.nonzero(~np.isnan(scored[b]))[0]
+                best = live[np.lexsort((docs[live], scored[b, live]))[:top_k]]
+                dist[b, :best.size], rows[b, :best.size] = scored[b, best], docs[best]
+        return dist, rows
 
     def maxsim_score_candidates(self, query_vectors, doc_ids: list, unit: str = "chunk") -> dict:
         """Late-interaction score of explicit candidates: {doc_id: mean_i max_j <q_i, d_j>} (reference HEAVEN

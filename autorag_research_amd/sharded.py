@@ -270,6 +270,61 @@ class ShardedSearcher:
         finish(pending)
         return out_d, out_r
 
+    # ---- search within a listed subset of rows: the same list on every rank, each keeps what falls in its shard ----
+    def _exchange_device(self):
+        import torch
+
+        return torch.device("cuda", self.device) if self.backend == "nccl" else torch.device("cpu")
+
+    def search_subset(self, queries, k: int, row_ids, block: int = 1024) -> tuple[np.ndarray, np.ndarray]:
+        """`search` restricted to the listed GLOBAL rows (Mi355Index.search_subset).  Every rank passes the same queries and the
+        same list; the library skips the ids outside its shard, so a rank may find nothing.  Local top-k, one all-gather of
+        the packed [2, B, k] block per query block, host merge: the host pipeline (a restricted search scores a candidate
+        list, not a corpus -- there is no pass to hide the exchange under)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        ids = np.ascontiguousarray(row_ids, dtype=np.int64).reshape(-1)
+        if self.world == 1 and not self.force_pipeline:
+            return self.index.search_subset(q, k, ids)
+        import torch
+
+        dev, B = self._exchange_device(), q.shape[0]
+        out_d = np.full((B, k), np.nan)
+        out_r = np.full((B, k), -1, dtype=np.int64)
+        for b0 in range(0, B, block):
+            nb = min(block, B - b0)
+            dist_l, rows_l = self.index.search_subset(q[b0:b0 + nb], k, ids)
+            pk = torch.from_numpy(np.stack([np.ascontiguousarray(dist_l).view(np.int64), rows_l]).reshape(-1)).to(dev)
+            ga = torch.empty((self.world * pk.numel(),), dtype=torch.int64, device=dev)
+            self._dist.all_gather_into_tensor(ga, pk, group=self.group)
+            g = ga.cpu().numpy().reshape(self.world, 2, nb, k)
+            out_d[b0:b0 + nb], out_r[b0:b0 + nb] = merge_topk_host(np.ascontiguousarray(g[:, 0]).view(np.float64),
+                                                                   np.ascontiguousarray(g[:, 1]), k)
+        return out_d, out_r
+
+    def score_subset(self, queries, row_ids) -> np.ndarray:
+        """Exact distance of every query to its OWN candidates (global rows, [B, m]) over a row-sharded corpus: every rank scores
+        the rows it owns (Mi355Index.score_subset leaves NaN for the others), ONE all-gather of the [B, m] float8 block, and
+        the owner's value wins -- the pattern of `maxsim_subset`.  Bit for bit what one index holding every row returns."""
+        ids = np.ascontiguousarray(row_ids, dtype=np.int64)
+        if ids.ndim == 1:
+            ids = ids[None, :]
+        local = np.ascontiguousarray(self.index.score_subset(queries, ids), dtype=np.float64)
+        if self.world == 1 and not self.force_pipeline:
+            return local
+        import torch
+
+        dev = self._exchange_device()
+        mine = torch.from_numpy(local).to(dev)
+        gathered = torch.empty((self.world,) + tuple(mine.shape), dtype=torch.float64, device=dev)
+        self._dist.all_gather_into_tensor(gathered.view(-1), mine.reshape(-1), group=self.group)
+        g = gathered.cpu().numpy()
+        out = g[0].copy()
+        for r in range(1, self.world):   # NaN = "not mine" (or a genuinely undefined distance, which then stays NaN)
+            out = np.where(np.isnan(out), g[r], out)
+        return out
+
     # ---- multi-vector (MaxSim): docs sharded by cumulative token count, same gather + merge ----
     def add_local_multivec(self, vecs, offsets, global_doc0: int) -> None:
         """Add this rank's docs (ragged [sum_T, d] + offsets starting at 0); `global_doc0` = global index of its first doc."""

@@ -3,7 +3,8 @@
     python -c "import __graft_entry__ as g; g.build()"
     python examples/quickstart.py
 
-1. single-vector index: add fp32 rows, exact cosine top-k for a block of queries (ids + float8 distances)
+1. single-vector index: add fp32 rows, exact cosine top-k for a block of queries (ids + float8 distances), the same search
+   within a listed subset of rows
 2. multi-vector store: ragged docs, exact MaxSim top-k, candidate re-scoring
 3. the reference-shaped pipelines over an in-memory store: vector search, image (MaxSim) search, HEAVEN two-stage,
    Guided Query Refinement, RRF / convex-combination fusion and HyDE over child retrievers
@@ -38,6 +39,11 @@ with amd.Mi355Index(d, "cosine") as idx:
     dist, rows = idx.search(queries, k=10)          # float8 cosine distances (pgvector <=>), row indices
     print("single-vector: planted neighbour found first for", int((rows[:, 0] == np.arange(64)).sum()), "of 64 queries;",
           "screen =", {1: "bf16", 2: "int8"}[idx.stat("screen_dtype_active")])
+    # the same search restricted to a candidate list (`AND id = ANY(:ids)`): exact top-k and scores among the listed rows only
+    pool = np.arange(0, n, 97)                      # e.g. a lexical retriever's candidates; row 0 is in it, rows 1..63 are not
+    sdist, srows = idx.search_subset(queries[:4], k=3, row_ids=pool)
+    print("within a 2062-row pool: best rows", srows[:, 0].tolist(), "| pairwise distances of query 0 to rows [0, 97, -1]:",
+          idx.score_subset(queries[:1], np.array([[0, 97, -1]])).round(4).tolist())
 
 # ---- 2. multi vectors (late interaction) ---------------------------------------------------------------------------------
 n_docs, dm = 5_000, 128

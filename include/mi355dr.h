@@ -154,6 +154,36 @@ int mi355dr_search_device_async(mi355dr_index* idx, const float* queries_dev, in
                                 int64_t* out_rows_dev, void* stream, int64_t* ticket);
 int mi355dr_search_wait(mi355dr_index* idx, int64_t ticket);
 
+/* ---- search within a listed subset of rows ----
+ * The restricted form of the same statement: `WHERE embedding IS NOT NULL AND id = ANY(:ids) ORDER BY distance LIMIT k`
+ * (orm/repository/base.py:409-415 with a key filter) -- re-ranking a lexical candidate list by dense similarity, a search
+ * scoped to one document's chunks or one tenant, scoring a pool before a fusion.
+ *   mi355dr_search_subset: the top-k of every query among the listed rows only.  The float8 distance bits, the total order
+ *     (distance asc, NaN last, row asc) and the NaN / -1 tail when fewer than k listed rows are live are those of
+ *     mi355dr_search; the order of the list never matters.
+ *   row_ids: HOST [m], GLOBAL rows as the searches return them (local row + option "row_offset"), shared by all B queries of
+ *     the call.  Values outside [row_offset, row_offset + mi355dr_size) are skipped -- negative values and -1 padding
+ *     included: the rule of mi355dr_maxsim_subset -- and a value listed twice counts once.
+ *   Removed rows are skipped; live irregular rows come last with NaN, as on the scan path; loose rows are ordinary rows here
+ *     (no screen is involved).  Both metrics, any k up to 1024 and any B that mi355dr_search accepts.  m == 0, or no live
+ *     listed row: all NaN / -1.  A bad shape (m < 0, a null list with m > 0): MI355DR_E_INVALID.
+ *   The call runs under the handle's mutex, first completes whatever search is in flight, and is complete on return (the
+ *     _device form too: `stream`, or the index's own when NULL, is synchronised).  The list is copied, made local, sorted
+ *     and uploaded as int32 into a buffer the index owns and grows; a failed allocation returns MI355DR_E_NOMEM with nothing
+ *     changed.  The pass is the exact scan (MI355DR_PATH_SCAN) walking the list instead of the index: no screen, the same
+ *     fp32 chains, cost proportional to m x B.  Options "chunk0_rows", "chunk_growth" and "cand_cap" apply as on that path.
+ *   Stats: "subset_searches" (calls), "subset_rows_scored" ((query, listed row) pairs scored), "subset_rerun_queries" (queries
+ *     whose candidate list overflowed in a chunk of the list, which was then re-run for them in list-sized pieces). */
+int mi355dr_search_subset(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* row_ids, int64_t m,
+                          double* out_dist, int64_t* out_rows); /* all host */
+/* queries_dev [B, dim], out_dist_dev [B, k], out_rows_dev [B, k] on the index's device; row_ids stay on the HOST */
+int mi355dr_search_subset_device(mi355dr_index* idx, const float* queries_dev, int B, int k, const int64_t* row_ids, int64_t m,
+                                 double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+/* The single-vector sibling of mi355dr_maxsim_subset: the exact float8 distance of every query to its OWN list of rows.
+ * row_ids: host [B, m] global rows (the skipping rule above), out_dist: host [B, m]; NaN for skipped ids, for removed rows
+ * and where the distance is undefined (a zero norm).  Same device code as mi355dr_debug_rescore. */
+int mi355dr_score_subset(mi355dr_index* idx, const float* queries, int B, const int64_t* row_ids, int m, double* out_dist);
+
 /* ---- corpus + search (multi-vector, MaxSim) ----
  * vecs: host [sum_T, dim] fp32, offsets: [n_docs+1] (doc i owns rows offsets[i]..offsets[i+1]). */
 int mi355dr_add_multivec(mi355dr_index* idx, const float* vecs, const int64_t* offsets, int64_t n_docs);
@@ -331,7 +361,8 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
  *          "maxsim_exact_launches" / "maxsim_exact_ns" (profile=1), "maxsim_packed_launches" / "maxsim_packed_blocks" / "maxsim_packed_built" (screen launches over the
  *          granule-packed copy / its 32-token blocks / blocks written into it so far: a store that grows is packed from its new granules on), "maxsim_screen_cols" (query columns the screen launches
  *          multiplied every token by), "maxsim_set_docs" (documents rewritten by mi355dr_set_multivec) / "maxsim_moved_blocks"
- *          (32-token blocks its relayouts copied; 0 on the in-place path),
+ *          (32-token blocks its relayouts copied; 0 on the in-place path), "subset_searches" / "subset_rows_scored" /
+ *          "subset_rerun_queries" (mi355dr_search_subset: calls, pairs scored, queries re-run in list-sized pieces),
  *          "hbm_bytes_resident" (the single-vector corpus with its shadows at its capacity + the multi-vector store's two
  *          images, offset table and granule-packed copy as allocated now). */
 int mi355dr_set_option(mi355dr_index* idx, const char* key, int64_t value);
