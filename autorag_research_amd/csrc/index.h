@@ -150,6 +150,12 @@ struct mi355dr_index {
     mi355::DevBuf<unsigned long long> stat_dev;  // [2*kQBlockMax]: per query (candidates, re-scored)
     mi355::DevBuf<int> prune_skip;   // [2 + 2*kQBlockMax] hand-over lists of k_prune (PruneArgs::skip_list)
     mi355::DevBuf<int32_t> subset_ids;  // the listed rows of the mi355dr_search_subset call in progress: local, ascending, unique
+    // a view (mi355dr_view_create; DESIGN.md "Views"): a read-only index built from listed rows / documents of a parent.  The
+    // maps are null on every other index: the result-writing kernels then add row_offset instead
+    bool is_view = false;
+    mi355::DevBuf<int64_t> view_row_map;  // [n] the parent's global id of view row j (k_finalize)
+    mi355::DevBuf<int64_t> view_doc_map;  // [n_docs] the same for the documents (k_ms_final, k_ms_write_out)
+    int64_t view_rows = 0, view_docs = 0;  // what the build kept (stats "view_rows" / "view_docs")
     int prune_parity = 0;
 
     // options
@@ -220,6 +226,7 @@ struct mi355dr_index {
     // late chunks (expensive hits) smaller; 100 = uniform ratios (option "chunk_taper_x100")
     int chunk_taper_x100 = 0;   // 0 = auto: 120 for passes of the two-wave prune (measured -1 % at k = 100), 100 otherwise (k = 10: no gain)
     int64_t compact_slice_rows = 65536;  // mi355dr_compact: destination rows per slice of its staging buffer (option "compact_slice_rows", 32 ... 2^22)
+    int64_t view_slice_rows = 65536;  // mi355dr_view_create on THIS index: rows per slice of its staging buffer (option "view_slice_rows", 32 ... 2^22)
     int64_t starter_rows_wide = 65536;  // the starter's sample at 33 <= k <= 128 (option "starter_rows_wide", tuning: 4096 ... 262144)
 
     // stats
@@ -273,7 +280,15 @@ struct mi355dr_index {
 namespace mi355 {
 
 int fail(mi355dr_index* idx, int code, const std::string& msg);  // mi355dr.hip
+// A view is read-only and speaks the parent's ids: the entry points that write, and those that take global ids or a
+// communicator (ask_parent), start with `if (idx->is_view) return view_refuses(...)` under the handle's mutex
+inline int view_refuses(mi355dr_index* idx, const char* what, bool ask_parent = false) {
+    return fail(idx, MI355DR_E_INVALID, std::string(what) + (ask_parent ? ": not on a view (it is a read-only snapshot under the parent's ids) -- ask the parent index"
+                                                                        : ": a view is read-only"));
+}
 void multivec_destroy(mi355dr_index* idx);                       // mi355dr_maxsim.hip
+// room for n_blocks 32-token blocks and n_docs documents, the store created if there is none (mi355dr_view_create reserves once)
+int multivec_reserve(mi355dr_index* idx, int64_t n_blocks, int64_t n_docs);  // mi355dr_maxsim.hip
 int64_t multivec_bytes(const mi355dr_index* idx);                // mi355dr_maxsim.hip: stat "hbm_bytes_resident"
 void comm_destroy(mi355dr_index* idx);                           // mi355dr_comm.hip
 // read-only view of the multi-vector store for kernels outside mi355dr_maxsim.hip (GQR refinement)
@@ -281,6 +296,7 @@ struct MultiVecView {
     const float* tok;             // [blocks*32, dpad] device
     const int64_t* blk_off;       // [n_docs+1] device
     const int64_t* blk_off_host;  // same, host
+    const int32_t* tok_cnt_host;  // [n_docs] token vectors of each doc, host
     int dpad;
     int64_t n_docs;
 };

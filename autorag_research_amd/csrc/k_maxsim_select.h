@@ -227,9 +227,11 @@ __global__ __launch_bounds__(256) void k_ms_tighten(const float* dist_a, const i
     }
 }
 
-// exact top-k of one query's re-scored candidates (grid.y = query): sort by (distance, doc) in LDS, write the result
+// exact top-k of one query's re-scored candidates (grid.y = query): sort by (distance, doc) in LDS, write the result.
+// doc_map (a view: mi355dr_view_create) names the global id of every stored document; else it is doc + row_offset
 __global__ __launch_bounds__(256) void k_ms_final(const float* cand_dist, const int32_t* cand_list, const int* ctl, int cap,
-                                                   int k, int64_t row_offset, float* out_d, int64_t* out_r) {
+                                                   int k, int64_t row_offset, const int64_t* __restrict__ doc_map, float* out_d,
+                                                   int64_t* out_r) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int y = blockIdx.y;
     const int n = min(ctl[2 * y], cap);
@@ -251,17 +253,17 @@ __global__ __launch_bounds__(256) void k_ms_final(const float* cand_dist, const 
     for (int i = threadIdx.x; i < k; i += blockDim.x) {
         const bool ok = i < n && SR[i] != 0x7FFFFFFF;
         out_d[(int64_t)y * k + i] = ok ? key_to_f32(SK[i]) : __uint_as_float(0x7FC00000u);
-        out_r[(int64_t)y * k + i] = ok ? (int64_t)SR[i] + row_offset : -1;
+        out_r[(int64_t)y * k + i] = !ok ? -1 : doc_map ? doc_map[SR[i]] : (int64_t)SR[i] + row_offset;
     }
 }
 
-__global__ void k_ms_write_out(const uint64_t* key, const int32_t* row, int k, int64_t row_offset, float* out_d,
-                               int64_t* out_r) {
+__global__ void k_ms_write_out(const uint64_t* key, const int32_t* row, int k, int64_t row_offset,
+                               const int64_t* __restrict__ doc_map, float* out_d, int64_t* out_r) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= k) return;
     const bool ok = row[i] != 0x7FFFFFFF;
     out_d[i] = ok ? key_to_f32(key[i]) : __uint_as_float(0x7FC00000u);
-    out_r[i] = ok ? (int64_t)row[i] + row_offset : -1;
+    out_r[i] = !ok ? -1 : doc_map ? doc_map[row[i]] : (int64_t)row[i] + row_offset;
 }
 
 }  // namespace mi355

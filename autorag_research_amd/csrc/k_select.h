@@ -594,16 +594,18 @@ __global__ __launch_bounds__(64) void k_emit_irregular(const int32_t* __restrict
     }
 }
 
-// grid: B blocks of 64 threads
-__global__ __launch_bounds__(64) void k_finalize(QueryState st, int k, int64_t row_offset, double* out_dist,
-                                                  int64_t* out_rows, int* status_or) {
+// grid: B blocks of 64 threads.  row_map (a view: mi355dr_view_create) names the global id of every stored row; else it is
+// row + row_offset
+__global__ __launch_bounds__(64) void k_finalize(QueryState st, int k, int64_t row_offset, const int64_t* __restrict__ row_map,
+                                                  double* out_dist, int64_t* out_rows, int* status_or) {
     const int q = blockIdx.x;
     const int n = st.best_n[q];
     for (int s = threadIdx.x; s < k; s += blockDim.x) {
         // (a kept entry with row kRowNone is a removed row that filled a slot no live row claimed: "no result")
         if (s < n && st.best_row[(int64_t)q * kKMax + s] != kRowNone) {
             out_dist[(int64_t)q * k + s] = key_to_dist(st.best_key[(int64_t)q * kKMax + s]);
-            out_rows[(int64_t)q * k + s] = (int64_t)st.best_row[(int64_t)q * kKMax + s] + row_offset;
+            const int32_t r = st.best_row[(int64_t)q * kKMax + s];
+            out_rows[(int64_t)q * k + s] = row_map ? row_map[r] : (int64_t)r + row_offset;
         } else {
             out_dist[(int64_t)q * k + s] = __longlong_as_double(0x7FF8000000000000ll);
             out_rows[(int64_t)q * k + s] = -1;

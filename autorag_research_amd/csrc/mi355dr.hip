@@ -19,6 +19,7 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "k_prune_wide.h"
 #include "k_update.h"
 #include "k_compact.h"
+#include "k_view.h"
 #include "k_block.h"
 
 using namespace mi355;
@@ -722,8 +723,8 @@ int subset_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, i
         HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q_dev, (size_t)B * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     CHECK(launch_prep(idx, s, B, (int)round_up(B, screen_tile(B)), idx->metric));
     if (m > 0) CHECK(run_scan_ids(idx, s, B, k, m));
-    hipLaunchKernelGGL(k_finalize, dim3(B), dim3(64), 0, s, idx->st, k, idx->row_offset, out_dist_dev, out_rows_dev,
-                       idx->status_or_dev);
+    hipLaunchKernelGGL(k_finalize, dim3(B), dim3(64), 0, s, idx->st, k, idx->row_offset, idx->view_row_map.p, out_dist_dev,
+                       out_rows_dev, idx->status_or_dev);
     HIPCHECK(idx, hipGetLastError());
     HIPCHECK(idx, hipMemcpyAsync(idx->status_host, idx->st.status, (size_t)kQBlockMax * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipStreamSynchronize(s));
@@ -782,8 +783,8 @@ int enqueue_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, 
             CHECK(run_scan(idx, s, all, k));  // (blocks on the host only where a chunk larger than the buffer overflowed)
         }
     }
-    hipLaunchKernelGGL(k_finalize, dim3(B), dim3(64), 0, s, idx->st, k, idx->row_offset, out_dist_dev, out_rows_dev,
-                       idx->status_or_dev);
+    hipLaunchKernelGGL(k_finalize, dim3(B), dim3(64), 0, s, idx->st, k, idx->row_offset, idx->view_row_map.p, out_dist_dev,
+                       out_rows_dev, idx->status_or_dev);
     HIPCHECK(idx, hipGetLastError());
     // (one copy: the per-query words and, behind them, their OR)
     HIPCHECK(idx, hipMemcpyAsync(p.status_host, idx->st.status, (size_t)(kQBlockMax + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1010,6 +1011,7 @@ void mi355dr_destroy(mi355dr_index* idx) {
 int mi355dr_reserve(mi355dr_index* idx, int64_t n_rows) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "reserve");
     HIPCHECK(idx, hipSetDevice(idx->device));
     if (n_rows < 0) return fail(idx, MI355DR_E_INVALID, "negative row count");
     if (n_rows >= (int64_t)1 << 31) return fail(idx, MI355DR_E_UNSUPPORTED, "more than 2^31-1 rows per index");
@@ -1078,6 +1080,7 @@ int commit_corpus(mi355dr_index* idx, hipStream_t s, bool mutated) {
 static int add_rows_impl(mi355dr_index* idx, const float* rows, int64_t n, hipMemcpyKind kind) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "add_rows");
     if (n < 0) return fail(idx, MI355DR_E_INVALID, "negative row count");
     if (n == 0) return MI355DR_OK;
     if (!rows) return fail(idx, MI355DR_E_INVALID, "rows is null");
@@ -1111,6 +1114,7 @@ constexpr int64_t kMutSlice = (int64_t)1 << 16;  // rows per staging upload and 
 int mutate_rows_impl(mi355dr_index* idx, const int64_t* row_ids, const float* rows, int64_t n, hipMemcpyKind kind, bool remove) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, remove ? "remove_rows" : "update_rows");
     if (n < 0) return fail(idx, MI355DR_E_INVALID, "negative row count");
     if (n == 0) {  // (nothing to change, but the ordering promise holds: what is in flight is complete on return)
         HIPCHECK(idx, hipSetDevice(idx->device));
@@ -1180,6 +1184,7 @@ int mi355dr_remove_rows(mi355dr_index* idx, const int64_t* row_ids, int64_t n) {
 int mi355dr_compact(mi355dr_index* idx, int64_t* new_of_old) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "compact");
     HIPCHECK(idx, hipSetDevice(idx->device));
     CHECK(drain_pending(idx));  // (a search in flight sees the index as it was, under the old ids)
     const int64_t n_old = idx->n;
@@ -1266,6 +1271,173 @@ int mi355dr_compact(mi355dr_index* idx, int64_t* new_of_old) {
         int64_t next = 0;
         for (int64_t r = 0; r < n_old; ++r) new_of_old[r] = row_is_dead(n2[(size_t)r]) ? -1 : next++;
     }
+    return MI355DR_OK;
+}
+
+// ---- views (DESIGN.md section 4.8c "Views") --------------------------------------------------------------------------------
+namespace {
+// a call on the view that failed: the caller asks the PARENT for the text
+#define VIEWCHECK(parent, view, expr)                                                         \
+    do {                                                                                      \
+        int rc__ = (expr);                                                                    \
+        if (rc__ != MI355DR_OK) return fail(parent, rc__, "view_create: " + (view)->err);     \
+    } while (0)
+
+// the caller's global ids -> `out`: local, ascending, unique (subset_ids.h: the rule of mi355dr_search_subset)
+int view_local_ids(mi355dr_index* parent, const int64_t* ids, int64_t m, int64_t n, std::vector<int32_t>& out) {
+    try {
+        subset_prepare_ids(ids, m, parent->row_offset, n, out);
+    } catch (const std::bad_alloc&) {
+        return fail(parent, MI355DR_E_NOMEM, "view_create: out of host memory for the id list");
+    }
+    return MI355DR_OK;
+}
+
+// `local` + the parent's row_offset -> a device map the view owns
+int view_upload_map(mi355dr_index* parent, const std::vector<int32_t>& local, DevBuf<int64_t>& map) {
+    if (local.empty()) return MI355DR_OK;
+    std::vector<int64_t> global;
+    try {
+        global.resize(local.size());
+    } catch (const std::bad_alloc&) {
+        return fail(parent, MI355DR_E_NOMEM, "view_create: out of host memory for the id map");
+    }
+    for (size_t j = 0; j < local.size(); ++j) global[j] = (int64_t)local[j] + parent->row_offset;
+    HIPCHECK(parent, map.grow(global.size() * sizeof(int64_t)));
+    HIPCHECK(parent, hipMemcpy(map.p, global.data(), global.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    return MI355DR_OK;
+}
+
+// Everything between the view's creation and its publication; the caller destroys the view when this fails.  The parent's
+// mutex is held and nothing of the parent is written.  Gathers run on the PARENT's stream and are waited for on the host
+// before the view's add path (its own stream, complete on return) reads the staging buffer -- one synchronisation per slice.
+int view_build(mi355dr_index* parent, mi355dr_index* view, const int64_t* row_ids, int64_t m_rows, const int64_t* doc_ids,
+               int64_t m_docs) {
+    hipStream_t s = parent->stream;
+    const int d = parent->dim;
+    const size_t row_b = (size_t)d * sizeof(float);
+    const int64_t slice = parent->view_slice_rows;  // rows -- and tokens: the token slices have the same byte count
+    // ---- the lists: local, ascending, unique; removed rows and documents without vectors leave
+    std::vector<int32_t> rows, docs;
+    CHECK(view_local_ids(parent, row_ids, m_rows, parent->n, rows));
+    DevBuf<int32_t> ids_dev;
+    if (!rows.empty()) {
+        HIPCHECK(parent, ids_dev.grow(rows.size() * sizeof(int32_t)));
+        HIPCHECK(parent, hipMemcpyAsync(ids_dev.p, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHECK(parent, hipStreamSynchronize(s));
+    }
+    if (!rows.empty() && parent->dead_n > 0) {  // the m norms are read back (4 m bytes) and the dead rows dropped on the host
+        const int64_t m = (int64_t)rows.size();
+        DevBuf<float> n2_dev;
+        std::vector<float> n2;
+        try {
+            n2.resize((size_t)m);
+        } catch (const std::bad_alloc&) {
+            return fail(parent, MI355DR_E_NOMEM, "view_create: out of host memory for the listed rows' norms");
+        }
+        HIPCHECK(parent, n2_dev.grow((size_t)m * sizeof(float)));
+        hipLaunchKernelGGL(k_view_gather_nrm2, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, parent->nrm2.p, ids_dev.p, m, n2_dev.p);
+        HIPCHECK(parent, hipGetLastError());
+        HIPCHECK(parent, hipMemcpyAsync(n2.data(), n2_dev.p, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHECK(parent, hipStreamSynchronize(s));
+        int64_t keep = 0;
+        for (int64_t j = 0; j < m; ++j)
+            if (!row_is_dead(n2[(size_t)j])) rows[(size_t)keep++] = rows[(size_t)j];
+        if (keep < m) {
+            rows.resize((size_t)keep);
+            if (keep > 0) {
+                HIPCHECK(parent, hipMemcpyAsync(ids_dev.p, rows.data(), (size_t)keep * sizeof(int32_t), hipMemcpyHostToDevice, s));
+                HIPCHECK(parent, hipStreamSynchronize(s));
+            }
+        }
+    }
+    MultiVecView pv{};
+    if (m_docs > 0 && multivec_view(parent, &pv)) {
+        CHECK(view_local_ids(parent, doc_ids, m_docs, pv.n_docs, docs));
+        docs.erase(std::remove_if(docs.begin(), docs.end(), [&](int32_t i) { return pv.tok_cnt_host[i] <= 0; }), docs.end());
+    }
+    const int64_t n_rows = (int64_t)rows.size(), n_docs = (int64_t)docs.size();
+    // ---- the one staging buffer: a slice of rows, or a slice of tokens (a document longer than a slice goes alone)
+    int64_t tok_total = 0, tok_longest = 0, blk_total = 0;
+    for (int32_t i : docs) {
+        const int64_t T = pv.tok_cnt_host[i];
+        tok_total += T;
+        tok_longest = std::max(tok_longest, T);
+        blk_total += (T + kMsBlkRows - 1) / kMsBlkRows;
+    }
+    const int64_t stage_rows = std::max(std::min(slice, n_rows), std::max(std::min(slice, tok_total), tok_longest));
+    DevBuf<float> stage;
+    if (stage_rows > 0) HIPCHECK(parent, stage.grow((size_t)stage_rows * row_b));
+    // ---- single-vector rows
+    if (n_rows > 0) {
+        VIEWCHECK(parent, view, mi355dr_reserve(view, n_rows));
+        const int vec4 = d % 4 == 0 && (uintptr_t)parent->rows.p % 16 == 0 && (uintptr_t)stage.p % 16 == 0;
+        for (int64_t j0 = 0; j0 < n_rows; j0 += slice) {
+            const int64_t m = std::min(slice, n_rows - j0);
+            hipLaunchKernelGGL(k_view_gather_rows, dim3((unsigned)((m + kViewWaves - 1) / kViewWaves)), dim3(64 * kViewWaves), 0, s,
+                               parent->rows.p, ids_dev.p + j0, m, d, vec4, stage.p);
+            HIPCHECK(parent, hipGetLastError());
+            HIPCHECK(parent, hipStreamSynchronize(s));
+            VIEWCHECK(parent, view, mi355dr_add_rows_device(view, stage.p, m));
+        }
+        CHECK(view_upload_map(parent, rows, view->view_row_map));
+    }
+    // ---- documents
+    if (n_docs > 0) {
+        VIEWCHECK(parent, view, multivec_reserve(view, blk_total, n_docs));
+        std::vector<ViewTokBlock> blocks;
+        std::vector<int64_t> offsets;
+        DevBuf<ViewTokBlock> blocks_dev;
+        for (int64_t i0 = 0, i1; i0 < n_docs; i0 = i1) {
+            blocks.clear();
+            offsets.assign(1, 0);
+            try {
+                for (i1 = i0; i1 < n_docs && (i1 == i0 || offsets.back() + pv.tok_cnt_host[docs[(size_t)i1]] <= slice); ++i1) {
+                    const int64_t T = pv.tok_cnt_host[docs[(size_t)i1]], blk0 = pv.blk_off_host[docs[(size_t)i1]];
+                    for (int64_t t = 0; t < T; t += kMsBlkRows)
+                        blocks.push_back(ViewTokBlock{blk0 + t / kMsBlkRows, offsets.back() + t, (int32_t)std::min<int64_t>(kMsBlkRows, T - t), 0});
+                    offsets.push_back(offsets.back() + T);
+                }
+            } catch (const std::bad_alloc&) {
+                return fail(parent, MI355DR_E_NOMEM, "view_create: out of host memory for a slice's block table");
+            }
+            HIPCHECK(parent, blocks_dev.grow(blocks.size() * sizeof(ViewTokBlock)));
+            HIPCHECK(parent, hipMemcpyAsync(blocks_dev.p, blocks.data(), blocks.size() * sizeof(ViewTokBlock), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_view_gather_toks, dim3((unsigned)blocks.size()), dim3(64 * kViewWaves), 0, s, pv.tok, blocks_dev.p, d,
+                               pv.dpad, stage.p);
+            HIPCHECK(parent, hipGetLastError());
+            HIPCHECK(parent, hipStreamSynchronize(s));  // (also: `blocks` is pageable and is rewritten for the next slice)
+            VIEWCHECK(parent, view, mi355dr_add_multivec_device(view, stage.p, offsets.data(), i1 - i0));
+        }
+        CHECK(view_upload_map(parent, docs, view->view_doc_map));
+    }
+    view->view_rows = n_rows;
+    view->view_docs = n_docs;
+    return MI355DR_OK;
+}
+}  // namespace
+
+int mi355dr_view_create(mi355dr_index* parent, const int64_t* row_ids, int64_t m_rows, const int64_t* doc_ids, int64_t m_docs,
+                        mi355dr_index** out_view) {
+    if (out_view) *out_view = nullptr;
+    if (!parent) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    if (!out_view) return fail(parent, MI355DR_E_INVALID, "view_create: out_view is null");
+    if (m_rows < 0 || m_docs < 0 || (m_rows > 0 && !row_ids) || (m_docs > 0 && !doc_ids))
+        return fail(parent, MI355DR_E_INVALID, "view_create: counts must be >= 0 and a list with a count not null");
+    std::lock_guard<std::mutex> g(parent->mu);
+    if (parent->is_view) return view_refuses(parent, "view_create", /*ask_parent=*/true);
+    HIPCHECK(parent, hipSetDevice(parent->device));
+    CHECK(drain_pending(parent));
+    mi355dr_index* view = nullptr;
+    int rc = mi355dr_create(&view, parent->device, parent->dim, parent->metric);
+    if (rc != MI355DR_OK) return fail(parent, rc, std::string("view_create: ") + mi355dr_last_error(nullptr));
+    rc = view_build(parent, view, row_ids, m_rows, doc_ids, m_docs);
+    if (rc != MI355DR_OK) {
+        mi355dr_destroy(view);  // (everything the view allocated goes with it; the parent was only read)
+        return rc;
+    }
+    view->is_view = true;  // from here on: read-only, and the id-taking entry points refer to the parent
+    *out_view = view;
     return MI355DR_OK;
 }
 
@@ -1373,6 +1545,7 @@ int subset_upload_ids(mi355dr_index* idx, hipStream_t s, const int64_t* row_ids,
 // host == true: queries / outputs are host buffers staged through the index's own; else device buffers used in place
 int search_subset_impl(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* row_ids, int64_t m,
                        double* out_dist, int64_t* out_rows, hipStream_t s, bool host) {
+    if (idx && idx->is_view) return view_refuses(idx, "search_subset", /*ask_parent=*/true);  // (set once, before the handle is handed out)
     CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
     if (m < 0 || (m > 0 && !row_ids)) return fail(idx, MI355DR_E_INVALID, "search_subset: m must be >= 0 and row_ids not null");
     std::lock_guard<std::mutex> g(idx->mu);
@@ -1416,6 +1589,7 @@ int mi355dr_search_subset_device(mi355dr_index* idx, const float* queries_dev, i
 
 int mi355dr_score_subset(mi355dr_index* idx, const float* queries, int B, const int64_t* row_ids, int m, double* out_dist) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    if (idx->is_view) return view_refuses(idx, "score_subset", /*ask_parent=*/true);
     if (B < 0 || m < 0) return fail(idx, MI355DR_E_INVALID, "score_subset: B and m must be >= 0");
     if (B > 0 && (!queries || (m > 0 && (!row_ids || !out_dist)))) return fail(idx, MI355DR_E_INVALID, "null buffer");
     std::lock_guard<std::mutex> g(idx->mu);
@@ -1572,6 +1746,7 @@ const Option kOptions[] = {
     {"chunk_taper_x100", &Index::chunk_taper_x100, 0, 300, nullptr, 0, 100},  // 0 (auto) or 100 ... 300
     {"starter_rows_wide", &Index::starter_rows_wide, 4096, 262144},
     {"compact_slice_rows", &Index::compact_slice_rows, 32, (int64_t)1 << 22},  // destination rows per staged slice of mi355dr_compact
+    {"view_slice_rows", &Index::view_slice_rows, 32, (int64_t)1 << 22},  // rows per staged slice of mi355dr_view_create on this index
 };
 
 struct Stat {
@@ -1612,6 +1787,9 @@ const Stat kStats[] = {
     {"subset_rerun_queries", &Index::s_subset_rerun_queries, true},
     {"compactions", &Index::s_compactions, true},
     {"compact_moved_rows", &Index::s_compact_moved_rows, true},
+    {"view", nullptr, false, [](const Index* x) -> int64_t { return x->is_view ? 1 : 0; }},
+    {"view_rows", &Index::view_rows, false},  // (what mi355dr_view_create kept: state, not activity; 0 on a parent)
+    {"view_docs", &Index::view_docs, false},
     {"i8_demoted", nullptr, false, [](const Index* x) -> int64_t { return x->i8_demoted_k != INT_MAX ? 1 : 0; }},
     {"i8_demoted_k", nullptr, false, [](const Index* x) -> int64_t { return x->i8_demoted_k == INT_MAX ? 0 : x->i8_demoted_k; }},
     {"irregular_rows", nullptr, false, [](const Index* x) -> int64_t { return x->irr_n; }},
@@ -1620,7 +1798,8 @@ const Stat kStats[] = {
     {"screen_dtype_active", nullptr, false, [](const Index* x) -> int64_t { return use_i8(x) ? MI355DR_SCREEN_I8 : MI355DR_SCREEN_BF16; }},
     {"hbm_bytes_resident", nullptr, false, [](const Index* x) -> int64_t {
          return x->cap_rows * ((int64_t)x->dim * 4 + (int64_t)x->dpad * 2 + (int64_t)x->dpad8 + 5) +
-                x->cap_rows / kI8GroupRows * (int64_t)sizeof(I8Group) + multivec_bytes(x);
+                x->cap_rows / kI8GroupRows * (int64_t)sizeof(I8Group) + multivec_bytes(x) +
+                (int64_t)(x->view_row_map.bytes + x->view_doc_map.bytes);  // (a view's two id maps; none on a parent)
      }},
 };
 }  // namespace
@@ -1632,6 +1811,7 @@ int mi355dr_set_option(mi355dr_index* idx, const char* key, int64_t value) {
         HIPCHECK(idx, hipSetDevice(idx->device));
         CHECK(drain_pending(idx));
     }
+    if (idx->is_view && strcmp(key, "row_offset") == 0) return view_refuses(idx, "option row_offset");  // (its rows are the parent's ids)
     for (const Option& o : kOptions) {
         if (strcmp(o.key, key) != 0) continue;
         if (value < o.lo || value > o.hi || (value > o.gap_lo && value < o.gap_hi)) {

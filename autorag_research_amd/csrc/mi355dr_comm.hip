@@ -107,6 +107,7 @@ int mi355dr_comm_unique_id(void* out, size_t len) {
 
 int mi355dr_comm_init(mi355dr_index* idx, int rank, int world, const void* nccl_unique_id, size_t id_len) {
     if (!idx) return mi355::fail(nullptr, MI355DR_E_INVALID, "null index");
+    if (idx->is_view) return mi355::view_refuses(idx, "comm_init", /*ask_parent=*/true);  // (set once, before the handle is handed out)
     if (world < 1 || rank < 0 || rank >= world) return mi355::fail(idx, MI355DR_E_INVALID, "need 0 <= rank < world");
     if (!nccl_unique_id || id_len < sizeof(NcclUniqueId)) return mi355::fail(idx, MI355DR_E_INVALID, "unique id must be 128 bytes");
     RcclApi& r = rccl();
@@ -127,6 +128,7 @@ int mi355dr_comm_init(mi355dr_index* idx, int rank, int world, const void* nccl_
 
 int mi355dr_comm_init_custom(mi355dr_index* idx, int rank, int world, mi355dr_allgather_fn fn, void* user) {
     if (!idx) return mi355::fail(nullptr, MI355DR_E_INVALID, "null index");
+    if (idx->is_view) return mi355::view_refuses(idx, "comm_init_custom", /*ask_parent=*/true);
     if (world < 1 || rank < 0 || rank >= world) return mi355::fail(idx, MI355DR_E_INVALID, "need 0 <= rank < world");
     if (!fn) return mi355::fail(idx, MI355DR_E_INVALID, "all-gather function is null");
     std::lock_guard<std::mutex> g(idx->mu);
@@ -166,6 +168,7 @@ int mi355dr_comm_count(mi355dr_index* idx, int* out) {
 int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, int B, int k, double* out_dist_dev,
                                   int64_t* out_rows_dev, void* stream) {
     if (!idx) return mi355::fail(nullptr, MI355DR_E_INVALID, "null index");
+    if (idx->is_view) return mi355::view_refuses(idx, "search_sharded_device", /*ask_parent=*/true);
     if (!idx->comm && !idx->comm_custom)
         return mi355::fail(idx, MI355DR_E_INVALID, "mi355dr_comm_init has not been called on this index");
     if (B < 0 || k <= 0 || k > mi355::kKMax) return mi355::fail(idx, MI355DR_E_INVALID, "bad B / k");

@@ -58,6 +58,7 @@ int mi355dr_gqr_refine(mi355dr_index* idx, const double* queries, int B, const i
                        double mixture_alpha, double* out_scores) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "gqr_refine", /*ask_parent=*/true);
     CHECK(check_params(idx, B, P, n_steps, learning_rate, temperature, mixture_alpha));
     if (B == 0 || P == 0) return MI355DR_OK;
     if (!queries || !cand_rows || !comp_dist || !out_scores) return fail(idx, MI355DR_E_INVALID, "gqr: null buffer");
@@ -135,6 +136,7 @@ int mi355dr_gqr_refine_maxsim(mi355dr_index* idx, const double* qtok, const int3
                               double temperature, double mixture_alpha, double* out_scores) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "gqr_refine_maxsim", /*ask_parent=*/true);
     CHECK(check_params(idx, B, P, n_steps, learning_rate, temperature, mixture_alpha));
     if (B == 0 || P == 0) return MI355DR_OK;
     if (!qtok || !q_offsets || !doc_ids || !comp_dist || !out_scores) return fail(idx, MI355DR_E_INVALID, "gqr: null buffer");

@@ -95,6 +95,7 @@ bool multivec_view(const mi355dr_index* idx, MultiVecView* out) {
     out->tok = m->tok.p;
     out->blk_off = m->blk_off.p;
     out->blk_off_host = m->blk_off_host.data();
+    out->tok_cnt_host = m->tok_cnt_host.data();
     out->dpad = m->dpad;
     out->n_docs = m->n_docs;
     return true;
@@ -267,6 +268,17 @@ void ms_commit_bounds(MultiVecStore* m, const unsigned long long st[4]) {
     if (nf) m->finite = false;
 }
 
+// the index's store, created empty on first use
+MultiVecStore* ms_store(mi355dr_index* idx) {
+    if (!idx->mv) {
+        idx->mv = new MultiVecStore();
+        idx->mv->dpad = (int)round_up(idx->dim, 8);
+        idx->mv->nkk = (int)round_up(idx->dim, 16) / 16;
+        idx->mv->blk_off_host.push_back(0);
+    }
+    return idx->mv;
+}
+
 // vecs: [offsets[n_docs], dim] on the host, or (on_device) on the index's GPU.  All or nothing: room for the whole call is
 // reserved first (what is stored is carried over, the device offset table included), the images of the new blocks and the new
 // docs' entries of the device offset table are written behind the stored ones (no search reads past n_blocks / n_docs), and
@@ -274,19 +286,14 @@ void ms_commit_bounds(MultiVecStore* m, const unsigned long long st[4]) {
 int ms_add(mi355dr_index* idx, const float* vecs, const int64_t* offsets, int64_t n_docs, bool on_device) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "add_multivec");
     if (n_docs < 0 || !offsets || (n_docs > 0 && offsets[n_docs] > 0 && !vecs))
         return fail(idx, MI355DR_E_INVALID, "bad multi-vector arguments");
     if (n_docs == 0) return MI355DR_OK;
     for (int64_t i = 0; i < n_docs; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(idx, MI355DR_E_INVALID, "offsets must be non-decreasing");
     HIPCHECK(idx, hipSetDevice(idx->device));
-    if (!idx->mv) {
-        idx->mv = new MultiVecStore();
-        idx->mv->dpad = (int)round_up(idx->dim, 8);
-        idx->mv->nkk = (int)round_up(idx->dim, 16) / 16;
-        idx->mv->blk_off_host.push_back(0);
-    }
-    MultiVecStore* m = idx->mv;
+    MultiVecStore* m = ms_store(idx);
     if (m->n_docs + n_docs >= ((int64_t)1 << 31)) return fail(idx, MI355DR_E_UNSUPPORTED, "too many docs");
     auto blocks_of = [&](int64_t i) { return (offsets[i + 1] - offsets[i] + kMsBlkRows - 1) / kMsBlkRows; };
     // the table with the new docs' block offsets, built on the side
@@ -343,6 +350,7 @@ void ms_pack8_stale(mi355dr_index* idx, MultiVecStore* m, bool release) {
 int ms_set(mi355dr_index* idx, const int64_t* doc_ids, const float* vecs, const int64_t* offsets, int64_t n, bool on_device) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "set_multivec");
     if (n < 0 || (n > 0 && (!doc_ids || !offsets))) return fail(idx, MI355DR_E_INVALID, "bad set_multivec arguments");
     if (n == 0) return MI355DR_OK;
     MultiVecStore* m = idx->mv;
@@ -713,7 +721,7 @@ int ms_emit_result(const MsSearch& c, int cur, int b) {
     int64_t* orow = c.out_rows + (int64_t)b * c.k;
     // (device outputs: straight into the caller's buffers)
     hipLaunchKernelGGL(k_ms_write_out, dim3((c.k + 255) / 256), dim3(256), 0, c.s, m->pk[cur].p, m->pr[cur].p, c.k, idx->row_offset,
-                       c.out_dev ? od : m->out_d.p, c.out_dev ? orow : m->out_r.p);
+                       idx->view_doc_map.p, c.out_dev ? od : m->out_d.p, c.out_dev ? orow : m->out_r.p);
     HIPCHECK(idx, hipGetLastError());
     if (c.out_dev) return MI355DR_OK;
     HIPCHECK(idx, hipMemcpyAsync(od, m->out_d.p, c.k * sizeof(float), hipMemcpyDeviceToHost, c.s));
@@ -1000,7 +1008,7 @@ int ms_fast_path(const MsSearch& c, const MsPass& p, bool* handled) {
     HIPCHECK(idx, hipGetLastError());
     if (idx->profile) HIPCHECK(idx, hipEventRecord(idx->ms_ev[3], s));
     hipLaunchKernelGGL(k_ms_final, dim3(1, p.n), dim3(256), (size_t)kMsCandCap * 12, s, m->cand_dist.p, list_f, ctl_f,
-                       kMsCandCap, k, idx->row_offset, m->out_d.p, m->out_r.p);
+                       kMsCandCap, k, idx->row_offset, idx->view_doc_map.p, m->out_d.p, m->out_r.p);
     HIPCHECK(idx, hipGetLastError());
     HIPCHECK(idx, hipMemcpyAsync(m->cand_ctl_host.p, ctl_f, 2 * kPQ * sizeof(int), hipMemcpyDeviceToHost, s));
     if (!c.out_dev) {  // (hd also staged `te`: its H2D copy precedes these copies in stream order)
@@ -1136,6 +1144,7 @@ int maxsim_subset_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_o
                        int m_ids, int clamp0, float* out_dist) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "maxsim_subset", /*ask_parent=*/true);
     if (B < 0 || m_ids < 0 || !q_offsets || (B > 0 && m_ids > 0 && (!doc_ids || !out_dist)))
         return fail(idx, MI355DR_E_INVALID, "bad maxsim_subset arguments");
     for (int64_t i = 0; i < (int64_t)B * m_ids; ++i) out_dist[i] = NAN;
@@ -1200,6 +1209,14 @@ int maxsim_subset_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_o
 }
 
 }  // namespace
+
+namespace mi355 {
+int multivec_reserve(mi355dr_index* idx, int64_t n_blocks, int64_t n_docs) {
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    return ms_reserve(idx, ms_store(idx), n_blocks, n_docs);
+}
+}  // namespace mi355
 
 extern "C" {
 

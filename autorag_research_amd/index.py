@@ -32,6 +32,7 @@ class Mi355Index:
         self.dim = int(dim)
         self.metric = metric
         self.device = int(device)
+        self._is_view = False
 
     # ---- lifetime ----
     def close(self) -> None:
@@ -201,6 +202,31 @@ class Mi355Index:
         check(self._h, self._lib.mi355dr_score_subset(self._h, ptr(q, ctypes.c_float), q.shape[0], ptr(ids, ctypes.c_int64),
                                                       ids.shape[1], ptr(out, ctypes.c_double)))
         return out
+
+    # ---- views: a listed subset as an index of its own (include/mi355dr.h "views") ----
+    def view(self, row_ids=None, doc_ids=None) -> "Mi355Index":
+        """The listed rows and / or documents of this index as a read-only index of their own, built on the device
+        (mi355dr_view_create).  Ids are global, under the hygiene of `search_subset` (out-of-range ids and -1 padding skipped,
+        duplicates once, any order); removed rows and documents without vectors are left out.  Every search of the view --
+        `search`, `search_device*`, `search_maxsim*` -- runs the ordinary paths, screens included, and returns THIS index's
+        ids: `view.search(Q, k)` equals `search_subset(Q, k, row_ids)` bit for bit.  The view is a snapshot (later changes
+        here do not reach it, it outlives this index) and is closed on its own.  Worth it when one list serves many query
+        blocks; a one-off list is cheaper through `search_subset`."""
+        if not self._h:
+            raise ValueError("view() on a closed index")
+        rows = self._row_ids(() if row_ids is None else row_ids)
+        docs = self._row_ids(() if doc_ids is None else doc_ids)
+        h = ctypes.c_void_p()
+        check(self._h, self._lib.mi355dr_view_create(self._h, ptr(rows, ctypes.c_int64), rows.shape[0],
+                                                     ptr(docs, ctypes.c_int64), docs.shape[0], ctypes.byref(h)))
+        v = object.__new__(type(self))
+        v._lib, v._h, v.dim, v.metric, v.device, v._is_view = self._lib, h, self.dim, self.metric, self.device, True
+        return v
+
+    @property
+    def is_view(self) -> bool:
+        """True for an index returned by `view`: read-only, rows and documents named by the parent's ids."""
+        return self._is_view
 
     def merge_topk_device(self, dist_all_ptr: int, rows_all_ptr: int, world: int, B: int, k: int, out_dist_ptr: int,
                           out_rows_ptr: int, stream: int | None = None) -> None:

@@ -413,6 +413,19 @@ class ShardedSearcher:
             out = np.where(np.isnan(out), g[r], out)
         return out
 
+    # ---- views: the same lists on every rank, each keeps what falls in its shard ----
+    def view(self, row_ids=None, doc_ids=None) -> "ShardedSearcher":
+        """A searcher over the listed GLOBAL rows / documents only (Mi355Index.view).  Every rank passes the same lists; each
+        builds a view of the ids inside its shard (possibly an empty one).  The result shares this searcher's process group
+        and holds the view as its `index`: a view already returns global ids, so `search` and `search_maxsim` run their
+        pipelines unchanged.  `close()` on the result releases the view only."""
+        v = object.__new__(type(self))
+        v.__dict__.update(self.__dict__)
+        v.index = self.index.view(row_ids, doc_ids)
+        v.overlapped_blocks = 0
+        v._ms_stream = None
+        return v
+
     def close(self) -> None:
         self.index.close()
 

@@ -4,8 +4,8 @@
     python examples/quickstart.py
 
 1. single-vector index: add fp32 rows, exact cosine top-k for a block of queries (ids + float8 distances), the same search
-   within a listed subset of rows
-2. multi-vector store: ragged docs, exact MaxSim top-k, candidate re-scoring
+   within a listed subset of rows, and a view of that subset for repeated searches
+2. multi-vector store: ragged docs, exact MaxSim top-k, candidate re-scoring, MaxSim top-k within a view
 3. the reference-shaped pipelines over an in-memory store: vector search, image (MaxSim) search, HEAVEN two-stage,
    Guided Query Refinement, RRF / convex-combination fusion and HyDE over child retrievers
 4. group-nDCG of the persisted results
@@ -44,6 +44,12 @@ with amd.Mi355Index(d, "cosine") as idx:
     sdist, srows = idx.search_subset(queries[:4], k=3, row_ids=pool)
     print("within a 2062-row pool: best rows", srows[:, 0].tolist(), "| pairwise distances of query 0 to rows [0, 97, -1]:",
           idx.score_subset(queries[:1], np.array([[0, 97, -1]])).round(4).tolist())
+    # a list that serves many query blocks (one tenant, one collection): gather it once into a view -- an index of its own
+    # that runs the ordinary screened search and answers under THIS index's row ids
+    with idx.view(row_ids=pool) as tenant:
+        vdist, vrows = tenant.search(queries[:4], k=3)
+        print("the same through a view of the pool:", len(tenant), "rows, identical =",
+              bool(np.array_equal(vrows, srows) and np.array_equal(vdist, sdist)))
 
 # ---- 2. multi vectors (late interaction) ---------------------------------------------------------------------------------
 n_docs, dm = 5_000, 128
@@ -58,6 +64,8 @@ with amd.Mi355Index(dm) as idx:
     mdist, mrows = idx.search_maxsim(qtok, qoff, k=5)   # VectorChord @#: -sum_i max_j <q_i, d_j>
     print("MaxSim: best doc", int(mrows[0, 0]), "score", float(-mdist[0, 0] / 16))
     print("candidate re-scoring of docs [42, 7, 9]:", (-idx.maxsim_subset(qtok, qoff, np.array([[42, 7, 9]])) / 16).round(4).tolist())
+    with idx.view(doc_ids=np.arange(0, n_docs, 2)) as even:   # MaxSim top-k restricted to a listed collection
+        print("MaxSim within the even-numbered docs: best doc", int(even.search_maxsim(qtok, qoff, k=5)[1][0, 0]))
 
 # ---- 3. the reference-shaped pipelines ------------------------------------------------------------------------------------
 store = InMemoryStore()

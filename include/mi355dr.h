@@ -184,6 +184,51 @@ int mi355dr_search_subset_device(mi355dr_index* idx, const float* queries_dev, i
  * and where the distance is undefined (a zero norm).  Same device code as mi355dr_debug_rescore. */
 int mi355dr_score_subset(mi355dr_index* idx, const float* queries, int B, const int64_t* row_ids, int m, double* out_dist);
 
+/* ---- views: a listed subset of rows / documents as an index of its own ----
+ * For a list that is searched again and again -- one tenant, one document collection, one PDF's pages: the key filter of the
+ * statement above, fixed for many query blocks.  mi355dr_search_subset scans the list exactly on every call (cost ~ m x B, no
+ * screen); a view pays once for gathering the listed rows on the device into a handle of their own, and every search path --
+ * the MFMA screens, the MaxSim screen -- then runs on that handle.  Results come back under the PARENT's ids.
+ *   row_ids: HOST [m_rows], doc_ids: HOST [m_docs]; either list may be empty (NULL with a count of 0).  Ids are GLOBAL (local
+ *     row / document + the parent's "row_offset").  List hygiene is that of mi355dr_search_subset: values outside the parent's
+ *     shard are skipped (negative values and -1 padding included), a value listed twice counts once, the order never matters.
+ *     Removed rows are left out, and so are documents without vectors.  m < 0, or a null list with m > 0: MI355DR_E_INVALID.
+ *     Two empty lists make a valid empty view.
+ *   The view is an ordinary mi355dr_index on the parent's device, with the parent's dim and metric and with options at their
+ *     defaults; it owns its memory, stream and mutex and is released with mi355dr_destroy.  It holds the live listed rows in
+ *     ascending id order and the listed documents with vectors in ascending id order, and answers as an index built fresh by
+ *     one mi355dr_add_rows / mi355dr_add_multivec of exactly those would: norm bits, both shadows, the irregular and loose
+ *     classes and the maxima are built by the view's own add paths, not copied (an int8 group of 32 rows depends on its
+ *     neighbours).  mi355dr_size == mi355dr_live_rows == the live listed rows, mi355dr_size_multivec == the listed documents
+ *     with vectors, mi355dr_get_rows(view, j, n) returns the listed rows in ascending id order.
+ *   Every search entry point works on it as on any handle -- mi355dr_search / _device / _device_async + _wait,
+ *     mi355dr_search_maxsim / _device, options, stats, timers, dev_* -- and RETURNS THE PARENT'S GLOBAL IDS:
+ *       mi355dr_search(view, Q, k)         == mi355dr_search_subset(parent, Q, k, row_ids): float8 bits, rows, NaN positions and
+ *                                             the NaN / -1 tail, on every path and screen_dtype, both metrics, any k and B (view
+ *                                             order is id order, so ties break by the parent's ids);
+ *       mi355dr_search_maxsim(view, ...)   == the top-k by (distance asc, document asc) of mi355dr_maxsim_subset(parent, ...)
+ *                                             over the listed documents with vectors, fp32 bits.
+ *   Snapshot: later update / remove / compact / set_multivec on the parent do not reach the view (after a parent compact the
+ *     view still speaks the OLD ids); the parent may be destroyed first.
+ *   Read-only: mi355dr_add_rows*, _update_rows*, _remove_rows, _compact, _reserve, _add_multivec*, _set_multivec* and option
+ *     "row_offset" return MI355DR_E_INVALID on a view and change nothing.  So does every entry point that takes global ids or a
+ *     communicator, with an error text that refers the caller to the parent: mi355dr_search_subset*, _score_subset,
+ *     _maxsim_subset*, _gqr_refine, _gqr_refine_maxsim, _comm_init*, _search_sharded_device, and mi355dr_view_create itself (no
+ *     views of views).  The stateless ones stay usable: mi355dr_merge_topk*, _pack_topk_device, _gqr_refine_scores.
+ *   The call takes the parent's mutex, first completes whatever search is in flight there, and is complete on return;
+ *     afterwards the two handles are independent.  The parent is only read.  On any error *out_view is NULL, everything
+ *     allocated for the view has been released and the parent is unchanged and usable (its last_error has the text); a failed
+ *     allocation returns MI355DR_E_NOMEM.
+ *   Memory: the view costs what a fresh index of that many rows / documents costs, plus 8 bytes per row and document for the id
+ *     maps.  During the call there is on top ONE staging buffer of the parent's option "view_slice_rows" rows (default 65536,
+ *     32 ... 2^22; fewer when less is listed): rows are gathered and added slice by slice, and the documents' tokens in slices
+ *     of the same byte count (a document longer than a slice goes alone and sizes the buffer).  The removed rows are found by
+ *     reading the m listed rows' norms back (4 m bytes), before any row is gathered.
+ *   Stats on the view: "view" = 1 (0 on any other index, where the next two are 0 as well), "view_rows" / "view_docs" = what
+ *     the build kept, "hbm_bytes_resident" counts the view's own memory. */
+int mi355dr_view_create(mi355dr_index* parent, const int64_t* row_ids, int64_t m_rows, const int64_t* doc_ids, int64_t m_docs,
+                        mi355dr_index** out_view);
+
 /* ---- corpus + search (multi-vector, MaxSim) ----
  * vecs: host [sum_T, dim] fp32, offsets: [n_docs+1] (doc i owns rows offsets[i]..offsets[i+1]). */
 int mi355dr_add_multivec(mi355dr_index* idx, const float* vecs, const int64_t* offsets, int64_t n_docs);
@@ -344,7 +389,7 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
  *          two-wave prune, a starter over "starter_rows_wide" [65536] rows and chunk ratios up to 4; 0 = the round-5 schedule),
  *          "screen_flush_sync" (1 [default]: the waves of a k_screen_rq workgroup flush their hit-lane queues at the same tiles;
  *          "screen_flush_lanes" [48] / "screen_flush_alone" [40] tune the period), "chunk_taper_x100" (0 [default] = 120 for
- *          prune_wide passes, 100 = uniform chunk ratios otherwise), "wide_inflation_x10" (the budget's inflation figure);
+ *          prune_wide passes, 100 = uniform chunk ratios otherwise), "wide_inflation_x10" (the budget's inflation figure); "view_slice_rows" (staging slice of mi355dr_view_create);
  *          "maxsim_pack8" (MaxSim screen, passes of 32-vector queries in the workgroup form and passes of up to four column blocks: a second bf16 shadow whose documents are
  *          rounded up to 8-token granules instead of 32-token blocks, built on the first such pass and extended by the next one after an add -- -1
  *          [default]: when it has at least 5 % fewer blocks than the padded copy and its memory is there, 1: always, 0: never;
@@ -363,6 +408,7 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
  *          multiplied every token by), "maxsim_set_docs" (documents rewritten by mi355dr_set_multivec) / "maxsim_moved_blocks"
  *          (32-token blocks its relayouts copied; 0 on the in-place path), "subset_searches" / "subset_rows_scored" /
  *          "subset_rerun_queries" (mi355dr_search_subset: calls, pairs scored, queries re-run in list-sized pieces),
+ *          "view" / "view_rows" / "view_docs" (mi355dr_view_create: 1 on a view / the rows / the documents it holds),
  *          "hbm_bytes_resident" (the single-vector corpus with its shadows at its capacity + the multi-vector store's two
  *          images, offset table and granule-packed copy as allocated now). */
 int mi355dr_set_option(mi355dr_index* idx, const char* key, int64_t value);
