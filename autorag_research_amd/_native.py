@@ -24,7 +24,7 @@ ABI_SYMBOLS = [
     "mi355dr_update_rows", "mi355dr_update_rows_device", "mi355dr_remove_rows", "mi355dr_live_rows", "mi355dr_compact",
     "mi355dr_search", "mi355dr_search_device", "mi355dr_search_device_async", "mi355dr_search_wait",
     "mi355dr_search_subset", "mi355dr_search_subset_device", "mi355dr_score_subset", "mi355dr_view_create", "mi355dr_add_multivec", "mi355dr_size_multivec",
-    "mi355dr_search_maxsim", "mi355dr_search_maxsim_device", "mi355dr_maxsim_subset", "mi355dr_maxsim_subset_ex", "mi355dr_add_multivec_device", "mi355dr_gqr_refine", "mi355dr_gqr_refine_maxsim",
+    "mi355dr_search_maxsim", "mi355dr_search_maxsim_device", "mi355dr_search_maxsim_subset", "mi355dr_search_maxsim_subset_device", "mi355dr_maxsim_subset", "mi355dr_maxsim_subset_ex", "mi355dr_add_multivec_device", "mi355dr_gqr_refine", "mi355dr_gqr_refine_maxsim",
     "mi355dr_set_multivec", "mi355dr_set_multivec_device", "mi355dr_live_multivec",
     "mi355dr_gqr_refine_scores", "mi355dr_merge_topk_device", "mi355dr_pack_topk_device",
     "mi355dr_merge_topk_packed_device", "mi355dr_comm_unique_id", "mi355dr_comm_init", "mi355dr_comm_world", "mi355dr_comm_count", "mi355dr_comm_init_custom",
@@ -142,6 +142,10 @@ def load() -> ctypes.CDLL:
     L.mi355dr_search_maxsim.argtypes = [vp, f32p, i32p, c_int, c_int, f32p, i64p]
     L.mi355dr_search_maxsim_device.restype = c_int
     L.mi355dr_search_maxsim_device.argtypes = [vp, vp, i32p, c_int, c_int, vp, vp, vp]
+    L.mi355dr_search_maxsim_subset.restype = c_int
+    L.mi355dr_search_maxsim_subset.argtypes = [vp, f32p, i32p, c_int, c_int, i64p, i64, f32p, i64p]
+    L.mi355dr_search_maxsim_subset_device.restype = c_int
+    L.mi355dr_search_maxsim_subset_device.argtypes = [vp, vp, i32p, c_int, c_int, i64p, i64, vp, vp, vp]
     L.mi355dr_maxsim_subset.restype = c_int
     L.mi355dr_maxsim_subset.argtypes = [vp, f32p, i32p, c_int, i64p, c_int, f32p]
     L.mi355dr_maxsim_subset_ex.restype = c_int

@@ -191,6 +191,11 @@ struct mi355dr_index {
     int maxsim_wg_bps = 4;  // k_maxsim16_wg: 32-token blocks per ring stage (2: 7 stages of 16 KiB, 4: 4 stages of 32 KiB); option, A/B
     int maxsim_pass_groups = 4;  // groups of <= 4 queries one pass of the MaxSim screen serves (1 .. 4; option "maxsim_pass_groups", A/B and tests)
     int maxsim_screen = 1; // 1: bf16 MFMA screen + exact re-score of the candidates, 0: exact kernel over every doc
+    // mi355dr_search_maxsim_subset: the list form of the screen (1), the exact list path (0), or (-1, default) the screen from
+    // maxsim_subset_screen_min listed documents with vectors on (512: the screen beat the exact list path at every measured list
+    // size, the smallest was 1 000 documents -- DESIGN.md 4.8d, profiles/maxsim_subset_time_1m.txt)
+    int maxsim_subset_screen = -1;
+    int64_t maxsim_subset_screen_min = 512;
     int64_t row_offset = 0;
     int round_a = 0;      // k_prune: rows re-scored before the cut is known (0 = max(32, 2k)); tuning option "round_a"
     int screen_rq = 1;      // query blocks above 128, int8 shadow of <= 768 B per row: k_screen_rq (query operand in registers) instead of k_screen256c (option "screen_rq")
@@ -254,6 +259,9 @@ struct mi355dr_index {
     int64_t s_subset_searches = 0;       // mi355dr_search_subset / _device calls ...
     int64_t s_subset_rows_scored = 0;    // ... the (query, listed row) pairs their gathered scans scored ...
     int64_t s_subset_rerun_queries = 0;  // ... and the queries whose list overflowed in a chunk that was then re-run in list-sized pieces
+    // mi355dr_search_maxsim_subset: calls, listed documents with vectors, queries served by the list screen / by the exact list
+    // path (fallbacks included), queries whose candidate list overflowed
+    int64_t s_mss_searches = 0, s_mss_docs = 0, s_mss_screened = 0, s_mss_exact = 0, s_mss_fallbacks = 0;
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
     mi355::EventPairs ev_pool, ev_pending;

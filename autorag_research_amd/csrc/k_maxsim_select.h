@@ -2,6 +2,7 @@
 //   k_topk_segments    segment-wise exact top-k by (distance, doc): full scans, and the path of k > kMsFastK
 //   k_ms_candidates    candidates of one query (k > kMsFastK)
 //   k_ms_select, k_ms_candidates_y, k_ms_tighten, k_ms_final    the fast path: every query of a pass at once (grid.y)
+//   k_ms_membership    a listed subset as the table the kernels above take in place of blk_off
 //   k_ms_write_out, k_ms_fill_empty    results to the caller's layout
 #pragma once
 #include "maxsim_common.h"
@@ -255,6 +256,22 @@ __global__ __launch_bounds__(256) void k_ms_final(const float* cand_dist, const 
         out_d[(int64_t)y * k + i] = ok ? key_to_f32(SK[i]) : __uint_as_float(0x7FC00000u);
         out_r[(int64_t)y * k + i] = !ok ? -1 : doc_map ? doc_map[SR[i]] : (int64_t)SR[i] + row_offset;
     }
+}
+
+// The membership table of a listed subset (mi355dr_search_maxsim_subset): T[d] = listed documents below d, d = 0 .. n_docs, by a
+// lower bound in the sorted, unique list of documents with vectors.  T[d + 1] > T[d] holds exactly for the listed documents:
+// k_topk_segments, k_ms_select and the two candidate kernels read T where they read blk_off ("this document has vectors"), and
+// never look at the positions of the dense screen distances that the list screen did not write.
+__global__ void k_ms_membership(const int32_t* __restrict__ list, int64_t n_list, int64_t n_docs, int64_t* __restrict__ T) {
+    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d > n_docs) return;
+    int64_t lo = 0, hi = n_list;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)list[mid] < d) lo = mid + 1;
+        else hi = mid;
+    }
+    T[d] = lo;
 }
 
 __global__ void k_ms_write_out(const uint64_t* key, const int32_t* row, int k, int64_t row_offset,

@@ -43,6 +43,10 @@ struct Ms16Args {
     int q_col0[kMsPassQueries];  // (k_maxsim16_d128 serves up to FOUR groups of <= 4 queries per launch: rows 4 g .. 4 g + 3)
     int q_len[kMsPassQueries];
     int aligned;             // k_maxsim16_wg: query r of the launch is exactly column block r (q_col0[r] = 32 r, q_len[r] <= 32)
+    // the LIST forms (mi355dr_search_maxsim_subset): work item i is document list[i] of a sorted, unique list of documents with
+    // vectors; its screen distance still goes to the DOCUMENT's position dist[qi * n_docs + doc]
+    const int32_t* list;
+    int64_t n_list;
 };
 
 // the granule-packed bf16 copy (k_maxsim_wg8.h): documents rounded up to whole 8-token granules, the stream cut into 32-token blocks
@@ -64,5 +68,7 @@ int ms16_d128_launch(mi355dr_index* idx, hipStream_t s, int ncb, int64_t n_docs,
 bool ms16_takes_wg(const mi355dr_index* idx, int ncb, int64_t n_docs, int64_t n_blocks);
 // ... dims > 128: the generic form (k_maxsim16)
 int ms16_generic_launch(mi355dr_index* idx, hipStream_t s, unsigned grid, size_t lds16, const Ms16Args& sa);
+// the LIST forms of the two one-wave-per-document screens over sa.list (grid sized by sa.n_list; no packed copy, no workgroup form)
+int ms16_list_launch(mi355dr_index* idx, hipStream_t s, int ncb, size_t lds16, const Ms16Args& sa);
 
 }  // namespace mi355

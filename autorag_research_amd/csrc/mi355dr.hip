@@ -1720,6 +1720,8 @@ const Option kOptions[] = {
     {"maxsim_pack8", &Index::maxsim_pack8, -1, 1},  // -1: when it pays
     {"maxsim_wg_bps", &Index::maxsim_wg_bps, 2, 4, nullptr, 2, 4},  // 2 or 4
     {"maxsim_pass_groups", &Index::maxsim_pass_groups, 1, 4},
+    {"maxsim_subset_screen", &Index::maxsim_subset_screen, -1, 1},  // -1: from maxsim_subset_screen_min listed documents on
+    {"maxsim_subset_screen_min", &Index::maxsim_subset_screen_min, 0},
     {"row_offset", &Index::row_offset},
     {"profile", {&Index::profile, kSwitch}},
     // (an explicit first chunk means the emit-all ladder: no starter)
@@ -1785,6 +1787,11 @@ const Stat kStats[] = {
     {"subset_searches", &Index::s_subset_searches, true},
     {"subset_rows_scored", &Index::s_subset_rows_scored, true},
     {"subset_rerun_queries", &Index::s_subset_rerun_queries, true},
+    {"maxsim_subset_searches", &Index::s_mss_searches, true},
+    {"maxsim_subset_docs", &Index::s_mss_docs, true},
+    {"maxsim_subset_screened", &Index::s_mss_screened, true},
+    {"maxsim_subset_exact", &Index::s_mss_exact, true},
+    {"maxsim_subset_fallbacks", &Index::s_mss_fallbacks, true},
     {"compactions", &Index::s_compactions, true},
     {"compact_moved_rows", &Index::s_compact_moved_rows, true},
     {"view", nullptr, false, [](const Index* x) -> int64_t { return x->is_view ? 1 : 0; }},

@@ -30,6 +30,7 @@
 #include <chrono>
 
 #include "maxsim_common.h"
+#include "subset_ids.h"
 
 #include "k_maxsim_build.h"
 #include "k_maxsim_exact.h"
@@ -87,6 +88,10 @@ struct MultiVecStore {
     DevBuf<uint32_t> sel[2];       // fast path: per-segment k best screen keys, [kMsPassQueries, ceil(cap_docs/1024) * 64]
     DevBuf<uint64_t> pk[2];        // segment-wise top-k partials (ms_topk)
     DevBuf<int32_t> pr[2];
+    // mi355dr_search_maxsim_subset, the call in progress: the listed documents with vectors (local, ascending, unique) and the
+    // membership table T[0 .. n_docs], T[d] = listed documents below d (k_ms_membership)
+    DevBuf<int32_t> sub_list;
+    DevBuf<int64_t> sub_memb;
 };
 
 bool multivec_view(const mi355dr_index* idx, MultiVecView* out) {
@@ -548,8 +553,19 @@ struct MsSearch {
     uint16_t* qf16;
     float* hd;
     int64_t* hr;
-    MsArgs a0;  // k_maxsim over every doc of the store, query image at m->qtok.p: the launches below start from it
+    MsArgs a0;  // k_maxsim over every doc of the store (a subset search: over its list), query image at m->qtok.p: the launches below start from it
+    // ---- a search within a listed subset (mi355dr_search_maxsim_subset; nullptr: every document).  The "full scan" of such a
+    // search walks the list, its screen is the list form, and the selection kernels read `has_vec` where they read blk_off.
+    const int32_t* list;     // DEVICE [n_list] documents with vectors: local, ascending, unique
+    int64_t n_list;
+    bool list_screen;        // option maxsim_subset_screen, resolved for this list
+    int64_t scan_n;          // items of a full scan: n_list, or n_docs
+    unsigned grid_scan;
+    const int64_t* has_vec;  // [n_docs + 1] table with t[d + 1] > t[d] for the documents a dense pass may look at: blk_off, or the membership table
 };
+
+// (the stats and the profile of mi355dr_search_maxsim do not move for a subset search)
+inline bool ms_prof(const MsSearch& c) { return c.idx->profile && !c.list; }
 
 // one group = up to 4 queries whose token counts fit `cols` columns (packed tightly: a query may start anywhere in a column block)
 struct MsGroup {
@@ -671,6 +687,10 @@ int ms_search_prepare(MsSearch& c) {
     for (auto& b : m->pk) HIPCHECK(idx, b.grow((size_t)nseg0 * kKMax * sizeof(uint64_t)));
     for (auto& b : m->pr) HIPCHECK(idx, b.grow((size_t)nseg0 * kKMax * sizeof(int32_t)));
     c.grid_all = (unsigned)((m->n_docs + 4 * kMsDocsPerWave - 1) / (4 * kMsDocsPerWave));
+    c.scan_n = c.list ? c.n_list : m->n_docs;
+    // (a list launch of k_maxsim strides over its items: two workgroups per CU)
+    c.grid_scan = c.list ? (unsigned)std::min<int64_t>((c.n_list + 3) / 4, 2 * kMsListGrid) : c.grid_all;
+    c.has_vec = c.list ? m->sub_memb.p : m->blk_off.p;
     c.n_cand_max = std::min<int64_t>(kMsCandCap, m->n_docs);
     // bf16 round-to-nearest: unit roundoff 2^-8 per operand -> 2^-7 + 2^-16 per product
     c.eps = std::ldexp(1.0, -7) + std::ldexp(1.0, -15) + 3.0 * idx->dim * std::ldexp(1.0, -24);
@@ -687,7 +707,8 @@ int ms_search_prepare(MsSearch& c) {
     c.a0.qtok = m->qtok.p;
     c.a0.dist = m->dist.p;
     c.a0.n_docs = m->n_docs;
-    c.a0.n_items = m->n_docs;
+    c.a0.doc_list = c.list;
+    c.a0.n_items = c.scan_n;
     c.a0.dpad = dp;
     return MI355DR_OK;
 }
@@ -700,7 +721,7 @@ int ms_topk(const MsSearch& c, const float* dist, int64_t n_in, const int32_t* r
     while (true) {
         const int64_t nseg = (n_in + c.seg - 1) / c.seg;
         hipLaunchKernelGGL(k_topk_segments, dim3((unsigned)nseg), dim3(256), (size_t)kSegSort * 12, c.s,
-                           first_stage ? dist : nullptr, m->blk_off.p, first_stage ? nullptr : m->pk[cur ^ 1].p,
+                           first_stage ? dist : nullptr, row_map ? m->blk_off.p : c.has_vec, first_stage ? nullptr : m->pk[cur ^ 1].p,
                            first_stage ? nullptr : m->pr[cur ^ 1].p, n_in, c.k, c.seg, m->pk[cur].p, m->pr[cur].p,
                            first_stage ? row_map : nullptr, first_stage ? n_in_dev : nullptr);
         HIPCHECK(c.idx, hipGetLastError());
@@ -729,19 +750,21 @@ int ms_emit_result(const MsSearch& c, int cur, int b) {
     return MI355DR_OK;
 }
 
-// exact kernel over EVERY doc for one query whose image sits at column c0 of m->qtok.p -> m->dist.p row 0 -> top-k -> outputs
+// exact kernel over EVERY doc (a subset search: every listed doc) for one query whose image sits at column c0 of m->qtok.p
+// -> m->dist.p row 0 -> top-k -> outputs
 int ms_full_scan_query(const MsSearch& c, int c0, int len, int b) {
     MsArgs f = c.a0;
     f.qtok = c.m->qtok.p + (int64_t)c0 * c.m->dpad;
     f.nq_launch = 1;
     f.q_col0[0] = 0;
     f.q_len[0] = len;
-    hipLaunchKernelGGL(k_maxsim, dim3(c.grid_all), dim3(kMsThreads), c.lds, c.s, f);
+    hipLaunchKernelGGL(k_maxsim, dim3(c.grid_scan), dim3(kMsThreads), c.lds, c.s, f);
     HIPCHECK(c.idx, hipGetLastError());
     int cur = 0;
-    CHECK(ms_topk(c, c.m->dist.p, c.m->n_docs, nullptr, nullptr, &cur));
+    CHECK(ms_topk(c, c.m->dist.p, c.scan_n, c.list, nullptr, &cur));
     CHECK(ms_emit_result(c, cur, b));
     HIPCHECK(c.idx, hipStreamSynchronize(c.s));
+    if (c.list) c.idx->s_mss_exact++;
     return MI355DR_OK;
 }
 
@@ -764,12 +787,12 @@ int ms_run_long_query(const MsSearch& c, int b) {
         f.q_col0[0] = 0;
         f.q_len[0] = tl;
         f.dist_in = t0 > 0 ? m->dist.p : nullptr;
-        hipLaunchKernelGGL(k_maxsim, dim3(c.grid_all), dim3(kMsThreads), c.lds, c.s, f);
+        hipLaunchKernelGGL(k_maxsim, dim3(c.grid_scan), dim3(kMsThreads), c.lds, c.s, f);
         HIPCHECK(idx, hipGetLastError());
     }
-    idx->s_ms_fallbacks++;
+    (c.list ? idx->s_mss_exact : idx->s_ms_fallbacks)++;
     int cur = 0;
-    CHECK(ms_topk(c, m->dist.p, m->n_docs, nullptr, nullptr, &cur));
+    CHECK(ms_topk(c, m->dist.p, c.scan_n, c.list, nullptr, &cur));
     CHECK(ms_emit_result(c, cur, b));
     HIPCHECK(idx, hipStreamSynchronize(c.s));
     return MI355DR_OK;
@@ -789,7 +812,7 @@ MsPass ms_plan_pass(const MsSearch& c, int b) {
     gs[0] = ms_pack_group(c, b, 0, 0);
     int n_acc = 1, bn = gs[0].b_end;
     p.total_col = gs[0].col;
-    p.screen = idx->maxsim_screen && m->finite && gs[0].finite && c.lds16 <= 160 * 1024;
+    p.screen = (c.list ? c.list_screen : idx->maxsim_screen != 0) && m->finite && gs[0].finite && c.lds16 <= 160 * 1024;
     if (p.screen && m->nkk == 8 && c.k <= kMsFastK) {
         // The NEXT groups ride the same pass over the token stream (dims <= 128, the single-launch selection path): their
         // columns packed behind the previous group's
@@ -822,12 +845,12 @@ MsPass ms_plan_pass(const MsSearch& c, int b) {
             p.two_e[p.n] = gs[g].two_e[qi];
             ++p.n;
         }
-    if (p.n > 0 && idx->profile)
+    if (p.n > 0 && ms_prof(c))
         idx->s_ms_pack_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_pack0).count();
     return p;
 }
 
-// ---- no screen: the exact kernel over every doc for the whole first group (one launch, <= 4 queries), then a top-k per query
+// ---- no screen: the exact kernel over every doc (a subset search: over the list) for the whole first group (one launch, <= 4 queries), then a top-k per query
 int ms_run_exact_group(const MsSearch& c, const MsPass& p) {
     MultiVecStore* m = c.m;
     MsArgs a = c.a0;
@@ -836,14 +859,15 @@ int ms_run_exact_group(const MsSearch& c, const MsPass& p) {
         a.q_col0[qi] = p.g0.q_col0[qi];
         a.q_len[qi] = p.g0.q_len[qi];
     }
-    hipLaunchKernelGGL(k_maxsim, dim3(c.grid_all), dim3(kMsThreads), c.lds, c.s, a);
+    hipLaunchKernelGGL(k_maxsim, dim3(c.grid_scan), dim3(kMsThreads), c.lds, c.s, a);
     HIPCHECK(c.idx, hipGetLastError());
     for (int qi = 0; qi < p.g0.nql; ++qi) {
         if (p.g0.q_len[qi] == 0) continue;
         int cur = 0;
-        CHECK(ms_topk(c, m->dist.p + (int64_t)qi * m->n_docs, m->n_docs, nullptr, nullptr, &cur));
+        CHECK(ms_topk(c, m->dist.p + (int64_t)qi * c.scan_n, c.scan_n, c.list, nullptr, &cur));
         CHECK(ms_emit_result(c, cur, p.first + qi));
         HIPCHECK(c.idx, hipStreamSynchronize(c.s));
+        if (c.list) c.idx->s_mss_exact++;
     }
     return MI355DR_OK;
 }
@@ -863,6 +887,8 @@ int ms_launch_screen(const MsSearch& c, const MsPass& p) {
     sa.nkk = nkk;
     sa.nq_launch = p.n;
     sa.aligned = idx->maxsim_aligned ? 1 : 0;
+    sa.list = c.list;
+    sa.n_list = c.n_list;
     for (int r = 0; r < p.n; ++r) {
         sa.q_col0[r] = p.col0[r];
         sa.q_len[r] = p.len[r];
@@ -871,12 +897,14 @@ int ms_launch_screen(const MsSearch& c, const MsPass& p) {
     const int ncb_launch = (p.total_col + 31) / 32;
     HIPCHECK(idx, hipMemcpyAsync(m->qfrag.p, c.qf16, (size_t)std::max(ncb_launch, 4) * nkk * 64 * 8 * sizeof(uint16_t),
                                  hipMemcpyHostToDevice, s));
-    if (idx->profile) {
+    if (ms_prof(c)) {
         for (auto& e : idx->ms_ev)
             HIPCHECK(idx, e.create());
         HIPCHECK(idx, hipEventRecord(idx->ms_ev[0], s));
     }
-    if (nkk == 8) {  // dims <= 128: the compile-time-unrolled forms, only as many column blocks as the pass has
+    if (c.list) {  // the listed documents where they lie: one wave per document, the padded copy
+        CHECK(ms16_list_launch(idx, s, ncb_launch, c.lds16, sa));
+    } else if (nkk == 8) {  // dims <= 128: the compile-time-unrolled forms, only as many column blocks as the pass has
         Ms16Pack pk{};
         bool packed = false;
         // the granule-packed copy serves the workgroup form's aligned passes (k_maxsim_wg8.h) and the passes of up to four column
@@ -897,8 +925,8 @@ int ms_launch_screen(const MsSearch& c, const MsPass& p) {
     } else {
         CHECK(ms16_generic_launch(idx, s, c.grid_all, c.lds16, sa));
     }
-    idx->s_ms_screen_cols += 32 * (int64_t)ncb_launch;
-    if (idx->profile) HIPCHECK(idx, hipEventRecord(idx->ms_ev[1], s));
+    if (!c.list) idx->s_ms_screen_cols += 32 * (int64_t)ncb_launch;
+    if (ms_prof(c)) HIPCHECK(idx, hipEventRecord(idx->ms_ev[1], s));
     return MI355DR_OK;
 }
 
@@ -924,7 +952,7 @@ int ms_select_kth(const MsSearch& c, const MsPass& p, int64_t sel_stride, int* c
     while (true) {
         const int64_t nseg = (n_in + kMsSelSeg - 1) / kMsSelSeg;
         hipLaunchKernelGGL(k_ms_select, dim3((unsigned)nseg, p.n), dim3(kWave), 0, c.s,
-                           first_stage ? m->dist16.p : nullptr, m->blk_off.p, first_stage ? nullptr : m->sel[cur ^ 1].p, n_in,
+                           first_stage ? m->dist16.p : nullptr, c.has_vec, first_stage ? nullptr : m->sel[cur ^ 1].p, n_in,
                            first_stage ? m->n_docs : sel_stride, c.k, m->sel[cur].p, sel_stride);
         HIPCHECK(c.idx, hipGetLastError());
         first_stage = false;
@@ -963,10 +991,10 @@ int ms_fast_path(const MsSearch& c, const MsPass& p, bool* handled) {
     HIPCHECK(idx, hipMemsetAsync(m->cand_ctl.p, 0, 3 * 2 * kPQ * sizeof(int), s));
     hipLaunchKernelGGL(k_ms_candidates_y, dim3((unsigned)((m->n_docs + 256 * kMsCandPerThread - 1) / (256 * kMsCandPerThread)), p.n),
                        dim3(256), 0, s, m->dist16.p,
-                       m->n_docs, m->blk_off.p, m->n_docs, m->sel[cur].p, sel_stride, k, m->two_e_dev.p, list_c, kMsCandCap, ctl_c,
+                       m->n_docs, c.has_vec, m->n_docs, m->sel[cur].p, sel_stride, k, m->two_e_dev.p, list_c, kMsCandCap, ctl_c,
                        tighten ? m->cand_sd.p : nullptr, tighten ? list_a : nullptr, tighten ? ctl_a : nullptr);
     HIPCHECK(idx, hipGetLastError());
-    MsArgs a = c.a0;
+    MsArgs a = c.a0;  // (the candidate lists replace a subset search's own list; blk_off stays the store's)
     a.dist = m->cand_dist.p;
     a.n_items = c.n_cand_max;
     a.list_stride = kMsCandCap;
@@ -988,7 +1016,7 @@ int ms_fast_path(const MsSearch& c, const MsPass& p, bool* handled) {
     const int64_t want_a = k + 8, want_f = tighten ? 256 : c.n_cand_max;  // documents a launch should cover in ONE round
     const dim3 grid_a((unsigned)std::min<int64_t>({coop ? want_a : (want_a + 3) / 4, c.n_cand_max, (int64_t)kMsListGrid}), p.n);
     const dim3 list_grid((unsigned)std::min<int64_t>({coop ? want_f : (want_f + 3) / 4, c.n_cand_max, (int64_t)kMsListGrid}), p.n);
-    if (idx->profile) HIPCHECK(idx, hipEventRecord(idx->ms_ev[2], s));
+    if (ms_prof(c)) HIPCHECK(idx, hipEventRecord(idx->ms_ev[2], s));
     const int32_t* list_f = list_c;
     const int* ctl_f = ctl_c;
     if (tighten) {
@@ -1006,7 +1034,7 @@ int ms_fast_path(const MsSearch& c, const MsPass& p, bool* handled) {
     a.n_items_dev = ctl_f;
     hipLaunchKernelGGL(k_maxsim, list_grid, dim3(kMsThreads), lds_list + kMsRedBytes, s, a);
     HIPCHECK(idx, hipGetLastError());
-    if (idx->profile) HIPCHECK(idx, hipEventRecord(idx->ms_ev[3], s));
+    if (ms_prof(c)) HIPCHECK(idx, hipEventRecord(idx->ms_ev[3], s));
     hipLaunchKernelGGL(k_ms_final, dim3(1, p.n), dim3(256), (size_t)kMsCandCap * 12, s, m->cand_dist.p, list_f, ctl_f,
                        kMsCandCap, k, idx->row_offset, idx->view_doc_map.p, m->out_d.p, m->out_r.p);
     HIPCHECK(idx, hipGetLastError());
@@ -1016,12 +1044,12 @@ int ms_fast_path(const MsSearch& c, const MsPass& p, bool* handled) {
         HIPCHECK(idx, hipMemcpyAsync(c.hr, m->out_r.p, (size_t)p.n * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     }
     HIPCHECK(idx, hipStreamSynchronize(s));
-    if (idx->profile) ms_read_profile(idx, true);
+    if (ms_prof(c)) ms_read_profile(idx, true);
     for (int r = 0; r < p.n; ++r) {
         if (m->cand_ctl_host.p[2 * r + 1] != 0) continue;  // list overflow: exact full scan (the caller's)
         handled[r] = true;
-        idx->s_ms_screened++;
-        idx->s_ms_candidates += m->cand_ctl_host.p[2 * r];
+        (c.list ? idx->s_mss_screened : idx->s_ms_screened)++;
+        if (!c.list) idx->s_ms_candidates += m->cand_ctl_host.p[2 * r];
         float* od = c.out_dist + (int64_t)p.b[r] * k;
         int64_t* orow = c.out_rows + (int64_t)p.b[r] * k;
         if (c.out_dev) {
@@ -1046,7 +1074,7 @@ int ms_slow_query(const MsSearch& c, const MsPass& p, int r) {
     HIPCHECK(idx, hipMemsetAsync(m->cand_ctl.p, 0, 2 * sizeof(int), s));
     float te = (float)p.two_e[r];
     if ((double)te < p.two_e[r]) te = std::nextafter(te, INFINITY);
-    hipLaunchKernelGGL(k_ms_candidates, dim3((unsigned)((m->n_docs + 255) / 256)), dim3(256), 0, s, dist16, m->blk_off.p,
+    hipLaunchKernelGGL(k_ms_candidates, dim3((unsigned)((m->n_docs + 255) / 256)), dim3(256), 0, s, dist16, c.has_vec,
                        m->n_docs, m->pk[cur].p, c.k, te, m->cand_list.p, kMsCandCap, m->cand_ctl.p);
     HIPCHECK(idx, hipGetLastError());
     MsArgs a = c.a0;
@@ -1066,19 +1094,21 @@ int ms_slow_query(const MsSearch& c, const MsPass& p, int r) {
     HIPCHECK(idx, hipMemcpyAsync(m->cand_ctl_host.p, m->cand_ctl.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipStreamSynchronize(s));
     if (m->cand_ctl_host.p[1] == 0) {
-        idx->s_ms_screened++;
-        idx->s_ms_candidates += m->cand_ctl_host.p[0];
+        (c.list ? idx->s_mss_screened : idx->s_ms_screened)++;
+        if (!c.list) idx->s_ms_candidates += m->cand_ctl_host.p[0];
     } else {
-        idx->s_ms_fallbacks++;  // more candidates than the list holds: this query takes the exact full scan
+        (c.list ? idx->s_mss_fallbacks : idx->s_ms_fallbacks)++;  // more candidates than the list holds: this query takes the exact full scan
         CHECK(ms_full_scan_query(c, p.col0[r], p.len[r], p.b[r]));
     }
     return MI355DR_OK;
 }
 
 // qtok: HOST [sum_nq, dim]; outputs on the host (out_dev = false) or in device memory of the index's GPU (out_dev = true:
-// written by kernels / device copies on the index's stream, complete on return)
+// written by kernels / device copies on the index's stream, complete on return).
+// sub (mi355dr_search_maxsim_subset; nullptr: every document): the listed documents with vectors -- local, ascending, unique --
+// on the HOST; the store's sub_list / sub_memb buffers already have room for them.
 int search_maxsim_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, int k, float* out_dist,
-                       int64_t* out_rows, bool out_dev) {
+                       int64_t* out_rows, bool out_dev, const std::vector<int32_t>* sub = nullptr) {
     if (k > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, "k exceeds 1024");
     if (out_dev) {
         if (B > 0) {
@@ -1095,12 +1125,25 @@ int search_maxsim_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_o
         }
     }
     MultiVecStore* m = idx->mv;
-    if (B == 0 || !m || m->n_docs == 0) return MI355DR_OK;
+    if (B == 0 || !m || m->n_docs == 0 || (sub && sub->empty())) return MI355DR_OK;
     for (int b = 0; b < B; ++b)
         if (q_offsets[b + 1] - q_offsets[b] < 0) return fail(idx, MI355DR_E_INVALID, "q_offsets must be non-decreasing");
     HIPCHECK(idx, hipSetDevice(idx->device));
     MsSearch c{idx, m, idx->stream, qtok, q_offsets, B, k, out_dist, out_rows, out_dev};
+    if (sub) {
+        c.list = m->sub_list.p;
+        c.n_list = (int64_t)sub->size();
+        c.list_screen = idx->maxsim_subset_screen > 0 || (idx->maxsim_subset_screen < 0 && c.n_list >= idx->maxsim_subset_screen_min);
+    }
     CHECK(ms_search_prepare(c));
+    if (sub) {
+        HIPCHECK(idx, hipMemcpyAsync(m->sub_list.p, sub->data(), sub->size() * sizeof(int32_t), hipMemcpyHostToDevice, c.s));
+        if (c.list_screen && m->finite && c.lds16 <= 160 * 1024) {  // (what ms_plan_pass asks of a pass that screens)
+            hipLaunchKernelGGL(k_ms_membership, dim3((unsigned)((m->n_docs + 256) / 256)), dim3(256), 0, c.s, m->sub_list.p, c.n_list,
+                               m->n_docs, m->sub_memb.p);
+            HIPCHECK(idx, hipGetLastError());
+        }
+    }
     int b = 0;
     while (b < B) {
         HIPCHECK(idx, hipStreamSynchronize(c.s));  // the staging buffers are free again
@@ -1122,14 +1165,14 @@ int search_maxsim_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_o
         bool handled[kPQ] = {};
         if (k <= kMsFastK) {
             CHECK(ms_fast_path(c, p, handled));
-        } else if (idx->profile) {  // (the screen launch of a slow-path pass is timed too)
+        } else if (ms_prof(c)) {  // (the screen launch of a slow-path pass is timed too)
             HIPCHECK(idx, hipStreamSynchronize(c.s));
             ms_read_profile(idx, false);
         }
         for (int r = 0; r < p.n; ++r) {
             if (handled[r]) continue;
             if (k <= kMsFastK) {  // the fast path gave this query up (candidate list overflow): exact full scan
-                idx->s_ms_fallbacks++;
+                (c.list ? idx->s_mss_fallbacks : idx->s_ms_fallbacks)++;
                 CHECK(ms_full_scan_query(c, p.col0[r], p.len[r], p.b[r]));
             } else {
                 CHECK(ms_slow_query(c, p, r));
@@ -1137,6 +1180,68 @@ int search_maxsim_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_o
         }
     }
     HIPCHECK(idx, hipStreamSynchronize(c.s));  // (device outputs: the last copies)
+    return MI355DR_OK;
+}
+
+// The query vectors of a _device entry point come down once: the query side of a pass is tiny (8 queries x 32 vectors x 128 dims
+// = 128 KiB) and its bound is evaluated in double on the host; the k results of every query never leave HBM.  `stream` (may be
+// null) produced qtok_dev.  qh / off: the vectors and their offsets from 0.
+int ms_fetch_queries(mi355dr_index* idx, const float* qtok_dev, const int32_t* q_offsets, int B, void* stream, std::vector<float>& qh,
+                     std::vector<int32_t>& off) {
+    for (int b = 0; b < B; ++b)
+        if (q_offsets[b + 1] < q_offsets[b]) return fail(idx, MI355DR_E_INVALID, "q_offsets must be non-decreasing");
+    const int64_t n_tok = q_offsets[B] - q_offsets[0];
+    if (n_tok > 0 && !qtok_dev) return fail(idx, MI355DR_E_INVALID, "null query vectors");
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    if (stream) HIPCHECK(idx, hipStreamSynchronize((hipStream_t)stream));
+    qh.resize((size_t)std::max<int64_t>(n_tok, 1) * idx->dim);
+    if (n_tok > 0)
+        HIPCHECK(idx, hipMemcpy(qh.data(), qtok_dev + (int64_t)q_offsets[0] * idx->dim, (size_t)n_tok * idx->dim * sizeof(float),
+                                hipMemcpyDeviceToHost));
+    off.resize((size_t)B + 1);
+    for (int b = 0; b <= B; ++b) off[b] = q_offsets[b] - q_offsets[0];
+    return MI355DR_OK;
+}
+
+// ---- MaxSim top-k within a listed subset of documents: search_maxsim_impl over the list.
+// out_dev: qtok and the outputs are device memory (the rule of mi355dr_search_maxsim_device); doc_ids and q_offsets are host.
+int search_maxsim_subset_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, int k, const int64_t* doc_ids,
+                              int64_t m_ids, float* out_dist, int64_t* out_rows, bool out_dev, void* stream) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "search_maxsim_subset", /*ask_parent=*/true);
+    if (B < 0 || k <= 0 || !q_offsets || m_ids < 0 || (m_ids > 0 && !doc_ids) || (B > 0 && (!out_dist || !out_rows)))
+        return fail(idx, MI355DR_E_INVALID, "bad search_maxsim_subset arguments");
+    if (k > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, "k exceeds 1024");
+    for (int b = 0; b < B; ++b)
+        if (q_offsets[b + 1] < q_offsets[b]) return fail(idx, MI355DR_E_INVALID, "q_offsets must be non-decreasing");
+    MultiVecStore* m = idx->mv;
+    // the caller's global ids -> the listed documents with vectors: local, ascending, unique (subset_ids.h)
+    std::vector<int32_t> list;
+    if (B > 0 && m && m->n_docs > 0 && m_ids > 0) {
+        try {
+            subset_prepare_ids(doc_ids, m_ids, idx->row_offset, m->n_docs, list);
+        } catch (const std::bad_alloc&) {
+            return fail(idx, MI355DR_E_NOMEM, "search_maxsim_subset: out of host memory for the document list");
+        }
+        const std::vector<int64_t>& off = m->blk_off_host;
+        list.erase(std::remove_if(list.begin(), list.end(), [&](int32_t d) { return off[(size_t)d + 1] <= off[(size_t)d]; }), list.end());
+    }
+    if (!list.empty()) {  // room for the list and the table before anything is launched
+        HIPCHECK(idx, hipSetDevice(idx->device));
+        HIPCHECK(idx, m->sub_list.grow(list.size() * sizeof(int32_t)));
+        HIPCHECK(idx, m->sub_memb.grow((size_t)(m->cap_docs + 1) * sizeof(int64_t)));
+    }
+    std::vector<float> qh;
+    std::vector<int32_t> off;
+    if (out_dev && B > 0) {
+        CHECK(ms_fetch_queries(idx, qtok, q_offsets, B, stream, qh, off));
+        qtok = qh.data();
+        q_offsets = off.data();
+    }
+    CHECK(search_maxsim_impl(idx, qtok, q_offsets, B, k, out_dist, out_rows, out_dev, &list));
+    idx->s_mss_searches++;
+    idx->s_mss_docs += (int64_t)list.size();
     return MI355DR_OK;
 }
 
@@ -1256,21 +1361,21 @@ int mi355dr_search_maxsim_device(mi355dr_index* idx, const float* qtok_dev, cons
     if (B < 0 || k <= 0 || !q_offsets || (B > 0 && (!out_dist_dev || !out_rows_dev)))
         return fail(idx, MI355DR_E_INVALID, "bad maxsim arguments");
     if (B == 0) return MI355DR_OK;
-    for (int b = 0; b < B; ++b)
-        if (q_offsets[b + 1] < q_offsets[b]) return fail(idx, MI355DR_E_INVALID, "q_offsets must be non-decreasing");
-    const int64_t n_tok = q_offsets[B] - q_offsets[0];
-    if (n_tok > 0 && !qtok_dev) return fail(idx, MI355DR_E_INVALID, "null query vectors");
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    // The query side of a pass is tiny (8 queries x 32 vectors x 128 dims = 128 KiB) and its bound is evaluated in double on
-    // the host: the vectors come down once (ordered behind the caller's stream), the k results of every query never leave HBM.
-    if (stream) HIPCHECK(idx, hipStreamSynchronize((hipStream_t)stream));
-    std::vector<float> qh((size_t)std::max<int64_t>(n_tok, 1) * idx->dim);
-    if (n_tok > 0)
-        HIPCHECK(idx, hipMemcpy(qh.data(), qtok_dev + (int64_t)q_offsets[0] * idx->dim, (size_t)n_tok * idx->dim * sizeof(float),
-                                hipMemcpyDeviceToHost));
-    std::vector<int32_t> off(B + 1);
-    for (int b = 0; b <= B; ++b) off[b] = q_offsets[b] - q_offsets[0];
+    std::vector<float> qh;
+    std::vector<int32_t> off;
+    CHECK(ms_fetch_queries(idx, qtok_dev, q_offsets, B, stream, qh, off));
     return search_maxsim_impl(idx, qh.data(), off.data(), B, k, out_dist_dev, out_rows_dev, true);
+}
+
+int mi355dr_search_maxsim_subset(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, int k,
+                                 const int64_t* doc_ids, int64_t m, float* out_dist, int64_t* out_rows) {
+    return search_maxsim_subset_impl(idx, qtok, q_offsets, B, k, doc_ids, m, out_dist, out_rows, false, nullptr);
+}
+
+int mi355dr_search_maxsim_subset_device(mi355dr_index* idx, const float* qtok_dev, const int32_t* q_offsets, int B, int k,
+                                        const int64_t* doc_ids, int64_t m, float* out_dist_dev, int64_t* out_rows_dev,
+                                        void* stream) {
+    return search_maxsim_subset_impl(idx, qtok_dev, q_offsets, B, k, doc_ids, m, out_dist_dev, out_rows_dev, true, stream);
 }
 
 int mi355dr_maxsim_subset(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, const int64_t* doc_ids,

@@ -48,6 +48,8 @@ __device__ __forceinline__ void ms16_compute_piece(f32x16 (&acc)[4], const uint4
     }
 }
 
+// LIST: the wave's work items are positions of a.list (documents of a listed subset) instead of documents
+template <bool LIST>
 __global__ __launch_bounds__(kMsThreads, 2) void k_maxsim16(Ms16Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint4* qs = (uint4*)smem;
@@ -58,8 +60,9 @@ __global__ __launch_bounds__(kMsThreads, 2) void k_maxsim16(Ms16Args a) {
     for (int qi = 0; qi < a.nq_launch; ++qi) ncb = max(ncb, (a.q_col0[qi] + a.q_len[qi] + 31) / 32);
     const int npp = (a.nkk + 7) / 8;  // pieces of 8 fragments per block
     for (int dw = 0; dw < kMsDocsPerWave; ++dw) {
-        const int64_t doc = ((int64_t)dw * gridDim.x + blockIdx.x) * 4 + wave;
-        if (doc >= a.n_docs) break;
+        const int64_t item = ((int64_t)dw * gridDim.x + blockIdx.x) * 4 + wave;
+        if (item >= (LIST ? a.n_list : a.n_docs)) break;
+        const int64_t doc = LIST ? (int64_t)a.list[item] : item;
         const int64_t b0 = a.blk_off[doc], b1 = a.blk_off[doc + 1];
         float run[4];
 #pragma unroll
@@ -124,8 +127,13 @@ __global__ __launch_bounds__(kMsThreads, 2) void k_maxsim16(Ms16Args a) {
 // passages, and up to ~8 column blocks this form is bound by exactly those bytes), and since register quad j of the accumulator IS
 // granule j of the block (both wave halves), a boundary block's maximum is taken over the document's quads only.  The rows of
 // lanes that were not loaded multiply whatever the registers held: an MFMA's rows do not mix, and their quads are never looked at.
-template <int NCB, int NW, bool PK>
+// LIST (mi355dr_search_maxsim_subset): the same walk over the documents a.list names -- work item i is document list[i], the
+// index is wave-uniform like the document index it replaces (the list entry and the block range it leads to stay in SGPRs), the
+// rounds cover a.n_list items, and the pipeline across documents is unchanged.  Never together with PK: the packed copy's
+// boundary blocks belong to a document's neighbours in the STORE, and a list has gaps.
+template <int NCB, int NW, bool PK, bool LIST = false>
 __global__ __launch_bounds__(NW * 64, 2) void k_maxsim16_d128(Ms16Args a, Ms16Pack pk) {
+    static_assert(!(PK && LIST), "the list form walks the padded copy");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     uint4* qs = (uint4*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -143,13 +151,15 @@ __global__ __launch_bounds__(NW * 64, 2) void k_maxsim16_d128(Ms16Args a, Ms16Pa
     // The grid may be smaller than the store (option maxsim_persistent): the workgroups then walk the documents in rounds of 4
     // docs per wave and stage the query fragments once.  Measured (round 3, interleaved on one box): no gain on 1 M text docs,
     // 4 % slower on 100 k pages -- the default grid is one round.
-    for (int64_t round = 0; round * ((int64_t)gridDim.x * NW * kMsDocsPerWave) < a.n_docs; ++round) {
+    const int64_t n_items = LIST ? a.n_list : a.n_docs;
+    for (int64_t round = 0; round * ((int64_t)gridDim.x * NW * kMsDocsPerWave) < n_items; ++round) {
     int64_t dq[kMsDocsPerWave], db0[kMsDocsPerWave], dnb[kMsDocsPerWave];
     int dlo[kMsDocsPerWave], dhi[kMsDocsPerWave];  // (PK) granules of the first block in front of the document, of the last block that are its own
 #pragma unroll
     for (int dw = 0; dw < kMsDocsPerWave; ++dw) {
         dq[dw] = ((round * kMsDocsPerWave + dw) * (int64_t)gridDim.x + blockIdx.x) * NW + wave;
-        const bool live = dq[dw] < a.n_docs;
+        const bool live = dq[dw] < n_items;
+        if constexpr (LIST) dq[dw] = live ? (int64_t)a.list[dq[dw]] : 0;  // (from here on dq is the document, as in the other forms)
         dlo[dw] = 0;
         dhi[dw] = 4;
         if constexpr (PK) {
@@ -322,6 +332,17 @@ const std::array<Ms16Kernel, mi355::kMsPassBlocks> kMs16Kernels = ms16_table<fal
 constexpr int kMs16PkMaxNcb = 4;
 const std::array<Ms16Kernel, kMs16PkMaxNcb> kMs16PkKernels = ms16_table<true>(std::make_integer_sequence<int, kMs16PkMaxNcb>{});
 inline int ms16_waves(int ncb) { return ncb <= 8 ? 4 : 8; }
+// ... over a document list (mi355dr_search_maxsim_subset): every column-block count, the padded copy
+template <int NCB>
+constexpr Ms16Kernel ms16_list_kernel_of() {
+    if constexpr (NCB <= 8) return mi355::k_maxsim16_d128<NCB, 4, false, true>;
+    else return mi355::k_maxsim16_d128<NCB, 8, false, true>;
+}
+template <int... I>
+constexpr std::array<Ms16Kernel, sizeof...(I)> ms16_list_table(std::integer_sequence<int, I...>) {
+    return {ms16_list_kernel_of<I + 1>()...};
+}
+const std::array<Ms16Kernel, mi355::kMsPassBlocks> kMs16ListKernels = ms16_list_table(std::make_integer_sequence<int, mi355::kMsPassBlocks>{});
 
 // the workgroup-cooperative form (k_maxsim_wg.h) for 9 .. 16 column blocks
 typedef void (*Ms16WgKernel)(mi355::Ms16Args, int64_t);
@@ -344,14 +365,18 @@ const Ms16WgKernel kMs16Wg8Kernels[2] = {mi355::k_maxsim16_wg<8, true, 4, true>,
 }  // namespace
 
 int ms16_prepare(mi355dr_index* idx, size_t lds16) {
-    if (lds16 <= 160 * 1024)
-        HIPCHECK(idx, hipFuncSetAttribute((const void*)k_maxsim16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+    if (lds16 <= 160 * 1024) {
+        HIPCHECK(idx, hipFuncSetAttribute((const void*)k_maxsim16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+        HIPCHECK(idx, hipFuncSetAttribute((const void*)k_maxsim16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
+    }
     for (auto kfn : kMs16Wg8Kernels)
         HIPCHECK(idx, hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, mi355::mw_lds(4)));
     HIPCHECK(idx, hipFuncSetAttribute((const void*)mi355::k_maxsim16_wg8, hipFuncAttributeMaxDynamicSharedMemorySize, mi355::mw_lds(4)));
     for (int ncb = 1; ncb <= mi355::kMsPassBlocks; ++ncb)
-        if (ncb * 8192 > 64 * 1024)
+        if (ncb * 8192 > 64 * 1024) {
             HIPCHECK(idx, hipFuncSetAttribute((const void*)kMs16Kernels[ncb - 1], hipFuncAttributeMaxDynamicSharedMemorySize, ncb * 8192));
+            HIPCHECK(idx, hipFuncSetAttribute((const void*)kMs16ListKernels[ncb - 1], hipFuncAttributeMaxDynamicSharedMemorySize, ncb * 8192));
+        }
     for (int b = 0; b < 3; ++b)
         for (int e = 0; e < 2; ++e)
             for (auto kfn : kMs16WgKernels[b][e])
@@ -408,7 +433,21 @@ int ms16_d128_launch(mi355dr_index* idx, hipStream_t s, int ncb, int64_t n_docs,
 }
 
 int ms16_generic_launch(mi355dr_index* idx, hipStream_t s, unsigned grid, size_t lds16, const Ms16Args& sa) {
-    hipLaunchKernelGGL(k_maxsim16, dim3(grid), dim3(kMsThreads), lds16, s, sa);
+    hipLaunchKernelGGL(k_maxsim16<false>, dim3(grid), dim3(kMsThreads), lds16, s, sa);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+// one round: every wave walks kMsDocsPerWave entries of the list
+int ms16_list_launch(mi355dr_index* idx, hipStream_t s, int ncb, size_t lds16, const Ms16Args& sa) {
+    if (!sa.list || sa.n_list <= 0 || sa.n_list > sa.n_docs) return fail(idx, MI355DR_E_INTERNAL, "list screen without a list");
+    const bool d128 = sa.nkk == 8;
+    const int nw = d128 ? ms16_waves(ncb) : kMsThreads / 64;
+    const unsigned grid = (unsigned)((sa.n_list + (int64_t)nw * mi355::kMsDocsPerWave - 1) / ((int64_t)nw * mi355::kMsDocsPerWave));
+    if (d128)
+        hipLaunchKernelGGL(kMs16ListKernels[ncb - 1], dim3(grid), dim3(nw * 64), (size_t)ncb * 8 * 64 * sizeof(uint4), s, sa, mi355::Ms16Pack{});
+    else
+        hipLaunchKernelGGL(k_maxsim16<true>, dim3(grid), dim3(kMsThreads), lds16, s, sa);
     HIPCHECK(idx, hipGetLastError());
     return MI355DR_OK;
 }

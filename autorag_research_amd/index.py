@@ -378,6 +378,35 @@ class Mi355Index:
             ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
             ctypes.c_void_p(int(stream) if stream else None)))
 
+    # ---- MaxSim search within a listed subset of documents (include/mi355dr.h) ----
+    def search_maxsim_subset(self, qtok, q_offsets, k: int, doc_ids) -> tuple[np.ndarray, np.ndarray]:
+        """MaxSim top-k among the listed documents only: `search_maxsim` with `AND id = ANY(doc_ids)`.  doc_ids: global ids
+        as the searches return them, ONE list for all queries, in any order; ids outside the index (-1 padding included) and
+        documents without vectors are skipped, an id listed twice counts once.  Same fp32 distances, order (distance, then
+        document) and NaN / -1 tail as `search_maxsim`; equal to `view(doc_ids=...).search_maxsim(...)` without building the
+        view.  Returns (distance float32 [B,k], docs int64 [B,k])."""
+        qtok = f32c(qtok).reshape(-1, self.dim)
+        q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int32)
+        ids = self._row_ids(doc_ids)
+        B = q_offsets.shape[0] - 1
+        dist = np.empty((B, k), dtype=np.float32)
+        docs = np.empty((B, k), dtype=np.int64)
+        check(self._h, self._lib.mi355dr_search_maxsim_subset(
+            self._h, ptr(qtok, ctypes.c_float), ptr(q_offsets, ctypes.c_int32), B, int(k), ptr(ids, ctypes.c_int64),
+            ids.shape[0], ptr(dist, ctypes.c_float), ptr(docs, ctypes.c_int64)))
+        return dist, docs
+
+    def search_maxsim_subset_device(self, qtok_ptr: int, q_offsets, k: int, doc_ids, out_dist_ptr: int, out_rows_ptr: int,
+                                    stream: int | None = None) -> None:
+        """The same with the query vectors and the results in device memory (the layout of `search_maxsim_device`);
+        `q_offsets` and `doc_ids` stay on the host.  Complete on return."""
+        q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int32)
+        ids = self._row_ids(doc_ids)
+        check(self._h, self._lib.mi355dr_search_maxsim_subset_device(
+            self._h, ctypes.c_void_p(int(qtok_ptr)), ptr(q_offsets, ctypes.c_int32), q_offsets.shape[0] - 1, int(k),
+            ptr(ids, ctypes.c_int64), ids.shape[0], ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
+            ctypes.c_void_p(int(stream) if stream else None)))
+
     def maxsim_subset(self, qtok, q_offsets, doc_ids, clamp0: bool = False) -> np.ndarray:
         """Exact MaxSim distance of each query to its own list of docs: doc_ids [B, m] -> distances [B, m] (NaN = skipped).
         `clamp0`: every query vector contributes max(0, max_j <q_i, d_j>) (the ColBERT reranker's MaxSim)."""

@@ -720,14 +720,21 @@ class Mi355RetrievalService:
 
     @staticmethod
     def _maxsim_within(u: _UnitIndex, ix: Any, qtok: np.ndarray, qoff: np.ndarray, top_k: int, within: list):
-        """`search_maxsim` among the listed keys: every query scores the same candidates exactly (maxsim_subset -- under a
-        _World each rank the documents it owns, one all-gather) and the host orders them by (distance, document)."""
+        """`search_maxsim` among the listed keys.  One `search_maxsim_subset` call where the searcher has it: the list is
+        screened and the top-k selected on the device (under a _World each rank the documents it owns, one all-gather of the
+        [2, B, k] block).  A searcher without it scores every candidate exactly for every query (maxsim_subset) and the host
+        orders them by (distance, document): the same (distance, document) lists."""
         pos, off = u.pos_of_id(), u.table.mv_offsets
         docs = np.array(sorted({pos[pk] for pk in within if pk in pos and off[pos[pk] + 1] > off[pos[pk]]}), dtype=np.int64)
         B = qoff.shape[0] - 1
         dist = np.full((B, top_k), np.nan, dtype=np.float32)
         rows = np.full((B, top_k), -1, dtype=np.int64)
-        if docs.size:
+        if docs.size and hasattr(ix, "search_maxsim_subset"):
+            d, r = ix.search_maxsim_subset(qtok, qoff, top_k, docs)
+            d, r = np.asarray(d, dtype=np.float32), np.asarray(r, dtype=np.int64)
+            keep = ~np.isnan(d)   # (an undefined distance is no result, as below)
+            dist[keep], rows[keep] = d[keep], r[keep]
+        elif docs.size:
             scored = np.asarray(ix.maxsim_subset(qtok, qoff, np.tile(docs, (B, 1))), dtype=np.float32)
             for b in range(B):
                 live = np.nonzero(~np.isnan(scored[b]))[0]

@@ -388,6 +388,26 @@ class ShardedSearcher:
         out_d, out_r = merge_topk_host(np.ascontiguousarray(g[:, 0]).view(np.float64), np.ascontiguousarray(g[:, 1]), k)
         return out_d.astype(np.float32), out_r
 
+    def search_maxsim_subset(self, qtok, q_offsets, k: int, doc_ids) -> tuple[np.ndarray, np.ndarray]:
+        """`search_maxsim` restricted to the listed GLOBAL documents (Mi355Index.search_maxsim_subset).  Every rank passes the
+        same queries and the same list; the library keeps what falls in its shard, so a rank may find nothing.  Local top-k,
+        ONE all-gather of the packed [2, B, k] block (fp32 -> float8 is exact and order-preserving, as in `search_maxsim`), host
+        merge: the host pipeline of `search_subset`."""
+        ids = np.ascontiguousarray(doc_ids, dtype=np.int64).reshape(-1)
+        dist_l, rows_l = self.index.search_maxsim_subset(qtok, q_offsets, k, ids)
+        if self.world == 1 and not self.force_pipeline:
+            return dist_l, rows_l
+        import torch
+
+        dev, B = self._exchange_device(), dist_l.shape[0]
+        d64 = np.ascontiguousarray(np.asarray(dist_l, dtype=np.float32).astype(np.float64))
+        pk = torch.from_numpy(np.stack([d64.view(np.int64), np.ascontiguousarray(rows_l, dtype=np.int64)]).reshape(-1)).to(dev)
+        ga = torch.empty((self.world * pk.numel(),), dtype=torch.int64, device=dev)
+        self._dist.all_gather_into_tensor(ga, pk, group=self.group)
+        g = ga.cpu().numpy().reshape(self.world, 2, B, k)
+        out_d, out_r = merge_topk_host(np.ascontiguousarray(g[:, 0]).view(np.float64), np.ascontiguousarray(g[:, 1]), k)
+        return out_d.astype(np.float32), out_r
+
     def maxsim_subset(self, qtok, q_offsets, doc_ids, clamp0: bool = False) -> np.ndarray:
         """Late-interaction distance of EXPLICIT candidates (global doc ids, [B,m]) over a token-sharded store: every rank
         scores the candidates it owns (mi355dr_maxsim_subset leaves NaN for ids outside its shard), ONE all-gather of the

@@ -5,7 +5,7 @@
 
 1. single-vector index: add fp32 rows, exact cosine top-k for a block of queries (ids + float8 distances), the same search
    within a listed subset of rows, and a view of that subset for repeated searches
-2. multi-vector store: ragged docs, exact MaxSim top-k, candidate re-scoring, MaxSim top-k within a view
+2. multi-vector store: ragged docs, exact MaxSim top-k, candidate re-scoring, MaxSim top-k within a listed subset and a view
 3. the reference-shaped pipelines over an in-memory store: vector search, image (MaxSim) search, HEAVEN two-stage,
    Guided Query Refinement, RRF / convex-combination fusion and HyDE over child retrievers
 4. group-nDCG of the persisted results
@@ -64,7 +64,10 @@ with amd.Mi355Index(dm) as idx:
     mdist, mrows = idx.search_maxsim(qtok, qoff, k=5)   # VectorChord @#: -sum_i max_j <q_i, d_j>
     print("MaxSim: best doc", int(mrows[0, 0]), "score", float(-mdist[0, 0] / 16))
     print("candidate re-scoring of docs [42, 7, 9]:", (-idx.maxsim_subset(qtok, qoff, np.array([[42, 7, 9]])) / 16).round(4).tolist())
-    with idx.view(doc_ids=np.arange(0, n_docs, 2)) as even:   # MaxSim top-k restricted to a listed collection
+    # MaxSim top-k restricted to a listed collection: one call for a list searched once ...
+    print("MaxSim within the even-numbered docs: best doc",
+          int(idx.search_maxsim_subset(qtok, qoff, k=5, doc_ids=np.arange(0, n_docs, 2))[1][0, 0]))
+    with idx.view(doc_ids=np.arange(0, n_docs, 2)) as even:   # ... a view for a list searched many times
         print("MaxSim within the even-numbered docs: best doc", int(even.search_maxsim(qtok, qoff, k=5)[1][0, 0]))
 
 # ---- 3. the reference-shaped pipelines ------------------------------------------------------------------------------------

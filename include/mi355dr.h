@@ -213,7 +213,7 @@ int mi355dr_score_subset(mi355dr_index* idx, const float* queries, int B, const 
  *   Read-only: mi355dr_add_rows*, _update_rows*, _remove_rows, _compact, _reserve, _add_multivec*, _set_multivec* and option
  *     "row_offset" return MI355DR_E_INVALID on a view and change nothing.  So does every entry point that takes global ids or a
  *     communicator, with an error text that refers the caller to the parent: mi355dr_search_subset*, _score_subset,
- *     _maxsim_subset*, _gqr_refine, _gqr_refine_maxsim, _comm_init*, _search_sharded_device, and mi355dr_view_create itself (no
+ *     _maxsim_subset*, _search_maxsim_subset*, _gqr_refine, _gqr_refine_maxsim, _comm_init*, _search_sharded_device, and mi355dr_view_create itself (no
  *     views of views).  The stateless ones stay usable: mi355dr_merge_topk*, _pack_topk_device, _gqr_refine_scores.
  *   The call takes the parent's mutex, first completes whatever search is in flight there, and is complete on return;
  *     afterwards the two handles are independent.  The parent is only read.  On any error *out_view is NULL, everything
@@ -294,6 +294,44 @@ int mi355dr_maxsim_subset(mi355dr_index* idx, const float* qtok, const int32_t* 
 #define MI355DR_MAXSIM_CLAMP0 1
 int mi355dr_maxsim_subset_ex(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, const int64_t* doc_ids,
                              int m, int flags, float* out_dist);
+
+/* ---- MaxSim search within a listed subset of documents ----
+ * `embeddings @# q ... WHERE embeddings IS NOT NULL AND id = ANY(:ids) ORDER BY distance LIMIT k`: maxsim_search
+ * (orm/repository/base.py:487-535) with a key filter -- one tenant's pages, one PDF's passages.  The multi-vector sibling of
+ * mi355dr_search_subset: ONE list shared by all B queries, the top-k selected on the device.
+ *   Result: the top-k of every query among the listed documents only.  The fp32 distance bits, the order (distance asc,
+ *     document asc) and the NaN / -1 tail when fewer than k listed documents have vectors are those of mi355dr_search_maxsim.
+ *     Equivalently: the (distance, document) ordering of mi355dr_maxsim_subset over the list, and mi355dr_search_maxsim on
+ *     mi355dr_view_create(parent, NULL, 0, doc_ids, m).
+ *   doc_ids: HOST [m], GLOBAL ids (local document + option "row_offset"), under the hygiene of mi355dr_search_subset: values
+ *     outside the shard are skipped (negative values and -1 padding included), a value listed twice counts once, the order
+ *     never matters.  Documents without vectors -- never given any, or removed by mi355dr_set_multivec -- are skipped.
+ *   m == 0, or no listed document with vectors: every output is NaN / -1.  A query without vectors gets a NaN / -1 row.
+ *     m < 0, a null list with m > 0, k <= 0 or a decreasing q_offsets: MI355DR_E_INVALID.  k > 1024: MI355DR_E_UNSUPPORTED.
+ *   The call runs under the handle's mutex and is complete on return; the _device form follows the stream rule of
+ *     mi355dr_search_maxsim_device (doc_ids and q_offsets stay on the HOST).  The list is made local, sorted and uploaded as
+ *     int32, together with a membership table of 8 bytes per stored document, into buffers the store owns and grows, before
+ *     anything is launched; a failed allocation returns MI355DR_E_NOMEM and changes nothing.
+ *   Two paths with identical results, option "maxsim_subset_screen":
+ *     exact list path  the exact fp32 kernel walks the list, up to 4 queries per launch, then the device top-k.  Small lists,
+ *                      stores that cannot be screened (dims whose query fragments exceed the LDS, non-finite values), queries
+ *                      with non-finite vectors or with more vectors than one launch stages.
+ *     list screen      the one-wave-per-document bf16 MFMA screens read the listed documents where they lie (grid sized by
+ *                      the list), the selection kernels see the list through the membership table, the candidates are
+ *                      re-scored exactly as in mi355dr_search_maxsim.  A query with more than 8192 candidates is re-run by the
+ *                      exact list path.
+ *     -1 (default): screen when at least "maxsim_subset_screen_min" listed documents have vectors (default 512: the smallest
+ *     measured list, 1 000 of 1 M documents, rounded down to a power of two -- the screen won at every measured size, DESIGN.md
+ *     section 4.8d); 0: never; 1: whenever the store can be screened.
+ *   Stats: "maxsim_subset_searches" (calls), "maxsim_subset_docs" (listed documents with vectors, summed over calls),
+ *     "maxsim_subset_screened" / "maxsim_subset_exact" (queries served by the list screen / by the exact list path, fallbacks
+ *     included), "maxsim_subset_fallbacks" (queries whose candidate list overflowed).  The other "maxsim_*" stats belong to
+ *     mi355dr_search_maxsim and do not move. */
+int mi355dr_search_maxsim_subset(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, int k,
+                                 const int64_t* doc_ids, int64_t m, float* out_dist, int64_t* out_rows); /* all host */
+int mi355dr_search_maxsim_subset_device(mi355dr_index* idx, const float* qtok_dev, const int32_t* q_offsets, int B, int k,
+                                        const int64_t* doc_ids, int64_t m, float* out_dist_dev, int64_t* out_rows_dev,
+                                        void* stream); /* doc_ids and q_offsets stay on the HOST */
 
 /* ---- Guided Query Refinement of candidate pools (GQR hybrid pipeline) ----
  * Replaces the per-query numpy loops of autorag_research/pipelines/retrieval/gqr_hybrid.py: `_optimize_query_embedding`
@@ -385,7 +423,8 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
  *          "maxsim_wg_pipe" (1 [default]: a block's maxima folded between the next block's MFMAs), "maxsim_wg_min" (8 [default]
  *          / 9: fewest column blocks that take the workgroup form), "maxsim_aligned" (1 [default]: queries that are exactly
  *          one 32-column block are summed by the wave that holds them), "maxsim_tighten" (1 [default]: candidate band from the
- *          exact distances of the screen's top-k); round 6: "prune_wide" (1 [default]: passes at 33 <= k <= 128 use the
+ *          exact distances of the screen's top-k), "maxsim_subset_screen" (-1 [default] / 0 / 1) and "maxsim_subset_screen_min"
+ *          (512 [default]): the two paths of mi355dr_search_maxsim_subset, described there; round 6: "prune_wide" (1 [default]: passes at 33 <= k <= 128 use the
  *          two-wave prune, a starter over "starter_rows_wide" [65536] rows and chunk ratios up to 4; 0 = the round-5 schedule),
  *          "screen_flush_sync" (1 [default]: the waves of a k_screen_rq workgroup flush their hit-lane queues at the same tiles;
  *          "screen_flush_lanes" [48] / "screen_flush_alone" [40] tune the period), "chunk_taper_x100" (0 [default] = 120 for
@@ -408,6 +447,8 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
  *          multiplied every token by), "maxsim_set_docs" (documents rewritten by mi355dr_set_multivec) / "maxsim_moved_blocks"
  *          (32-token blocks its relayouts copied; 0 on the in-place path), "subset_searches" / "subset_rows_scored" /
  *          "subset_rerun_queries" (mi355dr_search_subset: calls, pairs scored, queries re-run in list-sized pieces),
+ *          "maxsim_subset_searches" / "maxsim_subset_docs" / "maxsim_subset_screened" / "maxsim_subset_exact" /
+ *          "maxsim_subset_fallbacks" (mi355dr_search_maxsim_subset, described there),
  *          "view" / "view_rows" / "view_docs" (mi355dr_view_create: 1 on a view / the rows / the documents it holds),
  *          "hbm_bytes_resident" (the single-vector corpus with its shadows at its capacity + the multi-vector store's two
  *          images, offset table and granule-packed copy as allocated now). */
