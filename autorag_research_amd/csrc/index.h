@@ -150,6 +150,11 @@ struct mi355dr_index {
     mi355::DevBuf<unsigned long long> stat_dev;  // [2*kQBlockMax]: per query (candidates, re-scored)
     mi355::DevBuf<int> prune_skip;   // [2 + 2*kQBlockMax] hand-over lists of k_prune (PruneArgs::skip_list)
     mi355::DevBuf<int32_t> subset_ids;  // the listed rows of the mi355dr_search_subset call in progress: local, ascending, unique
+    // MMR (mi355dr_search_mmr / mi355dr_mmr_select): one block's candidate lists in the total order
+    // [nb, fetch_k], the host forms' result staging [nb, k], and the kernel's pair counter -- grown by ensure_mmr
+    mi355::DevBuf<double> mmr_cand_dist, mmr_out_dist;
+    mi355::DevBuf<int64_t> mmr_cand_rows, mmr_out_rows;
+    mi355::DevBuf<unsigned long long> mmr_pairs_dev;
     // a view (mi355dr_view_create; DESIGN.md "Views"): a read-only index built from listed rows / documents of a parent.  The
     // maps are null on every other index: the result-writing kernels then add row_offset instead
     bool is_view = false;
@@ -262,6 +267,8 @@ struct mi355dr_index {
     // mi355dr_search_maxsim_subset: calls, listed documents with vectors, queries served by the list screen / by the exact list
     // path (fallbacks included), queries whose candidate list overflowed
     int64_t s_mss_searches = 0, s_mss_docs = 0, s_mss_screened = 0, s_mss_exact = 0, s_mss_fallbacks = 0;
+    // mi355dr_search_mmr* / mi355dr_mmr_select: calls, queries, (picked row, unselected candidate) dots of k_mmr_select
+    int64_t s_mmr_searches = 0, s_mmr_queries = 0, s_mmr_pairs = 0;
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
     mi355::EventPairs ev_pool, ev_pending;

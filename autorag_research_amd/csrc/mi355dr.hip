@@ -21,6 +21,8 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "k_compact.h"
 #include "k_view.h"
 #include "k_block.h"
+#include "k_mmr.h"
+#include "mmr_order.h"
 
 using namespace mi355;
 
@@ -165,6 +167,10 @@ int ensure_qstate(mi355dr_index* idx) {
     HIPCHECK(idx, hipFuncSetAttribute((const void*)k_screen_rq<6, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, rq_lds(6)));
     HIPCHECK(idx, hipFuncSetAttribute((const void*)k_merge_topk, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       kSortMax * 12));
+    if (mmr_lds_bytes(idx->dim, kMmrMax) > 160 * 1024)
+        return fail(idx, MI355DR_E_UNSUPPORTED, "dim too large for the select kernels' LDS budget");
+    HIPCHECK(idx, hipFuncSetAttribute((const void*)k_mmr_select, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)mmr_lds_bytes(idx->dim, kMmrMax)));
     idx->qstate_ready = true;  // (behind the last step that can fail)
     return MI355DR_OK;
 }
@@ -1644,6 +1650,178 @@ int mi355dr_score_subset(mi355dr_index* idx, const float* queries, int B, const 
     return MI355DR_OK;
 }
 
+// ---- MMR: diversity-aware top-k over a candidate list (csrc/k_mmr.h) -----------------------------
+namespace {
+int check_mmr_lambda(mi355dr_index* idx, const char* what, double lambda) {
+    if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(idx, MI355DR_E_INVALID, std::string(what) + ": lambda must be in [0, 1]");
+    return MI355DR_OK;
+}
+
+// the handle's MMR buffers for a block of nb lists of `stride` candidates and (host forms) nb x k results
+int ensure_mmr(mi355dr_index* idx, int nb, int stride, int k, bool host) {
+    HIPCHECK(idx, idx->mmr_cand_dist.grow((size_t)nb * stride * sizeof(double)));
+    HIPCHECK(idx, idx->mmr_cand_rows.grow((size_t)nb * stride * sizeof(int64_t)));
+    if (host) {
+        HIPCHECK(idx, idx->mmr_out_dist.grow((size_t)nb * k * sizeof(double)));
+        HIPCHECK(idx, idx->mmr_out_rows.grow((size_t)nb * k * sizeof(int64_t)));
+    }
+    HIPCHECK(idx, idx->mmr_pairs_dev.grow(sizeof(unsigned long long)));
+    return MI355DR_OK;
+}
+
+// nb lists [nb, stride] in idx->mmr_cand_* -> [nb, k] picks; asynchronous on the stream
+int launch_mmr(mi355dr_index* idx, hipStream_t s, int nb, int stride, int k, double lambda, double* out_dist_dev,
+               int64_t* out_rows_dev) {
+    hipLaunchKernelGGL(k_mmr_select, dim3(nb), dim3(kMmrThreads), mmr_lds_bytes(idx->dim, stride), s, idx->mmr_cand_rows.p,
+                       idx->mmr_cand_dist.p, stride, idx->rows.p, idx->nrm2.p, idx->n, idx->row_offset, idx->dim, idx->metric, k,
+                       lambda, out_dist_dev, out_rows_dev, idx->mmr_pairs_dev.p);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+// the call's last step (the stream is idle): the kernel's pair counter into the stats
+int mmr_finish(mi355dr_index* idx, int B) {
+    unsigned long long pairs = 0;
+    HIPCHECK(idx, hipMemcpy(&pairs, idx->mmr_pairs_dev.p, sizeof(pairs), hipMemcpyDeviceToHost));
+    idx->s_mmr_searches++;
+    idx->s_mmr_queries += B;
+    idx->s_mmr_pairs += (int64_t)pairs;
+    return MI355DR_OK;
+}
+
+// host == true: queries / outputs are host buffers staged through the index's own; else device buffers used in place
+int search_mmr_impl(mi355dr_index* idx, const float* queries, int B, int k, int fetch_k, double lambda, double* out_dist,
+                    int64_t* out_rows, hipStream_t s, bool host) {
+    if (idx && idx->is_view) return view_refuses(idx, "search_mmr", /*ask_parent=*/true);  // (set once, before the handle is handed out)
+    CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
+    CHECK(check_mmr_lambda(idx, "search_mmr", lambda));
+    if (fetch_k < k) return fail(idx, MI355DR_E_INVALID, "search_mmr: fetch_k must be >= k");
+    if (fetch_k > kMmrMax) return fail(idx, MI355DR_E_UNSUPPORTED, "search_mmr: fetch_k exceeds 1024");
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_pending(idx));
+    if (B == 0) return MI355DR_OK;
+    if (!s) s = idx->stream;
+    CHECK(ensure_qstate(idx));
+    CHECK(ensure_mmr(idx, std::min(B, kQBlockMax), fetch_k, k, host));
+    HIPCHECK(idx, hipMemsetAsync(idx->mmr_pairs_dev.p, 0, sizeof(unsigned long long), s));
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        const float* q = queries + (int64_t)b0 * idx->dim;
+        double* od = out_dist + (int64_t)b0 * k;
+        int64_t* orow = out_rows + (int64_t)b0 * k;
+        if (host) {
+            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q, (size_t)nb * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
+            q = idx->qdev;
+        }
+        // the ordinary search of the block at fetch_k (screened, fix-ups completed), then the selection behind it
+        CHECK(search_block(idx, s, q, nb, fetch_k, idx->mmr_cand_dist.p, idx->mmr_cand_rows.p));
+        CHECK(launch_mmr(idx, s, nb, fetch_k, k, lambda, host ? idx->mmr_out_dist.p : od, host ? idx->mmr_out_rows.p : orow));
+        if (host) {
+            HIPCHECK(idx, hipMemcpyAsync(od, idx->mmr_out_dist.p, (size_t)nb * k * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHECK(idx, hipMemcpyAsync(orow, idx->mmr_out_rows.p, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        }
+    }
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    return mmr_finish(idx, B);
+}
+}  // namespace
+
+int mi355dr_search_mmr(mi355dr_index* idx, const float* queries, int B, int k, int fetch_k, double lambda, double* out_dist,
+                       int64_t* out_rows) {
+    return search_mmr_impl(idx, queries, B, k, fetch_k, lambda, out_dist, out_rows, nullptr, /*host=*/true);
+}
+
+int mi355dr_search_mmr_device(mi355dr_index* idx, const float* queries_dev, int B, int k, int fetch_k, double lambda,
+                              double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
+    return search_mmr_impl(idx, queries_dev, B, k, fetch_k, lambda, out_dist_dev, out_rows_dev, (hipStream_t)stream, /*host=*/false);
+}
+
+int mi355dr_mmr_select(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* cand_rows, int m, double lambda,
+                       double* out_dist, int64_t* out_rows) {
+    if (idx && idx->is_view) return view_refuses(idx, "mmr_select", /*ask_parent=*/true);
+    CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
+    CHECK(check_mmr_lambda(idx, "mmr_select", lambda));
+    if (m < 0 || (B > 0 && m > 0 && !cand_rows)) return fail(idx, MI355DR_E_INVALID, "mmr_select: m must be >= 0 and cand_rows not null");
+    if (m > kMmrMax) return fail(idx, MI355DR_E_UNSUPPORTED, "mmr_select: m exceeds 1024");
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_pending(idx));
+    if (B == 0) return MI355DR_OK;
+    for (int64_t i = 0; i < (int64_t)B * k; ++i) {
+        out_dist[i] = NAN;
+        out_rows[i] = -1;
+    }
+    hipStream_t s = idx->stream;
+    CHECK(ensure_qstate(idx));
+    CHECK(ensure_mmr(idx, std::min(B, kQBlockMax), std::max(m, 1), k, /*host=*/true));
+    HIPCHECK(idx, hipMemsetAsync(idx->mmr_pairs_dev.p, 0, sizeof(unsigned long long), s));
+    std::vector<int32_t> pq;
+    std::vector<int64_t> pr, first, ordered_rows;  // first[b]: query b's first pair
+    std::vector<double> got, ordered_dist;
+    std::vector<MmrCand> list;
+    DevBuf<int32_t> pq_dev;
+    DevBuf<int64_t> pr_dev;
+    DevBuf<float> dot_dev;
+    DevBuf<double> dist_dev;
+    for (int b0 = 0; b0 < B && m > 0; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        try {  // every query's list: in-index rows, each once (k_rescore_pairs does not range-check)
+            pr.clear();
+            first.assign(1, 0);
+            for (int b = 0; b < nb; ++b) {
+                mmr_unique_rows(cand_rows + (int64_t)(b0 + b) * m, m, idx->row_offset, idx->n, pr);
+                first.push_back((int64_t)pr.size());
+            }
+            pq.resize(pr.size());
+            for (int b = 0; b < nb; ++b) std::fill(pq.begin() + first[b], pq.begin() + first[b + 1], b);
+            got.resize(pr.size());
+            ordered_dist.assign((size_t)nb * m, (double)NAN);
+            ordered_rows.assign((size_t)nb * m, -1);
+        } catch (const std::bad_alloc&) {
+            return fail(idx, MI355DR_E_NOMEM, "mmr_select: out of host memory for the candidate lists");
+        }
+        const int64_t n_pairs = (int64_t)pr.size();
+        if (n_pairs == 0) continue;
+        HIPCHECK(idx, pq_dev.grow(n_pairs * sizeof(int32_t)));
+        HIPCHECK(idx, pr_dev.grow(n_pairs * sizeof(int64_t)));
+        HIPCHECK(idx, dot_dev.grow(n_pairs * sizeof(float)));
+        HIPCHECK(idx, dist_dev.grow(n_pairs * sizeof(double)));
+        CHECK(upload_and_prep(idx, queries + (int64_t)b0 * idx->dim, nb, idx->metric));
+        HIPCHECK(idx, hipMemcpyAsync(pq_dev.p, pq.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(pr_dev.p, pr.data(), n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_rescore_pairs, dim3((unsigned)((n_pairs + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows,
+                           idx->nrm2, idx->qdev, idx->st.qn, pq_dev.p, pr_dev.p, n_pairs, idx->dim, idx->metric, dot_dev.p,
+                           dist_dev.p);
+        HIPCHECK(idx, hipGetLastError());
+        HIPCHECK(idx, hipMemcpyAsync(got.data(), dist_dev.p, n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipStreamSynchronize(s));
+        // each list into the total order: a removed row (the kernel's NaN) and a live row without a distance come last, behind
+        // the eligible prefix k_mmr_select stops at
+        try {
+            for (int b = 0; b < nb; ++b) {
+                list.clear();
+                for (int64_t i = first[b]; i < first[b + 1]; ++i) list.push_back(MmrCand{got[i], pr[i]});
+                mmr_order(list.data(), (int64_t)list.size());
+                for (size_t j = 0; j < list.size(); ++j) {
+                    ordered_dist[(size_t)b * m + j] = list[j].dist;
+                    ordered_rows[(size_t)b * m + j] = list[j].row + idx->row_offset;
+                }
+            }
+        } catch (const std::bad_alloc&) {
+            return fail(idx, MI355DR_E_NOMEM, "mmr_select: out of host memory for the candidate lists");
+        }
+        HIPCHECK(idx, hipMemcpyAsync(idx->mmr_cand_dist.p, ordered_dist.data(), (size_t)nb * m * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(idx->mmr_cand_rows.p, ordered_rows.data(), (size_t)nb * m * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        CHECK(launch_mmr(idx, s, nb, m, k, lambda, idx->mmr_out_dist.p, idx->mmr_out_rows.p));
+        HIPCHECK(idx, hipMemcpyAsync(out_dist + (int64_t)b0 * k, idx->mmr_out_dist.p, (size_t)nb * k * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipMemcpyAsync(out_rows + (int64_t)b0 * k, idx->mmr_out_rows.p, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipStreamSynchronize(s));  // (the ordered lists are pageable and are rewritten for the next block)
+    }
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    return mmr_finish(idx, B);
+}
+
 int mi355dr_merge_topk_device(mi355dr_index* idx, const double* dist_all_dev, const int64_t* rows_all_dev, int world,
                               int B, int k, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
@@ -1792,6 +1970,9 @@ const Stat kStats[] = {
     {"maxsim_subset_screened", &Index::s_mss_screened, true},
     {"maxsim_subset_exact", &Index::s_mss_exact, true},
     {"maxsim_subset_fallbacks", &Index::s_mss_fallbacks, true},
+    {"mmr_searches", &Index::s_mmr_searches, true},
+    {"mmr_queries", &Index::s_mmr_queries, true},
+    {"mmr_pairs_scored", &Index::s_mmr_pairs, true},
     {"compactions", &Index::s_compactions, true},
     {"compact_moved_rows", &Index::s_compact_moved_rows, true},
     {"view", nullptr, false, [](const Index* x) -> int64_t { return x->is_view ? 1 : 0; }},

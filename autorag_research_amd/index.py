@@ -203,6 +203,53 @@ class Mi355Index:
                                                       ids.shape[1], ptr(out, ctypes.c_double)))
         return out
 
+    # ---- MMR: a diversity-aware top-k selected on the device (include/mi355dr.h "MMR search") ----
+    def _queries_2d(self, queries) -> np.ndarray:
+        q = f32c(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [B, {self.dim}], got {q.shape}")
+        return q
+
+    def search_mmr(self, queries, k: int, fetch_k: int, lambda_mult: float = 0.5) -> tuple[np.ndarray, np.ndarray]:
+        """Maximal Marginal Relevance: the ordinary search at `fetch_k`, then `k` of its results picked greedily by
+        lambda_mult * sim(query, row) - (1 - lambda_mult) * max sim(row, already picked), on the device.  Returns
+        (distance float64 [B,k], rows int64 [B,k]) in selection order, NaN / -1 padded; lambda_mult = 1 is `search(k)`."""
+        q = self._queries_2d(queries)
+        B = q.shape[0]
+        dist = np.empty((B, k), dtype=np.float64)
+        rows = np.empty((B, k), dtype=np.int64)
+        check(self._h, self._lib.mi355dr_search_mmr(self._h, ptr(q, ctypes.c_float), B, int(k), int(fetch_k), float(lambda_mult),
+                                                    ptr(dist, ctypes.c_double), ptr(rows, ctypes.c_int64)))
+        return dist, rows
+
+    def search_mmr_device(self, q_ptr: int, B: int, k: int, fetch_k: int, out_dist_ptr: int, out_rows_ptr: int,
+                          lambda_mult: float = 0.5, stream: int | None = None) -> None:
+        """The same with queries and outputs in device memory; complete on return."""
+        check(self._h, self._lib.mi355dr_search_mmr_device(
+            self._h, ctypes.c_void_p(int(q_ptr)), int(B), int(k), int(fetch_k), float(lambda_mult),
+            ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
+            ctypes.c_void_p(int(stream) if stream else None)))
+
+    def mmr_select(self, queries, k: int, cand_rows, lambda_mult: float = 0.5) -> tuple[np.ndarray, np.ndarray]:
+        """MMR over each query's OWN candidate pool: cand_rows [B, m] global rows (m <= 1024) under the hygiene of
+        `score_subset` / `search_subset` -- ids outside the index and -1 padding skipped, duplicates once, removed rows
+        skipped, any order.  Each pool is scored, put into the search's order and picked from on the device."""
+        q = self._queries_2d(queries)
+        ids = np.ascontiguousarray(cand_rows, dtype=np.int64)
+        if ids.ndim == 1:
+            ids = ids[None, :]
+        if ids.ndim != 2 or ids.shape[0] != q.shape[0]:
+            raise ValueError(f"cand_rows must be [B, m] with B = {q.shape[0]}, got {ids.shape}")
+        B = q.shape[0]
+        dist = np.empty((B, k), dtype=np.float64)
+        rows = np.empty((B, k), dtype=np.int64)
+        check(self._h, self._lib.mi355dr_mmr_select(self._h, ptr(q, ctypes.c_float), B, int(k), ptr(ids, ctypes.c_int64),
+                                                    ids.shape[1], float(lambda_mult), ptr(dist, ctypes.c_double),
+                                                    ptr(rows, ctypes.c_int64)))
+        return dist, rows
+
     # ---- views: a listed subset as an index of its own (include/mi355dr.h "views") ----
     def view(self, row_ids=None, doc_ids=None) -> "Mi355Index":
         """The listed rows and / or documents of this index as a read-only index of their own, built on the device

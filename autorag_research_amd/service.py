@@ -614,10 +614,15 @@ class Mi355RetrievalService:
     # ---- the hot path ----
     def vector_search(self, query_ids: list[int | str], top_k: int = 10,
                       search_mode: Literal["single", "multi"] = "single", unit: str = "chunk",
-                      within: list | None = None) -> list[list[dict]]:
+                      within: list | None = None, mmr_fetch_k: int | None = None,
+                      mmr_lambda: float = 0.5) -> list[list[dict]]:
         """Top-k for every query id, scored as one block.  Raises ValueError exactly like the reference.
         `within` (not in the reference's signature; None = today's behaviour): primary keys the search is restricted to --
-        the statement with `AND id = ANY(:within)`.  Keys unknown to the table or without a stored embedding are left out."""
+        the statement with `AND id = ANY(:within)`.  Keys unknown to the table or without a stored embedding are left out.
+        `mmr_fetch_k` (None = today's behaviour; single mode only): diversify -- the top_k results are picked from the
+        mmr_fetch_k nearest by Maximal Marginal Relevance with weight `mmr_lambda` on the query similarity
+        (Mi355Index.search_mmr), and come in selection order."""
+        self._check_mmr(search_mode, mmr_fetch_k)
         queries = []
         for qid, q in zip(query_ids, self.get_queries(list(query_ids)), strict=True):
             if q is None:
@@ -634,7 +639,17 @@ class Mi355RetrievalService:
         if search_mode == "multi":
             return self.maxsim_search_by_embeddings([q.embeddings for q in queries], top_k, unit, within=within)
         Q = np.stack([q.embedding for q in queries]).astype(np.float32, copy=False)
-        return self._single_block(Q, top_k, unit, within)
+        return self._single_block(Q, top_k, unit, within, mmr_fetch_k, mmr_lambda)
+
+    def _check_mmr(self, search_mode: str, mmr_fetch_k: int | None) -> None:
+        """MMR is a single-vector, single-GPU selection: it scores stored rows against each other, and under row shards the
+        candidates' vectors lie on different GPUs.  Raised on every rank alike, before any collective."""
+        if mmr_fetch_k is None:
+            return
+        if search_mode == "multi":
+            raise ValueError("mmr_fetch_k applies to search_mode='single' only")  # noqa: TRY003
+        if self._world is not None:
+            raise NotImplementedError("MMR under a process group: the candidates' vectors lie on different GPUs")
 
     @staticmethod
     def _results_from_block(table: ChunkTable, pos_of_row: np.ndarray, rows: np.ndarray, scores: np.ndarray,
@@ -663,11 +678,20 @@ class Mi355RetrievalService:
         known = {pk: row[pos[pk]] for pk in doc_ids if pk in pos and pos[pk] in row}
         return list(known), np.fromiter(known.values(), dtype=np.int64, count=len(known))
 
-    def _single_block(self, Q: np.ndarray, top_k: int, unit: str, within: list | None = None) -> list[list[dict]]:
+    def _single_block(self, Q: np.ndarray, top_k: int, unit: str, within: list | None = None,
+                      mmr_fetch_k: int | None = None, mmr_lambda: float = 0.5) -> list[list[dict]]:
         u = self._unit(unit)
         # (one process per GPU, every rank: local top-k of its rows, all-gather, merge -> the same global lists)
         searcher = u.single_searcher(self._world)
-        if within is None:
+        if mmr_fetch_k is not None:
+            if within is None:
+                dist, rows = searcher.search_mmr(Q, top_k, mmr_fetch_k, mmr_lambda)
+            else:   # the mmr_fetch_k nearest of the listed rows are each query's pool (-1 padding is skipped by the library)
+                if mmr_fetch_k < top_k:
+                    raise ValueError("mmr_fetch_k must be >= top_k")  # noqa: TRY003
+                pool = searcher.search_subset(Q, mmr_fetch_k, self._single_rows_of(u, within)[1])[1]
+                dist, rows = searcher.mmr_select(Q, top_k, pool, mmr_lambda)
+        elif within is None:
             dist, rows = searcher.search(Q, top_k)
         else:   # ... among the listed rows: every rank passes the whole list, the library keeps what falls in its shard
             dist, rows = searcher.search_subset(Q, top_k, self._single_rows_of(u, within)[1])
@@ -675,10 +699,12 @@ class Mi355RetrievalService:
         return self._results_from_block(u.table, u.single_rows, rows, 1.0 - dist, unit == "chunk")
 
     def vector_search_by_embedding(self, embedding: list[float], top_k: int = 10, unit: str = "chunk",
-                                   within: list | None = None) -> list[dict]:
+                                   within: list | None = None, mmr_fetch_k: int | None = None,
+                                   mmr_lambda: float = 0.5) -> list[dict]:
+        self._check_mmr("single", mmr_fetch_k)
         if len(embedding) == 0:  # reference: `if not query_vector: return []` (base.py:403-404)
             return []
-        return self._single_block(np.asarray(embedding, dtype=np.float32)[None, :], top_k, unit, within)[0]
+        return self._single_block(np.asarray(embedding, dtype=np.float32)[None, :], top_k, unit, within, mmr_fetch_k, mmr_lambda)[0]
 
     def score_candidates(self, embedding: list[float], doc_ids: list, unit: str = "chunk") -> dict:
         """Dense score of explicit candidates: {doc_id: 1.0 - cosine distance}, the score `vector_search_by_embedding` gives

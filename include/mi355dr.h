@@ -184,6 +184,41 @@ int mi355dr_search_subset_device(mi355dr_index* idx, const float* queries_dev, i
  * and where the distance is undefined (a zero norm).  Same device code as mi355dr_debug_rescore. */
 int mi355dr_score_subset(mi355dr_index* idx, const float* queries, int B, const int64_t* row_ids, int m, double* out_dist);
 
+/* ---- MMR search: a diversity-aware top-k, selected on the device ----
+ * Maximal Marginal Relevance: fetch fetch_k candidates, then pick k of them greedily, each time the candidate that is similar
+ * to the query and dissimilar to what was already picked.  The candidates' vectors never leave the device.
+ *   Candidate order: the library's total order (distance asc, NaN last, row asc) -- for mi355dr_search_mmr the result of the
+ *     ordinary search at k = fetch_k; for mi355dr_mmr_select the caller's list put into that order: the in-index live rows,
+ *     each once, as mi355dr_search_subset orders them.
+ *   Eligible candidates: the leading entries with row >= 0 and a non-NaN distance; n of them.
+ *   sim(dist) = 1.0 - dist (cosine), -dist (inner product).  pairdist(a, b) of two stored rows: the library's exact distance --
+ *     the k-ascending fp32 fmaf chain for the dot, the stored squared norms of both rows, the float8 formula of the searches;
+ *     it is symmetric.  Everything below is IEEE double, separate operations, no fused multiply-add:
+ *       sq[i] = sim(dist[i]), one_m = 1.0 - lambda;  pick 0 = candidate 0;
+ *       after each pick c, except the last, for every unselected i:  s = sim(pairdist(c, i));
+ *           ms[i] = s at the first pick;  ms[i] = s > ms[i] ? s : ms[i] afterwards (a NaN s is ignored);
+ *       pick t >= 1:  score[i] = lambda * sq[i] - one_m * ms[i] over the unselected i;  the first i, in candidate order, whose
+ *           score is strictly greater than every earlier unselected score; a NaN score never wins; if none wins, the first
+ *           unselected i.
+ *     Stop after min(k, n) picks.  Output slot t: pick t's query distance (the bits the search returned) and its global row;
+ *     slots from min(k, n) on: NaN / -1.  lambda = 1.0 reproduces the ordinary top-k over the eligible candidates bit for bit.
+ *   mi355dr_search_mmr / _device: the ordinary search of the block at fetch_k (the code of mi355dr_search_device: screened,
+ *     fix-ups completed) into buffers the index owns and grows, then the selection kernel on the same stream.  B above 1024
+ *     runs in internal blocks.  Under the handle's mutex; first completes what is in flight; complete on return.
+ *   mi355dr_mmr_select: the lower layer for explicit per-query pools (hybrid or HEAVEN candidates, a key filter).  cand_rows:
+ *     HOST [B, m] GLOBAL rows under the hygiene of mi355dr_score_subset / mi355dr_search_subset (ids outside the index and -1
+ *     padding skipped, duplicates once, removed rows skipped, any order); distances from the device code of
+ *     mi355dr_score_subset; the host orders each list and uploads it; the same kernel.  k may exceed m (NaN / -1 tail).
+ *   MI355DR_E_INVALID: lambda outside [0, 1] or NaN, k <= 0, fetch_k < k, m < 0, a null buffer with work to do, and all three
+ *     on a view (ask the parent).  MI355DR_E_UNSUPPORTED: fetch_k > 1024, m > 1024.
+ *   Stats: "mmr_searches" (calls), "mmr_queries", "mmr_pairs_scored" ((picked row, unselected candidate) dots). */
+int mi355dr_search_mmr(mi355dr_index* idx, const float* queries, int B, int k, int fetch_k, double lambda, double* out_dist,
+                       int64_t* out_rows); /* all host */
+int mi355dr_search_mmr_device(mi355dr_index* idx, const float* queries_dev, int B, int k, int fetch_k, double lambda,
+                              double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+int mi355dr_mmr_select(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* cand_rows /* host [B, m] */, int m,
+                       double lambda, double* out_dist, int64_t* out_rows); /* all host */
+
 /* ---- views: a listed subset of rows / documents as an index of its own ----
  * For a list that is searched again and again -- one tenant, one document collection, one PDF's pages: the key filter of the
  * statement above, fixed for many query blocks.  mi355dr_search_subset scans the list exactly on every call (cost ~ m x B, no
@@ -212,7 +247,7 @@ int mi355dr_score_subset(mi355dr_index* idx, const float* queries, int B, const 
  *     view still speaks the OLD ids); the parent may be destroyed first.
  *   Read-only: mi355dr_add_rows*, _update_rows*, _remove_rows, _compact, _reserve, _add_multivec*, _set_multivec* and option
  *     "row_offset" return MI355DR_E_INVALID on a view and change nothing.  So does every entry point that takes global ids or a
- *     communicator, with an error text that refers the caller to the parent: mi355dr_search_subset*, _score_subset,
+ *     communicator, with an error text that refers the caller to the parent: mi355dr_search_subset*, _score_subset, _search_mmr*, _mmr_select,
  *     _maxsim_subset*, _search_maxsim_subset*, _gqr_refine, _gqr_refine_maxsim, _comm_init*, _search_sharded_device, and mi355dr_view_create itself (no
  *     views of views).  The stateless ones stay usable: mi355dr_merge_topk*, _pack_topk_device, _gqr_refine_scores.
  *   The call takes the parent's mutex, first completes whatever search is in flight there, and is complete on return;
@@ -447,6 +482,7 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
  *          multiplied every token by), "maxsim_set_docs" (documents rewritten by mi355dr_set_multivec) / "maxsim_moved_blocks"
  *          (32-token blocks its relayouts copied; 0 on the in-place path), "subset_searches" / "subset_rows_scored" /
  *          "subset_rerun_queries" (mi355dr_search_subset: calls, pairs scored, queries re-run in list-sized pieces),
+ *          "mmr_searches" / "mmr_queries" / "mmr_pairs_scored" (mi355dr_search_mmr* and mi355dr_mmr_select, described there),
  *          "maxsim_subset_searches" / "maxsim_subset_docs" / "maxsim_subset_screened" / "maxsim_subset_exact" /
  *          "maxsim_subset_fallbacks" (mi355dr_search_maxsim_subset, described there),
  *          "view" / "view_rows" / "view_docs" (mi355dr_view_create: 1 on a view / the rows / the documents it holds),
