@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "mi355dr_reset_stats", "mi355dr_timer_start", "mi355dr_timer_stop", "mi355dr_synchronize",
     "mi355dr_dev_alloc", "mi355dr_dev_free", "mi355dr_dev_upload", "mi355dr_dev_download",
     "mi355dr_diag_mfma_stream",
-    "mi355dr_debug_screen_dense", "mi355dr_debug_screen_bound", "mi355dr_debug_i8_state", "mi355dr_debug_rescore",
+    "mi355dr_debug_screen_dense", "mi355dr_debug_screen_hits", "mi355dr_debug_screen_bound", "mi355dr_debug_i8_state", "mi355dr_debug_rescore",
 ]
 
 
@@ -212,6 +212,9 @@ def load() -> ctypes.CDLL:
     L.mi355dr_dev_download.argtypes = [vp, vp, vp, ctypes.c_size_t]
     L.mi355dr_debug_screen_dense.restype = c_int
     L.mi355dr_debug_screen_dense.argtypes = [vp, f32p, c_int, i64, i64, f32p]
+    L.mi355dr_debug_screen_hits.restype = c_int
+    L.mi355dr_debug_screen_hits.argtypes = [vp, f32p, c_int, i64, i64, f32p, c_int, ctypes.POINTER(c_int), i32p, f32p,
+                                            ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     L.mi355dr_debug_screen_bound.restype = c_int
     L.mi355dr_debug_screen_bound.argtypes = [vp, f32p, c_int, f32p]
     L.mi355dr_debug_i8_state.restype = c_int

@@ -315,13 +315,29 @@ inline int screen_tile(int B) { return B > kTileN ? kT2 : kTileM; }
 
 constexpr int kRetryLevels = 2;  // re-screens of an overflowed query (bf16, growth/2, then growth 0.25) before the exact scan
 
-// launch one screen pass over rows [r0, r_end) (r0 a multiple of the tile edge)
-int launch_screen(mi355dr_index* idx, hipStream_t s, int B, int64_t r0, int64_t r_end, int cap, int emit_mode) {
-    const bool emit_all = emit_mode != 0;  // (both special epilogues live in k_screen)
+// which kernel one screen launch over `rows` rows takes (launch_screen switches on it; mi355dr_debug_screen_hits reports it)
+enum ScreenKernel { kKernTile = 0, kKernStream = 1, kKern256c = 2, kKernRq = 3 };
+inline ScreenKernel screen_kernel_for(const mi355dr_index* idx, int B, int64_t rows, bool emit_all) {
     // the emit-all first chunk always goes through the 128x128 kernel (k_screen256c and k_screen_rq have no emit-all epilogue)
     // ... and so do chunks of a few thousand rows: their thresholds are still so low that a good part of the tile is a
     // hit, which the per-lane global append of k_screen handles better than the small per-wave queues of k_screen256c and k_screen_rq
-    const int tile = (emit_all || r_end - r0 <= idx->small_chunk_rows) ? kTileM : screen_tile(B);
+    const int tile = (emit_all || rows <= idx->small_chunk_rows) ? kTileM : screen_tile(B);
+    const bool i8 = use_i8(idx);
+    const int row_bytes = i8 ? idx->dpad8 : idx->dpad * 2;
+    const int ksteps = row_bytes / kRowB;
+    // query operand resident in registers, 128-row tiles (k_screen_rq.h): int8 shadows of at most 768 bytes per row
+    if (tile == kT2) return i8 && idx->screen_rq && screen_rq_has(ksteps) ? kKernRq : kKern256c;
+    // small query blocks: the streaming form (resident query block, deep row ring, one persistent workgroup per CU)
+    if (!emit_all && idx->screen_stream && B <= 64 && ksteps >= 1 && (B <= 32 ? 32 : 64) * row_bytes <= kStreamQueryBytesMax)
+        return kKernStream;
+    return kKernTile;
+}
+
+// launch one screen pass over rows [r0, r_end) (r0 a multiple of the tile edge)
+int launch_screen(mi355dr_index* idx, hipStream_t s, int B, int64_t r0, int64_t r_end, int cap, int emit_mode) {
+    const bool emit_all = emit_mode != 0;  // (both special epilogues live in k_screen)
+    const ScreenKernel kern = screen_kernel_for(idx, B, r_end - r0, emit_all);
+    const int tile = kern == kKern256c || kern == kKernRq ? kT2 : kTileM;
     const bool i8 = use_i8(idx);
     ScreenArgs2 sa{};
     sa.status = idx->st.status;
@@ -345,8 +361,8 @@ int launch_screen(mi355dr_index* idx, hipStream_t s, int B, int64_t r0, int64_t 
     sa.row0 = r0;
     sa.emit_all = emit_mode;
     const int64_t grid = round_up(sa.n_ctiles, 8) * sa.n_qtiles;
-    if (tile == kT2 && i8 && idx->screen_rq && screen_rq_has(sa.ksteps)) {
-        // query operand resident in registers, 128-row tiles (k_screen_rq.h): int8 shadows of at most 768 bytes per row
+    switch (kern) {
+    case kKernRq: {
         sa.ct0 = (int)(r0 / kRqRows);
         sa.n_ctiles = (int)(round_up(r_end, kRqRows) / kRqRows) - sa.ct0;
         const unsigned g2 = screen_rq_grid(sa.n_ctiles, sa.n_qtiles);
@@ -377,13 +393,15 @@ int launch_screen(mi355dr_index* idx, hipStream_t s, int B, int64_t r0, int64_t 
 #undef MI355_RQ_LAUNCH
             }
         }
-    } else if (tile == kT2) {
+        break;
+    }
+    case kKern256c: {
         const unsigned g2 = screen256_grid(sa.n_ctiles, sa.n_qtiles);  // persistent: <= one workgroup per CU
         if (i8) hipLaunchKernelGGL((k_screen256c<true>), dim3(g2), dim3(512), kScreen256Lds, s, sa);
         else hipLaunchKernelGGL((k_screen256c<false>), dim3(g2), dim3(512), kScreen256Lds, s, sa);
-    } else if (!emit_all && idx->screen_stream && B <= 64 && sa.ksteps >= 1 &&
-               (B <= 32 ? 32 : 64) * sa.row_bytes <= kStreamQueryBytesMax) {
-        // small query blocks: the streaming form (resident query block, deep row ring, one persistent workgroup per CU)
+        break;
+    }
+    case kKernStream: {
         const int nq = B <= 32 ? 32 : 64;
         const unsigned gs = (unsigned)std::min(sa.n_ctiles, 256);
         const size_t lds = screen_stream_lds(nq, sa.row_bytes);
@@ -391,9 +409,12 @@ int launch_screen(mi355dr_index* idx, hipStream_t s, int B, int64_t r0, int64_t 
         else if (i8) hipLaunchKernelGGL((k_screen_stream<true, 64>), dim3(gs), dim3(256), lds, s, (ScreenArgs)sa);
         else if (nq == 32) hipLaunchKernelGGL((k_screen_stream<false, 32>), dim3(gs), dim3(256), lds, s, (ScreenArgs)sa);
         else hipLaunchKernelGGL((k_screen_stream<false, 64>), dim3(gs), dim3(256), lds, s, (ScreenArgs)sa);
-    } else {
+        break;
+    }
+    case kKernTile:
         if (i8) hipLaunchKernelGGL(k_screen<true>, dim3((unsigned)grid), dim3(256), kScreenLds, s, (ScreenArgs)sa);
         else hipLaunchKernelGGL(k_screen<false>, dim3((unsigned)grid), dim3(256), kScreenLds, s, (ScreenArgs)sa);
+        break;
     }
     HIPCHECK(idx, hipGetLastError());
     if (emit_mode == kEmitAll) {  // every row of the chunk was stored at slot row-r0 for every query
@@ -2127,6 +2148,47 @@ int mi355dr_debug_screen_dense(mi355dr_index* idx, const float* queries, int B, 
             if (r >= 0 && r < n && !flag[r]) out_t[(int64_t)b * n + r] = cval[(size_t)b * kCandCap + j];
         }
     }
+    return MI355DR_OK;
+}
+
+int mi355dr_debug_screen_hits(mi355dr_index* idx, const float* queries, int B, int64_t row0, int64_t n, const float* thr,
+                              int cap, int* out_count, int32_t* out_rows, float* out_vals, int* out_status, int* out_kernel) {
+    if (!idx || !queries || !thr || !out_count || !out_rows || !out_vals || !out_status || !out_kernel)
+        return fail(idx, MI355DR_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (B <= 0 || B > kQBlockMax || n <= 0 || row0 < 0 || row0 % screen_tile(B) != 0 || row0 + n > idx->n || cap < 16 ||
+        cap > kCandCapWide)
+        return fail(idx, MI355DR_E_INVALID,
+                    "debug_screen_hits: need 1<=B<=1024, n>=1, row0 a multiple of the tile (128; 256 if B>128), 16<=cap<=4096");
+    for (int b = 0; b < B; ++b)
+        if (!(thr[b] < INFINITY))  // (NaN compares false)
+            return fail(idx, MI355DR_E_INVALID, "debug_screen_hits: thresholds must be finite or -inf");
+    CHECK(upload_and_prep(idx, queries, B, /*metric=*/2));  // (queries behind B, padding of the last tile: thresholds at +inf)
+    hipStream_t s = idx->stream;
+    HIPCHECK(idx, hipMemcpyAsync(idx->st.thr, thr, (size_t)B * sizeof(float), hipMemcpyHostToDevice, s));
+    // k_screen_rq's synchronised flushes: run_screen derives the period from k and the rows seen, neither of which exists
+    // here -- two tiles, so that a workgroup of a few visits takes both the common flush and (at flush_alone) a wave's own
+    idx->flush_mask_now = idx->screen_flush_sync ? 1 : -1;
+    *out_kernel = (int)screen_kernel_for(idx, B, n, /*emit_all=*/false);
+    CHECK(launch_screen(idx, s, B, row0, row0 + n, cap, /*emit_mode=*/0));
+    HIPCHECK(idx, hipMemcpyAsync(out_count, idx->st.cnt, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(out_status, idx->st.status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(out_rows, idx->cand_row, (size_t)B * cap * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(out_vals, idx->cand_val, (size_t)B * cap * sizeof(float), hipMemcpyDeviceToHost, s));
+    std::vector<uint8_t> flag;  // int8 screen: rows outside the shadow carry a stale 0 (k_prune drops them)
+    if (use_i8(idx)) {
+        flag.resize((size_t)n);
+        HIPCHECK(idx, hipMemcpyAsync(flag.data(), idx->flag8 + row0, (size_t)n, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    if (!flag.empty())
+        for (int b = 0; b < B; ++b) {
+            const int c = std::min(std::max(out_count[b], 0), cap);
+            for (int j = 0; j < c; ++j) {
+                int32_t& r = out_rows[(size_t)b * cap + j];
+                if (r >= row0 && r < row0 + n && flag[(size_t)(r - row0)]) r = -1 - r;
+            }
+        }
     return MI355DR_OK;
 }
 

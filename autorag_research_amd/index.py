@@ -575,6 +575,31 @@ class Mi355Index:
                                                             int(n), ptr(out, ctypes.c_float)))
         return out
 
+    def debug_screen_hits(self, queries, row0: int, n: int, thr, cap: int = 2048) -> dict:
+        """One production screen launch over rows [row0, row0 + n) with the caller's thresholds (mi355dr_debug_screen_hits).
+        Returns {"kernel": 0 k_screen / 1 k_screen_stream / 2 k_screen256c / 3 k_screen_rq, "count" [B]: the device's
+        counters (may exceed cap), "status" [B], and the lists' entries flat, in list order: "q", "row", "val"} -- without
+        the entries of rows outside the int8 shadow (their value is a stale accumulator's); "dropped" [B] counts those."""
+        q = f32c(queries)
+        B = q.shape[0]
+        t = f32c(thr)
+        if t.shape != (B,):
+            raise ValueError("thr must hold one threshold per query")
+        count = np.empty(B, dtype=np.int32)
+        status = np.empty(B, dtype=np.int32)
+        rows = np.empty((B, cap), dtype=np.int32)
+        vals = np.empty((B, cap), dtype=np.float32)
+        kernel = ctypes.c_int(-1)
+        check(self._h, self._lib.mi355dr_debug_screen_hits(self._h, ptr(q, ctypes.c_float), B, int(row0), int(n),
+                                                           ptr(t, ctypes.c_float), int(cap), ptr(count, ctypes.c_int),
+                                                           ptr(rows, ctypes.c_int32), ptr(vals, ctypes.c_float),
+                                                           ptr(status, ctypes.c_int), ctypes.byref(kernel)))
+        held = np.arange(cap)[None, :] < np.minimum(count, cap)[:, None]
+        flagged = held & (rows < 0)
+        keep = held & ~flagged
+        return {"kernel": int(kernel.value), "count": count, "status": status, "dropped": flagged.sum(axis=1),
+                "q": np.nonzero(keep)[0].astype(np.int32), "row": rows[keep], "val": vals[keep]}
+
     def debug_i8_state(self, queries, g0: int, n_groups: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """int8 screen: (S_q [B], kq [B], S_g [n_groups], e_g [n_groups]) -- screen value = S_q S_g (q8.c8) + e_g kq."""
         q = f32c(queries)

@@ -503,8 +503,23 @@ int mi355dr_dev_upload(mi355dr_index* idx, void* dst_dev, const void* src_host, 
 int mi355dr_dev_download(mi355dr_index* idx, void* dst_host, const void* src_dev, size_t bytes);
 
 /* ---- test hooks (used by tests/ only; exercise the production kernels on small inputs) ----
- * dense screen values t[b, r] for rows [row0,row0+n): runs the screen kernel with thresholds at -inf. */
+ * dense screen values t[b, r] for rows [row0,row0+n), n <= 2048: runs the screen kernel with thresholds at -inf.  With the
+ * default options a range this short is below small_chunk_rows, so the kernel it reaches is k_screen (the 128 x 128 tile),
+ * or k_screen_stream for B <= 64 -- whatever B is; k_screen256c and k_screen_rq are reached by mi355dr_debug_screen_hits. */
 int mi355dr_debug_screen_dense(mi355dr_index* idx, const float* queries, int B, int64_t row0, int64_t n, float* out_t);
+/* one production screen launch over rows [row0, row0 + n) with the caller's thresholds: the raw candidate lists.
+ * thr: host [B], finite or -inf.  cap: list slots per query, 16 .. the capacity the lists are allocated for (4096).
+ * out_count [B]: the device's counter (may exceed cap: the list then holds its first cap entries);
+ * out_rows / out_vals: host [B, cap]; out_status [B]: the status word (bit 0 = a wave queue overflowed);
+ * *out_kernel: which kernel the launch took (0 k_screen, 1 k_screen_stream, 2 k_screen256c, 3 k_screen_rq) -- steered by
+ * the options small_chunk_rows, screen_rq, screen_stream, screen_dtype as in a search.
+ * row0 must be a multiple of the tile edge (128; 256 if B > 128) and row0 + n <= size; n is not limited.
+ * int8 screen: an entry whose row lies outside the int8 shadow (a loose, irregular or removed row: its accumulator is a
+ * stale 0, the prune drops it) is marked by out_rows = -1 - row.
+ * k_screen_rq's common flush period, which a search derives from k and the rows already seen, is two tiles here
+ * (option screen_flush_sync = 0: none, as in a search). */
+int mi355dr_debug_screen_hits(mi355dr_index* idx, const float* queries, int B, int64_t row0, int64_t n, const float* thr,
+                              int cap, int* out_count, int32_t* out_rows, float* out_vals, int* out_status, int* out_kernel);
 /* the per-query screen bound E of the active screen dtype: exact cosine <= screen value + E  (bf16 screen: also
  * |screen value - exact cosine| <= E; int8 screen: the screen value already carries its row group's share of the bound) */
 int mi355dr_debug_screen_bound(mi355dr_index* idx, const float* queries, int B, float* out_E);

@@ -3,14 +3,9 @@
 import numpy as np
 import pytest
 
+from screen_ref import bf16_round as _bf16_round
+
 pytestmark = pytest.mark.gpu
-
-
-def _bf16_round(x: np.ndarray) -> np.ndarray:
-    """numpy emulation of round-to-nearest-even fp32 -> bf16 -> fp32."""
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
-    return u.astype(np.uint32).view(np.float32)
 
 
 @pytest.fixture(scope="module")
