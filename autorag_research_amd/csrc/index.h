@@ -155,6 +155,11 @@ struct mi355dr_index {
     mi355::DevBuf<double> mmr_cand_dist, mmr_out_dist;
     mi355::DevBuf<int64_t> mmr_cand_rows, mmr_out_rows;
     mi355::DevBuf<unsigned long long> mmr_pairs_dev;
+    // grouped search (mi355dr_search_groups* / mi355dr_merge_groups_device): the call's group offsets
+    // [G + 1], the sub-queries' lists [S, fetch_k] and the host form's result staging [G, k] / [G] -- grown by the calls
+    mi355::DevBuf<int32_t> grp_offsets, grp_count;
+    mi355::DevBuf<double> grp_cand_dist, grp_out_dist;
+    mi355::DevBuf<int64_t> grp_cand_rows, grp_out_rows;
     // a view (mi355dr_view_create; DESIGN.md "Views"): a read-only index built from listed rows / documents of a parent.  The
     // maps are null on every other index: the result-writing kernels then add row_offset instead
     bool is_view = false;
@@ -269,6 +274,8 @@ struct mi355dr_index {
     int64_t s_mss_searches = 0, s_mss_docs = 0, s_mss_screened = 0, s_mss_exact = 0, s_mss_fallbacks = 0;
     // mi355dr_search_mmr* / mi355dr_mmr_select: calls, queries, (picked row, unselected candidate) dots of k_mmr_select
     int64_t s_mmr_searches = 0, s_mmr_queries = 0, s_mmr_pairs = 0;
+    // mi355dr_search_groups*: calls, sub-queries; groups merged by them and by mi355dr_merge_groups_device
+    int64_t s_group_searches = 0, s_group_subqueries = 0, s_groups_merged = 0;
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
     mi355::EventPairs ev_pool, ev_pending;

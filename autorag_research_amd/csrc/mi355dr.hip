@@ -23,6 +23,7 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "k_block.h"
 #include "k_mmr.h"
 #include "mmr_order.h"
+#include "k_groups.h"
 
 using namespace mi355;
 
@@ -171,6 +172,8 @@ int ensure_qstate(mi355dr_index* idx) {
         return fail(idx, MI355DR_E_UNSUPPORTED, "dim too large for the select kernels' LDS budget");
     HIPCHECK(idx, hipFuncSetAttribute((const void*)k_mmr_select, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)mmr_lds_bytes(idx->dim, kMmrMax)));
+    HIPCHECK(idx, hipFuncSetAttribute((const void*)k_merge_groups, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)groups_lds_bytes(kSortMax)));
     idx->qstate_ready = true;  // (behind the last step that can fail)
     return MI355DR_OK;
 }
@@ -1843,6 +1846,130 @@ int mi355dr_mmr_select(mi355dr_index* idx, const float* queries, int B, int k, c
     return mmr_finish(idx, B);
 }
 
+// ---- grouped search: sub-query top-k lists fused into one per group (csrc/k_groups.h) -------------
+namespace {
+// the call's shape: S lists of `width` entries in G groups, k_out results per group.  *np_max: the padded size of the largest
+// group (a power of two, >= 1).  Nothing has been touched when this fails.
+int check_groups(mi355dr_index* idx, const char* what, int S, int width, const int32_t* offs, int G, int k_out, int* np_max) {
+    const std::string w(what);
+    if (G < 0 || S < 0) return fail(idx, MI355DR_E_INVALID, w + ": G and S must be >= 0");
+    if (width <= 0 || k_out <= 0) return fail(idx, MI355DR_E_INVALID, w + ": the list width and k must be > 0");
+    *np_max = 1;
+    if (G == 0) {
+        if (S != 0) return fail(idx, MI355DR_E_INVALID, w + ": group_offsets must end at S");
+        return MI355DR_OK;
+    }
+    if (!offs) return fail(idx, MI355DR_E_INVALID, w + ": group_offsets is null");
+    if (offs[0] != 0) return fail(idx, MI355DR_E_INVALID, w + ": group_offsets must start at 0");
+    int64_t largest = 0;
+    for (int g = 0; g < G; ++g) {
+        if (offs[g + 1] < offs[g]) return fail(idx, MI355DR_E_INVALID, w + ": group_offsets must not decrease");
+        largest = std::max(largest, (int64_t)(offs[g + 1] - offs[g]) * width);
+    }
+    if (offs[G] != S) return fail(idx, MI355DR_E_INVALID, w + ": group_offsets must end at S");
+    if (k_out > kSortMax) return fail(idx, MI355DR_E_UNSUPPORTED, w + ": k exceeds 4096");
+    if (largest > kSortMax) return fail(idx, MI355DR_E_UNSUPPORTED, w + ": a group holds more than 4096 entries");
+    *np_max = groups_pow2(largest);
+    return MI355DR_OK;
+}
+
+// the offsets into the handle's buffer, then ONE launch over all G groups; asynchronous on the stream (the caller waits:
+// `offs` is pageable host memory)
+int launch_groups(mi355dr_index* idx, hipStream_t s, const double* vals, const int64_t* rows, int width, const int32_t* offs,
+                  int G, int np_max, int k_out, double* out_vals, int64_t* out_rows, int32_t* out_count) {
+    HIPCHECK(idx, hipMemcpyAsync(idx->grp_offsets.p, offs, (size_t)(G + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_merge_groups, dim3(G), dim3(kGroupsThreads), groups_lds_bytes(np_max), s, vals, rows, width,
+                       idx->grp_offsets.p, np_max, k_out, out_vals, out_rows, out_count);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+// host == true: queries / outputs are host buffers staged through the index's own; else device buffers used in place
+int search_groups_impl(mi355dr_index* idx, const float* queries, const int32_t* offs, int G, int k, int fetch_k, double* out_dist,
+                       int64_t* out_rows, int32_t* out_count, hipStream_t s, bool host) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    if (G < 0 || k <= 0 || fetch_k <= 0) return fail(idx, MI355DR_E_INVALID, "search_groups: G must be >= 0, k and fetch_k > 0");
+    if (G > 0 && !offs) return fail(idx, MI355DR_E_INVALID, "search_groups: group_offsets is null");
+    const int S = G > 0 ? offs[G] : 0;
+    if (G > 0 && (!out_dist || !out_rows || (S > 0 && !queries))) return fail(idx, MI355DR_E_INVALID, "search_groups: null buffer");
+    if (fetch_k > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, "search_groups: fetch_k exceeds 1024");
+    int np_max = 1;
+    CHECK(check_groups(idx, "search_groups", S, fetch_k, offs, G, k, &np_max));
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_pending(idx));
+    if (G == 0) return MI355DR_OK;
+    if (!s) s = idx->stream;
+    CHECK(ensure_qstate(idx));
+    HIPCHECK(idx, idx->grp_offsets.grow((size_t)(G + 1) * sizeof(int32_t)));
+    HIPCHECK(idx, idx->grp_cand_dist.grow((size_t)std::max(S, 1) * fetch_k * sizeof(double)));
+    HIPCHECK(idx, idx->grp_cand_rows.grow((size_t)std::max(S, 1) * fetch_k * sizeof(int64_t)));
+    if (host) {
+        HIPCHECK(idx, idx->grp_out_dist.grow((size_t)G * k * sizeof(double)));
+        HIPCHECK(idx, idx->grp_out_rows.grow((size_t)G * k * sizeof(int64_t)));
+        HIPCHECK(idx, idx->grp_count.grow((size_t)G * sizeof(int32_t)));
+    }
+    // the ordinary search of every sub-query at fetch_k (screened, fix-ups completed), block by block ...
+    for (int b0 = 0; b0 < S; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, S - b0);
+        const float* q = queries + (int64_t)b0 * idx->dim;
+        if (host) {
+            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q, (size_t)nb * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
+            q = idx->qdev;
+        }
+        CHECK(search_block(idx, s, q, nb, fetch_k, idx->grp_cand_dist.p + (int64_t)b0 * fetch_k,
+                           idx->grp_cand_rows.p + (int64_t)b0 * fetch_k));
+    }
+    // ... then one merge behind all of them: a group may straddle two blocks
+    double* od = host ? idx->grp_out_dist.p : out_dist;
+    int64_t* orow = host ? idx->grp_out_rows.p : out_rows;
+    int32_t* oc = !out_count ? nullptr : host ? idx->grp_count.p : out_count;
+    CHECK(launch_groups(idx, s, idx->grp_cand_dist.p, idx->grp_cand_rows.p, fetch_k, offs, G, np_max, k, od, orow, oc));
+    if (host) {
+        HIPCHECK(idx, hipMemcpyAsync(out_dist, od, (size_t)G * k * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipMemcpyAsync(out_rows, orow, (size_t)G * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        if (oc) HIPCHECK(idx, hipMemcpyAsync(out_count, oc, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    idx->s_group_searches++;
+    idx->s_group_subqueries += S;
+    idx->s_groups_merged += G;
+    return MI355DR_OK;
+}
+}  // namespace
+
+int mi355dr_merge_groups_device(mi355dr_index* idx, const double* vals_dev, const int64_t* rows_dev, int S, int width,
+                                const int32_t* group_offsets, int G, int k_out, double* out_vals_dev, int64_t* out_rows_dev,
+                                int32_t* out_count_dev, void* stream) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    int np_max = 1;
+    CHECK(check_groups(idx, "merge_groups", S, width, group_offsets, G, k_out, &np_max));
+    if (G > 0 && (!out_vals_dev || !out_rows_dev || (S > 0 && (!vals_dev || !rows_dev))))
+        return fail(idx, MI355DR_E_INVALID, "merge_groups: null buffer");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (G == 0) return MI355DR_OK;
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(ensure_qstate(idx));
+    HIPCHECK(idx, idx->grp_offsets.grow((size_t)(G + 1) * sizeof(int32_t)));
+    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
+    CHECK(launch_groups(idx, s, vals_dev, rows_dev, width, group_offsets, G, np_max, k_out, out_vals_dev, out_rows_dev,
+                        out_count_dev));
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    idx->s_groups_merged += G;
+    return MI355DR_OK;
+}
+
+int mi355dr_search_groups(mi355dr_index* idx, const float* queries, const int32_t* group_offsets, int G, int k, int fetch_k,
+                          double* out_dist, int64_t* out_rows, int32_t* out_count) {
+    return search_groups_impl(idx, queries, group_offsets, G, k, fetch_k, out_dist, out_rows, out_count, nullptr, /*host=*/true);
+}
+
+int mi355dr_search_groups_device(mi355dr_index* idx, const float* queries_dev, const int32_t* group_offsets, int G, int k,
+                                 int fetch_k, double* out_dist_dev, int64_t* out_rows_dev, int32_t* out_count_dev, void* stream) {
+    return search_groups_impl(idx, queries_dev, group_offsets, G, k, fetch_k, out_dist_dev, out_rows_dev, out_count_dev,
+                              (hipStream_t)stream, /*host=*/false);
+}
+
 int mi355dr_merge_topk_device(mi355dr_index* idx, const double* dist_all_dev, const int64_t* rows_all_dev, int world,
                               int B, int k, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
@@ -1994,6 +2121,9 @@ const Stat kStats[] = {
     {"mmr_searches", &Index::s_mmr_searches, true},
     {"mmr_queries", &Index::s_mmr_queries, true},
     {"mmr_pairs_scored", &Index::s_mmr_pairs, true},
+    {"group_searches", &Index::s_group_searches, true},
+    {"group_subqueries", &Index::s_group_subqueries, true},
+    {"groups_merged", &Index::s_groups_merged, true},
     {"compactions", &Index::s_compactions, true},
     {"compact_moved_rows", &Index::s_compact_moved_rows, true},
     {"view", nullptr, false, [](const Index* x) -> int64_t { return x->is_view ? 1 : 0; }},

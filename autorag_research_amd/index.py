@@ -250,6 +250,86 @@ class Mi355Index:
                                                     ptr(rows, ctypes.c_int64)))
         return dist, rows
 
+    # ---- grouped search: sub-query lists fused into one per group on the device (include/mi355dr.h "grouped search") ----
+    @staticmethod
+    def _group_offsets(group_offsets) -> np.ndarray:
+        offs = np.ascontiguousarray(group_offsets, dtype=np.int32)
+        if offs.ndim != 1 or offs.shape[0] < 1:
+            raise ValueError("group_offsets must be one-dimensional [G + 1]")
+        return offs
+
+    def search_groups(self, queries, group_offsets, k: int, fetch_k: int | None = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Several searches per question, fused on the device: group g owns sub-queries group_offsets[g] ..
+        group_offsets[g + 1] - 1 of `queries` [S, dim]; every sub-query is searched at `fetch_k` (default k) and the lists of
+        a group become one -- every row once, at its smallest distance, in the order of `search`.  Returns (distance float64
+        [G,k], rows int64 [G,k], count int32 [G] = distinct rows in the group's union); NaN / -1 padded."""
+        offs = self._group_offsets(group_offsets)
+        G = offs.shape[0] - 1
+        q = f32c(queries)
+        q = q.reshape(0, self.dim) if q.size == 0 else self._queries_2d(q)
+        if q.shape[0] != int(offs[-1]):
+            raise ValueError(f"group_offsets must end at the number of queries ({q.shape[0]}), got {int(offs[-1])}")
+        fetch_k = int(k if fetch_k is None else fetch_k)
+        dist = np.empty((G, k), dtype=np.float64)
+        rows = np.empty((G, k), dtype=np.int64)
+        count = np.empty(G, dtype=np.int32)
+        check(self._h, self._lib.mi355dr_search_groups(self._h, ptr(q, ctypes.c_float), ptr(offs, ctypes.c_int32), G, int(k),
+                                                       fetch_k, ptr(dist, ctypes.c_double), ptr(rows, ctypes.c_int64),
+                                                       ptr(count, ctypes.c_int32)))
+        return dist, rows, count
+
+    def search_groups_device(self, q_ptr: int, group_offsets, k: int, fetch_k: int, out_dist_ptr: int, out_rows_ptr: int,
+                             out_count_ptr: int | None = None, stream: int | None = None) -> None:
+        """The same with queries ([group_offsets[-1], dim] fp32) and outputs (float64 [G,k], int64 [G,k], int32 [G] or
+        None) in device memory; `group_offsets` stays on the host.  Complete on return."""
+        offs = self._group_offsets(group_offsets)
+        check(self._h, self._lib.mi355dr_search_groups_device(
+            self._h, ctypes.c_void_p(int(q_ptr)), ptr(offs, ctypes.c_int32), offs.shape[0] - 1, int(k), int(fetch_k),
+            ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
+            ctypes.c_void_p(int(out_count_ptr) if out_count_ptr else None), ctypes.c_void_p(int(stream) if stream else None)))
+
+    def merge_groups_device(self, vals_ptr: int, rows_ptr: int, S: int, width: int, group_offsets, k: int, out_vals_ptr: int,
+                            out_rows_ptr: int, out_count_ptr: int | None = None, stream: int | None = None) -> None:
+        """The merge alone over device lists (float64 / int64 [S, width]); `group_offsets` stays on the host."""
+        offs = self._group_offsets(group_offsets)
+        check(self._h, self._lib.mi355dr_merge_groups_device(
+            self._h, ctypes.c_void_p(int(vals_ptr)), ctypes.c_void_p(int(rows_ptr)), int(S), int(width),
+            ptr(offs, ctypes.c_int32), offs.shape[0] - 1, int(k), ctypes.c_void_p(int(out_vals_ptr)),
+            ctypes.c_void_p(int(out_rows_ptr)), ctypes.c_void_p(int(out_count_ptr) if out_count_ptr else None),
+            ctypes.c_void_p(int(stream) if stream else None)))
+
+    def merge_groups(self, vals, rows, group_offsets, k: int, want_count: bool = True):
+        """Fuse host lists on the device: vals float64 [S, width] (any doubles: distances, negated scores), rows int64
+        [S, width] (-1 = no entry), group g = lists group_offsets[g] .. group_offsets[g + 1] - 1.  Every row once, at its
+        smallest value (NaN last), sorted by (value, row); returns (vals [G,k], rows [G,k], count [G]) -- count is None with
+        want_count=False (the kernel then writes none)."""
+        v = np.ascontiguousarray(vals, dtype=np.float64)
+        r = np.ascontiguousarray(rows, dtype=np.int64)
+        if v.ndim != 2 or r.shape != v.shape:
+            raise ValueError("vals and rows must both be [S, width]")
+        offs = self._group_offsets(group_offsets)
+        G, (S, width) = offs.shape[0] - 1, v.shape
+        out_v = np.empty((G, k), dtype=np.float64)
+        out_r = np.empty((G, k), dtype=np.int64)
+        out_c = np.empty(G, dtype=np.int32) if want_count else None
+        bufs = []
+        try:
+            for nbytes in (max(v.nbytes, 8), max(r.nbytes, 8), max(out_v.nbytes, 8), max(out_r.nbytes, 8), max(4 * G, 8)):
+                bufs.append(self.dev_alloc(nbytes))
+            if v.size:
+                self.dev_upload(bufs[0], v)
+                self.dev_upload(bufs[1], r)
+            self.merge_groups_device(bufs[0], bufs[1], S, width, offs, k, bufs[2], bufs[3], bufs[4] if want_count else None)
+            if G:
+                self.dev_download(bufs[2], out_v)
+                self.dev_download(bufs[3], out_r)
+                if want_count:
+                    self.dev_download(bufs[4], out_c)
+        finally:
+            for b in bufs:
+                self.dev_free(b)
+        return out_v, out_r, out_c
+
     # ---- views: a listed subset as an index of its own (include/mi355dr.h "views") ----
     def view(self, row_ids=None, doc_ids=None) -> "Mi355Index":
         """The listed rows and / or documents of this index as a read-only index of their own, built on the device

@@ -706,6 +706,55 @@ class Mi355RetrievalService:
             return []
         return self._single_block(np.asarray(embedding, dtype=np.float32)[None, :], top_k, unit, within, mmr_fetch_k, mmr_lambda)[0]
 
+    def vector_search_groups(self, embeddings_per_query: list, top_k: int, fetch_k: int | None = None, unit: str = "chunk",
+                             search_mode: Literal["single", "multi"] = "single") -> list[list[dict]]:
+        """Several searches per question, fused on the device (not in the reference's service: its callers loop in Python,
+        e.g. question_decomposition.py:203-220).  `embeddings_per_query[g]` lists the embeddings of question g -- vectors in
+        single mode, [n_q, d] matrices in multi mode; every one is searched at `fetch_k` (default top_k) and the lists of a
+        question become one: every chunk once, at its best score, the best `top_k` of them.  One result list per question,
+        in the reference's order (-score, str(doc_id)).
+        single: Mi355Index.search_groups; score = 1.0 - distance, as `_single_block` computes it.
+        multi: one `search_maxsim` over all sub-queries, then Mi355Index.merge_groups over val = -(-distance / n_q) in
+        float64 -- sub-queries differ in token count, so scores are merged, not distances; score = -val is bit for bit what
+        `maxsim_search_by_embeddings` reports.
+        Documented difference: the cut at `top_k` is made by (distance, index row) in single mode and (-score, document row)
+        in multi mode, so an exact score tie that straddles the cut may keep another member of the tie than the reference's
+        (-score, str(doc_id)) order would."""
+        fetch_k = int(top_k if fetch_k is None else fetch_k)
+        u = self._unit(unit)
+        out: list[list[dict]] = [[] for _ in embeddings_per_query]
+        if search_mode == "multi":
+            ix = u.multi_searcher(self._world)
+            dim = u.table.mv_tokens.shape[1]
+            mats, sizes = [], []
+            for embs in embeddings_per_query:
+                ms = [m for m in (np.asarray(e, dtype=np.float32).reshape(-1, dim) for e in embs) if m.shape[0] > 0]
+                mats.extend(ms)   # (no query vectors: no results -- `maxsim_search_by_embeddings`)
+                sizes.append(len(ms))
+            if not mats:
+                return out
+            lens = np.asarray([m.shape[0] for m in mats], dtype=np.int64)
+            qoff = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+            dist, rows = ix.search_maxsim(np.concatenate(mats, axis=0), qoff, fetch_k)
+            vals = -(-np.asarray(dist).astype(np.float64) / lens[:, None])
+            merger = ix if hasattr(ix, "merge_groups") else ix.index   # (a ShardedSearcher's lists are global on every rank)
+            vals, rows, _ = merger.merge_groups(vals, np.asarray(rows, dtype=np.int64), self._offsets_of(sizes), top_k)
+            scores, pos_of_row = -vals, u.multi_rows
+        else:
+            searcher = u.single_searcher(self._world)
+            sizes = [len(embs) for embs in embeddings_per_query]
+            if sum(sizes) == 0:
+                return out
+            Q = np.stack([np.asarray(e, dtype=np.float32) for embs in embeddings_per_query for e in embs])
+            dist, rows, _ = searcher.search_groups(Q, self._offsets_of(sizes), top_k, fetch_k)
+            scores, pos_of_row = 1.0 - dist, u.single_rows
+        block = self._results_from_block(u.table, pos_of_row, rows, scores, unit == "chunk")
+        return [sorted(res, key=lambda r: (-r["score"], str(r["doc_id"]))) for res in block]
+
+    @staticmethod
+    def _offsets_of(sizes: list[int]) -> np.ndarray:
+        return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+
     def score_candidates(self, embedding: list[float], doc_ids: list, unit: str = "chunk") -> dict:
         """Dense score of explicit candidates: {doc_id: 1.0 - cosine distance}, the score `vector_search_by_embedding` gives
         the same chunk (Python float arithmetic).  Ids unknown to the table or without a stored embedding are left out (as

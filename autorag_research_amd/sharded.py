@@ -61,6 +61,37 @@ def merge_topk_host(dist_all: np.ndarray, rows_all: np.ndarray, k: int) -> tuple
     return out_d, out_r
 
 
+def merge_groups_host(vals: np.ndarray, rows: np.ndarray, group_offsets, k: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The grouped merge of Mi355Index.merge_groups in numpy (include/mi355dr.h "grouped search"): vals float64 / rows int64
+    [S, width], group g = lists group_offsets[g] .. group_offsets[g + 1] - 1 -> (vals [G,k], rows [G,k], count int32 [G]).
+    Every row with an id >= 0 once, at its smallest value (NaN last), sorted by (value, row); NaN / -1 padded.  Values order
+    by their bits, as on the device: the sign-magnitude image of the int64 view, so -0.0 comes before +0.0."""
+    vals = np.ascontiguousarray(vals, dtype=np.float64)
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    offs = np.asarray(group_offsets, dtype=np.int64)
+    G = offs.shape[0] - 1
+    out_v = np.full((G, k), np.nan)
+    out_r = np.full((G, k), -1, dtype=np.int64)
+    count = np.zeros(G, dtype=np.int32)
+    for g in range(G):
+        v = vals[offs[g]:offs[g + 1]].reshape(-1)
+        r = rows[offs[g]:offs[g + 1]].reshape(-1)
+        v, r = v[r >= 0], r[r >= 0]
+        bits = v.view(np.int64)
+        nan = np.isnan(v)
+        order_key = bits ^ ((bits >> 63) & np.int64(0x7FFFFFFFFFFFFFFF))  # signed compare == (value asc, -0.0 < +0.0)
+        order_key = np.where(nan, np.int64(0), order_key)  # every NaN is one key, whatever its sign or payload: rows decide
+        best: dict[int, int] = {}  # row -> position of its best occurrence
+        for i in np.lexsort((order_key, nan)):  # best first: a row's first sight is the one that stays
+            best.setdefault(int(r[i]), int(i))
+        kept = np.fromiter(best.values(), dtype=np.int64, count=len(best))
+        count[g] = kept.size
+        kept = kept[np.lexsort((r[kept], order_key[kept], nan[kept]))][:k]
+        out_v[g, :kept.size] = np.where(nan[kept], np.nan, v[kept])
+        out_r[g, :kept.size] = r[kept]
+    return out_v, out_r, count
+
+
 def resident_bytes_per_row(dim: int) -> int:
     """HBM bytes one stored row costs in libmi355dr: fp32 row + bf16 shadow (64-element pad) + int8 shadow (128-element
     pad) + squared norm + int8 flag."""
@@ -302,6 +333,28 @@ class ShardedSearcher:
             out_d[b0:b0 + nb], out_r[b0:b0 + nb] = merge_topk_host(np.ascontiguousarray(g[:, 0]).view(np.float64),
                                                                    np.ascontiguousarray(g[:, 1]), k)
         return out_d, out_r
+
+    def search_groups(self, queries, group_offsets, k: int, fetch_k: int | None = None, block: int = 1024):
+        """Mi355Index.search_groups over a row-sharded corpus: sub-queries group_offsets[g] .. group_offsets[g + 1] - 1 of
+        `queries` belong to group g.  `search(queries, fetch_k)` already is the single-GPU lists bit for bit on every rank, so
+        the grouped merge runs locally behind it -- on the device where the index offers `merge_groups`, in numpy
+        (`merge_groups_host`) on a stand-in without it -- and needs no further collective.  Returns (distance [G,k], rows
+        [G,k], count [G])."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        fetch_k = int(k if fetch_k is None else fetch_k)
+        if self.world == 1 and not self.force_pipeline and hasattr(self.index, "search_groups"):
+            return self.index.search_groups(q, group_offsets, k, fetch_k)
+        offs = np.ascontiguousarray(group_offsets, dtype=np.int32)
+        if offs.ndim != 1 or offs.shape[0] < 1 or offs[0] != 0 or (np.diff(offs) < 0).any() or int(offs[-1]) != q.shape[0]:
+            raise ValueError("group_offsets must start at 0, not decrease and end at the number of queries")
+        if q.shape[0]:
+            dist, rows = self.search(q, fetch_k, block)
+        else:
+            dist, rows = np.empty((0, fetch_k)), np.empty((0, fetch_k), dtype=np.int64)
+        merge = getattr(self.index, "merge_groups", None)
+        return merge(dist, rows, offs, k) if merge is not None else merge_groups_host(dist, rows, offs, k)
 
     def score_subset(self, queries, row_ids) -> np.ndarray:
         """Exact distance of every query to its OWN candidates (global rows, [B, m]) over a row-sharded corpus: every rank scores

@@ -219,6 +219,43 @@ int mi355dr_search_mmr_device(mi355dr_index* idx, const float* queries_dev, int 
 int mi355dr_mmr_select(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* cand_rows /* host [B, m] */, int m,
                        double lambda, double* out_dist, int64_t* out_rows); /* all host */
 
+/* ---- grouped search: sub-query top-k lists fused into one on the device ----
+ * Several searches per question -- the question and its decomposed sub-questions, several hypothetical passages, a set of
+ * rewrites -- fused by "every row once, at its best value".  The lists never leave the device.
+ *   Input: S lists of `width` (value, row) entries and G groups; group g owns lists group_offsets[g] .. group_offsets[g+1]-1
+ *     (HOST int32 [G+1], starting at 0, not decreasing, ending at S).  An entry with row < 0 is no entry; an entry with a row
+ *     and a NaN value is one (an irregular row's result).
+ *   Result of group g: the union of its lists' entries, each row ONCE at its smallest value under the library's order
+ *     (value asc, NaN last -- a row keeps a NaN only if every occurrence was NaN), sorted by (value asc, NaN last, row asc);
+ *     the first k_out of them.  A number is written with the bits it came with (+0.0 and -0.0 are different values, -0.0
+ *     first), a NaN as the library's NaN; rows are int64 as given.  Slots behind the union: NaN / -1.  count[g] = the number of
+ *     distinct rows in the union (it may exceed k_out); an empty group gives NaN / -1 and 0.  Values are plain doubles: the
+ *     MaxSim callers merge scores.
+ *   mi355dr_merge_groups_device: the merge alone, over device lists.  Stateless (it reads no index state: allowed on a view,
+ *     like mi355dr_merge_topk*); the offsets are copied into a buffer the index owns and grows; under the handle's mutex;
+ *     complete on return; a failed allocation returns MI355DR_E_NOMEM with nothing changed.  out_count_dev may be NULL.
+ *   mi355dr_search_groups / _device: the ordinary search of all S = group_offsets[G] sub-queries at fetch_k (the code of
+ *     mi355dr_search_device: screened, fix-ups completed, internal blocks of 1024 queries; a group may straddle two) into
+ *     buffers the index owns and grows, then ONE merge launch on the same stream.  Group g's result is the top-k under
+ *     (distance asc, NaN last, row asc) of the union of its sub-queries' top-fetch_k lists, each row once at its smallest
+ *     distance, with the bits the search returned and global rows.  k may exceed fetch_k (up to max_g(s_g) x fetch_k entries
+ *     exist; the rest is NaN / -1).  Works on views (results under the parent's ids): it takes no global ids.  First completes
+ *     what is in flight; complete on return.
+ *   MI355DR_E_INVALID: G < 0, S < 0, k_out / k / fetch_k / width <= 0, a null pointer with work to do, offsets that do not start
+ *     at 0, decrease, or do not end at S.  MI355DR_E_UNSUPPORTED: fetch_k > 1024, k_out / k > 4096, a group of more than 4096
+ *     entries (s_g x width; the kernel sorts next_pow2 of it in 64 KiB of LDS).  G == 0 is a valid no-op.  A refused call
+ *     changes nothing.
+ *   Stats: "group_searches" (calls of mi355dr_search_groups*), "group_subqueries" (S, summed), "groups_merged" (groups merged,
+ *     both entry families). */
+int mi355dr_merge_groups_device(mi355dr_index* idx, const double* vals_dev, const int64_t* rows_dev, int S, int width,
+                                const int32_t* group_offsets /* HOST [G+1] */, int G, int k_out, double* out_vals_dev,
+                                int64_t* out_rows_dev, int32_t* out_count_dev /* may be NULL */, void* stream);
+int mi355dr_search_groups(mi355dr_index* idx, const float* queries /* host [S, dim] */, const int32_t* group_offsets, int G, int k,
+                          int fetch_k, double* out_dist /* [G,k] */, int64_t* out_rows /* [G,k] */,
+                          int32_t* out_count /* [G] or NULL */); /* all host */
+int mi355dr_search_groups_device(mi355dr_index* idx, const float* queries_dev, const int32_t* group_offsets /* HOST */, int G, int k,
+                                 int fetch_k, double* out_dist_dev, int64_t* out_rows_dev, int32_t* out_count_dev, void* stream);
+
 /* ---- views: a listed subset of rows / documents as an index of its own ----
  * For a list that is searched again and again -- one tenant, one document collection, one PDF's pages: the key filter of the
  * statement above, fixed for many query blocks.  mi355dr_search_subset scans the list exactly on every call (cost ~ m x B, no
@@ -249,7 +286,7 @@ int mi355dr_mmr_select(mi355dr_index* idx, const float* queries, int B, int k, c
  *     "row_offset" return MI355DR_E_INVALID on a view and change nothing.  So does every entry point that takes global ids or a
  *     communicator, with an error text that refers the caller to the parent: mi355dr_search_subset*, _score_subset, _search_mmr*, _mmr_select,
  *     _maxsim_subset*, _search_maxsim_subset*, _gqr_refine, _gqr_refine_maxsim, _comm_init*, _search_sharded_device, and mi355dr_view_create itself (no
- *     views of views).  The stateless ones stay usable: mi355dr_merge_topk*, _pack_topk_device, _gqr_refine_scores.
+ *     views of views).  The stateless ones stay usable: mi355dr_merge_topk*, _pack_topk_device, _gqr_refine_scores, _merge_groups_device.
  *   The call takes the parent's mutex, first completes whatever search is in flight there, and is complete on return;
  *     afterwards the two handles are independent.  The parent is only read.  On any error *out_view is NULL, everything
  *     allocated for the view has been released and the parent is unchanged and usable (its last_error has the text); a failed
@@ -483,6 +520,7 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
  *          (32-token blocks its relayouts copied; 0 on the in-place path), "subset_searches" / "subset_rows_scored" /
  *          "subset_rerun_queries" (mi355dr_search_subset: calls, pairs scored, queries re-run in list-sized pieces),
  *          "mmr_searches" / "mmr_queries" / "mmr_pairs_scored" (mi355dr_search_mmr* and mi355dr_mmr_select, described there),
+ *          "group_searches" / "group_subqueries" / "groups_merged" (mi355dr_search_groups* and mi355dr_merge_groups_device, described there),
  *          "maxsim_subset_searches" / "maxsim_subset_docs" / "maxsim_subset_screened" / "maxsim_subset_exact" /
  *          "maxsim_subset_fallbacks" (mi355dr_search_maxsim_subset, described there),
  *          "view" / "view_rows" / "view_docs" (mi355dr_view_create: 1 on a view / the rows / the documents it holds),
