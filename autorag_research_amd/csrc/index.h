@@ -160,6 +160,17 @@ struct mi355dr_index {
     mi355::DevBuf<int32_t> grp_offsets, grp_count;
     mi355::DevBuf<double> grp_cand_dist, grp_out_dist;
     mi355::DevBuf<int64_t> grp_cand_rows, grp_out_rows;
+    // range search (mi355dr_search_range*): one block's result buffers [nb, range_slots] with their
+    // per-query words, the radii, the redo list, the two device counters, the host forms' result staging [nb, max_results] /
+    // [nb] and the sub-block of the queries the ordinary search serves -- grown by ensure_range
+    mi355::DevBuf<uint64_t> rng_key, rng_rkey;
+    mi355::DevBuf<int32_t> rng_row, rng_xfrom;
+    mi355::DevBuf<unsigned long long> rng_count, rng_stat;
+    mi355::DevBuf<double> rng_radius, rng_out_dist, rng_fb_dist;
+    mi355::DevBuf<int> rng_redo, rng_flag, rng_fb_map;
+    mi355::DevBuf<int64_t> rng_out_rows, rng_out_count, rng_fb_rows;
+    mi355::DevBuf<float> rng_fb_q;
+    int rng_collect_lds = 0;  // dynamic LDS k_range_collect is registered for (0: not yet)
     // a view (mi355dr_view_create; DESIGN.md "Views"): a read-only index built from listed rows / documents of a parent.  The
     // maps are null on every other index: the result-writing kernels then add row_offset instead
     bool is_view = false;
@@ -242,6 +253,11 @@ struct mi355dr_index {
     int chunk_taper_x100 = 0;   // 0 = auto: 120 for passes of the two-wave prune (measured -1 % at k = 100), 100 otherwise (k = 10: no gain)
     int64_t compact_slice_rows = 65536;  // mi355dr_compact: destination rows per slice of its staging buffer (option "compact_slice_rows", 32 ... 2^22)
     int64_t view_slice_rows = 65536;  // mi355dr_view_create on THIS index: rows per slice of its staging buffer (option "view_slice_rows", 32 ... 2^22)
+    // mi355dr_search_range*: rows per screen launch / exact-scan span (option "range_chunk_rows": 10 M rows are 5 launches, each
+    // long enough to run at the long screens' rate) and slots of a query's result buffer (option "range_slots", 16 ... 4096 =
+    // what the finishing sort holds; never below the call's max_results)
+    int64_t range_chunk_rows = (int64_t)1 << 21;
+    int range_slots = mi355::kSortMax;
     int64_t starter_rows_wide = 65536;  // the starter's sample at 33 <= k <= 128 (option "starter_rows_wide", tuning: 4096 ... 262144)
 
     // stats
@@ -276,6 +292,10 @@ struct mi355dr_index {
     int64_t s_mmr_searches = 0, s_mmr_queries = 0, s_mmr_pairs = 0;
     // mi355dr_search_groups*: calls, sub-queries; groups merged by them and by mi355dr_merge_groups_device
     int64_t s_group_searches = 0, s_group_subqueries = 0, s_groups_merged = 0;
+    // mi355dr_search_range*: calls, queries, rows in range (the counts, summed); screen path: candidates taken from the screens
+    // and of them re-scored; (query, chunk) pairs run again on the exact path; queries whose list the ordinary search served
+    int64_t s_range_searches = 0, s_range_queries = 0, s_range_in_range = 0, s_range_candidates = 0, s_range_rescored = 0,
+            s_range_redo_chunks = 0, s_range_fallback_queries = 0;
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
     mi355::EventPairs ev_pool, ev_pending;

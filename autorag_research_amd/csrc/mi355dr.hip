@@ -24,6 +24,7 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "k_mmr.h"
 #include "mmr_order.h"
 #include "k_groups.h"
+#include "k_range.h"
 
 using namespace mi355;
 
@@ -1970,6 +1971,308 @@ int mi355dr_search_groups_device(mi355dr_index* idx, const float* queries_dev, c
                               (hipStream_t)stream, /*host=*/false);
 }
 
+// ---- range search: every row within a distance, counted on the device (csrc/k_range.h) ------------
+namespace {
+struct RangeSpan {
+    int64_t r0, r1;
+};
+
+// slots of a query's result buffer: the option, never below the call's max_results (<= kKMax <= kSortMax)
+inline int range_slots_for(const mi355dr_index* idx, int m) { return std::max(idx->range_slots, m); }
+
+// the handle's range buffers for a block of nb queries, R slots each, a redo list of `pairs` pairs and (host forms) nb x m
+// results; registers k_range_collect's LDS once.  A failure leaves the buffers it already grew: they are only ever larger.
+int ensure_range(mi355dr_index* idx, int nb, int R, int m, int64_t pairs, bool host) {
+    HIPCHECK(idx, idx->rng_key.grow((size_t)nb * R * sizeof(uint64_t)));
+    HIPCHECK(idx, idx->rng_row.grow((size_t)nb * R * sizeof(int32_t)));
+    HIPCHECK(idx, idx->rng_count.grow((size_t)nb * sizeof(unsigned long long)));
+    HIPCHECK(idx, idx->rng_rkey.grow((size_t)nb * sizeof(uint64_t)));
+    HIPCHECK(idx, idx->rng_xfrom.grow((size_t)nb * sizeof(int32_t)));
+    HIPCHECK(idx, idx->rng_radius.grow((size_t)nb * sizeof(double)));
+    HIPCHECK(idx, idx->rng_flag.grow((size_t)nb * sizeof(int)));
+    HIPCHECK(idx, idx->rng_stat.grow(2 * sizeof(unsigned long long)));
+    HIPCHECK(idx, idx->rng_redo.grow((size_t)(2 + 2 * pairs) * sizeof(int)));
+    HIPCHECK(idx, idx->rng_fb_map.grow((size_t)nb * sizeof(int)));
+    HIPCHECK(idx, idx->rng_fb_q.grow((size_t)nb * idx->dim * sizeof(float)));
+    HIPCHECK(idx, idx->rng_fb_dist.grow((size_t)nb * m * sizeof(double)));
+    HIPCHECK(idx, idx->rng_fb_rows.grow((size_t)nb * m * sizeof(int64_t)));
+    if (host) {
+        HIPCHECK(idx, idx->rng_out_dist.grow((size_t)nb * m * sizeof(double)));
+        HIPCHECK(idx, idx->rng_out_rows.grow((size_t)nb * m * sizeof(int64_t)));
+        HIPCHECK(idx, idx->rng_out_count.grow((size_t)nb * sizeof(int64_t)));
+    }
+    if (idx->rng_collect_lds == 0) {
+        const size_t lds = range_collect_lds(idx->dim);
+        if (lds > 160 * 1024) return fail(idx, MI355DR_E_UNSUPPORTED, "dim too large for the range kernels' LDS budget");
+        HIPCHECK(idx, hipFuncSetAttribute((const void*)k_range_collect, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        idx->rng_collect_lds = (int)lds;
+    }
+    return MI355DR_OK;
+}
+
+RangeState range_state(const mi355dr_index* idx, int R, int64_t pairs) {
+    RangeState rs{};
+    rs.key = idx->rng_key;
+    rs.row = idx->rng_row;
+    rs.count = idx->rng_count;
+    rs.rkey = idx->rng_rkey;
+    rs.xfrom = idx->rng_xfrom;
+    rs.redo = idx->rng_redo;
+    rs.redo_cap = (int)pairs;
+    rs.stat = idx->rng_stat;
+    rs.flag = idx->rng_flag;
+    rs.R = R;
+    return rs;
+}
+
+// k_range_collect over the block's nq queries (qlist == nullptr: queries 0 .. nq-1) behind the launch that filled their lists
+int launch_range_collect(mi355dr_index* idx, hipStream_t s, const RangeState& rs, int form, int nq, const int* qlist, int cap,
+                         int span, int64_t row0) {
+    RangeCollectArgs ca{};
+    ca.rows = idx->rows;
+    ca.nrm2 = idx->nrm2;
+    ca.q = idx->qdev;
+    ca.st = idx->st;
+    ca.rs = rs;
+    ca.cand_row = idx->cand_row;
+    ca.cand_val = idx->cand_val;
+    ca.qlist = qlist;
+    ca.flag8 = form != kRangeFormExact && use_i8(idx) ? idx->flag8.p : nullptr;
+    ca.cap = cap;
+    ca.d = idx->dim;
+    ca.metric = idx->metric;
+    ca.form = form;
+    ca.span = span;
+    ca.row0 = row0;
+    ca.n_rows = idx->n;
+    hipLaunchKernelGGL(k_range_collect, dim3(nq), dim3(kRangeThreads), range_collect_lds(idx->dim), s, ca);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+// exact range scan of rows [r0, r1) for the queries in qlist_dev[0 .. nq_all): groups of kScanQ, the scan launches as they
+// are (their fixed thresholds were preset by k_range_prep), each followed by the exact form of k_range_collect
+int range_scan_span(mi355dr_index* idx, hipStream_t s, const RangeState& rs, int nq_all, int cap, int span, int64_t r0, int64_t r1) {
+    for (int off = 0; off < nq_all; off += kScanQ) {
+        const int nq = std::min(kScanQ, nq_all - off);
+        ScanArgs sa{};
+        sa.rows = idx->rows;
+        sa.nrm2 = idx->nrm2;
+        sa.q = idx->qdev;
+        sa.st = idx->st;
+        sa.cand_row = idx->cand_row;
+        sa.cand_val = idx->cand_val;
+        sa.qlist = idx->qlist_dev + off;
+        sa.nq = nq;
+        sa.cap = cap;
+        sa.d = idx->dim;
+        sa.metric = idx->metric;
+        sa.row0 = r0;
+        sa.row1 = r1;
+        const int64_t grid = (r1 - r0 + kScanThreads - 1) / kScanThreads;
+        if (idx->dim % kScan32PieceCols == 0 && idx->scan_dma)
+            hipLaunchKernelGGL(k_scan32, dim3((unsigned)grid), dim3(kScanThreads), kScan32Lds, s, sa, idx->n);
+        else
+            hipLaunchKernelGGL(k_scan, dim3((unsigned)grid), dim3(kScanThreads), scan_lds_bytes(idx->dim, nq), s, sa);
+        HIPCHECK(idx, hipGetLastError());
+        CHECK(launch_range_collect(idx, s, rs, kRangeFormExact, nq, idx->qlist_dev + off, cap, span, r0));
+    }
+    return MI355DR_OK;
+}
+
+// one block of nb <= kQBlockMax device-resident queries -> device outputs [nb, m] / [nb], complete on return
+int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, const double* radius, int m, double* od,
+                int64_t* orow, int64_t* ocount, bool host) {
+    // the screens' element type and the lists' stride follow k_now: 1 keeps the int8 screen wherever AUTO has it at all and
+    // the lists at option "cand_cap".  An ordinary search sets both words again before its first launch; they are put back
+    // all the same (stat "screen_dtype_active" reads k_now)
+    struct Restore {
+        mi355dr_index* idx;
+        int k_now;
+        bool screening_now;
+        ~Restore() {
+            idx->k_now = k_now;
+            idx->screening_now = screening_now;
+        }
+    } restore{idx, idx->k_now, idx->screening_now};
+    idx->k_now = 1;
+    idx->screening_now = false;
+    const int cap = cap_now(idx);
+    if (idx->screen_dtype == MI355DR_SCREEN_I8 && !i8_available(idx) && idx->path != MI355DR_PATH_SCAN)
+        return fail(idx, MI355DR_E_UNSUPPORTED, "int8 screen unavailable: too many rows outside the residual limit");
+    const bool i8 = use_i8(idx);
+    const bool screen_possible = i8 ? i8_available(idx) : idx->irr_n <= kIrrCap;
+    const bool use_screen = idx->n > 0 && screen_possible && idx->path != MI355DR_PATH_SCAN;
+    if (idx->path == MI355DR_PATH_SCREEN && !screen_possible && idx->n > 0)
+        return fail(idx, MI355DR_E_UNSUPPORTED, "screen path unavailable (too many irregular rows)");
+    // the spans: chunks of option "range_chunk_rows" rows, whole 256-row tiles (a screen launch starts at a tile edge)
+    const int64_t chunk = round_up(std::max<int64_t>(idx->range_chunk_rows, kT2), kT2);
+    std::vector<RangeSpan> spans;
+    for (int64_t r0 = 0; r0 < idx->n; r0 += chunk) spans.push_back(RangeSpan{r0, std::min(idx->n, r0 + chunk)});
+    const int n_main = (int)spans.size();
+    const int R = range_slots_for(idx, m);
+    const int64_t pairs = (int64_t)nb * std::max(n_main, 1);
+    CHECK(ensure_range(idx, nb, R, m, pairs, host));
+    const RangeState rs = range_state(idx, R, pairs);
+    if (q_dev != idx->qdev)
+        HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q_dev, (size_t)nb * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+    CHECK(launch_prep(idx, s, nb, (int)round_up(nb, screen_tile(nb)), idx->metric));
+    HIPCHECK(idx, hipMemcpyAsync(idx->rng_radius.p, radius, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHECK(idx, hipMemsetAsync(idx->rng_redo.p, 0, 2 * sizeof(int), s));
+    HIPCHECK(idx, hipMemsetAsync(idx->rng_stat.p, 0, 2 * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_range_prep, dim3((nb + kRangeThreads - 1) / kRangeThreads), dim3(kRangeThreads), 0, s,
+                       (const double*)idx->rng_radius.p, nb, idx->metric, use_screen ? 1 : 0, idx->st, rs);
+    HIPCHECK(idx, hipGetLastError());
+    std::vector<int> all(nb);
+    for (int i = 0; i < nb; ++i) all[i] = i;
+    if (use_screen) {
+        for (int i = 0; i < n_main; ++i) {
+            // k_screen_rq's common flush period: hits are rare under a fixed, tight threshold (a wave whose queue fills
+            // faster still flushes on its own)
+            idx->flush_mask_now = idx->screen_flush_sync ? 15 : -1;
+            CHECK(launch_screen(idx, s, nb, spans[i].r0, spans[i].r1, cap, /*emit_mode=*/0));
+            CHECK(launch_range_collect(idx, s, rs, kRangeFormScreen, nb, nullptr, cap, i, spans[i].r0));
+        }
+        // rows this screen cannot see (irregular; for int8 also loose), as a search pass feeds them: "no bound" candidates,
+        // here in list-sized pieces with a collect step each, so that they cannot overflow a list
+        const int side_n = i8 ? idx->irr8_n : idx->irr_n;
+        const int32_t* side = i8 ? idx->irr8_rows.p : idx->irr_rows.p;
+        for (int i0 = 0; i0 < side_n; i0 += cap) {
+            hipLaunchKernelGGL(k_emit_irregular, dim3(nb), dim3(64), 0, s, side + i0, std::min(cap, side_n - i0), idx->st,
+                               idx->cand_row, idx->cand_val, cap, 0);
+            HIPCHECK(idx, hipGetLastError());
+            CHECK(launch_range_collect(idx, s, rs, kRangeFormSide, nb, nullptr, cap, -1, 0));
+        }
+    } else if (n_main > 0) {
+        HIPCHECK(idx, hipMemcpyAsync(idx->qlist_dev, all.data(), (size_t)nb * sizeof(int), hipMemcpyHostToDevice, s));
+        for (int i = 0; i < n_main; ++i) CHECK(range_scan_span(idx, s, rs, nb, cap, i, spans[i].r0, spans[i].r1));
+    }
+    // ---- the recorded (query, span) pairs, on the exact path: a pair that came from the screen form runs its span whole; one
+    // whose list overflowed under the exact scan runs it in pieces of `cap` rows, which cannot overflow
+    for (int round = 0;; ++round) {
+        int hdr[2] = {0, 0};
+        HIPCHECK(idx, hipMemcpyAsync(hdr, idx->rng_redo.p, sizeof(hdr), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipStreamSynchronize(s));
+        if (hdr[1] != 0) return fail(idx, MI355DR_E_INTERNAL, "range search: the redo list overflowed");
+        if (hdr[0] == 0) break;
+        if (round >= 3) return fail(idx, MI355DR_E_INTERNAL, "range search: a list-sized piece overflowed its list");
+        std::vector<int> rec((size_t)2 * hdr[0]);
+        HIPCHECK(idx, hipMemcpyAsync(rec.data(), idx->rng_redo.p + 2, rec.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipMemsetAsync(idx->rng_redo.p, 0, 2 * sizeof(int), s));
+        HIPCHECK(idx, hipStreamSynchronize(s));
+        std::vector<std::vector<int>> by_code((size_t)2 * spans.size());  // [2 * span + in_pieces]: the queries
+        for (int i = 0; i < hdr[0]; ++i) {
+            const int q = rec[2 * i], code = rec[2 * i + 1];
+            if (q < 0 || q >= nb || code < 0 || code >= (int)by_code.size())
+                return fail(idx, MI355DR_E_INTERNAL, "range search: a redo record out of range");
+            by_code[code].push_back(q);
+        }
+        for (size_t code = 0; code < by_code.size(); ++code) {
+            const std::vector<int>& qs = by_code[code];
+            if (qs.empty()) continue;
+            const RangeSpan sp = spans[code >> 1];
+            HIPCHECK(idx, hipMemcpyAsync(idx->qlist_dev, qs.data(), qs.size() * sizeof(int), hipMemcpyHostToDevice, s));
+            if (code & 1) {
+                for (int64_t p = sp.r0; p < sp.r1; p += cap) {
+                    spans.push_back(RangeSpan{p, std::min(sp.r1, p + cap)});
+                    CHECK(range_scan_span(idx, s, rs, (int)qs.size(), cap, (int)spans.size() - 1, p, std::min(sp.r1, p + cap)));
+                }
+            } else {
+                CHECK(range_scan_span(idx, s, rs, (int)qs.size(), cap, (int)(code >> 1), sp.r0, sp.r1));
+            }
+        }
+        HIPCHECK(idx, hipStreamSynchronize(s));  // (the query lists are pageable and leave with this round)
+        idx->s_range_redo_chunks += hdr[0];
+    }
+    // ---- sort, write out, flag
+    const int np_max = groups_pow2(R);
+    hipLaunchKernelGGL(k_range_finish, dim3(nb), dim3(kRangeThreads), range_finish_lds(np_max), s, rs, np_max, m, idx->row_offset,
+                       (const int64_t*)idx->view_row_map.p, od, orow, ocount);
+    HIPCHECK(idx, hipGetLastError());
+    std::vector<int> flag(nb);
+    std::vector<int64_t> counts(nb);
+    unsigned long long st2[2] = {0, 0};
+    HIPCHECK(idx, hipMemcpyAsync(flag.data(), idx->rng_flag.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(counts.data(), ocount, (size_t)nb * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(st2, idx->rng_stat.p, sizeof(st2), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    for (int i = 0; i < nb; ++i) idx->s_range_in_range += counts[i];
+    idx->s_range_candidates += (int64_t)st2[0];
+    idx->s_range_rescored += (int64_t)st2[1];
+    // ---- more rows in range than the buffer holds: the list is the ordinary top-max_results (all of it is in range); the
+    // device count stands
+    std::vector<int> fb;
+    for (int i = 0; i < nb; ++i)
+        if (flag[i]) fb.push_back(i);
+    if (!fb.empty()) {
+        const int nf = (int)fb.size();
+        HIPCHECK(idx, hipMemcpyAsync(idx->rng_fb_map.p, fb.data(), (size_t)nf * sizeof(int), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_gather_queries, dim3(nf), dim3(128), 0, s, (const float*)idx->qdev.p, (const int*)idx->rng_fb_map.p,
+                           idx->dim, idx->rng_fb_q.p);
+        HIPCHECK(idx, hipGetLastError());
+        HIPCHECK(idx, hipStreamSynchronize(s));  // `fb` (pageable) was read by the copy
+        CHECK(search_block(idx, s, idx->rng_fb_q.p, nf, m, idx->rng_fb_dist.p, idx->rng_fb_rows.p));
+        hipLaunchKernelGGL(k_scatter_results, dim3(nf), dim3(128), 0, s, (const double*)idx->rng_fb_dist.p,
+                           (const int64_t*)idx->rng_fb_rows.p, (const int*)idx->rng_fb_map.p, m, od, orow);
+        HIPCHECK(idx, hipGetLastError());
+        HIPCHECK(idx, hipStreamSynchronize(s));
+        idx->s_range_fallback_queries += nf;
+    }
+    return MI355DR_OK;
+}
+
+// host == true: queries / outputs are host buffers staged through the index's own; else device buffers used in place
+int search_range_impl(mi355dr_index* idx, const float* queries, int B, const double* radius, int m, double* out_dist,
+                      int64_t* out_rows, int64_t* out_count, hipStream_t s, bool host) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    if (B <= 0 || m < 1) return fail(idx, MI355DR_E_INVALID, "search_range: B and max_results must be >= 1");
+    if (m > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, "search_range: max_results exceeds 1024");
+    if (!queries || !radius || !out_dist || !out_rows || !out_count) return fail(idx, MI355DR_E_INVALID, "search_range: null buffer");
+    for (int b = 0; b < B; ++b)
+        if (radius[b] != radius[b]) return fail(idx, MI355DR_E_INVALID, "search_range: radius " + std::to_string(b) + " is NaN");
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_pending(idx));
+    if (!s) s = idx->stream;
+    CHECK(ensure_qstate(idx));
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        const float* q = queries + (int64_t)b0 * idx->dim;
+        double* od = out_dist + (int64_t)b0 * m;
+        int64_t* orow = out_rows + (int64_t)b0 * m;
+        int64_t* oc = out_count + b0;
+        if (host) {
+            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q, (size_t)nb * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
+            // (the staging buffers are grown by the block's ensure_range: sized here first)
+            HIPCHECK(idx, idx->rng_out_dist.grow((size_t)std::min(B, kQBlockMax) * m * sizeof(double)));
+            HIPCHECK(idx, idx->rng_out_rows.grow((size_t)std::min(B, kQBlockMax) * m * sizeof(int64_t)));
+            HIPCHECK(idx, idx->rng_out_count.grow((size_t)std::min(B, kQBlockMax) * sizeof(int64_t)));
+            CHECK(range_block(idx, s, idx->qdev, nb, radius + b0, m, idx->rng_out_dist.p, idx->rng_out_rows.p, idx->rng_out_count.p, true));
+            HIPCHECK(idx, hipMemcpyAsync(od, idx->rng_out_dist.p, (size_t)nb * m * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHECK(idx, hipMemcpyAsync(orow, idx->rng_out_rows.p, (size_t)nb * m * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            HIPCHECK(idx, hipMemcpyAsync(oc, idx->rng_out_count.p, (size_t)nb * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            HIPCHECK(idx, hipStreamSynchronize(s));
+        } else {
+            CHECK(range_block(idx, s, q, nb, radius + b0, m, od, orow, oc, false));
+        }
+    }
+    idx->s_range_searches++;
+    idx->s_range_queries += B;
+    return MI355DR_OK;
+}
+}  // namespace
+
+int mi355dr_search_range(mi355dr_index* idx, const float* queries, int B, const double* radius, int max_results, double* out_dist,
+                         int64_t* out_rows, int64_t* out_count) {
+    return search_range_impl(idx, queries, B, radius, max_results, out_dist, out_rows, out_count, nullptr, /*host=*/true);
+}
+
+int mi355dr_search_range_device(mi355dr_index* idx, const float* queries_dev, int B, const double* radius, int max_results,
+                                double* out_dist_dev, int64_t* out_rows_dev, int64_t* out_count_dev, void* stream) {
+    return search_range_impl(idx, queries_dev, B, radius, max_results, out_dist_dev, out_rows_dev, out_count_dev,
+                             (hipStream_t)stream, /*host=*/false);
+}
+
 int mi355dr_merge_topk_device(mi355dr_index* idx, const double* dist_all_dev, const int64_t* rows_all_dev, int world,
                               int B, int k, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
@@ -2075,6 +2378,8 @@ const Option kOptions[] = {
     {"starter_rows_wide", &Index::starter_rows_wide, 4096, 262144},
     {"compact_slice_rows", &Index::compact_slice_rows, 32, (int64_t)1 << 22},  // destination rows per staged slice of mi355dr_compact
     {"view_slice_rows", &Index::view_slice_rows, 32, (int64_t)1 << 22},  // rows per staged slice of mi355dr_view_create on this index
+    {"range_chunk_rows", &Index::range_chunk_rows, 256, (int64_t)1 << 31},  // rows per screen launch / exact span of mi355dr_search_range (rounded up to 256)
+    {"range_slots", &Index::range_slots, 16, kSortMax},  // slots of a query's range result buffer (never below max_results)
 };
 
 struct Stat {
@@ -2124,6 +2429,13 @@ const Stat kStats[] = {
     {"group_searches", &Index::s_group_searches, true},
     {"group_subqueries", &Index::s_group_subqueries, true},
     {"groups_merged", &Index::s_groups_merged, true},
+    {"range_searches", &Index::s_range_searches, true},
+    {"range_queries", &Index::s_range_queries, true},
+    {"range_in_range", &Index::s_range_in_range, true},
+    {"range_candidates", &Index::s_range_candidates, true},
+    {"range_rescored", &Index::s_range_rescored, true},
+    {"range_redo_chunks", &Index::s_range_redo_chunks, true},
+    {"range_fallback_queries", &Index::s_range_fallback_queries, true},
     {"compactions", &Index::s_compactions, true},
     {"compact_moved_rows", &Index::s_compact_moved_rows, true},
     {"view", nullptr, false, [](const Index* x) -> int64_t { return x->is_view ? 1 : 0; }},

@@ -330,6 +330,45 @@ class Mi355Index:
                 self.dev_free(b)
         return out_v, out_r, out_c
 
+    # ---- range search: every row within a distance, counted on the device (include/mi355dr.h "range search") ----
+    @staticmethod
+    def _radius(radius, B: int) -> np.ndarray:
+        """A scalar or a [B] array -> float64 [B]; NaN and any other shape are refused before the library is called."""
+        r = np.asarray(radius, dtype=np.float64)
+        if r.ndim == 0:
+            r = np.full(B, float(r), dtype=np.float64)
+        if r.ndim != 1 or r.shape[0] != B:
+            raise ValueError(f"radius must be a scalar or one-dimensional [{B}], got shape {r.shape}")
+        if np.isnan(r).any():
+            raise ValueError("radius must not be NaN")
+        return np.ascontiguousarray(r)
+
+    def search_range(self, queries, radius, max_results: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`WHERE distance <= radius ORDER BY distance LIMIT max_results`, and `count(*)` under the same filter.  `radius`: a
+        scalar or [B], in the metric's distance units (cosine distance; -dot for "ip"); +inf = every row with a defined
+        distance.  Returns (distance float64 [B,m], rows int64 [B,m], count int64 [B]): the first min(count, m) in-range rows
+        in the order of `search`, with its bits, NaN / -1 behind them; count is exact and may exceed m."""
+        q = self._queries_2d(queries)
+        B, m = q.shape[0], int(max_results)
+        r = self._radius(radius, B)
+        dist = np.empty((B, max(m, 0)), dtype=np.float64)
+        rows = np.empty((B, max(m, 0)), dtype=np.int64)
+        count = np.empty(B, dtype=np.int64)
+        check(self._h, self._lib.mi355dr_search_range(self._h, ptr(q, ctypes.c_float), B, ptr(r, ctypes.c_double), m,
+                                                      ptr(dist, ctypes.c_double), ptr(rows, ctypes.c_int64),
+                                                      ptr(count, ctypes.c_int64)))
+        return dist, rows, count
+
+    def search_range_device(self, q_ptr: int, B: int, radius, max_results: int, out_dist_ptr: int, out_rows_ptr: int,
+                            out_count_ptr: int, stream: int | None = None) -> None:
+        """The same with queries ([B, dim] fp32) and outputs (float64 [B,m], int64 [B,m], int64 [B]) in device memory; the
+        radii stay on the host.  Complete on return."""
+        r = self._radius(radius, int(B))
+        check(self._h, self._lib.mi355dr_search_range_device(
+            self._h, ctypes.c_void_p(int(q_ptr)), int(B), ptr(r, ctypes.c_double), int(max_results),
+            ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)), ctypes.c_void_p(int(out_count_ptr)),
+            ctypes.c_void_p(int(stream) if stream else None)))
+
     # ---- views: a listed subset as an index of its own (include/mi355dr.h "views") ----
     def view(self, row_ids=None, doc_ids=None) -> "Mi355Index":
         """The listed rows and / or documents of this index as a read-only index of their own, built on the device

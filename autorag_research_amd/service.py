@@ -706,6 +706,42 @@ class Mi355RetrievalService:
             return []
         return self._single_block(np.asarray(embedding, dtype=np.float32)[None, :], top_k, unit, within, mmr_fetch_k, mmr_lambda)[0]
 
+    # ---- range search: everything within a distance, and how many (not in the reference's service) ----
+    def _range_block(self, Q: np.ndarray, max_distance, limit: int, unit: str) -> list[tuple[list[dict], int]]:
+        """`_single_block` for `WHERE distance <= max_distance ORDER BY distance LIMIT limit`: the same row map and score
+        conversion; with every result list the exact number of chunks within the distance (it may exceed `limit`)."""
+        if self._world is not None:
+            raise NotImplementedError("range search under a process group: the shards' counts and lists are not merged yet")
+        u = self._unit(unit)
+        dist, rows, count = u.single_searcher(None).search_range(Q, max_distance, limit)
+        block = self._results_from_block(u.table, u.single_rows, rows, 1.0 - dist, unit == "chunk")
+        return [(res, int(c)) for res, c in zip(block, count.tolist())]
+
+    def vector_search_range_by_embedding(self, embedding: list[float], max_distance: float, limit: int = 10,
+                                         unit: str = "chunk") -> tuple[list[dict], int]:
+        """(the up to `limit` nearest chunks with cosine distance <= max_distance -- the result dicts and scores of
+        `vector_search_by_embedding` --, the number of chunks within that distance)."""
+        if len(embedding) == 0:  # (as `vector_search_by_embedding`)
+            return [], 0
+        return self._range_block(np.asarray(embedding, dtype=np.float32)[None, :], float(max_distance), limit, unit)[0]
+
+    def vector_search_range(self, query_ids: list[int | str], max_distance, limit: int = 10,
+                            unit: str = "chunk") -> list[tuple[list[dict], int]]:
+        """`vector_search_range_by_embedding` for every stored query id, scored as one block; `max_distance` is a scalar or
+        one value per query.  Raises ValueError for an unknown query or one without an embedding, like `vector_search`."""
+        queries = []
+        for qid, q in zip(query_ids, self.get_queries(list(query_ids)), strict=True):
+            if q is None:
+                raise ValueError(f"Query {qid} not found")  # noqa: TRY003
+            if q.embedding is None:
+                msg = f"Query {qid} has no embedding" if unit == "chunk" else f"Query {qid} has no single-vector embedding"
+                raise ValueError(msg)
+            queries.append(q)
+        if not queries:
+            return []
+        Q = np.stack([q.embedding for q in queries]).astype(np.float32, copy=False)
+        return self._range_block(Q, max_distance, limit, unit)
+
     def vector_search_groups(self, embeddings_per_query: list, top_k: int, fetch_k: int | None = None, unit: str = "chunk",
                              search_mode: Literal["single", "multi"] = "single") -> list[list[dict]]:
         """Several searches per question, fused on the device (not in the reference's service: its callers loop in Python,

@@ -256,6 +256,53 @@ int mi355dr_search_groups(mi355dr_index* idx, const float* queries /* host [S, d
 int mi355dr_search_groups_device(mi355dr_index* idx, const float* queries_dev, const int32_t* group_offsets /* HOST */, int G, int k,
                                  int fetch_k, double* out_dist_dev, int64_t* out_rows_dev, int32_t* out_count_dev, void* stream);
 
+/* ---- range search: every row within a distance, counted on the device ----
+ * The other half of the statement: `WHERE embedding IS NOT NULL AND embedding <=> :q <= :r ORDER BY distance LIMIT :m`, and
+ * `SELECT count(*)` under the same filter -- adaptive-k retrieval, near-duplicate and semantic-cache checks, "how many chunks
+ * are relevant at all" before a fusion.
+ *   In range: a live row whose float8 distance d to the query -- the bits mi355dr_search returns for the pair -- satisfies
+ *     d <= radius[b], compared as doubles.  A NaN distance (an irregular row, a zero-norm query under cosine) is never in
+ *     range, a removed row never.  Both metrics; for inner product the radius is in the operator's own units, -dot.
+ *     radius: HOST [B], any double but NaN; +inf = every row with a defined distance, -inf = none.
+ *   out_count[b]: the number of in-range rows of this handle; exact, it may exceed max_results.
+ *   The list: the first min(count, max_results) in-range rows under the library's total order (distance asc, row asc), with the
+ *     bits of mi355dr_search and global rows (option "row_offset" added; on a view the parent's ids); slots behind it hold
+ *     NaN / -1.  Equivalently: mi355dr_search at k = max_results with every entry whose distance is NaN or above the radius
+ *     replaced by NaN / -1.
+ *   MI355DR_E_INVALID: B <= 0, max_results < 1, a NaN radius, a null buffer.  MI355DR_E_UNSUPPORTED: max_results > 1024.  A
+ *     refused call changes nothing.  B above 1024 runs in internal blocks.
+ *   The call runs under the handle's mutex, first completes whatever search is in flight and is complete on return (the
+ *     _device form too: `stream`, or the index's own when NULL, is synchronised).  It uses the per-search state of the handle
+ *     and leaves it to the next search, which prepares all of it anew: that search returns what it would have returned
+ *     without the range call.  Works on a view (it takes no global ids).
+ *   Two paths with identical results, steered by option "path".  Exact range scan (MI355DR_PATH_SCAN, every query no screen
+ *     can serve, every chunk a screen overflowed): the exact scan's launches with the radius as their fixed threshold, chunk by
+ *     chunk; a chunk whose list overflowed is run again in list-sized pieces, unless its count alone already puts the query
+ *     beyond its result buffer.  Screened (AUTO wherever a search would screen, and SCREEN): the screens of the ordinary search
+ *     with the FIXED threshold the radius allows (the function the prunes publish thresholds with) -- no starter, no ladder of
+ *     prunes --, every candidate re-scored by the exact chain and kept iff it is in range; rows the screens cannot see
+ *     (irregular, loose) are re-scored for every query; irregular queries, a threshold that admits every row, and every
+ *     (query, chunk) whose candidate list overflowed take the exact path, that query's later chunks with it.
+ *   A query keeps its in-range rows in a buffer of option "range_slots" (default and most 4096, at least max_results) entries
+ *     that the index owns and grows; with more rows in range than that, its list comes from the ordinary search at
+ *     k = max_results (every entry of which is in range) and its count from the device counter.
+ *   Options: "range_chunk_rows" (rows per screen launch / exact span, default 2097152, rounded up to whole 256-row tiles),
+ *     "range_slots"; "cand_cap", "small_chunk_rows", "screen_dtype", "screen_rq", "screen_stream" and "scan_dma" apply as in a
+ *     search.
+ *   Stats: "range_searches" (calls), "range_queries", "range_in_range" (the counts, summed), "range_candidates" /
+ *     "range_rescored" (screen path: candidates taken from the screens / of them re-scored), "range_redo_chunks" ((query, chunk)
+ *     pairs run again on the exact path), "range_fallback_queries" (queries whose list the ordinary search served: that search
+ *     moves the ordinary stats, nothing else of a range call does).
+ *   Sharding is not built in, but the contract is shard-friendly: counts add across shards, and the lists -- global rows, the
+ *     total order -- merge with mi355dr_merge_topk_device like any top-k lists. */
+int mi355dr_search_range(mi355dr_index* idx, const float* queries, int B, const double* radius /* host [B] */,
+                         int max_results, double* out_dist /* [B, max_results] */, int64_t* out_rows /* [B, max_results] */,
+                         int64_t* out_count /* [B] */); /* all host */
+/* queries_dev [B, dim], out_dist_dev / out_rows_dev [B, max_results], out_count_dev [B] on the index's device; the radii stay on the HOST */
+int mi355dr_search_range_device(mi355dr_index* idx, const float* queries_dev, int B, const double* radius /* HOST [B] */,
+                                int max_results, double* out_dist_dev, int64_t* out_rows_dev, int64_t* out_count_dev,
+                                void* stream);
+
 /* ---- views: a listed subset of rows / documents as an index of its own ----
  * For a list that is searched again and again -- one tenant, one document collection, one PDF's pages: the key filter of the
  * statement above, fixed for many query blocks.  mi355dr_search_subset scans the list exactly on every call (cost ~ m x B, no
@@ -504,7 +551,7 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
  *          "maxsim_pack8" (MaxSim screen, passes of 32-vector queries in the workgroup form and passes of up to four column blocks: a second bf16 shadow whose documents are
  *          rounded up to 8-token granules instead of 32-token blocks, built on the first such pass and extended by the next one after an add -- -1
  *          [default]: when it has at least 5 % fewer blocks than the padded copy and its memory is there, 1: always, 0: never;
- *          identical results).
+ *          identical results); "range_chunk_rows" and "range_slots" (mi355dr_search_range, described there).
  * stats:   "screen_launches", "screen_ns" (profile=1), "screen_rows" (all screen launches) and their k_screen256 share
  *          "screen256_launches", "screen256_ns", "screen256_rows"; "candidates", "rescored",
  *          "fallback_queries" (queries recomputed by the exact scan), "retry_queries" (queries whose candidate list
@@ -521,6 +568,8 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
  *          "subset_rerun_queries" (mi355dr_search_subset: calls, pairs scored, queries re-run in list-sized pieces),
  *          "mmr_searches" / "mmr_queries" / "mmr_pairs_scored" (mi355dr_search_mmr* and mi355dr_mmr_select, described there),
  *          "group_searches" / "group_subqueries" / "groups_merged" (mi355dr_search_groups* and mi355dr_merge_groups_device, described there),
+ *          "range_searches" / "range_queries" / "range_in_range" / "range_candidates" / "range_rescored" / "range_redo_chunks" /
+ *          "range_fallback_queries" (mi355dr_search_range*, described there),
  *          "maxsim_subset_searches" / "maxsim_subset_docs" / "maxsim_subset_screened" / "maxsim_subset_exact" /
  *          "maxsim_subset_fallbacks" (mi355dr_search_maxsim_subset, described there),
  *          "view" / "view_rows" / "view_docs" (mi355dr_view_create: 1 on a view / the rows / the documents it holds),
