@@ -23,7 +23,8 @@ ABI_SYMBOLS = [
     "mi355dr_add_rows", "mi355dr_add_rows_device", "mi355dr_size", "mi355dr_dim", "mi355dr_get_rows",
     "mi355dr_update_rows", "mi355dr_update_rows_device", "mi355dr_remove_rows", "mi355dr_live_rows", "mi355dr_compact",
     "mi355dr_search", "mi355dr_search_device", "mi355dr_search_device_async", "mi355dr_search_wait",
-    "mi355dr_search_subset", "mi355dr_search_subset_device", "mi355dr_score_subset", "mi355dr_search_mmr", "mi355dr_search_mmr_device", "mi355dr_mmr_select", "mi355dr_merge_groups_device", "mi355dr_search_groups", "mi355dr_search_groups_device", "mi355dr_search_range", "mi355dr_search_range_device", "mi355dr_view_create", "mi355dr_add_multivec", "mi355dr_size_multivec",
+    "mi355dr_search_subset", "mi355dr_search_subset_device", "mi355dr_score_subset", "mi355dr_search_mmr", "mi355dr_search_mmr_device", "mi355dr_mmr_select", "mi355dr_merge_groups_device", "mi355dr_search_groups", "mi355dr_search_groups_device", "mi355dr_search_range", "mi355dr_search_range_device",
+    "mi355dr_search_rows", "mi355dr_search_rows_device", "mi355dr_search_range_rows", "mi355dr_search_range_rows_device", "mi355dr_view_create", "mi355dr_add_multivec", "mi355dr_size_multivec",
     "mi355dr_search_maxsim", "mi355dr_search_maxsim_device", "mi355dr_search_maxsim_subset", "mi355dr_search_maxsim_subset_device", "mi355dr_maxsim_subset", "mi355dr_maxsim_subset_ex", "mi355dr_add_multivec_device", "mi355dr_gqr_refine", "mi355dr_gqr_refine_maxsim",
     "mi355dr_set_multivec", "mi355dr_set_multivec_device", "mi355dr_live_multivec",
     "mi355dr_gqr_refine_scores", "mi355dr_merge_topk_device", "mi355dr_pack_topk_device",
@@ -148,6 +149,14 @@ def load() -> ctypes.CDLL:
     L.mi355dr_search_range.argtypes = [vp, f32p, c_int, f64p, c_int, f64p, i64p, i64p]
     L.mi355dr_search_range_device.restype = c_int
     L.mi355dr_search_range_device.argtypes = [vp, vp, c_int, f64p, c_int, vp, vp, vp, vp]
+    L.mi355dr_search_rows.restype = c_int
+    L.mi355dr_search_rows.argtypes = [vp, i64p, c_int, c_int, c_int, f64p, i64p]
+    L.mi355dr_search_rows_device.restype = c_int
+    L.mi355dr_search_rows_device.argtypes = [vp, i64p, c_int, c_int, c_int, vp, vp, vp]
+    L.mi355dr_search_range_rows.restype = c_int
+    L.mi355dr_search_range_rows.argtypes = [vp, i64p, c_int, f64p, c_int, c_int, f64p, i64p, i64p]
+    L.mi355dr_search_range_rows_device.restype = c_int
+    L.mi355dr_search_range_rows_device.argtypes = [vp, i64p, c_int, f64p, c_int, c_int, vp, vp, vp, vp]
     L.mi355dr_view_create.restype = c_int
     L.mi355dr_view_create.argtypes = [vp, i64p, i64, i64p, i64, ctypes.POINTER(vp)]
     L.mi355dr_add_multivec.restype = c_int

@@ -171,6 +171,16 @@ struct mi355dr_index {
     mi355::DevBuf<int64_t> rng_out_rows, rng_out_count, rng_fb_rows;
     mi355::DevBuf<float> rng_fb_q;
     int rng_collect_lds = 0;  // dynamic LDS k_range_collect is registered for (0: not yet)
+    // search by stored row (mi355dr_search_rows* / mi355dr_search_range_rows*): one block's ids, gathered
+    // query vectors [nb, dim] and validity words, the inner pass's lists [nb, k + 1] / counts, the range form's (slot, row) pairs
+    // with their row-with-itself distances and the radii, the host forms' result staging, the skipped-slot counter -- grown
+    // by ensure_rows
+    mi355::DevBuf<int64_t> rowq_ids, rowq_pair_row, rowq_cand_rows, rowq_cand_count, rowq_out_rows, rowq_out_count;
+    mi355::DevBuf<float> rowq_q, rowq_self_dot;
+    mi355::DevBuf<int> rowq_valid;
+    mi355::DevBuf<int32_t> rowq_pair_q;
+    mi355::DevBuf<double> rowq_cand_dist, rowq_self_dist, rowq_radius, rowq_out_dist;
+    mi355::DevBuf<unsigned long long> rowq_skipped_dev;
     // a view (mi355dr_view_create; DESIGN.md "Views"): a read-only index built from listed rows / documents of a parent.  The
     // maps are null on every other index: the result-writing kernels then add row_offset instead
     bool is_view = false;
@@ -296,6 +306,8 @@ struct mi355dr_index {
     // and of them re-scored; (query, chunk) pairs run again on the exact path; queries whose list the ordinary search served
     int64_t s_range_searches = 0, s_range_queries = 0, s_range_in_range = 0, s_range_candidates = 0, s_range_rescored = 0,
             s_range_redo_chunks = 0, s_range_fallback_queries = 0;
+    // mi355dr_search_rows* / mi355dr_search_range_rows*: calls, slots, slots whose id was outside the shard or a removed row
+    int64_t s_rows_searches = 0, s_rows_queries = 0, s_rows_skipped = 0;
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
     mi355::EventPairs ev_pool, ev_pending;

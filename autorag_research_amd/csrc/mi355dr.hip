@@ -25,6 +25,7 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "mmr_order.h"
 #include "k_groups.h"
 #include "k_range.h"
+#include "k_rows.h"
 
 using namespace mi355;
 
@@ -2273,6 +2274,135 @@ int mi355dr_search_range_device(mi355dr_index* idx, const float* queries_dev, in
                              (hipStream_t)stream, /*host=*/false);
 }
 
+// ---- search by stored row: neighbours of rows, self excluded (csrc/k_rows.h) ---------------------
+namespace {
+// the handle's buffers for a block of nb slots, inner lists of `stride` entries and (host forms) nb x kout results
+int ensure_rows(mi355dr_index* idx, int nb, int stride, int kout, bool range, bool host) {
+    HIPCHECK(idx, idx->rowq_ids.grow((size_t)nb * sizeof(int64_t)));
+    HIPCHECK(idx, idx->rowq_q.grow((size_t)nb * idx->dim * sizeof(float)));
+    HIPCHECK(idx, idx->rowq_valid.grow((size_t)nb * sizeof(int)));
+    HIPCHECK(idx, idx->rowq_pair_q.grow((size_t)nb * sizeof(int32_t)));
+    HIPCHECK(idx, idx->rowq_pair_row.grow((size_t)nb * sizeof(int64_t)));
+    HIPCHECK(idx, idx->rowq_cand_dist.grow((size_t)nb * stride * sizeof(double)));
+    HIPCHECK(idx, idx->rowq_cand_rows.grow((size_t)nb * stride * sizeof(int64_t)));
+    HIPCHECK(idx, idx->rowq_skipped_dev.grow(sizeof(unsigned long long)));
+    if (range) {
+        HIPCHECK(idx, idx->rowq_cand_count.grow((size_t)nb * sizeof(int64_t)));
+        HIPCHECK(idx, idx->rowq_self_dot.grow((size_t)nb * sizeof(float)));
+        HIPCHECK(idx, idx->rowq_self_dist.grow((size_t)nb * sizeof(double)));
+        HIPCHECK(idx, idx->rowq_radius.grow((size_t)nb * sizeof(double)));
+    }
+    if (host) {
+        HIPCHECK(idx, idx->rowq_out_dist.grow((size_t)nb * kout * sizeof(double)));
+        HIPCHECK(idx, idx->rowq_out_rows.grow((size_t)nb * kout * sizeof(int64_t)));
+        if (range) HIPCHECK(idx, idx->rowq_out_count.grow((size_t)nb * sizeof(int64_t)));
+    }
+    return MI355DR_OK;
+}
+
+// both families.  radius == nullptr: the top-k form (kout = k); else the range form (kout = max_results, out_count used).
+// host == true: the outputs are host buffers staged through the index's own; else device buffers used in place
+int search_rows_impl(mi355dr_index* idx, const char* what, const int64_t* row_ids, int B, const double* radius, bool range,
+                     int kout, int flags, double* out_dist, int64_t* out_rows, int64_t* out_count, hipStream_t s, bool host) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    if (idx->is_view) return view_refuses(idx, what, /*ask_parent=*/true);  // (set once, before the handle is handed out)
+    const std::string w(what);
+    if (B < 0) return fail(idx, MI355DR_E_INVALID, w + ": B must be >= 0");
+    if (kout < 1) return fail(idx, MI355DR_E_INVALID, w + (range ? ": max_results must be >= 1" : ": k must be > 0"));
+    if (flags & ~MI355DR_ROWS_INCLUDE_SELF) return fail(idx, MI355DR_E_INVALID, w + ": unknown flag bits");
+    if (B > 0 && (!row_ids || !out_dist || !out_rows || (range && (!radius || !out_count))))
+        return fail(idx, MI355DR_E_INVALID, w + ": null buffer");
+    if (range)
+        for (int b = 0; b < B; ++b)
+            if (radius[b] != radius[b]) return fail(idx, MI355DR_E_INVALID, w + ": radius " + std::to_string(b) + " is NaN");
+    const bool include_self = (flags & MI355DR_ROWS_INCLUDE_SELF) != 0;
+    const int stride = kout + (include_self ? 0 : 1);  // the inner pass's list: room for the row itself
+    if (stride > kKMax)
+        return fail(idx, MI355DR_E_UNSUPPORTED, w + (range ? ": max_results" : ": k") + (include_self ? "" : " + 1 (the row itself)") + " exceeds 1024");
+    std::lock_guard<std::mutex> g(idx->mu);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_pending(idx));
+    if (B == 0) return MI355DR_OK;
+    if (!s) s = idx->stream;
+    CHECK(ensure_qstate(idx));
+    CHECK(ensure_rows(idx, std::min(B, kQBlockMax), stride, kout, range, host));
+    HIPCHECK(idx, hipMemsetAsync(idx->rowq_skipped_dev.p, 0, sizeof(unsigned long long), s));
+    std::vector<double> rad;
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        double* od = host ? idx->rowq_out_dist.p : out_dist + (int64_t)b0 * kout;
+        int64_t* orow = host ? idx->rowq_out_rows.p : out_rows + (int64_t)b0 * kout;
+        int64_t* oc = !range ? nullptr : host ? idx->rowq_out_count.p : out_count + b0;
+        HIPCHECK(idx, hipMemcpyAsync(idx->rowq_ids.p, row_ids + b0, (size_t)nb * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_rows_gather, dim3(nb), dim3(kRowsThreads), 0, s, (const int64_t*)idx->rowq_ids.p, idx->row_offset,
+                           idx->n, (const float*)idx->rows.p, (const float*)idx->nrm2.p, idx->dim, idx->rowq_q.p,
+                           idx->rowq_valid.p, idx->rowq_pair_q.p, idx->rowq_pair_row.p, idx->rowq_skipped_dev.p);
+        HIPCHECK(idx, hipGetLastError());
+        if (idx->n > 0 && !range) {
+            // the ordinary search of the gathered block (screened, fix-ups completed)
+            CHECK(search_block(idx, s, idx->rowq_q.p, nb, stride, idx->rowq_cand_dist.p, idx->rowq_cand_rows.p));
+        } else if (idx->n > 0) {
+            // an id outside the shard asks for nothing (its slot is blanked below): no row is within -inf
+            rad.assign(radius + b0, radius + b0 + nb);
+            for (int b = 0; b < nb; ++b)
+                if (subset_local_row(row_ids[b0 + b], idx->row_offset, idx->n) < 0) rad[b] = -INFINITY;
+            HIPCHECK(idx, hipMemcpyAsync(idx->rowq_radius.p, rad.data(), (size_t)nb * sizeof(double), hipMemcpyHostToDevice, s));
+            // every slot's distance to its own row, from the block's prepared queries: the bits a search returns for the pair
+            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, idx->rowq_q.p, (size_t)nb * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+            CHECK(launch_prep(idx, s, nb, (int)round_up(nb, screen_tile(nb)), idx->metric));
+            hipLaunchKernelGGL(k_rescore_pairs, dim3((unsigned)((nb + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows, idx->nrm2,
+                               idx->qdev, idx->st.qn, idx->rowq_pair_q.p, idx->rowq_pair_row.p, (int64_t)nb, idx->dim, idx->metric,
+                               idx->rowq_self_dot.p, idx->rowq_self_dist.p);
+            HIPCHECK(idx, hipGetLastError());
+            // the range pass of the gathered block (it prepares the block again; complete on return, `rad` has been read)
+            CHECK(range_block(idx, s, idx->rowq_q.p, nb, rad.data(), stride, idx->rowq_cand_dist.p, idx->rowq_cand_rows.p,
+                              idx->rowq_cand_count.p, /*host=*/false));
+        }
+        // (an empty index: every slot is invalid and the lists are not read)
+        hipLaunchKernelGGL(k_rows_drop, dim3(nb), dim3(kRowsThreads), 0, s, (const double*)idx->rowq_cand_dist.p,
+                           (const int64_t*)idx->rowq_cand_rows.p, stride, (const int64_t*)idx->rowq_ids.p,
+                           (const int*)idx->rowq_valid.p, kout, include_self ? 1 : 0,
+                           range ? (const int64_t*)idx->rowq_cand_count.p : nullptr, (const double*)idx->rowq_self_dist.p,
+                           (const double*)idx->rowq_radius.p, od, orow, oc);
+        HIPCHECK(idx, hipGetLastError());
+        if (host) {
+            HIPCHECK(idx, hipMemcpyAsync(out_dist + (int64_t)b0 * kout, od, (size_t)nb * kout * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHECK(idx, hipMemcpyAsync(out_rows + (int64_t)b0 * kout, orow, (size_t)nb * kout * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            if (range) HIPCHECK(idx, hipMemcpyAsync(out_count + b0, oc, (size_t)nb * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHECK(idx, hipStreamSynchronize(s));  // (the next block reuses the id, query and list buffers)
+    }
+    unsigned long long skipped = 0;
+    HIPCHECK(idx, hipMemcpy(&skipped, idx->rowq_skipped_dev.p, sizeof(skipped), hipMemcpyDeviceToHost));
+    idx->s_rows_searches++;
+    idx->s_rows_queries += B;
+    idx->s_rows_skipped += (int64_t)skipped;
+    return MI355DR_OK;
+}
+}  // namespace
+
+int mi355dr_search_rows(mi355dr_index* idx, const int64_t* row_ids, int B, int k, int flags, double* out_dist, int64_t* out_rows) {
+    return search_rows_impl(idx, "search_rows", row_ids, B, nullptr, false, k, flags, out_dist, out_rows, nullptr, nullptr, /*host=*/true);
+}
+
+int mi355dr_search_rows_device(mi355dr_index* idx, const int64_t* row_ids, int B, int k, int flags, double* out_dist_dev,
+                               int64_t* out_rows_dev, void* stream) {
+    return search_rows_impl(idx, "search_rows", row_ids, B, nullptr, false, k, flags, out_dist_dev, out_rows_dev, nullptr,
+                            (hipStream_t)stream, /*host=*/false);
+}
+
+int mi355dr_search_range_rows(mi355dr_index* idx, const int64_t* row_ids, int B, const double* radius, int max_results, int flags,
+                              double* out_dist, int64_t* out_rows, int64_t* out_count) {
+    return search_rows_impl(idx, "search_range_rows", row_ids, B, radius, true, max_results, flags, out_dist, out_rows, out_count,
+                            nullptr, /*host=*/true);
+}
+
+int mi355dr_search_range_rows_device(mi355dr_index* idx, const int64_t* row_ids, int B, const double* radius, int max_results,
+                                     int flags, double* out_dist_dev, int64_t* out_rows_dev, int64_t* out_count_dev, void* stream) {
+    return search_rows_impl(idx, "search_range_rows", row_ids, B, radius, true, max_results, flags, out_dist_dev, out_rows_dev,
+                            out_count_dev, (hipStream_t)stream, /*host=*/false);
+}
+
 int mi355dr_merge_topk_device(mi355dr_index* idx, const double* dist_all_dev, const int64_t* rows_all_dev, int world,
                               int B, int k, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
@@ -2436,6 +2566,9 @@ const Stat kStats[] = {
     {"range_rescored", &Index::s_range_rescored, true},
     {"range_redo_chunks", &Index::s_range_redo_chunks, true},
     {"range_fallback_queries", &Index::s_range_fallback_queries, true},
+    {"rows_searches", &Index::s_rows_searches, true},
+    {"rows_queries", &Index::s_rows_queries, true},
+    {"rows_skipped", &Index::s_rows_skipped, true},
     {"compactions", &Index::s_compactions, true},
     {"compact_moved_rows", &Index::s_compact_moved_rows, true},
     {"view", nullptr, false, [](const Index* x) -> int64_t { return x->is_view ? 1 : 0; }},

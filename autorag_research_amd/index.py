@@ -369,6 +369,87 @@ class Mi355Index:
             ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)), ctypes.c_void_p(int(out_count_ptr)),
             ctypes.c_void_p(int(stream) if stream else None)))
 
+    # ---- search by stored row: neighbours of rows, self excluded (include/mi355dr.h "search by stored row") ----
+    def search_rows(self, row_ids, k: int, include_self: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """The top-k of the stored rows `row_ids` (global ids, any order, repeats allowed), the query vectors read on the
+        device.  By default the row itself is left out: the top-k of the OTHER live rows, in the order and with the bits of
+        `search`; include_self=True is `search(get_rows(row_ids), k)`.  An id outside the index and a removed row give a
+        NaN / -1 line.  Returns (distance float64 [B,k], rows int64 [B,k])."""
+        ids = self._row_ids(row_ids)
+        B = ids.shape[0]
+        dist = np.empty((B, max(int(k), 0)), dtype=np.float64)
+        rows = np.empty((B, max(int(k), 0)), dtype=np.int64)
+        check(self._h, self._lib.mi355dr_search_rows(self._h, ptr(ids, ctypes.c_int64), B, int(k), 1 if include_self else 0,
+                                                     ptr(dist, ctypes.c_double), ptr(rows, ctypes.c_int64)))
+        return dist, rows
+
+    def search_rows_device(self, row_ids, k: int, out_dist_ptr: int, out_rows_ptr: int, include_self: bool = False,
+                           stream: int | None = None) -> None:
+        """The same with the outputs (float64 / int64 [B,k]) in device memory; the ids stay on the host.  Complete on return."""
+        ids = self._row_ids(row_ids)
+        check(self._h, self._lib.mi355dr_search_rows_device(
+            self._h, ptr(ids, ctypes.c_int64), ids.shape[0], int(k), 1 if include_self else 0, ctypes.c_void_p(int(out_dist_ptr)),
+            ctypes.c_void_p(int(out_rows_ptr)), ctypes.c_void_p(int(stream) if stream else None)))
+
+    def search_range_rows(self, row_ids, radius, max_results: int,
+                          include_self: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`search_range` with the stored rows `row_ids` as queries; by default the row itself is left out of the count and
+        of the list.  Returns (distance float64 [B,m], rows int64 [B,m], count int64 [B]); count is exact and may exceed m."""
+        ids = self._row_ids(row_ids)
+        B, m = ids.shape[0], int(max_results)
+        r = self._radius(radius, B)
+        dist = np.empty((B, max(m, 0)), dtype=np.float64)
+        rows = np.empty((B, max(m, 0)), dtype=np.int64)
+        count = np.empty(B, dtype=np.int64)
+        check(self._h, self._lib.mi355dr_search_range_rows(
+            self._h, ptr(ids, ctypes.c_int64), B, ptr(r, ctypes.c_double), m, 1 if include_self else 0,
+            ptr(dist, ctypes.c_double), ptr(rows, ctypes.c_int64), ptr(count, ctypes.c_int64)))
+        return dist, rows, count
+
+    def search_range_rows_device(self, row_ids, radius, max_results: int, out_dist_ptr: int, out_rows_ptr: int,
+                                 out_count_ptr: int, include_self: bool = False, stream: int | None = None) -> None:
+        """The same with the three outputs in device memory; ids and radii stay on the host.  Complete on return."""
+        ids = self._row_ids(row_ids)
+        r = self._radius(radius, ids.shape[0])
+        check(self._h, self._lib.mi355dr_search_range_rows_device(
+            self._h, ptr(ids, ctypes.c_int64), ids.shape[0], ptr(r, ctypes.c_double), int(max_results),
+            1 if include_self else 0, ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
+            ctypes.c_void_p(int(out_count_ptr)), ctypes.c_void_p(int(stream) if stream else None)))
+
+    def _row_span(self, row0: int, row1: int | None, block: int) -> tuple[int, int, int]:
+        row0, row1, block = int(row0), len(self) if row1 is None else int(row1), int(block)
+        if row1 < row0 or block < 1:
+            raise ValueError("need row0 <= row1 and block >= 1")
+        return row0, row1, block
+
+    def knn_graph(self, k: int, row0: int = 0, row1: int | None = None, block: int = 1024) -> tuple[np.ndarray, np.ndarray]:
+        """The exact k-NN graph of rows row0 .. row1-1 (global ids; row1=None: len(self)): line i holds the k nearest OTHER
+        live rows of row row0 + i, from `search_rows` in blocks of `block` ids.  Removed rows give NaN / -1 lines.  Returns
+        (distance float64 [n,k], rows int64 [n,k]); the rows never leave the device."""
+        row0, row1, block = self._row_span(row0, row1, block)
+        dist = np.empty((row1 - row0, int(k)), dtype=np.float64)
+        rows = np.empty((row1 - row0, int(k)), dtype=np.int64)
+        for a in range(row0, row1, block):
+            b = min(a + block, row1)
+            dist[a - row0:b - row0], rows[a - row0:b - row0] = self.search_rows(np.arange(a, b, dtype=np.int64), k)
+        return dist, rows
+
+    def near_duplicates(self, radius, max_results: int = 10, row0: int = 0, row1: int | None = None,
+                        block: int = 1024) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """For rows row0 .. row1-1 (global ids; row1=None: len(self)) the OTHER live rows within `radius` (a scalar), from
+        `search_range_rows` in blocks of `block` ids.  Returns (distance [n,m], rows [n,m], count [n]); count[i] > 0 means
+        row row0 + i has a near-copy.  Removed rows give NaN / -1 lines and count 0."""
+        row0, row1, block = self._row_span(row0, row1, block)
+        m = int(max_results)
+        dist = np.empty((row1 - row0, m), dtype=np.float64)
+        rows = np.empty((row1 - row0, m), dtype=np.int64)
+        count = np.empty(row1 - row0, dtype=np.int64)
+        for a in range(row0, row1, block):
+            b = min(a + block, row1)
+            s = slice(a - row0, b - row0)
+            dist[s], rows[s], count[s] = self.search_range_rows(np.arange(a, b, dtype=np.int64), float(radius), m)
+        return dist, rows, count
+
     # ---- views: a listed subset as an index of its own (include/mi355dr.h "views") ----
     def view(self, row_ids=None, doc_ids=None) -> "Mi355Index":
         """The listed rows and / or documents of this index as a read-only index of their own, built on the device

@@ -742,6 +742,36 @@ class Mi355RetrievalService:
         Q = np.stack([q.embedding for q in queries]).astype(np.float32, copy=False)
         return self._range_block(Q, max_distance, limit, unit)
 
+    # ---- search by stored chunk: "more like this" from a primary key (not in the reference's service) ----
+    def similar_chunks(self, doc_ids: list, top_k: int = 10, unit: str = "chunk", max_distance=None) -> list:
+        """For every key of `doc_ids` the `top_k` nearest OTHER chunks: the result dicts and scores of
+        `vector_search_by_embedding` on the chunk's stored embedding, the chunk itself absent.  The stored vectors are read on
+        the device.  With `max_distance` (a scalar or one value per key) every entry is (the up to `top_k` nearest other chunks
+        within that cosine distance, their exact number), as `vector_search_range` returns.  Raises ValueError for a key
+        unknown to the table or without a stored embedding, NotImplementedError under a process group."""
+        if self._world is not None:  # (every rank alike, before any collective)
+            raise NotImplementedError("similar_chunks under a process group: the query row lives on one shard only")
+        doc_ids = list(doc_ids)
+        if not doc_ids:
+            return []
+        u = self._unit(unit)
+        row_of = dict(zip(*self._single_rows_of(u, doc_ids)))
+        pos = u.pos_of_id()
+        for pk in doc_ids:
+            if pk not in pos:
+                raise ValueError(f"Chunk {pk} not found")  # noqa: TRY003
+            if pk not in row_of:
+                msg = f"Chunk {pk} has no embedding" if unit == "chunk" else f"Chunk {pk} has no single-vector embedding"
+                raise ValueError(msg)
+        ids = np.fromiter((row_of[pk] for pk in doc_ids), dtype=np.int64, count=len(doc_ids))
+        searcher = u.single_searcher(None)
+        if max_distance is None:
+            dist, rows = searcher.search_rows(ids, top_k)
+            return self._results_from_block(u.table, u.single_rows, rows, 1.0 - dist, unit == "chunk")
+        dist, rows, count = searcher.search_range_rows(ids, max_distance, top_k)
+        block = self._results_from_block(u.table, u.single_rows, rows, 1.0 - dist, unit == "chunk")
+        return [(res, int(c)) for res, c in zip(block, count.tolist())]
+
     def vector_search_groups(self, embeddings_per_query: list, top_k: int, fetch_k: int | None = None, unit: str = "chunk",
                              search_mode: Literal["single", "multi"] = "single") -> list[list[dict]]:
         """Several searches per question, fused on the device (not in the reference's service: its callers loop in Python,

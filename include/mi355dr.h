@@ -303,6 +303,58 @@ int mi355dr_search_range_device(mi355dr_index* idx, const float* queries_dev, in
                                 int max_results, double* out_dist_dev, int64_t* out_rows_dev, int64_t* out_count_dev,
                                 void* stream);
 
+/* ---- search by stored row: neighbours of rows, self excluded, on the device ----
+ * The self-join form of the two statements above: `SELECT b.id FROM chunk a, chunk b WHERE a.id = :r AND b.id <> a.id ORDER BY
+ * a.embedding <=> b.embedding LIMIT k`, and the same under `a.embedding <=> b.embedding <= :radius` with `count(*)` --
+ * near-duplicate detection at ingest, "more like this" from a primary key, the exact k-NN graph of a corpus.  The query
+ * vectors are read where they lie; they never leave the device.
+ *   The query of slot b: the stored fp32 vector of row row_ids[b].  row_ids: HOST [B], GLOBAL rows (local row + option
+ *     "row_offset"), under the hygiene of mi355dr_search_subset: an id outside [row_offset, row_offset + mi355dr_size) --
+ *     negative values and -1 included -- and a removed row (not a row of the index, although its bytes are still there) give an
+ *     all-NaN / -1 output row and count 0, and are counted in stat "rows_skipped".  An id may be listed more than once: every
+ *     slot is answered.
+ *   flags: 0, or MI355DR_ROWS_INCLUDE_SELF.
+ *   mi355dr_search_rows: with INCLUDE_SELF exactly mi355dr_search(idx, the stored vectors, B, k) -- float8 bits, rows, NaN
+ *     positions and the NaN / -1 tail.  Without it (the default) the top-k of the live rows OTHER than row_ids[b] under the
+ *     library's total order (distance asc, NaN last, row asc), with the same bits.  Equivalently: take the top-(k + 1) list; if
+ *     the row itself is in it, remove it and close the gap; otherwise cut the list to k -- with more than k exact copies of the
+ *     row at lower ids the row itself lies behind the list.  Rows with a NaN distance stay where the ordinary search puts them:
+ *     a zero-norm query row under cosine gives an all-NaN list in row order, itself taken out.
+ *   mi355dr_search_range_rows: with INCLUDE_SELF mi355dr_search_range of the stored vectors.  Without it "in range" is as
+ *     there, and the row itself is left out of the count and of the list.  Whether the row itself was in range is decided from
+ *     the row-with-itself distance -- the bits mi355dr_search returns for the pair -- compared with the radius as doubles (a NaN
+ *     is never in range), not from whether the row appears in the truncated list.  The count stays exact and may exceed
+ *     max_results.  radius: HOST [B].
+ *   MI355DR_E_INVALID: B < 0, k <= 0, max_results < 1, a NaN radius, a null buffer with work to do, unknown flag bits, and all
+ *     four on a view (they take global ids: ask the parent).  MI355DR_E_UNSUPPORTED: without INCLUDE_SELF k + 1 > 1024 or
+ *     max_results + 1 > 1024 (the inner pass needs room for the row itself); with it k or max_results > 1024.  B == 0 is a valid
+ *     no-op.  A refused call changes nothing.
+ *   The call runs under the handle's mutex, first completes whatever search is in flight and is complete on return (the _device
+ *     forms too: `stream`, or the index's own when NULL, is synchronised).  B above 1024 runs in internal blocks.  Per block: the
+ *     ids are uploaded, k_rows_gather copies the rows into a query buffer the index owns, the ordinary search of the block runs
+ *     at k + 1 (the range pass at max_results + 1; k and max_results with INCLUDE_SELF) into lists the index owns, and
+ *     k_rows_drop writes the outputs.  Options and paths apply as in mi355dr_search / mi355dr_search_range.
+ *   Known cost: the inner pass runs at k + 1, so k = 32 is served by the 33 ... 128 class of the search (two-wave prune) and
+ *     k = 128 by the class above it.
+ *   Stats: "rows_searches" (calls), "rows_queries" (slots), "rows_skipped"; the ordinary and the range stats move as the inner
+ *     pass moves them ("passes", "chunks", "range_in_range" -- the inner counts, the rows themselves included -- and so on; the
+ *     call counters "range_searches" / "range_queries" belong to mi355dr_search_range* and stay).
+ *   Not served: views (above); a row-sharded searcher or a process group -- the query row lives on one shard only, so its vector
+ *     has to be broadcast first (mi355dr_get_rows on the owner, then the ordinary sharded search at k + 1). */
+#define MI355DR_ROWS_INCLUDE_SELF 1 /* flags: the query row itself stays in the result (default 0: it is left out) */
+int mi355dr_search_rows(mi355dr_index* idx, const int64_t* row_ids /* HOST [B], global */, int B, int k, int flags,
+                        double* out_dist /* [B, k] */, int64_t* out_rows /* [B, k] */); /* outputs on the host */
+/* out_dist_dev / out_rows_dev [B, k] on the index's device; row_ids stay on the HOST */
+int mi355dr_search_rows_device(mi355dr_index* idx, const int64_t* row_ids /* HOST [B] */, int B, int k, int flags,
+                               double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+int mi355dr_search_range_rows(mi355dr_index* idx, const int64_t* row_ids /* HOST [B] */, int B, const double* radius /* HOST [B] */,
+                              int max_results, int flags, double* out_dist /* [B, max_results] */,
+                              int64_t* out_rows /* [B, max_results] */, int64_t* out_count /* [B] */); /* outputs on the host */
+/* out_dist_dev / out_rows_dev [B, max_results], out_count_dev [B] on the index's device; row_ids and the radii stay on the HOST */
+int mi355dr_search_range_rows_device(mi355dr_index* idx, const int64_t* row_ids /* HOST [B] */, int B,
+                                     const double* radius /* HOST [B] */, int max_results, int flags, double* out_dist_dev,
+                                     int64_t* out_rows_dev, int64_t* out_count_dev, void* stream);
+
 /* ---- views: a listed subset of rows / documents as an index of its own ----
  * For a list that is searched again and again -- one tenant, one document collection, one PDF's pages: the key filter of the
  * statement above, fixed for many query blocks.  mi355dr_search_subset scans the list exactly on every call (cost ~ m x B, no
@@ -332,7 +384,7 @@ int mi355dr_search_range_device(mi355dr_index* idx, const float* queries_dev, in
  *   Read-only: mi355dr_add_rows*, _update_rows*, _remove_rows, _compact, _reserve, _add_multivec*, _set_multivec* and option
  *     "row_offset" return MI355DR_E_INVALID on a view and change nothing.  So does every entry point that takes global ids or a
  *     communicator, with an error text that refers the caller to the parent: mi355dr_search_subset*, _score_subset, _search_mmr*, _mmr_select,
- *     _maxsim_subset*, _search_maxsim_subset*, _gqr_refine, _gqr_refine_maxsim, _comm_init*, _search_sharded_device, and mi355dr_view_create itself (no
+ *     _search_rows*, _search_range_rows*, _maxsim_subset*, _search_maxsim_subset*, _gqr_refine, _gqr_refine_maxsim, _comm_init*, _search_sharded_device, and mi355dr_view_create itself (no
  *     views of views).  The stateless ones stay usable: mi355dr_merge_topk*, _pack_topk_device, _gqr_refine_scores, _merge_groups_device.
  *   The call takes the parent's mutex, first completes whatever search is in flight there, and is complete on return;
  *     afterwards the two handles are independent.  The parent is only read.  On any error *out_view is NULL, everything
@@ -570,6 +622,7 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
  *          "group_searches" / "group_subqueries" / "groups_merged" (mi355dr_search_groups* and mi355dr_merge_groups_device, described there),
  *          "range_searches" / "range_queries" / "range_in_range" / "range_candidates" / "range_rescored" / "range_redo_chunks" /
  *          "range_fallback_queries" (mi355dr_search_range*, described there),
+ *          "rows_searches" / "rows_queries" / "rows_skipped" (mi355dr_search_rows* and mi355dr_search_range_rows*, described there),
  *          "maxsim_subset_searches" / "maxsim_subset_docs" / "maxsim_subset_screened" / "maxsim_subset_exact" /
  *          "maxsim_subset_fallbacks" (mi355dr_search_maxsim_subset, described there),
  *          "view" / "view_rows" / "view_docs" (mi355dr_view_create: 1 on a view / the rows / the documents it holds),
