@@ -98,6 +98,84 @@ struct RetryBufs {
     DevBuf<int> map;       // [kQBlockMax] position of each sub-block query in its block
 };
 constexpr int kPendingRing = 4;
+
+// ---- per-family scratch of the derived searches: plain owners, each grown by its reserve() at the start of a call (or block).
+// A reserve() that fails leaves what it already grew: the buffers are only ever larger.  None of them stages results for the
+// host (mi355dr_index::out_*_dev does), except the grouped search's [G, k], which is not block-shaped.
+template <class... Bufs>
+hipError_t grow_each(size_t n, Bufs&... bufs) {  // every buffer to at least n of ITS elements, in order, up to the first failure
+    hipError_t e = hipSuccess;
+    (void)(((e = bufs.grow(n * sizeof(*bufs.p))) == hipSuccess) && ...);
+    return e;
+}
+// MMR (mi355dr_search_mmr / mi355dr_mmr_select): one block's candidate lists in the total order
+// [nb, stride] and the kernel's pair counter
+struct MmrBufs {
+    DevBuf<double> cand_dist;
+    DevBuf<int64_t> cand_rows;
+    DevBuf<unsigned long long> pairs_dev;
+    hipError_t reserve(size_t nb, size_t stride) {
+        hipError_t e = grow_each(nb * stride, cand_dist, cand_rows);
+        if (!e) e = grow_each(1, pairs_dev);
+        return e;
+    }
+};
+// grouped search (mi355dr_search_groups* / mi355dr_merge_groups_device): the call's group offsets
+// [G + 1], the sub-queries' lists [S, fetch_k] and the host form's result staging [G, k] / [G] (k up to 4096, G unbounded:
+// not block-shaped, so it grows here; the count is int32 as in the C ABI)
+struct GroupBufs {
+    DevBuf<int32_t> offsets, count;
+    DevBuf<double> cand_dist, out_dist;
+    DevBuf<int64_t> cand_rows, out_rows;
+    hipError_t reserve(size_t G, size_t S, size_t fetch_k, size_t k, bool host) {  // (the merge alone: S = 0, host = false)
+        hipError_t e = grow_each(G + 1, offsets);
+        if (!e) e = grow_each(S * fetch_k, cand_dist, cand_rows);
+        if (!e && host) e = grow_each(G * k, out_dist, out_rows);
+        if (!e && host) e = grow_each(G, count);
+        return e;
+    }
+};
+// range search (mi355dr_search_range*): one block's result buffers [nb, R slots] with their per-query
+// words, the radii, the redo list of `pairs` pairs, the two device counters and the sub-block of the queries the ordinary
+// search serves (fb_*: map, gathered queries, lists [nb, m])
+struct RangeBufs {
+    DevBuf<uint64_t> key, rkey;
+    DevBuf<int32_t> row, xfrom;
+    DevBuf<unsigned long long> count, stat;
+    DevBuf<double> radius, fb_dist;
+    DevBuf<int> redo, flag, fb_map;
+    DevBuf<int64_t> fb_rows;
+    DevBuf<float> fb_q;
+    int collect_lds = 0;  // dynamic LDS k_range_collect is registered for (0: not yet)
+    hipError_t reserve(size_t nb, size_t R, size_t m, size_t pairs, size_t dim) {
+        hipError_t e = grow_each(nb * R, key, row);
+        if (!e) e = grow_each(nb, count, rkey, xfrom, radius, flag, fb_map);
+        if (!e) e = grow_each(2, stat);
+        if (!e) e = grow_each(2 + 2 * pairs, redo);
+        if (!e) e = grow_each(nb * dim, fb_q);
+        if (!e) e = grow_each(nb * m, fb_dist, fb_rows);
+        return e;
+    }
+};
+// search by stored row (mi355dr_search_rows* / mi355dr_search_range_rows*): one block's ids, gathered
+// query vectors [nb, dim] and validity words, the inner pass's lists [nb, stride = k + 1] / counts, the range form's (slot, row)
+// pairs with their row-with-itself distances and the radii, the skipped-slot counter
+struct RowQueryBufs {
+    DevBuf<int64_t> ids, pair_row, cand_rows, cand_count;
+    DevBuf<float> q, self_dot;
+    DevBuf<int> valid;
+    DevBuf<int32_t> pair_q;
+    DevBuf<double> cand_dist, self_dist, radius;
+    DevBuf<unsigned long long> skipped_dev;
+    hipError_t reserve(size_t nb, size_t stride, size_t dim, bool range) {
+        hipError_t e = grow_each(nb, ids, valid, pair_q, pair_row);
+        if (!e) e = grow_each(nb * dim, q);
+        if (!e) e = grow_each(nb * stride, cand_dist, cand_rows);
+        if (!e) e = grow_each(1, skipped_dev);
+        if (!e && range) e = grow_each(nb, cand_count, self_dot, self_dist, radius);
+        return e;
+    }
+};
 }  // namespace mi355
 
 struct mi355dr_index {
@@ -145,42 +223,21 @@ struct mi355dr_index {
     mi355::DevBuf<int> qlist_dev;    // [2 * kQBlockMax] second half: overflow re-runs of the exact scan
     int* status_or_dev = nullptr;    // = st.status + kQBlockMax
     mi355::HostBuf<int> status_host;  // pinned [kQBlockMax + 1]
-    mi355::DevBuf<double> out_dist_dev;  // [kQBlockMax, kKMax]
-    mi355::DevBuf<int64_t> out_rows_dev;
+    // THE result staging of every host form (search, subset, MMR, range, by-row; mi355dr.hip block_outputs / block_return): one
+    // block's [nb <= kQBlockMax, width <= kKMax] distances and rows and its [nb] counts.  One set is enough because only an
+    // OUTERMOST entry point stages, and it holds `mu` from before its first block until its last copy has landed.  Inner passes
+    // never stage: range_block under the by-row search, search_block under range_block's fallback, under MMR and under the
+    // grouped search, and complete_block's fix-up levels each write to the *_cand_*, rng.fb_* or retry[] buffer they were given.
+    mi355::DevBuf<double> out_dist_dev;    // [kQBlockMax, kKMax]
+    mi355::DevBuf<int64_t> out_rows_dev;   // [kQBlockMax, kKMax]
+    mi355::DevBuf<int64_t> out_count_dev;  // [kQBlockMax]
     mi355::DevBuf<unsigned long long> stat_dev;  // [2*kQBlockMax]: per query (candidates, re-scored)
     mi355::DevBuf<int> prune_skip;   // [2 + 2*kQBlockMax] hand-over lists of k_prune (PruneArgs::skip_list)
     mi355::DevBuf<int32_t> subset_ids;  // the listed rows of the mi355dr_search_subset call in progress: local, ascending, unique
-    // MMR (mi355dr_search_mmr / mi355dr_mmr_select): one block's candidate lists in the total order
-    // [nb, fetch_k], the host forms' result staging [nb, k], and the kernel's pair counter -- grown by ensure_mmr
-    mi355::DevBuf<double> mmr_cand_dist, mmr_out_dist;
-    mi355::DevBuf<int64_t> mmr_cand_rows, mmr_out_rows;
-    mi355::DevBuf<unsigned long long> mmr_pairs_dev;
-    // grouped search (mi355dr_search_groups* / mi355dr_merge_groups_device): the call's group offsets
-    // [G + 1], the sub-queries' lists [S, fetch_k] and the host form's result staging [G, k] / [G] -- grown by the calls
-    mi355::DevBuf<int32_t> grp_offsets, grp_count;
-    mi355::DevBuf<double> grp_cand_dist, grp_out_dist;
-    mi355::DevBuf<int64_t> grp_cand_rows, grp_out_rows;
-    // range search (mi355dr_search_range*): one block's result buffers [nb, range_slots] with their
-    // per-query words, the radii, the redo list, the two device counters, the host forms' result staging [nb, max_results] /
-    // [nb] and the sub-block of the queries the ordinary search serves -- grown by ensure_range
-    mi355::DevBuf<uint64_t> rng_key, rng_rkey;
-    mi355::DevBuf<int32_t> rng_row, rng_xfrom;
-    mi355::DevBuf<unsigned long long> rng_count, rng_stat;
-    mi355::DevBuf<double> rng_radius, rng_out_dist, rng_fb_dist;
-    mi355::DevBuf<int> rng_redo, rng_flag, rng_fb_map;
-    mi355::DevBuf<int64_t> rng_out_rows, rng_out_count, rng_fb_rows;
-    mi355::DevBuf<float> rng_fb_q;
-    int rng_collect_lds = 0;  // dynamic LDS k_range_collect is registered for (0: not yet)
-    // search by stored row (mi355dr_search_rows* / mi355dr_search_range_rows*): one block's ids, gathered
-    // query vectors [nb, dim] and validity words, the inner pass's lists [nb, k + 1] / counts, the range form's (slot, row) pairs
-    // with their row-with-itself distances and the radii, the host forms' result staging, the skipped-slot counter -- grown
-    // by ensure_rows
-    mi355::DevBuf<int64_t> rowq_ids, rowq_pair_row, rowq_cand_rows, rowq_cand_count, rowq_out_rows, rowq_out_count;
-    mi355::DevBuf<float> rowq_q, rowq_self_dot;
-    mi355::DevBuf<int> rowq_valid;
-    mi355::DevBuf<int32_t> rowq_pair_q;
-    mi355::DevBuf<double> rowq_cand_dist, rowq_self_dist, rowq_radius, rowq_out_dist;
-    mi355::DevBuf<unsigned long long> rowq_skipped_dev;
+    mi355::MmrBufs mmr;      // per-family scratch of the derived searches (above): grown by each family's reserve()
+    mi355::GroupBufs grp;
+    mi355::RangeBufs rng;
+    mi355::RowQueryBufs rowq;
     // a view (mi355dr_view_create; DESIGN.md "Views"): a read-only index built from listed rows / documents of a parent.  The
     // maps are null on every other index: the result-writing kernels then add row_offset instead
     bool is_view = false;

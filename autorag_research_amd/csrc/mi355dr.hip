@@ -127,6 +127,7 @@ int ensure_qstate(mi355dr_index* idx) {
     HIPCHECK(idx, idx->status_host.grow((B + 1) * sizeof(int)));
     HIPCHECK(idx, idx->out_dist_dev.grow(B * kKMax * sizeof(double)));
     HIPCHECK(idx, idx->out_rows_dev.grow(B * kKMax * sizeof(int64_t)));
+    HIPCHECK(idx, idx->out_count_dev.grow(B * sizeof(int64_t)));
     HIPCHECK(idx, idx->prune_skip.grow((2 + 2 * B) * sizeof(int)));
     HIPCHECK(idx, idx->stat_dev.grow(2 * B * sizeof(unsigned long long)));
     HIPCHECK(idx, hipMemsetAsync(idx->stat_dev, 0, 2 * B * sizeof(unsigned long long), idx->stream));
@@ -961,7 +962,7 @@ int launch_merge(mi355dr_index* idx, const double* dist_all, const int64_t* rows
     return MI355DR_OK;
 }
 
-// the debug entry points' start: blocks in flight finished, the B queries uploaded and prepared (`metric`: k_prep_queries)
+// the start of the debug entry points and of a host pair list (rescore_host_pairs): blocks in flight finished, the B queries uploaded and prepared (`metric`: k_prep_queries)
 int upload_and_prep(mi355dr_index* idx, const float* queries, int B, int metric) {
     HIPCHECK(idx, hipSetDevice(idx->device));
     CHECK(drain_pending(idx));
@@ -975,6 +976,114 @@ int check_search_args(mi355dr_index* idx, const void* q, int B, int k, const voi
     if (B < 0 || k <= 0) return fail(idx, MI355DR_E_INVALID, "B must be >= 0 and k > 0");
     if (k > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, "k exceeds 1024");
     if (B > 0 && (!q || !od || !orow)) return fail(idx, MI355DR_E_INVALID, "null buffer");
+    return MI355DR_OK;
+}
+
+int check_radii(mi355dr_index* idx, const std::string& what, const double* radius, int B) {
+    for (int b = 0; b < B; ++b)
+        if (radius[b] != radius[b]) return fail(idx, MI355DR_E_INVALID, what + ": radius " + std::to_string(b) + " is NaN");
+    return MI355DR_OK;
+}
+
+// ---- the call frame of the search entry points ---------------------------------------------------------------------------
+// begin_call(), in this order: null handle; a view refuses (kCallNoView; is_view is set once, before the handle is handed
+// out); the call's own argument checks (`args_ok`: nothing has been touched when they fail); the handle's mutex, held until
+// `c` leaves; the device; blocks in flight finished (kCallDrain: they complete, and their errors surface, on an empty call too);
+// the caller's stream or the handle's; the per-search state.  The empty-call return is the caller's, behind this.
+enum : unsigned { kCallNoView = 1, kCallDrain = 2 };
+struct Call {
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s = nullptr;
+};
+template <class ArgCheck>
+int begin_call(mi355dr_index* idx, const char* what, void* stream, unsigned flags, Call& c, ArgCheck&& args_ok) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    if ((flags & kCallNoView) && idx->is_view) return view_refuses(idx, what, /*ask_parent=*/true);
+    CHECK(args_ok());
+    c.lock = std::unique_lock<std::mutex>(idx->mu);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    if (flags & kCallDrain) CHECK(drain_pending(idx));
+    c.s = stream ? (hipStream_t)stream : idx->stream;
+    return ensure_qstate(idx);
+}
+
+// ---- one call's queries and results, block by block ------------------------------------------------------------------------
+// host == true: the caller's buffers are host memory -- a block's queries are staged through idx->qdev, its results through
+// the handle's one result staging (index.h: out_*_dev); else they are device memory used in place.  `width`: entries per
+// result line; `count` (int64, the grouped search's int32): null when the call has none.
+template <class Count>
+struct BlockOut {
+    double* dist;
+    int64_t* rows;
+    Count* count;
+};
+template <class Count = int64_t>
+struct CallIO {
+    bool host;
+    hipStream_t s;
+    const float* q;       // the caller's queries [B, dim] (null: the call brings none)
+    BlockOut<Count> out;  // the caller's results [B, width] / [B]
+    int width;
+};
+
+// the device pointer of queries [b0, b0 + nb) (host form: uploaded behind whatever still reads qdev on the stream)
+template <class Count>
+int block_queries(mi355dr_index* idx, const CallIO<Count>& io, int b0, int nb, const float** q_dev) {
+    *q_dev = io.q + (int64_t)b0 * idx->dim;
+    if (!io.host) return MI355DR_OK;
+    HIPCHECK(idx, hipMemcpyAsync(idx->qdev, *q_dev, (size_t)nb * idx->dim * sizeof(float), hipMemcpyHostToDevice, io.s));
+    *q_dev = idx->qdev;
+    return MI355DR_OK;
+}
+
+// where the kernels write the results of the block that starts at b0
+BlockOut<int64_t> block_outputs(mi355dr_index* idx, const CallIO<>& io, int b0) {
+    if (io.host) return {idx->out_dist_dev, idx->out_rows_dev, io.out.count ? idx->out_count_dev.p : nullptr};
+    return {io.out.dist + (int64_t)b0 * io.width, io.out.rows + (int64_t)b0 * io.width, io.out.count ? io.out.count + b0 : nullptr};
+}
+
+// host form: the block's nb lines (and counts) from where they were staged (`o`) to the caller's, asynchronous on the
+// stream; device form: they are in place
+template <class Count>
+int block_return(mi355dr_index* idx, const CallIO<Count>& io, int b0, int nb, const BlockOut<Count>& o) {
+    if (!io.host) return MI355DR_OK;
+    const size_t n = (size_t)nb * io.width;
+    HIPCHECK(idx, hipMemcpyAsync(io.out.dist + (int64_t)b0 * io.width, o.dist, n * sizeof(double), hipMemcpyDeviceToHost, io.s));
+    HIPCHECK(idx, hipMemcpyAsync(io.out.rows + (int64_t)b0 * io.width, o.rows, n * sizeof(int64_t), hipMemcpyDeviceToHost, io.s));
+    if (o.count) HIPCHECK(idx, hipMemcpyAsync(io.out.count + b0, o.count, (size_t)nb * sizeof(Count), hipMemcpyDeviceToHost, io.s));
+    return MI355DR_OK;
+}
+
+// ---- exact distances of listed (query, row) pairs ---------------------------------------------------------------------------
+// the pairs' queries are the prepared block in qdev; k_rescore_pairs does not range-check: rows are local and inside the index
+int launch_rescore(mi355dr_index* idx, hipStream_t s, const int32_t* pair_q_dev, const int64_t* pair_row_dev, int64_t n_pairs,
+                   float* dot_dev, double* dist_dev) {
+    hipLaunchKernelGGL(k_rescore_pairs, dim3((unsigned)((n_pairs + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows, idx->nrm2,
+                       idx->qdev, idx->st.qn, pair_q_dev, pair_row_dev, n_pairs, idx->dim, idx->metric, dot_dev, dist_dev);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+// the same for pairs listed on the host, against a block of B host queries: blocks in flight finished, the queries uploaded
+// and prepared, the lists uploaded, the distances (out_dot != null: and the dots) back in the caller's arrays on return.
+// `bufs` is the caller's local: it grows with the largest list of the call and leaves with it.
+struct PairBufs {
+    DevBuf<int32_t> q;
+    DevBuf<int64_t> row;
+    DevBuf<float> dot;
+    DevBuf<double> dist;
+};
+int rescore_host_pairs(mi355dr_index* idx, PairBufs& bufs, const float* queries, int B, const int32_t* pair_q,
+                       const int64_t* pair_row, int64_t n_pairs, float* out_dot, double* out_dist) {
+    hipStream_t s = idx->stream;
+    CHECK(upload_and_prep(idx, queries, B, idx->metric));
+    HIPCHECK(idx, grow_each(n_pairs, bufs.q, bufs.row, bufs.dot, bufs.dist));
+    HIPCHECK(idx, hipMemcpyAsync(bufs.q.p, pair_q, n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHECK(idx, hipMemcpyAsync(bufs.row.p, pair_row, n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    CHECK(launch_rescore(idx, s, bufs.q.p, bufs.row.p, n_pairs, bufs.dot.p, bufs.dist.p));
+    if (out_dot) HIPCHECK(idx, hipMemcpyAsync(out_dot, bufs.dot.p, n_pairs * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(out_dist, bufs.dist.p, n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipStreamSynchronize(s));
     return MI355DR_OK;
 }
 
@@ -1490,22 +1599,17 @@ int mi355dr_get_rows(mi355dr_index* idx, int64_t row0, int64_t n, float* out) {
 }
 
 int mi355dr_search(mi355dr_index* idx, const float* queries, int B, int k, double* out_dist, int64_t* out_rows) {
-    CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
-    CHECK(ensure_qstate(idx));
-    hipStream_t s = idx->stream;
+    Call c;
+    CHECK(begin_call(idx, "search", nullptr, kCallDrain, c, [&] { return check_search_args(idx, queries, B, k, out_dist, out_rows); }));
+    const CallIO<> io{/*host=*/true, c.s, queries, {out_dist, out_rows, nullptr}, k};
     for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
         const int nb = std::min(kQBlockMax, B - b0);
-        HIPCHECK(idx, hipMemcpyAsync(idx->qdev, queries + (int64_t)b0 * idx->dim, (size_t)nb * idx->dim * sizeof(float),
-                                     hipMemcpyHostToDevice, s));
-        CHECK(search_block(idx, s, idx->qdev, nb, k, idx->out_dist_dev, idx->out_rows_dev));
-        HIPCHECK(idx, hipMemcpyAsync(out_dist + (int64_t)b0 * k, idx->out_dist_dev, (size_t)nb * k * sizeof(double),
-                                     hipMemcpyDeviceToHost, s));
-        HIPCHECK(idx, hipMemcpyAsync(out_rows + (int64_t)b0 * k, idx->out_rows_dev, (size_t)nb * k * sizeof(int64_t),
-                                     hipMemcpyDeviceToHost, s));
-        HIPCHECK(idx, hipStreamSynchronize(s));
+        const float* q = nullptr;
+        CHECK(block_queries(idx, io, b0, nb, &q));
+        const BlockOut<int64_t> o = block_outputs(idx, io, b0);
+        CHECK(search_block(idx, c.s, q, nb, k, o.dist, o.rows));
+        CHECK(block_return(idx, io, b0, nb, o));
+        HIPCHECK(idx, hipStreamSynchronize(c.s));
     }
     return MI355DR_OK;
 }
@@ -1574,34 +1678,27 @@ int subset_upload_ids(mi355dr_index* idx, hipStream_t s, const int64_t* row_ids,
     return MI355DR_OK;
 }
 
-// host == true: queries / outputs are host buffers staged through the index's own; else device buffers used in place
+// (for `host`, here and in the families below, see CallIO)
 int search_subset_impl(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* row_ids, int64_t m,
-                       double* out_dist, int64_t* out_rows, hipStream_t s, bool host) {
-    if (idx && idx->is_view) return view_refuses(idx, "search_subset", /*ask_parent=*/true);  // (set once, before the handle is handed out)
-    CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
-    if (m < 0 || (m > 0 && !row_ids)) return fail(idx, MI355DR_E_INVALID, "search_subset: m must be >= 0 and row_ids not null");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
+                       double* out_dist, int64_t* out_rows, void* stream, bool host) {
+    Call c;
+    CHECK(begin_call(idx, "search_subset", stream, kCallNoView | kCallDrain, c, [&]() -> int {
+        CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
+        if (m < 0 || (m > 0 && !row_ids)) return fail(idx, MI355DR_E_INVALID, "search_subset: m must be >= 0 and row_ids not null");
+        return MI355DR_OK;
+    }));
     if (B == 0) return MI355DR_OK;
-    if (!s) s = idx->stream;
     int64_t m_valid = 0;
-    CHECK(subset_upload_ids(idx, s, row_ids, m, &m_valid));
-    CHECK(ensure_qstate(idx));
+    CHECK(subset_upload_ids(idx, c.s, row_ids, m, &m_valid));
+    const CallIO<> io{host, c.s, queries, {out_dist, out_rows, nullptr}, k};
     for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
         const int nb = std::min(kQBlockMax, B - b0);
-        const float* q = queries + (int64_t)b0 * idx->dim;
-        double* od = out_dist + (int64_t)b0 * k;
-        int64_t* orow = out_rows + (int64_t)b0 * k;
-        if (host) {
-            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q, (size_t)nb * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
-            CHECK(subset_block(idx, s, idx->qdev, nb, k, m_valid, idx->out_dist_dev, idx->out_rows_dev));
-            HIPCHECK(idx, hipMemcpyAsync(od, idx->out_dist_dev, (size_t)nb * k * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIPCHECK(idx, hipMemcpyAsync(orow, idx->out_rows_dev, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            HIPCHECK(idx, hipStreamSynchronize(s));
-        } else {
-            CHECK(subset_block(idx, s, q, nb, k, m_valid, od, orow));
-        }
+        const float* q = nullptr;
+        CHECK(block_queries(idx, io, b0, nb, &q));
+        const BlockOut<int64_t> o = block_outputs(idx, io, b0);
+        CHECK(subset_block(idx, c.s, q, nb, k, m_valid, o.dist, o.rows));  // (complete on return)
+        CHECK(block_return(idx, io, b0, nb, o));
+        if (host) HIPCHECK(idx, hipStreamSynchronize(c.s));
     }
     idx->s_subset_searches++;
     idx->s_subset_rows_scored += m_valid * B;
@@ -1616,28 +1713,23 @@ int mi355dr_search_subset(mi355dr_index* idx, const float* queries, int B, int k
 
 int mi355dr_search_subset_device(mi355dr_index* idx, const float* queries_dev, int B, int k, const int64_t* row_ids, int64_t m,
                                  double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
-    return search_subset_impl(idx, queries_dev, B, k, row_ids, m, out_dist_dev, out_rows_dev, (hipStream_t)stream, /*host=*/false);
+    return search_subset_impl(idx, queries_dev, B, k, row_ids, m, out_dist_dev, out_rows_dev, stream, /*host=*/false);
 }
 
 int mi355dr_score_subset(mi355dr_index* idx, const float* queries, int B, const int64_t* row_ids, int m, double* out_dist) {
-    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
-    if (idx->is_view) return view_refuses(idx, "score_subset", /*ask_parent=*/true);
-    if (B < 0 || m < 0) return fail(idx, MI355DR_E_INVALID, "score_subset: B and m must be >= 0");
-    if (B > 0 && (!queries || (m > 0 && (!row_ids || !out_dist)))) return fail(idx, MI355DR_E_INVALID, "null buffer");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
+    Call c;
+    CHECK(begin_call(idx, "score_subset", nullptr, kCallNoView | kCallDrain, c, [&]() -> int {
+        if (B < 0 || m < 0) return fail(idx, MI355DR_E_INVALID, "score_subset: B and m must be >= 0");
+        if (B > 0 && (!queries || (m > 0 && (!row_ids || !out_dist)))) return fail(idx, MI355DR_E_INVALID, "null buffer");
+        return MI355DR_OK;
+    }));
     const int64_t total = (int64_t)B * m;
     for (int64_t i = 0; i < total; ++i) out_dist[i] = NAN;
     if (total == 0) return MI355DR_OK;
-    hipStream_t s = idx->stream;
     std::vector<int32_t> pq;
     std::vector<int64_t> pr, where;  // where: the pair's slot in out_dist
     std::vector<double> got;
-    DevBuf<int32_t> pq_dev;
-    DevBuf<int64_t> pr_dev;
-    DevBuf<float> dot_dev;
-    DevBuf<double> dist_dev;
+    PairBufs bufs;
     for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
         const int nb = std::min(kQBlockMax, B - b0);
         try {  // pairs for the ids inside this index only: k_rescore_pairs does not range-check
@@ -1658,19 +1750,7 @@ int mi355dr_score_subset(mi355dr_index* idx, const float* queries, int B, const 
         }
         const int64_t n_pairs = (int64_t)pq.size();
         if (n_pairs == 0) continue;
-        HIPCHECK(idx, pq_dev.grow(n_pairs * sizeof(int32_t)));
-        HIPCHECK(idx, pr_dev.grow(n_pairs * sizeof(int64_t)));
-        HIPCHECK(idx, dot_dev.grow(n_pairs * sizeof(float)));
-        HIPCHECK(idx, dist_dev.grow(n_pairs * sizeof(double)));
-        CHECK(upload_and_prep(idx, queries + (int64_t)b0 * idx->dim, nb, idx->metric));
-        HIPCHECK(idx, hipMemcpyAsync(pq_dev.p, pq.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIPCHECK(idx, hipMemcpyAsync(pr_dev.p, pr.data(), n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_rescore_pairs, dim3((unsigned)((n_pairs + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows,
-                           idx->nrm2, idx->qdev, idx->st.qn, pq_dev.p, pr_dev.p, n_pairs, idx->dim, idx->metric, dot_dev.p,
-                           dist_dev.p);
-        HIPCHECK(idx, hipGetLastError());
-        HIPCHECK(idx, hipMemcpyAsync(got.data(), dist_dev.p, n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHECK(idx, hipStreamSynchronize(s));
+        CHECK(rescore_host_pairs(idx, bufs, queries + (int64_t)b0 * idx->dim, nb, pq.data(), pr.data(), n_pairs, nullptr, got.data()));
         for (int64_t i = 0; i < n_pairs; ++i) out_dist[where[i]] = got[i];  // (a removed row, an undefined distance: the kernel's NaN)
     }
     return MI355DR_OK;
@@ -1683,24 +1763,12 @@ int check_mmr_lambda(mi355dr_index* idx, const char* what, double lambda) {
     return MI355DR_OK;
 }
 
-// the handle's MMR buffers for a block of nb lists of `stride` candidates and (host forms) nb x k results
-int ensure_mmr(mi355dr_index* idx, int nb, int stride, int k, bool host) {
-    HIPCHECK(idx, idx->mmr_cand_dist.grow((size_t)nb * stride * sizeof(double)));
-    HIPCHECK(idx, idx->mmr_cand_rows.grow((size_t)nb * stride * sizeof(int64_t)));
-    if (host) {
-        HIPCHECK(idx, idx->mmr_out_dist.grow((size_t)nb * k * sizeof(double)));
-        HIPCHECK(idx, idx->mmr_out_rows.grow((size_t)nb * k * sizeof(int64_t)));
-    }
-    HIPCHECK(idx, idx->mmr_pairs_dev.grow(sizeof(unsigned long long)));
-    return MI355DR_OK;
-}
-
-// nb lists [nb, stride] in idx->mmr_cand_* -> [nb, k] picks; asynchronous on the stream
+// nb lists [nb, stride] in idx->mmr.cand_* -> [nb, k] picks; asynchronous on the stream
 int launch_mmr(mi355dr_index* idx, hipStream_t s, int nb, int stride, int k, double lambda, double* out_dist_dev,
                int64_t* out_rows_dev) {
-    hipLaunchKernelGGL(k_mmr_select, dim3(nb), dim3(kMmrThreads), mmr_lds_bytes(idx->dim, stride), s, idx->mmr_cand_rows.p,
-                       idx->mmr_cand_dist.p, stride, idx->rows.p, idx->nrm2.p, idx->n, idx->row_offset, idx->dim, idx->metric, k,
-                       lambda, out_dist_dev, out_rows_dev, idx->mmr_pairs_dev.p);
+    hipLaunchKernelGGL(k_mmr_select, dim3(nb), dim3(kMmrThreads), mmr_lds_bytes(idx->dim, stride), s, idx->mmr.cand_rows.p,
+                       idx->mmr.cand_dist.p, stride, idx->rows.p, idx->nrm2.p, idx->n, idx->row_offset, idx->dim, idx->metric, k,
+                       lambda, out_dist_dev, out_rows_dev, idx->mmr.pairs_dev.p);
     HIPCHECK(idx, hipGetLastError());
     return MI355DR_OK;
 }
@@ -1708,47 +1776,38 @@ int launch_mmr(mi355dr_index* idx, hipStream_t s, int nb, int stride, int k, dou
 // the call's last step (the stream is idle): the kernel's pair counter into the stats
 int mmr_finish(mi355dr_index* idx, int B) {
     unsigned long long pairs = 0;
-    HIPCHECK(idx, hipMemcpy(&pairs, idx->mmr_pairs_dev.p, sizeof(pairs), hipMemcpyDeviceToHost));
+    HIPCHECK(idx, hipMemcpy(&pairs, idx->mmr.pairs_dev.p, sizeof(pairs), hipMemcpyDeviceToHost));
     idx->s_mmr_searches++;
     idx->s_mmr_queries += B;
     idx->s_mmr_pairs += (int64_t)pairs;
     return MI355DR_OK;
 }
 
-// host == true: queries / outputs are host buffers staged through the index's own; else device buffers used in place
 int search_mmr_impl(mi355dr_index* idx, const float* queries, int B, int k, int fetch_k, double lambda, double* out_dist,
-                    int64_t* out_rows, hipStream_t s, bool host) {
-    if (idx && idx->is_view) return view_refuses(idx, "search_mmr", /*ask_parent=*/true);  // (set once, before the handle is handed out)
-    CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
-    CHECK(check_mmr_lambda(idx, "search_mmr", lambda));
-    if (fetch_k < k) return fail(idx, MI355DR_E_INVALID, "search_mmr: fetch_k must be >= k");
-    if (fetch_k > kMmrMax) return fail(idx, MI355DR_E_UNSUPPORTED, "search_mmr: fetch_k exceeds 1024");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
+                    int64_t* out_rows, void* stream, bool host) {
+    Call c;
+    CHECK(begin_call(idx, "search_mmr", stream, kCallNoView | kCallDrain, c, [&]() -> int {
+        CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
+        CHECK(check_mmr_lambda(idx, "search_mmr", lambda));
+        if (fetch_k < k) return fail(idx, MI355DR_E_INVALID, "search_mmr: fetch_k must be >= k");
+        if (fetch_k > kMmrMax) return fail(idx, MI355DR_E_UNSUPPORTED, "search_mmr: fetch_k exceeds 1024");
+        return MI355DR_OK;
+    }));
     if (B == 0) return MI355DR_OK;
-    if (!s) s = idx->stream;
-    CHECK(ensure_qstate(idx));
-    CHECK(ensure_mmr(idx, std::min(B, kQBlockMax), fetch_k, k, host));
-    HIPCHECK(idx, hipMemsetAsync(idx->mmr_pairs_dev.p, 0, sizeof(unsigned long long), s));
+    HIPCHECK(idx, idx->mmr.reserve(std::min(B, kQBlockMax), fetch_k));
+    HIPCHECK(idx, hipMemsetAsync(idx->mmr.pairs_dev.p, 0, sizeof(unsigned long long), c.s));
+    const CallIO<> io{host, c.s, queries, {out_dist, out_rows, nullptr}, k};
     for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
         const int nb = std::min(kQBlockMax, B - b0);
-        const float* q = queries + (int64_t)b0 * idx->dim;
-        double* od = out_dist + (int64_t)b0 * k;
-        int64_t* orow = out_rows + (int64_t)b0 * k;
-        if (host) {
-            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q, (size_t)nb * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
-            q = idx->qdev;
-        }
+        const float* q = nullptr;
+        CHECK(block_queries(idx, io, b0, nb, &q));
+        const BlockOut<int64_t> o = block_outputs(idx, io, b0);
         // the ordinary search of the block at fetch_k (screened, fix-ups completed), then the selection behind it
-        CHECK(search_block(idx, s, q, nb, fetch_k, idx->mmr_cand_dist.p, idx->mmr_cand_rows.p));
-        CHECK(launch_mmr(idx, s, nb, fetch_k, k, lambda, host ? idx->mmr_out_dist.p : od, host ? idx->mmr_out_rows.p : orow));
-        if (host) {
-            HIPCHECK(idx, hipMemcpyAsync(od, idx->mmr_out_dist.p, (size_t)nb * k * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIPCHECK(idx, hipMemcpyAsync(orow, idx->mmr_out_rows.p, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        }
+        CHECK(search_block(idx, c.s, q, nb, fetch_k, idx->mmr.cand_dist.p, idx->mmr.cand_rows.p));
+        CHECK(launch_mmr(idx, c.s, nb, fetch_k, k, lambda, o.dist, o.rows));
+        CHECK(block_return(idx, io, b0, nb, o));
     }
-    HIPCHECK(idx, hipStreamSynchronize(s));
+    HIPCHECK(idx, hipStreamSynchronize(c.s));
     return mmr_finish(idx, B);
 }
 }  // namespace
@@ -1760,36 +1819,33 @@ int mi355dr_search_mmr(mi355dr_index* idx, const float* queries, int B, int k, i
 
 int mi355dr_search_mmr_device(mi355dr_index* idx, const float* queries_dev, int B, int k, int fetch_k, double lambda,
                               double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
-    return search_mmr_impl(idx, queries_dev, B, k, fetch_k, lambda, out_dist_dev, out_rows_dev, (hipStream_t)stream, /*host=*/false);
+    return search_mmr_impl(idx, queries_dev, B, k, fetch_k, lambda, out_dist_dev, out_rows_dev, stream, /*host=*/false);
 }
 
 int mi355dr_mmr_select(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* cand_rows, int m, double lambda,
                        double* out_dist, int64_t* out_rows) {
-    if (idx && idx->is_view) return view_refuses(idx, "mmr_select", /*ask_parent=*/true);
-    CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
-    CHECK(check_mmr_lambda(idx, "mmr_select", lambda));
-    if (m < 0 || (B > 0 && m > 0 && !cand_rows)) return fail(idx, MI355DR_E_INVALID, "mmr_select: m must be >= 0 and cand_rows not null");
-    if (m > kMmrMax) return fail(idx, MI355DR_E_UNSUPPORTED, "mmr_select: m exceeds 1024");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
+    Call c;
+    CHECK(begin_call(idx, "mmr_select", nullptr, kCallNoView | kCallDrain, c, [&]() -> int {
+        CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
+        CHECK(check_mmr_lambda(idx, "mmr_select", lambda));
+        if (m < 0 || (B > 0 && m > 0 && !cand_rows)) return fail(idx, MI355DR_E_INVALID, "mmr_select: m must be >= 0 and cand_rows not null");
+        if (m > kMmrMax) return fail(idx, MI355DR_E_UNSUPPORTED, "mmr_select: m exceeds 1024");
+        return MI355DR_OK;
+    }));
     if (B == 0) return MI355DR_OK;
     for (int64_t i = 0; i < (int64_t)B * k; ++i) {
         out_dist[i] = NAN;
         out_rows[i] = -1;
     }
-    hipStream_t s = idx->stream;
-    CHECK(ensure_qstate(idx));
-    CHECK(ensure_mmr(idx, std::min(B, kQBlockMax), std::max(m, 1), k, /*host=*/true));
-    HIPCHECK(idx, hipMemsetAsync(idx->mmr_pairs_dev.p, 0, sizeof(unsigned long long), s));
+    hipStream_t s = c.s;
+    HIPCHECK(idx, idx->mmr.reserve(std::min(B, kQBlockMax), std::max(m, 1)));
+    HIPCHECK(idx, hipMemsetAsync(idx->mmr.pairs_dev.p, 0, sizeof(unsigned long long), s));
+    const CallIO<> io{/*host=*/true, s, nullptr, {out_dist, out_rows, nullptr}, k};  // (the queries go with the pairs)
     std::vector<int32_t> pq;
     std::vector<int64_t> pr, first, ordered_rows;  // first[b]: query b's first pair
     std::vector<double> got, ordered_dist;
     std::vector<MmrCand> list;
-    DevBuf<int32_t> pq_dev;
-    DevBuf<int64_t> pr_dev;
-    DevBuf<float> dot_dev;
-    DevBuf<double> dist_dev;
+    PairBufs bufs;
     for (int b0 = 0; b0 < B && m > 0; b0 += kQBlockMax) {
         const int nb = std::min(kQBlockMax, B - b0);
         try {  // every query's list: in-index rows, each once (k_rescore_pairs does not range-check)
@@ -1809,19 +1865,7 @@ int mi355dr_mmr_select(mi355dr_index* idx, const float* queries, int B, int k, c
         }
         const int64_t n_pairs = (int64_t)pr.size();
         if (n_pairs == 0) continue;
-        HIPCHECK(idx, pq_dev.grow(n_pairs * sizeof(int32_t)));
-        HIPCHECK(idx, pr_dev.grow(n_pairs * sizeof(int64_t)));
-        HIPCHECK(idx, dot_dev.grow(n_pairs * sizeof(float)));
-        HIPCHECK(idx, dist_dev.grow(n_pairs * sizeof(double)));
-        CHECK(upload_and_prep(idx, queries + (int64_t)b0 * idx->dim, nb, idx->metric));
-        HIPCHECK(idx, hipMemcpyAsync(pq_dev.p, pq.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIPCHECK(idx, hipMemcpyAsync(pr_dev.p, pr.data(), n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_rescore_pairs, dim3((unsigned)((n_pairs + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows,
-                           idx->nrm2, idx->qdev, idx->st.qn, pq_dev.p, pr_dev.p, n_pairs, idx->dim, idx->metric, dot_dev.p,
-                           dist_dev.p);
-        HIPCHECK(idx, hipGetLastError());
-        HIPCHECK(idx, hipMemcpyAsync(got.data(), dist_dev.p, n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHECK(idx, hipStreamSynchronize(s));
+        CHECK(rescore_host_pairs(idx, bufs, queries + (int64_t)b0 * idx->dim, nb, pq.data(), pr.data(), n_pairs, nullptr, got.data()));
         // each list into the total order: a removed row (the kernel's NaN) and a live row without a distance come last, behind
         // the eligible prefix k_mmr_select stops at
         try {
@@ -1837,11 +1881,11 @@ int mi355dr_mmr_select(mi355dr_index* idx, const float* queries, int B, int k, c
         } catch (const std::bad_alloc&) {
             return fail(idx, MI355DR_E_NOMEM, "mmr_select: out of host memory for the candidate lists");
         }
-        HIPCHECK(idx, hipMemcpyAsync(idx->mmr_cand_dist.p, ordered_dist.data(), (size_t)nb * m * sizeof(double), hipMemcpyHostToDevice, s));
-        HIPCHECK(idx, hipMemcpyAsync(idx->mmr_cand_rows.p, ordered_rows.data(), (size_t)nb * m * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        CHECK(launch_mmr(idx, s, nb, m, k, lambda, idx->mmr_out_dist.p, idx->mmr_out_rows.p));
-        HIPCHECK(idx, hipMemcpyAsync(out_dist + (int64_t)b0 * k, idx->mmr_out_dist.p, (size_t)nb * k * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHECK(idx, hipMemcpyAsync(out_rows + (int64_t)b0 * k, idx->mmr_out_rows.p, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipMemcpyAsync(idx->mmr.cand_dist.p, ordered_dist.data(), (size_t)nb * m * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(idx->mmr.cand_rows.p, ordered_rows.data(), (size_t)nb * m * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        const BlockOut<int64_t> o = block_outputs(idx, io, b0);
+        CHECK(launch_mmr(idx, s, nb, m, k, lambda, o.dist, o.rows));
+        CHECK(block_return(idx, io, b0, nb, o));
         HIPCHECK(idx, hipStreamSynchronize(s));  // (the ordered lists are pageable and are rewritten for the next block)
     }
     HIPCHECK(idx, hipStreamSynchronize(s));
@@ -1879,60 +1923,42 @@ int check_groups(mi355dr_index* idx, const char* what, int S, int width, const i
 // `offs` is pageable host memory)
 int launch_groups(mi355dr_index* idx, hipStream_t s, const double* vals, const int64_t* rows, int width, const int32_t* offs,
                   int G, int np_max, int k_out, double* out_vals, int64_t* out_rows, int32_t* out_count) {
-    HIPCHECK(idx, hipMemcpyAsync(idx->grp_offsets.p, offs, (size_t)(G + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHECK(idx, hipMemcpyAsync(idx->grp.offsets.p, offs, (size_t)(G + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_merge_groups, dim3(G), dim3(kGroupsThreads), groups_lds_bytes(np_max), s, vals, rows, width,
-                       idx->grp_offsets.p, np_max, k_out, out_vals, out_rows, out_count);
+                       idx->grp.offsets.p, np_max, k_out, out_vals, out_rows, out_count);
     HIPCHECK(idx, hipGetLastError());
     return MI355DR_OK;
 }
 
-// host == true: queries / outputs are host buffers staged through the index's own; else device buffers used in place
 int search_groups_impl(mi355dr_index* idx, const float* queries, const int32_t* offs, int G, int k, int fetch_k, double* out_dist,
-                       int64_t* out_rows, int32_t* out_count, hipStream_t s, bool host) {
-    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
-    if (G < 0 || k <= 0 || fetch_k <= 0) return fail(idx, MI355DR_E_INVALID, "search_groups: G must be >= 0, k and fetch_k > 0");
-    if (G > 0 && !offs) return fail(idx, MI355DR_E_INVALID, "search_groups: group_offsets is null");
-    const int S = G > 0 ? offs[G] : 0;
-    if (G > 0 && (!out_dist || !out_rows || (S > 0 && !queries))) return fail(idx, MI355DR_E_INVALID, "search_groups: null buffer");
-    if (fetch_k > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, "search_groups: fetch_k exceeds 1024");
-    int np_max = 1;
-    CHECK(check_groups(idx, "search_groups", S, fetch_k, offs, G, k, &np_max));
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
+                       int64_t* out_rows, int32_t* out_count, void* stream, bool host) {
+    int S = 0, np_max = 1;
+    Call c;
+    CHECK(begin_call(idx, "search_groups", stream, kCallDrain, c, [&]() -> int {
+        if (G < 0 || k <= 0 || fetch_k <= 0) return fail(idx, MI355DR_E_INVALID, "search_groups: G must be >= 0, k and fetch_k > 0");
+        if (G > 0 && !offs) return fail(idx, MI355DR_E_INVALID, "search_groups: group_offsets is null");
+        S = G > 0 ? offs[G] : 0;
+        if (G > 0 && (!out_dist || !out_rows || (S > 0 && !queries))) return fail(idx, MI355DR_E_INVALID, "search_groups: null buffer");
+        if (fetch_k > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, "search_groups: fetch_k exceeds 1024");
+        return check_groups(idx, "search_groups", S, fetch_k, offs, G, k, &np_max);
+    }));
     if (G == 0) return MI355DR_OK;
-    if (!s) s = idx->stream;
-    CHECK(ensure_qstate(idx));
-    HIPCHECK(idx, idx->grp_offsets.grow((size_t)(G + 1) * sizeof(int32_t)));
-    HIPCHECK(idx, idx->grp_cand_dist.grow((size_t)std::max(S, 1) * fetch_k * sizeof(double)));
-    HIPCHECK(idx, idx->grp_cand_rows.grow((size_t)std::max(S, 1) * fetch_k * sizeof(int64_t)));
-    if (host) {
-        HIPCHECK(idx, idx->grp_out_dist.grow((size_t)G * k * sizeof(double)));
-        HIPCHECK(idx, idx->grp_out_rows.grow((size_t)G * k * sizeof(int64_t)));
-        HIPCHECK(idx, idx->grp_count.grow((size_t)G * sizeof(int32_t)));
-    }
+    HIPCHECK(idx, idx->grp.reserve(G, std::max(S, 1), fetch_k, k, host));
     // the ordinary search of every sub-query at fetch_k (screened, fix-ups completed), block by block ...
+    const CallIO<int32_t> io{host, c.s, queries, {out_dist, out_rows, out_count}, k};
     for (int b0 = 0; b0 < S; b0 += kQBlockMax) {
         const int nb = std::min(kQBlockMax, S - b0);
-        const float* q = queries + (int64_t)b0 * idx->dim;
-        if (host) {
-            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q, (size_t)nb * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
-            q = idx->qdev;
-        }
-        CHECK(search_block(idx, s, q, nb, fetch_k, idx->grp_cand_dist.p + (int64_t)b0 * fetch_k,
-                           idx->grp_cand_rows.p + (int64_t)b0 * fetch_k));
+        const float* q = nullptr;
+        CHECK(block_queries(idx, io, b0, nb, &q));
+        CHECK(search_block(idx, c.s, q, nb, fetch_k, idx->grp.cand_dist.p + (int64_t)b0 * fetch_k,
+                           idx->grp.cand_rows.p + (int64_t)b0 * fetch_k));
     }
-    // ... then one merge behind all of them: a group may straddle two blocks
-    double* od = host ? idx->grp_out_dist.p : out_dist;
-    int64_t* orow = host ? idx->grp_out_rows.p : out_rows;
-    int32_t* oc = !out_count ? nullptr : host ? idx->grp_count.p : out_count;
-    CHECK(launch_groups(idx, s, idx->grp_cand_dist.p, idx->grp_cand_rows.p, fetch_k, offs, G, np_max, k, od, orow, oc));
-    if (host) {
-        HIPCHECK(idx, hipMemcpyAsync(out_dist, od, (size_t)G * k * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHECK(idx, hipMemcpyAsync(out_rows, orow, (size_t)G * k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        if (oc) HIPCHECK(idx, hipMemcpyAsync(out_count, oc, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHECK(idx, hipStreamSynchronize(s));
+    // ... then one merge behind all of them: a group may straddle two blocks.  The [G, k] results are one "block" of G lines
+    const BlockOut<int32_t> o =
+        host ? BlockOut<int32_t>{idx->grp.out_dist.p, idx->grp.out_rows.p, out_count ? idx->grp.count.p : nullptr} : io.out;
+    CHECK(launch_groups(idx, c.s, idx->grp.cand_dist.p, idx->grp.cand_rows.p, fetch_k, offs, G, np_max, k, o.dist, o.rows, o.count));
+    CHECK(block_return(idx, io, 0, G, o));
+    HIPCHECK(idx, hipStreamSynchronize(c.s));
     idx->s_group_searches++;
     idx->s_group_subqueries += S;
     idx->s_groups_merged += G;
@@ -1943,20 +1969,19 @@ int search_groups_impl(mi355dr_index* idx, const float* queries, const int32_t* 
 int mi355dr_merge_groups_device(mi355dr_index* idx, const double* vals_dev, const int64_t* rows_dev, int S, int width,
                                 const int32_t* group_offsets, int G, int k_out, double* out_vals_dev, int64_t* out_rows_dev,
                                 int32_t* out_count_dev, void* stream) {
-    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     int np_max = 1;
-    CHECK(check_groups(idx, "merge_groups", S, width, group_offsets, G, k_out, &np_max));
-    if (G > 0 && (!out_vals_dev || !out_rows_dev || (S > 0 && (!vals_dev || !rows_dev))))
-        return fail(idx, MI355DR_E_INVALID, "merge_groups: null buffer");
-    std::lock_guard<std::mutex> g(idx->mu);
+    Call c;
+    CHECK(begin_call(idx, "merge_groups", stream, /*flags=*/0, c, [&]() -> int {  // (no drain: it touches no per-search state)
+        CHECK(check_groups(idx, "merge_groups", S, width, group_offsets, G, k_out, &np_max));
+        if (G > 0 && (!out_vals_dev || !out_rows_dev || (S > 0 && (!vals_dev || !rows_dev))))
+            return fail(idx, MI355DR_E_INVALID, "merge_groups: null buffer");
+        return MI355DR_OK;
+    }));
     if (G == 0) return MI355DR_OK;
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(ensure_qstate(idx));
-    HIPCHECK(idx, idx->grp_offsets.grow((size_t)(G + 1) * sizeof(int32_t)));
-    hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
-    CHECK(launch_groups(idx, s, vals_dev, rows_dev, width, group_offsets, G, np_max, k_out, out_vals_dev, out_rows_dev,
+    HIPCHECK(idx, idx->grp.reserve(G, 0, 0, 0, /*host=*/false));
+    CHECK(launch_groups(idx, c.s, vals_dev, rows_dev, width, group_offsets, G, np_max, k_out, out_vals_dev, out_rows_dev,
                         out_count_dev));
-    HIPCHECK(idx, hipStreamSynchronize(s));
+    HIPCHECK(idx, hipStreamSynchronize(c.s));
     idx->s_groups_merged += G;
     return MI355DR_OK;
 }
@@ -1969,7 +1994,7 @@ int mi355dr_search_groups(mi355dr_index* idx, const float* queries, const int32_
 int mi355dr_search_groups_device(mi355dr_index* idx, const float* queries_dev, const int32_t* group_offsets, int G, int k,
                                  int fetch_k, double* out_dist_dev, int64_t* out_rows_dev, int32_t* out_count_dev, void* stream) {
     return search_groups_impl(idx, queries_dev, group_offsets, G, k, fetch_k, out_dist_dev, out_rows_dev, out_count_dev,
-                              (hipStream_t)stream, /*host=*/false);
+                              stream, /*host=*/false);
 }
 
 // ---- range search: every row within a distance, counted on the device (csrc/k_range.h) ------------
@@ -1981,47 +2006,30 @@ struct RangeSpan {
 // slots of a query's result buffer: the option, never below the call's max_results (<= kKMax <= kSortMax)
 inline int range_slots_for(const mi355dr_index* idx, int m) { return std::max(idx->range_slots, m); }
 
-// the handle's range buffers for a block of nb queries, R slots each, a redo list of `pairs` pairs and (host forms) nb x m
-// results; registers k_range_collect's LDS once.  A failure leaves the buffers it already grew: they are only ever larger.
-int ensure_range(mi355dr_index* idx, int nb, int R, int m, int64_t pairs, bool host) {
-    HIPCHECK(idx, idx->rng_key.grow((size_t)nb * R * sizeof(uint64_t)));
-    HIPCHECK(idx, idx->rng_row.grow((size_t)nb * R * sizeof(int32_t)));
-    HIPCHECK(idx, idx->rng_count.grow((size_t)nb * sizeof(unsigned long long)));
-    HIPCHECK(idx, idx->rng_rkey.grow((size_t)nb * sizeof(uint64_t)));
-    HIPCHECK(idx, idx->rng_xfrom.grow((size_t)nb * sizeof(int32_t)));
-    HIPCHECK(idx, idx->rng_radius.grow((size_t)nb * sizeof(double)));
-    HIPCHECK(idx, idx->rng_flag.grow((size_t)nb * sizeof(int)));
-    HIPCHECK(idx, idx->rng_stat.grow(2 * sizeof(unsigned long long)));
-    HIPCHECK(idx, idx->rng_redo.grow((size_t)(2 + 2 * pairs) * sizeof(int)));
-    HIPCHECK(idx, idx->rng_fb_map.grow((size_t)nb * sizeof(int)));
-    HIPCHECK(idx, idx->rng_fb_q.grow((size_t)nb * idx->dim * sizeof(float)));
-    HIPCHECK(idx, idx->rng_fb_dist.grow((size_t)nb * m * sizeof(double)));
-    HIPCHECK(idx, idx->rng_fb_rows.grow((size_t)nb * m * sizeof(int64_t)));
-    if (host) {
-        HIPCHECK(idx, idx->rng_out_dist.grow((size_t)nb * m * sizeof(double)));
-        HIPCHECK(idx, idx->rng_out_rows.grow((size_t)nb * m * sizeof(int64_t)));
-        HIPCHECK(idx, idx->rng_out_count.grow((size_t)nb * sizeof(int64_t)));
-    }
-    if (idx->rng_collect_lds == 0) {
+// the handle's range buffers for a block of nb queries, R slots each, lists of m entries and a redo list of `pairs` pairs;
+// registers k_range_collect's LDS once
+int ensure_range(mi355dr_index* idx, int nb, int R, int m, int64_t pairs) {
+    HIPCHECK(idx, idx->rng.reserve(nb, R, m, pairs, idx->dim));
+    if (idx->rng.collect_lds == 0) {
         const size_t lds = range_collect_lds(idx->dim);
         if (lds > 160 * 1024) return fail(idx, MI355DR_E_UNSUPPORTED, "dim too large for the range kernels' LDS budget");
         HIPCHECK(idx, hipFuncSetAttribute((const void*)k_range_collect, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        idx->rng_collect_lds = (int)lds;
+        idx->rng.collect_lds = (int)lds;
     }
     return MI355DR_OK;
 }
 
 RangeState range_state(const mi355dr_index* idx, int R, int64_t pairs) {
     RangeState rs{};
-    rs.key = idx->rng_key;
-    rs.row = idx->rng_row;
-    rs.count = idx->rng_count;
-    rs.rkey = idx->rng_rkey;
-    rs.xfrom = idx->rng_xfrom;
-    rs.redo = idx->rng_redo;
+    rs.key = idx->rng.key;
+    rs.row = idx->rng.row;
+    rs.count = idx->rng.count;
+    rs.rkey = idx->rng.rkey;
+    rs.xfrom = idx->rng.xfrom;
+    rs.redo = idx->rng.redo;
     rs.redo_cap = (int)pairs;
-    rs.stat = idx->rng_stat;
-    rs.flag = idx->rng_flag;
+    rs.stat = idx->rng.stat;
+    rs.flag = idx->rng.flag;
     rs.R = R;
     return rs;
 }
@@ -2083,7 +2091,7 @@ int range_scan_span(mi355dr_index* idx, hipStream_t s, const RangeState& rs, int
 
 // one block of nb <= kQBlockMax device-resident queries -> device outputs [nb, m] / [nb], complete on return
 int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, const double* radius, int m, double* od,
-                int64_t* orow, int64_t* ocount, bool host) {
+                int64_t* orow, int64_t* ocount) {
     // the screens' element type and the lists' stride follow k_now: 1 keeps the int8 screen wherever AUTO has it at all and
     // the lists at option "cand_cap".  An ordinary search sets both words again before its first launch; they are put back
     // all the same (stat "screen_dtype_active" reads k_now)
@@ -2113,16 +2121,16 @@ int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, c
     const int n_main = (int)spans.size();
     const int R = range_slots_for(idx, m);
     const int64_t pairs = (int64_t)nb * std::max(n_main, 1);
-    CHECK(ensure_range(idx, nb, R, m, pairs, host));
+    CHECK(ensure_range(idx, nb, R, m, pairs));
     const RangeState rs = range_state(idx, R, pairs);
     if (q_dev != idx->qdev)
         HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q_dev, (size_t)nb * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     CHECK(launch_prep(idx, s, nb, (int)round_up(nb, screen_tile(nb)), idx->metric));
-    HIPCHECK(idx, hipMemcpyAsync(idx->rng_radius.p, radius, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHECK(idx, hipMemsetAsync(idx->rng_redo.p, 0, 2 * sizeof(int), s));
-    HIPCHECK(idx, hipMemsetAsync(idx->rng_stat.p, 0, 2 * sizeof(unsigned long long), s));
+    HIPCHECK(idx, hipMemcpyAsync(idx->rng.radius.p, radius, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHECK(idx, hipMemsetAsync(idx->rng.redo.p, 0, 2 * sizeof(int), s));
+    HIPCHECK(idx, hipMemsetAsync(idx->rng.stat.p, 0, 2 * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_range_prep, dim3((nb + kRangeThreads - 1) / kRangeThreads), dim3(kRangeThreads), 0, s,
-                       (const double*)idx->rng_radius.p, nb, idx->metric, use_screen ? 1 : 0, idx->st, rs);
+                       (const double*)idx->rng.radius.p, nb, idx->metric, use_screen ? 1 : 0, idx->st, rs);
     HIPCHECK(idx, hipGetLastError());
     std::vector<int> all(nb);
     for (int i = 0; i < nb; ++i) all[i] = i;
@@ -2152,14 +2160,14 @@ int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, c
     // whose list overflowed under the exact scan runs it in pieces of `cap` rows, which cannot overflow
     for (int round = 0;; ++round) {
         int hdr[2] = {0, 0};
-        HIPCHECK(idx, hipMemcpyAsync(hdr, idx->rng_redo.p, sizeof(hdr), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipMemcpyAsync(hdr, idx->rng.redo.p, sizeof(hdr), hipMemcpyDeviceToHost, s));
         HIPCHECK(idx, hipStreamSynchronize(s));
         if (hdr[1] != 0) return fail(idx, MI355DR_E_INTERNAL, "range search: the redo list overflowed");
         if (hdr[0] == 0) break;
         if (round >= 3) return fail(idx, MI355DR_E_INTERNAL, "range search: a list-sized piece overflowed its list");
         std::vector<int> rec((size_t)2 * hdr[0]);
-        HIPCHECK(idx, hipMemcpyAsync(rec.data(), idx->rng_redo.p + 2, rec.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHECK(idx, hipMemsetAsync(idx->rng_redo.p, 0, 2 * sizeof(int), s));
+        HIPCHECK(idx, hipMemcpyAsync(rec.data(), idx->rng.redo.p + 2, rec.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipMemsetAsync(idx->rng.redo.p, 0, 2 * sizeof(int), s));
         HIPCHECK(idx, hipStreamSynchronize(s));
         std::vector<std::vector<int>> by_code((size_t)2 * spans.size());  // [2 * span + in_pieces]: the queries
         for (int i = 0; i < hdr[0]; ++i) {
@@ -2193,9 +2201,9 @@ int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, c
     std::vector<int> flag(nb);
     std::vector<int64_t> counts(nb);
     unsigned long long st2[2] = {0, 0};
-    HIPCHECK(idx, hipMemcpyAsync(flag.data(), idx->rng_flag.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(flag.data(), idx->rng.flag.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipMemcpyAsync(counts.data(), ocount, (size_t)nb * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIPCHECK(idx, hipMemcpyAsync(st2, idx->rng_stat.p, sizeof(st2), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(st2, idx->rng.stat.p, sizeof(st2), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipStreamSynchronize(s));
     for (int i = 0; i < nb; ++i) idx->s_range_in_range += counts[i];
     idx->s_range_candidates += (int64_t)st2[0];
@@ -2207,14 +2215,14 @@ int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, c
         if (flag[i]) fb.push_back(i);
     if (!fb.empty()) {
         const int nf = (int)fb.size();
-        HIPCHECK(idx, hipMemcpyAsync(idx->rng_fb_map.p, fb.data(), (size_t)nf * sizeof(int), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_gather_queries, dim3(nf), dim3(128), 0, s, (const float*)idx->qdev.p, (const int*)idx->rng_fb_map.p,
-                           idx->dim, idx->rng_fb_q.p);
+        HIPCHECK(idx, hipMemcpyAsync(idx->rng.fb_map.p, fb.data(), (size_t)nf * sizeof(int), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_gather_queries, dim3(nf), dim3(128), 0, s, (const float*)idx->qdev.p, (const int*)idx->rng.fb_map.p,
+                           idx->dim, idx->rng.fb_q.p);
         HIPCHECK(idx, hipGetLastError());
         HIPCHECK(idx, hipStreamSynchronize(s));  // `fb` (pageable) was read by the copy
-        CHECK(search_block(idx, s, idx->rng_fb_q.p, nf, m, idx->rng_fb_dist.p, idx->rng_fb_rows.p));
-        hipLaunchKernelGGL(k_scatter_results, dim3(nf), dim3(128), 0, s, (const double*)idx->rng_fb_dist.p,
-                           (const int64_t*)idx->rng_fb_rows.p, (const int*)idx->rng_fb_map.p, m, od, orow);
+        CHECK(search_block(idx, s, idx->rng.fb_q.p, nf, m, idx->rng.fb_dist.p, idx->rng.fb_rows.p));
+        hipLaunchKernelGGL(k_scatter_results, dim3(nf), dim3(128), 0, s, (const double*)idx->rng.fb_dist.p,
+                           (const int64_t*)idx->rng.fb_rows.p, (const int*)idx->rng.fb_map.p, m, od, orow);
         HIPCHECK(idx, hipGetLastError());
         HIPCHECK(idx, hipStreamSynchronize(s));
         idx->s_range_fallback_queries += nf;
@@ -2222,40 +2230,24 @@ int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, c
     return MI355DR_OK;
 }
 
-// host == true: queries / outputs are host buffers staged through the index's own; else device buffers used in place
 int search_range_impl(mi355dr_index* idx, const float* queries, int B, const double* radius, int m, double* out_dist,
-                      int64_t* out_rows, int64_t* out_count, hipStream_t s, bool host) {
-    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
-    if (B <= 0 || m < 1) return fail(idx, MI355DR_E_INVALID, "search_range: B and max_results must be >= 1");
-    if (m > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, "search_range: max_results exceeds 1024");
-    if (!queries || !radius || !out_dist || !out_rows || !out_count) return fail(idx, MI355DR_E_INVALID, "search_range: null buffer");
-    for (int b = 0; b < B; ++b)
-        if (radius[b] != radius[b]) return fail(idx, MI355DR_E_INVALID, "search_range: radius " + std::to_string(b) + " is NaN");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
-    if (!s) s = idx->stream;
-    CHECK(ensure_qstate(idx));
+                      int64_t* out_rows, int64_t* out_count, void* stream, bool host) {
+    Call c;
+    CHECK(begin_call(idx, "search_range", stream, kCallDrain, c, [&]() -> int {
+        if (B <= 0 || m < 1) return fail(idx, MI355DR_E_INVALID, "search_range: B and max_results must be >= 1");
+        if (m > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, "search_range: max_results exceeds 1024");
+        if (!queries || !radius || !out_dist || !out_rows || !out_count) return fail(idx, MI355DR_E_INVALID, "search_range: null buffer");
+        return check_radii(idx, "search_range", radius, B);
+    }));
+    const CallIO<> io{host, c.s, queries, {out_dist, out_rows, out_count}, m};
     for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
         const int nb = std::min(kQBlockMax, B - b0);
-        const float* q = queries + (int64_t)b0 * idx->dim;
-        double* od = out_dist + (int64_t)b0 * m;
-        int64_t* orow = out_rows + (int64_t)b0 * m;
-        int64_t* oc = out_count + b0;
-        if (host) {
-            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q, (size_t)nb * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
-            // (the staging buffers are grown by the block's ensure_range: sized here first)
-            HIPCHECK(idx, idx->rng_out_dist.grow((size_t)std::min(B, kQBlockMax) * m * sizeof(double)));
-            HIPCHECK(idx, idx->rng_out_rows.grow((size_t)std::min(B, kQBlockMax) * m * sizeof(int64_t)));
-            HIPCHECK(idx, idx->rng_out_count.grow((size_t)std::min(B, kQBlockMax) * sizeof(int64_t)));
-            CHECK(range_block(idx, s, idx->qdev, nb, radius + b0, m, idx->rng_out_dist.p, idx->rng_out_rows.p, idx->rng_out_count.p, true));
-            HIPCHECK(idx, hipMemcpyAsync(od, idx->rng_out_dist.p, (size_t)nb * m * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIPCHECK(idx, hipMemcpyAsync(orow, idx->rng_out_rows.p, (size_t)nb * m * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            HIPCHECK(idx, hipMemcpyAsync(oc, idx->rng_out_count.p, (size_t)nb * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            HIPCHECK(idx, hipStreamSynchronize(s));
-        } else {
-            CHECK(range_block(idx, s, q, nb, radius + b0, m, od, orow, oc, false));
-        }
+        const float* q = nullptr;
+        CHECK(block_queries(idx, io, b0, nb, &q));
+        const BlockOut<int64_t> o = block_outputs(idx, io, b0);
+        CHECK(range_block(idx, c.s, q, nb, radius + b0, m, o.dist, o.rows, o.count));  // (complete on return)
+        CHECK(block_return(idx, io, b0, nb, o));
+        if (host) HIPCHECK(idx, hipStreamSynchronize(c.s));
     }
     idx->s_range_searches++;
     idx->s_range_queries += B;
@@ -2271,109 +2263,73 @@ int mi355dr_search_range(mi355dr_index* idx, const float* queries, int B, const 
 int mi355dr_search_range_device(mi355dr_index* idx, const float* queries_dev, int B, const double* radius, int max_results,
                                 double* out_dist_dev, int64_t* out_rows_dev, int64_t* out_count_dev, void* stream) {
     return search_range_impl(idx, queries_dev, B, radius, max_results, out_dist_dev, out_rows_dev, out_count_dev,
-                             (hipStream_t)stream, /*host=*/false);
+                             stream, /*host=*/false);
 }
 
 // ---- search by stored row: neighbours of rows, self excluded (csrc/k_rows.h) ---------------------
 namespace {
-// the handle's buffers for a block of nb slots, inner lists of `stride` entries and (host forms) nb x kout results
-int ensure_rows(mi355dr_index* idx, int nb, int stride, int kout, bool range, bool host) {
-    HIPCHECK(idx, idx->rowq_ids.grow((size_t)nb * sizeof(int64_t)));
-    HIPCHECK(idx, idx->rowq_q.grow((size_t)nb * idx->dim * sizeof(float)));
-    HIPCHECK(idx, idx->rowq_valid.grow((size_t)nb * sizeof(int)));
-    HIPCHECK(idx, idx->rowq_pair_q.grow((size_t)nb * sizeof(int32_t)));
-    HIPCHECK(idx, idx->rowq_pair_row.grow((size_t)nb * sizeof(int64_t)));
-    HIPCHECK(idx, idx->rowq_cand_dist.grow((size_t)nb * stride * sizeof(double)));
-    HIPCHECK(idx, idx->rowq_cand_rows.grow((size_t)nb * stride * sizeof(int64_t)));
-    HIPCHECK(idx, idx->rowq_skipped_dev.grow(sizeof(unsigned long long)));
-    if (range) {
-        HIPCHECK(idx, idx->rowq_cand_count.grow((size_t)nb * sizeof(int64_t)));
-        HIPCHECK(idx, idx->rowq_self_dot.grow((size_t)nb * sizeof(float)));
-        HIPCHECK(idx, idx->rowq_self_dist.grow((size_t)nb * sizeof(double)));
-        HIPCHECK(idx, idx->rowq_radius.grow((size_t)nb * sizeof(double)));
-    }
-    if (host) {
-        HIPCHECK(idx, idx->rowq_out_dist.grow((size_t)nb * kout * sizeof(double)));
-        HIPCHECK(idx, idx->rowq_out_rows.grow((size_t)nb * kout * sizeof(int64_t)));
-        if (range) HIPCHECK(idx, idx->rowq_out_count.grow((size_t)nb * sizeof(int64_t)));
-    }
-    return MI355DR_OK;
-}
-
 // both families.  radius == nullptr: the top-k form (kout = k); else the range form (kout = max_results, out_count used).
-// host == true: the outputs are host buffers staged through the index's own; else device buffers used in place
+// (the outputs' `host`: see CallIO; the ids are host memory in both forms)
 int search_rows_impl(mi355dr_index* idx, const char* what, const int64_t* row_ids, int B, const double* radius, bool range,
-                     int kout, int flags, double* out_dist, int64_t* out_rows, int64_t* out_count, hipStream_t s, bool host) {
-    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
-    if (idx->is_view) return view_refuses(idx, what, /*ask_parent=*/true);  // (set once, before the handle is handed out)
-    const std::string w(what);
-    if (B < 0) return fail(idx, MI355DR_E_INVALID, w + ": B must be >= 0");
-    if (kout < 1) return fail(idx, MI355DR_E_INVALID, w + (range ? ": max_results must be >= 1" : ": k must be > 0"));
-    if (flags & ~MI355DR_ROWS_INCLUDE_SELF) return fail(idx, MI355DR_E_INVALID, w + ": unknown flag bits");
-    if (B > 0 && (!row_ids || !out_dist || !out_rows || (range && (!radius || !out_count))))
-        return fail(idx, MI355DR_E_INVALID, w + ": null buffer");
-    if (range)
-        for (int b = 0; b < B; ++b)
-            if (radius[b] != radius[b]) return fail(idx, MI355DR_E_INVALID, w + ": radius " + std::to_string(b) + " is NaN");
+                     int kout, int flags, double* out_dist, int64_t* out_rows, int64_t* out_count, void* stream, bool host) {
     const bool include_self = (flags & MI355DR_ROWS_INCLUDE_SELF) != 0;
     const int stride = kout + (include_self ? 0 : 1);  // the inner pass's list: room for the row itself
-    if (stride > kKMax)
-        return fail(idx, MI355DR_E_UNSUPPORTED, w + (range ? ": max_results" : ": k") + (include_self ? "" : " + 1 (the row itself)") + " exceeds 1024");
-    std::lock_guard<std::mutex> g(idx->mu);
-    HIPCHECK(idx, hipSetDevice(idx->device));
-    CHECK(drain_pending(idx));
+    Call c;
+    CHECK(begin_call(idx, what, stream, kCallNoView | kCallDrain, c, [&]() -> int {
+        const std::string w(what);
+        if (B < 0) return fail(idx, MI355DR_E_INVALID, w + ": B must be >= 0");
+        if (kout < 1) return fail(idx, MI355DR_E_INVALID, w + (range ? ": max_results must be >= 1" : ": k must be > 0"));
+        if (flags & ~MI355DR_ROWS_INCLUDE_SELF) return fail(idx, MI355DR_E_INVALID, w + ": unknown flag bits");
+        if (B > 0 && (!row_ids || !out_dist || !out_rows || (range && (!radius || !out_count))))
+            return fail(idx, MI355DR_E_INVALID, w + ": null buffer");
+        if (range) CHECK(check_radii(idx, w, radius, B));
+        if (stride > kKMax)
+            return fail(idx, MI355DR_E_UNSUPPORTED, w + (range ? ": max_results" : ": k") + (include_self ? "" : " + 1 (the row itself)") + " exceeds 1024");
+        return MI355DR_OK;
+    }));
     if (B == 0) return MI355DR_OK;
-    if (!s) s = idx->stream;
-    CHECK(ensure_qstate(idx));
-    CHECK(ensure_rows(idx, std::min(B, kQBlockMax), stride, kout, range, host));
-    HIPCHECK(idx, hipMemsetAsync(idx->rowq_skipped_dev.p, 0, sizeof(unsigned long long), s));
+    hipStream_t s = c.s;
+    HIPCHECK(idx, idx->rowq.reserve(std::min(B, kQBlockMax), stride, idx->dim, range));
+    HIPCHECK(idx, hipMemsetAsync(idx->rowq.skipped_dev.p, 0, sizeof(unsigned long long), s));
+    const CallIO<> io{host, s, nullptr, {out_dist, out_rows, out_count}, kout};  // (the queries are gathered rows; top-k form: no count)
     std::vector<double> rad;
     for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
         const int nb = std::min(kQBlockMax, B - b0);
-        double* od = host ? idx->rowq_out_dist.p : out_dist + (int64_t)b0 * kout;
-        int64_t* orow = host ? idx->rowq_out_rows.p : out_rows + (int64_t)b0 * kout;
-        int64_t* oc = !range ? nullptr : host ? idx->rowq_out_count.p : out_count + b0;
-        HIPCHECK(idx, hipMemcpyAsync(idx->rowq_ids.p, row_ids + b0, (size_t)nb * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_rows_gather, dim3(nb), dim3(kRowsThreads), 0, s, (const int64_t*)idx->rowq_ids.p, idx->row_offset,
-                           idx->n, (const float*)idx->rows.p, (const float*)idx->nrm2.p, idx->dim, idx->rowq_q.p,
-                           idx->rowq_valid.p, idx->rowq_pair_q.p, idx->rowq_pair_row.p, idx->rowq_skipped_dev.p);
+        const BlockOut<int64_t> o = block_outputs(idx, io, b0);
+        HIPCHECK(idx, hipMemcpyAsync(idx->rowq.ids.p, row_ids + b0, (size_t)nb * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_rows_gather, dim3(nb), dim3(kRowsThreads), 0, s, (const int64_t*)idx->rowq.ids.p, idx->row_offset,
+                           idx->n, (const float*)idx->rows.p, (const float*)idx->nrm2.p, idx->dim, idx->rowq.q.p,
+                           idx->rowq.valid.p, idx->rowq.pair_q.p, idx->rowq.pair_row.p, idx->rowq.skipped_dev.p);
         HIPCHECK(idx, hipGetLastError());
         if (idx->n > 0 && !range) {
             // the ordinary search of the gathered block (screened, fix-ups completed)
-            CHECK(search_block(idx, s, idx->rowq_q.p, nb, stride, idx->rowq_cand_dist.p, idx->rowq_cand_rows.p));
+            CHECK(search_block(idx, s, idx->rowq.q.p, nb, stride, idx->rowq.cand_dist.p, idx->rowq.cand_rows.p));
         } else if (idx->n > 0) {
             // an id outside the shard asks for nothing (its slot is blanked below): no row is within -inf
             rad.assign(radius + b0, radius + b0 + nb);
             for (int b = 0; b < nb; ++b)
                 if (subset_local_row(row_ids[b0 + b], idx->row_offset, idx->n) < 0) rad[b] = -INFINITY;
-            HIPCHECK(idx, hipMemcpyAsync(idx->rowq_radius.p, rad.data(), (size_t)nb * sizeof(double), hipMemcpyHostToDevice, s));
+            HIPCHECK(idx, hipMemcpyAsync(idx->rowq.radius.p, rad.data(), (size_t)nb * sizeof(double), hipMemcpyHostToDevice, s));
             // every slot's distance to its own row, from the block's prepared queries: the bits a search returns for the pair
-            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, idx->rowq_q.p, (size_t)nb * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, idx->rowq.q.p, (size_t)nb * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
             CHECK(launch_prep(idx, s, nb, (int)round_up(nb, screen_tile(nb)), idx->metric));
-            hipLaunchKernelGGL(k_rescore_pairs, dim3((unsigned)((nb + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows, idx->nrm2,
-                               idx->qdev, idx->st.qn, idx->rowq_pair_q.p, idx->rowq_pair_row.p, (int64_t)nb, idx->dim, idx->metric,
-                               idx->rowq_self_dot.p, idx->rowq_self_dist.p);
-            HIPCHECK(idx, hipGetLastError());
+            CHECK(launch_rescore(idx, s, idx->rowq.pair_q.p, idx->rowq.pair_row.p, nb, idx->rowq.self_dot.p, idx->rowq.self_dist.p));
             // the range pass of the gathered block (it prepares the block again; complete on return, `rad` has been read)
-            CHECK(range_block(idx, s, idx->rowq_q.p, nb, rad.data(), stride, idx->rowq_cand_dist.p, idx->rowq_cand_rows.p,
-                              idx->rowq_cand_count.p, /*host=*/false));
+            CHECK(range_block(idx, s, idx->rowq.q.p, nb, rad.data(), stride, idx->rowq.cand_dist.p, idx->rowq.cand_rows.p,
+                              idx->rowq.cand_count.p));
         }
         // (an empty index: every slot is invalid and the lists are not read)
-        hipLaunchKernelGGL(k_rows_drop, dim3(nb), dim3(kRowsThreads), 0, s, (const double*)idx->rowq_cand_dist.p,
-                           (const int64_t*)idx->rowq_cand_rows.p, stride, (const int64_t*)idx->rowq_ids.p,
-                           (const int*)idx->rowq_valid.p, kout, include_self ? 1 : 0,
-                           range ? (const int64_t*)idx->rowq_cand_count.p : nullptr, (const double*)idx->rowq_self_dist.p,
-                           (const double*)idx->rowq_radius.p, od, orow, oc);
+        hipLaunchKernelGGL(k_rows_drop, dim3(nb), dim3(kRowsThreads), 0, s, (const double*)idx->rowq.cand_dist.p,
+                           (const int64_t*)idx->rowq.cand_rows.p, stride, (const int64_t*)idx->rowq.ids.p,
+                           (const int*)idx->rowq.valid.p, kout, include_self ? 1 : 0,
+                           range ? (const int64_t*)idx->rowq.cand_count.p : nullptr, (const double*)idx->rowq.self_dist.p,
+                           (const double*)idx->rowq.radius.p, o.dist, o.rows, o.count);
         HIPCHECK(idx, hipGetLastError());
-        if (host) {
-            HIPCHECK(idx, hipMemcpyAsync(out_dist + (int64_t)b0 * kout, od, (size_t)nb * kout * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIPCHECK(idx, hipMemcpyAsync(out_rows + (int64_t)b0 * kout, orow, (size_t)nb * kout * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            if (range) HIPCHECK(idx, hipMemcpyAsync(out_count + b0, oc, (size_t)nb * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        }
+        CHECK(block_return(idx, io, b0, nb, o));
         HIPCHECK(idx, hipStreamSynchronize(s));  // (the next block reuses the id, query and list buffers)
     }
     unsigned long long skipped = 0;
-    HIPCHECK(idx, hipMemcpy(&skipped, idx->rowq_skipped_dev.p, sizeof(skipped), hipMemcpyDeviceToHost));
+    HIPCHECK(idx, hipMemcpy(&skipped, idx->rowq.skipped_dev.p, sizeof(skipped), hipMemcpyDeviceToHost));
     idx->s_rows_searches++;
     idx->s_rows_queries += B;
     idx->s_rows_skipped += (int64_t)skipped;
@@ -2388,7 +2344,7 @@ int mi355dr_search_rows(mi355dr_index* idx, const int64_t* row_ids, int B, int k
 int mi355dr_search_rows_device(mi355dr_index* idx, const int64_t* row_ids, int B, int k, int flags, double* out_dist_dev,
                                int64_t* out_rows_dev, void* stream) {
     return search_rows_impl(idx, "search_rows", row_ids, B, nullptr, false, k, flags, out_dist_dev, out_rows_dev, nullptr,
-                            (hipStream_t)stream, /*host=*/false);
+                            stream, /*host=*/false);
 }
 
 int mi355dr_search_range_rows(mi355dr_index* idx, const int64_t* row_ids, int B, const double* radius, int max_results, int flags,
@@ -2400,7 +2356,7 @@ int mi355dr_search_range_rows(mi355dr_index* idx, const int64_t* row_ids, int B,
 int mi355dr_search_range_rows_device(mi355dr_index* idx, const int64_t* row_ids, int B, const double* radius, int max_results,
                                      int flags, double* out_dist_dev, int64_t* out_rows_dev, int64_t* out_count_dev, void* stream) {
     return search_rows_impl(idx, "search_range_rows", row_ids, B, radius, true, max_results, flags, out_dist_dev, out_rows_dev,
-                            out_count_dev, (hipStream_t)stream, /*host=*/false);
+                            out_count_dev, stream, /*host=*/false);
 }
 
 int mi355dr_merge_topk_device(mi355dr_index* idx, const double* dist_all_dev, const int64_t* rows_all_dev, int world,
@@ -2810,25 +2766,8 @@ int mi355dr_debug_rescore(mi355dr_index* idx, const float* queries, int B, const
     for (int64_t i = 0; i < n_pairs; ++i)
         if (pair_q[i] < 0 || pair_q[i] >= B || pair_row[i] < 0 || pair_row[i] >= idx->n)
             return fail(idx, MI355DR_E_INVALID, "pair out of range");
-    CHECK(upload_and_prep(idx, queries, B, idx->metric));
-    hipStream_t s = idx->stream;
-    DevBuf<int32_t> pq;
-    DevBuf<int64_t> pr;
-    DevBuf<float> od;
-    DevBuf<double> ods;
-    HIPCHECK(idx, pq.grow(n_pairs * sizeof(int32_t)));
-    HIPCHECK(idx, pr.grow(n_pairs * sizeof(int64_t)));
-    HIPCHECK(idx, od.grow(n_pairs * sizeof(float)));
-    HIPCHECK(idx, ods.grow(n_pairs * sizeof(double)));
-    HIPCHECK(idx, hipMemcpyAsync(pq.p, pair_q, n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIPCHECK(idx, hipMemcpyAsync(pr.p, pair_row, n_pairs * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_rescore_pairs, dim3((unsigned)((n_pairs + kWave - 1) / kWave)), dim3(kWave), 0, s, idx->rows,
-                       idx->nrm2, idx->qdev, idx->st.qn, pq.p, pr.p, n_pairs, idx->dim, idx->metric, od.p, ods.p);
-    HIPCHECK(idx, hipGetLastError());
-    HIPCHECK(idx, hipMemcpyAsync(out_dot, od.p, n_pairs * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIPCHECK(idx, hipMemcpyAsync(out_dist, ods.p, n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHECK(idx, hipStreamSynchronize(s));
-    return MI355DR_OK;
+    PairBufs bufs;
+    return rescore_host_pairs(idx, bufs, queries, B, pair_q, pair_row, n_pairs, out_dot, out_dist);
 }
 
 /* ---- multi-vector (MaxSim): implemented in mi355dr_maxsim.hip ---- */

@@ -19,6 +19,11 @@ PATHS = {"auto": 0, "screen": 1, "scan": 2}
 SCREEN_DTYPES = {"auto": 0, "bf16": 1, "i8": 2}
 
 
+def _stream_arg(stream) -> ctypes.c_void_p:
+    """A HIP stream handle (int) as the C ABI's `void* stream`; None / 0 = the index's own stream."""
+    return ctypes.c_void_p(int(stream) if stream else None)
+
+
 class Mi355Index:
     def __init__(self, dim: int, metric: str = "cosine", device: int = 0):
         if metric not in METRICS:
@@ -142,7 +147,7 @@ class Mi355Index:
         check(self._h, self._lib.mi355dr_search_device(self._h, ctypes.c_void_p(int(q_ptr)), int(B), int(k),
                                                        ctypes.c_void_p(int(out_dist_ptr)),
                                                        ctypes.c_void_p(int(out_rows_ptr)),
-                                                       ctypes.c_void_p(int(stream) if stream else None)))
+                                                       _stream_arg(stream)))
 
     def search_device_async(self, q_ptr: int, B: int, k: int, out_dist_ptr: int, out_rows_ptr: int,
                             stream: int | None = None) -> int:
@@ -152,7 +157,7 @@ class Mi355Index:
         check(self._h, self._lib.mi355dr_search_device_async(self._h, ctypes.c_void_p(int(q_ptr)), int(B), int(k),
                                                              ctypes.c_void_p(int(out_dist_ptr)),
                                                              ctypes.c_void_p(int(out_rows_ptr)),
-                                                             ctypes.c_void_p(int(stream) if stream else None),
+                                                             _stream_arg(stream),
                                                              ctypes.byref(t)))
         return int(t.value)
 
@@ -185,7 +190,7 @@ class Mi355Index:
         check(self._h, self._lib.mi355dr_search_subset_device(
             self._h, ctypes.c_void_p(int(q_ptr)), int(B), int(k), ptr(ids, ctypes.c_int64), ids.shape[0],
             ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
-            ctypes.c_void_p(int(stream) if stream else None)))
+            _stream_arg(stream)))
 
     def score_subset(self, queries, row_ids) -> np.ndarray:
         """Exact distance of each query to its own list of rows: row_ids [B, m] (global) -> float64 [B, m]; NaN for ids
@@ -230,7 +235,7 @@ class Mi355Index:
         check(self._h, self._lib.mi355dr_search_mmr_device(
             self._h, ctypes.c_void_p(int(q_ptr)), int(B), int(k), int(fetch_k), float(lambda_mult),
             ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
-            ctypes.c_void_p(int(stream) if stream else None)))
+            _stream_arg(stream)))
 
     def mmr_select(self, queries, k: int, cand_rows, lambda_mult: float = 0.5) -> tuple[np.ndarray, np.ndarray]:
         """MMR over each query's OWN candidate pool: cand_rows [B, m] global rows (m <= 1024) under the hygiene of
@@ -286,7 +291,7 @@ class Mi355Index:
         check(self._h, self._lib.mi355dr_search_groups_device(
             self._h, ctypes.c_void_p(int(q_ptr)), ptr(offs, ctypes.c_int32), offs.shape[0] - 1, int(k), int(fetch_k),
             ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
-            ctypes.c_void_p(int(out_count_ptr) if out_count_ptr else None), ctypes.c_void_p(int(stream) if stream else None)))
+            ctypes.c_void_p(int(out_count_ptr) if out_count_ptr else None), _stream_arg(stream)))
 
     def merge_groups_device(self, vals_ptr: int, rows_ptr: int, S: int, width: int, group_offsets, k: int, out_vals_ptr: int,
                             out_rows_ptr: int, out_count_ptr: int | None = None, stream: int | None = None) -> None:
@@ -296,7 +301,7 @@ class Mi355Index:
             self._h, ctypes.c_void_p(int(vals_ptr)), ctypes.c_void_p(int(rows_ptr)), int(S), int(width),
             ptr(offs, ctypes.c_int32), offs.shape[0] - 1, int(k), ctypes.c_void_p(int(out_vals_ptr)),
             ctypes.c_void_p(int(out_rows_ptr)), ctypes.c_void_p(int(out_count_ptr) if out_count_ptr else None),
-            ctypes.c_void_p(int(stream) if stream else None)))
+            _stream_arg(stream)))
 
     def merge_groups(self, vals, rows, group_offsets, k: int, want_count: bool = True):
         """Fuse host lists on the device: vals float64 [S, width] (any doubles: distances, negated scores), rows int64
@@ -367,7 +372,7 @@ class Mi355Index:
         check(self._h, self._lib.mi355dr_search_range_device(
             self._h, ctypes.c_void_p(int(q_ptr)), int(B), ptr(r, ctypes.c_double), int(max_results),
             ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)), ctypes.c_void_p(int(out_count_ptr)),
-            ctypes.c_void_p(int(stream) if stream else None)))
+            _stream_arg(stream)))
 
     # ---- search by stored row: neighbours of rows, self excluded (include/mi355dr.h "search by stored row") ----
     def search_rows(self, row_ids, k: int, include_self: bool = False) -> tuple[np.ndarray, np.ndarray]:
@@ -389,7 +394,7 @@ class Mi355Index:
         ids = self._row_ids(row_ids)
         check(self._h, self._lib.mi355dr_search_rows_device(
             self._h, ptr(ids, ctypes.c_int64), ids.shape[0], int(k), 1 if include_self else 0, ctypes.c_void_p(int(out_dist_ptr)),
-            ctypes.c_void_p(int(out_rows_ptr)), ctypes.c_void_p(int(stream) if stream else None)))
+            ctypes.c_void_p(int(out_rows_ptr)), _stream_arg(stream)))
 
     def search_range_rows(self, row_ids, radius, max_results: int,
                           include_self: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -414,7 +419,7 @@ class Mi355Index:
         check(self._h, self._lib.mi355dr_search_range_rows_device(
             self._h, ptr(ids, ctypes.c_int64), ids.shape[0], ptr(r, ctypes.c_double), int(max_results),
             1 if include_self else 0, ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
-            ctypes.c_void_p(int(out_count_ptr)), ctypes.c_void_p(int(stream) if stream else None)))
+            ctypes.c_void_p(int(out_count_ptr)), _stream_arg(stream)))
 
     def _row_span(self, row0: int, row1: int | None, block: int) -> tuple[int, int, int]:
         row0, row1, block = int(row0), len(self) if row1 is None else int(row1), int(block)
@@ -480,18 +485,18 @@ class Mi355Index:
         check(self._h, self._lib.mi355dr_merge_topk_device(
             self._h, ctypes.c_void_p(int(dist_all_ptr)), ctypes.c_void_p(int(rows_all_ptr)), int(world), int(B),
             int(k), ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
-            ctypes.c_void_p(int(stream) if stream else None)))
+            _stream_arg(stream)))
 
     def pack_topk_device(self, dist_ptr: int, rows_ptr: int, B: int, k: int, packed_ptr: int, stream: int | None = None) -> None:
         check(self._h, self._lib.mi355dr_pack_topk_device(self._h, ctypes.c_void_p(int(dist_ptr)), ctypes.c_void_p(int(rows_ptr)),
                                                           int(B), int(k), ctypes.c_void_p(int(packed_ptr)),
-                                                          ctypes.c_void_p(int(stream) if stream else None)))
+                                                          _stream_arg(stream)))
 
     def merge_topk_packed_device(self, packed_all_ptr: int, world: int, B: int, k: int, out_dist_ptr: int, out_rows_ptr: int,
                                  stream: int | None = None) -> None:
         check(self._h, self._lib.mi355dr_merge_topk_packed_device(
             self._h, ctypes.c_void_p(int(packed_all_ptr)), int(world), int(B), int(k), ctypes.c_void_p(int(out_dist_ptr)),
-            ctypes.c_void_p(int(out_rows_ptr)), ctypes.c_void_p(int(stream) if stream else None)))
+            ctypes.c_void_p(int(out_rows_ptr)), _stream_arg(stream)))
 
     # ---- row-sharded search inside the library (RCCL, no torch): include/mi355dr.h "row-sharded search" ----
     @staticmethod
@@ -541,7 +546,7 @@ class Mi355Index:
         """Local search + ONE ncclAllGather + merge, on device buffers (every rank: same queries in, same result out)."""
         check(self._h, self._lib.mi355dr_search_sharded_device(
             self._h, ctypes.c_void_p(int(q_ptr)), int(B), int(k), ctypes.c_void_p(int(out_dist_ptr)),
-            ctypes.c_void_p(int(out_rows_ptr)), ctypes.c_void_p(int(stream) if stream else None)))
+            ctypes.c_void_p(int(out_rows_ptr)), _stream_arg(stream)))
 
     # ---- multi-vector ----
     def add_multivec(self, vecs, offsets) -> None:
@@ -623,7 +628,7 @@ class Mi355Index:
         check(self._h, self._lib.mi355dr_search_maxsim_device(
             self._h, ctypes.c_void_p(int(qtok_ptr)), ptr(q_offsets, ctypes.c_int32), q_offsets.shape[0] - 1, int(k),
             ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
-            ctypes.c_void_p(int(stream) if stream else None)))
+            _stream_arg(stream)))
 
     # ---- MaxSim search within a listed subset of documents (include/mi355dr.h) ----
     def search_maxsim_subset(self, qtok, q_offsets, k: int, doc_ids) -> tuple[np.ndarray, np.ndarray]:
@@ -652,7 +657,7 @@ class Mi355Index:
         check(self._h, self._lib.mi355dr_search_maxsim_subset_device(
             self._h, ctypes.c_void_p(int(qtok_ptr)), ptr(q_offsets, ctypes.c_int32), q_offsets.shape[0] - 1, int(k),
             ptr(ids, ctypes.c_int64), ids.shape[0], ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
-            ctypes.c_void_p(int(stream) if stream else None)))
+            _stream_arg(stream)))
 
     def maxsim_subset(self, qtok, q_offsets, doc_ids, clamp0: bool = False) -> np.ndarray:
         """Exact MaxSim distance of each query to its own list of docs: doc_ids [B, m] -> distances [B, m] (NaN = skipped).
