@@ -78,6 +78,17 @@ struct EventPairs {
     }
 };
 struct MultiVecStore;  // mi355dr_maxsim.hip
+// What one search pass has decided, once, before its first launch (mi355dr.hip decide_pass): every function of the pass takes
+// it, or the field it needs, as a parameter -- none reads a decision from the handle
+struct Pass {
+    int k = 0;
+    int level = 0;           // 0: a first attempt; 1 .. 3: the fix-up passes of complete_block (bf16 bound, slower chunk growth)
+    bool screening = false;  // the pass screens; else the exact scan (path = scan, a forced scan, no screen that can serve)
+    bool i8 = false;         // the screen's element type: int8, else bf16 (also what k_prep_queries quantises for)
+    bool wide = false;       // its prunes take the two-wave form (screening passes at 33 <= k <= 128)
+    int cap = 0;             // candidate slots per query = the lists' stride
+    const char* refused = nullptr;  // not null: no pass may run, MI355DR_E_UNSUPPORTED with this text
+};
 // one block between enqueue_block() and complete_block() (mi355dr.hip)
 struct Pending {
     bool active = false;
@@ -85,12 +96,12 @@ struct Pending {
     HostBuf<int> status_host;     // pinned [kQBlockMax + 1]: the block's per-query status words + their OR
     hipStream_t stream = nullptr;
     const float* q_dev = nullptr; // the caller's queries (valid until the wait: a fix-up gathers from them)
-    int B = 0, k = 0, level = 0;
+    int B = 0;
+    Pass pass;                    // what the block was enqueued under
     double* out_dist = nullptr;
     int64_t* out_rows = nullptr;
-    bool used_screen = false, was_i8 = false;
 };
-// buffers of the sub-block a search at retry level L re-screens (complete_block grows all four before it uses one)
+// buffers of the sub-block that the fix-ups of a level-L block search (complete_block grows all four before it uses one)
 struct RetryBufs {
     DevBuf<float> q;       // [kQBlockMax, dim] queries being re-screened / re-scanned
     DevBuf<double> dist;   // [kQBlockMax, kKMax]
@@ -249,19 +260,19 @@ struct mi355dr_index {
     // options
     int path = 0;  // MI355DR_PATH_AUTO
     int screen_dtype = 0;  // MI355DR_SCREEN_AUTO
-    int retry_level = 0;   // > 0 while overflowed queries are re-screened: bf16 bound, slower chunk growth
     int i8_backoff = 0, i8_probation = 0;  // demotion is not for ever: after i8_probation more blocks at such a k AUTO tries int8 again;
                                            // the wait doubles (16 ... 4096 blocks) every time that try overflows again
     int i8_demoted_k = INT_MAX;  // AUTO saw the int8 bound overflow on this corpus' score distribution at this k: bf16 from there up
     double i8_min_budget = 0.25;  // AUTO keeps the int8 screen while growth_budget(k, int8) stays above this (k <= 133)
     mi355::RetryBufs retry[3];  // one set per level: the nested call owns the next
     // blocks in flight: sequence numbers [seq_done, seq_next) live in pend[seq % kPendingRing]; sub_pend[level]: the
-    // synchronous blocks of the fix-up levels
+    // synchronous blocks of level `level` (search_block)
     mi355::Pending pend[mi355::kPendingRing];
     mi355::Pending sub_pend[4];
     int64_t seq_next = 0, seq_done = 0;
-    int k_now = 10;        // k of the search in progress (the screen element type and the chunk growth depend on it)
-    bool screening_now = false;  // the pass in progress screens (enqueue_block); only such passes take the two-wave prune's stride
+    // k of the most recent top-k pass (enqueue_block, subset_block).  No pass reads it: between searches, stat
+    // "screen_dtype_active" and the debug entry points decide as a first attempt at this k would (idle_i8)
+    int last_pass_k = 10;
     int maxsim_coop = -1;       // exact MaxSim on candidate lists: one workgroup per candidate (1), one wave (0), by document length (-1)
     int maxsim_persistent = 0;  // MaxSim screen (dims <= 128): persistent workgroups walking the docs in rounds.  A/B on one box
                                 // (interleaved A/B through this option, 1 M text docs / 100 k pages): text +-0, pages 4 % SLOWER -- off
@@ -314,7 +325,6 @@ struct mi355dr_index {
     // option "screen_flush_sync" (0 = every wave on its own, round 5), "screen_flush_lanes" (tuning)
     int screen_flush_sync = 1, screen_flush_lanes = 48, screen_flush_alone = 40;
     int wide_inflation_x10 = 100;  // growth budget of the two-wave prune's passes: inflation of the int8 bound it plans for, x 10 (tuning)
-    int flush_mask_now = -1;     // ... of the chunk being launched (run_screen)
     // pass schedule: ratio of chunk i = (geometric mean) x taper^((n-1)/2 - i) -- early chunks (cheap hits, loose bound) larger,
     // late chunks (expensive hits) smaller; 100 = uniform ratios (option "chunk_taper_x100")
     int chunk_taper_x100 = 0;   // 0 = auto: 120 for passes of the two-wave prune (measured -1 % at k = 100), 100 otherwise (k = 10: no gain)

@@ -228,11 +228,6 @@ constexpr double kSmallBlockBudget = 1.6;  // (the measured inflations are ~4 an
 // by the Gaussian tail ratio, ~6 measured over the round-5 pass at k = 100 -- budgeted as 10 with a quarter of the entries spare.
 constexpr double kInflationI8Wide = 10.0, kInflationBf16Wide = 4.0;
 inline bool wide_ok(const mi355dr_index* idx, int k) { return idx->prune_wide && k >= kWideKMin && k <= kWideKMax; }
-// the prunes of the search in progress take the two-wave form -- passes that screen only (enqueue_block sets the flag): the
-// exact scan keeps the general form and its <= 2048-slot lists, on path = scan and on an AUTO pass no screen can serve alike
-inline bool wide_now(const mi355dr_index* idx) { return idx->screening_now && wide_ok(idx, idx->k_now); }
-// candidate slots per query (= the lists' stride) of the search in progress
-inline int cap_now(const mi355dr_index* idx) { return !idx->cap_set && wide_now(idx) ? kCandCapWide : idx->cap; }
 inline double growth_budget(const mi355dr_index* idx, int k, bool i8) {
     if (wide_ok(idx, k) && idx->path != MI355DR_PATH_SCAN) {
         const int room = std::min(kWideEntries, idx->cap_set ? idx->cap : kCandCapWide);
@@ -242,21 +237,41 @@ inline double growth_budget(const mi355dr_index* idx, int k, bool i8) {
     return 0.6 * std::min(room, idx->cap) / ((double)k * (i8 ? kInflationI8 : kInflationBf16));
 }
 
-// which screen the search in progress uses: int8 needs a corpus that quantised within the limit and (in AUTO) a k small
-// enough that its wider bound still allows chunks to grow (k <= 133 at the default budget line); larger k keeps bf16
+// THE decision of a pass at k and fix-up level `level` (force_scan: as under path = scan, whatever the option says), made once
+// from the handle's options and corpus as they are now and handed down as a value.  `no_screen`: the caller's text for a
+// path = screen pass that no screen can serve (the int8 refusal reads the same everywhere).
+// Which screen: int8 needs a corpus that quantised within the limit and (in AUTO) a k small enough that its wider bound still
+// allows chunks to grow (k <= 133 at the default budget line); larger k keeps bf16.
 inline bool i8_available(const mi355dr_index* idx) { return idx->irr8_n <= kIrrCap; }
-inline bool use_i8(const mi355dr_index* idx) {
-    if (idx->retry_level > 0) return false;  // re-screening overflowed queries: the ~3x tighter bf16 bound
-    if (idx->screen_dtype == MI355DR_SCREEN_I8) return true;
+Pass decide_pass(const mi355dr_index* idx, int k, int level, bool force_scan, const char* no_screen = nullptr) {
+    Pass ps;
+    ps.k = k;
+    ps.level = level;
+    const int path = force_scan ? (int)MI355DR_PATH_SCAN : idx->path;
+    if (level > 0) ps.i8 = false;  // re-screening overflowed queries: the ~3x tighter bf16 bound
+    else if (idx->screen_dtype == MI355DR_SCREEN_I8) ps.i8 = true;
     // (measured round 3, N = 10 M, 1024 queries: int8 7.4 / 8.0 / 9.5 / 11.7 / 12.7 ms at k = 10 / 32 / 64 / 100 / 128 against
     // 13-14.4 ms for bf16, whose kernel alone is 11 ms; 22 against 16 at k = 200, where the int8 chunks hardly grow any more:
     // the cross-over is near k = 160, budget 0.2; round 2 drew the line at k = 24, budget 1.5)
-    return idx->screen_dtype == MI355DR_SCREEN_AUTO && i8_available(idx) && idx->k_now < idx->i8_demoted_k &&
-           growth_budget(idx, idx->k_now, true) >= idx->i8_min_budget;
+    else ps.i8 = idx->screen_dtype == MI355DR_SCREEN_AUTO && i8_available(idx) && k < idx->i8_demoted_k &&
+                 growth_budget(idx, k, true) >= idx->i8_min_budget;
+    // (inner product rides the same cosine screens: thresholds become cos >= dot_k / (|q| cmax), see k_prune)
+    const bool screen_possible = ps.i8 ? i8_available(idx) : idx->irr_n <= kIrrCap;
+    ps.screening = idx->n > 0 && screen_possible && path != MI355DR_PATH_SCAN;
+    // the two-wave prune and its 4096-slot lists are for passes that screen: the exact scan keeps the general form and its
+    // <= 2048-slot lists, on path = scan and on an AUTO pass no screen can serve alike
+    ps.wide = ps.screening && wide_ok(idx, k);
+    ps.cap = !idx->cap_set && ps.wide ? kCandCapWide : idx->cap;
+    if (idx->screen_dtype == MI355DR_SCREEN_I8 && !i8_available(idx) && path != MI355DR_PATH_SCAN)
+        ps.refused = "int8 screen unavailable: too many rows outside the residual limit";
+    else if (path == MI355DR_PATH_SCREEN && !screen_possible && idx->n > 0) ps.refused = no_screen;
+    return ps;
 }
+// between searches (stat "screen_dtype_active", the debug entry points): the screen a first attempt at the last k would take
+inline bool idle_i8(const mi355dr_index* idx) { return decide_pass(idx, idx->last_pass_k, 0, false).i8; }
 
-int launch_prune(mi355dr_index* idx, hipStream_t s, int nblocks, const int* qlist, int k, int exact, bool thr_only = false,
-                 bool one_wave_only = false, bool defer_b = false) {
+int launch_prune(mi355dr_index* idx, hipStream_t s, const Pass& ps, int nblocks, const int* qlist, int exact,
+                 bool thr_only = false, bool one_wave_only = false, bool defer_b = false) {
     PruneArgs pa{};
     pa.thr_only = thr_only ? 1 : 0;
     pa.one_wave_only = one_wave_only ? 1 : 0;
@@ -269,23 +284,23 @@ int launch_prune(mi355dr_index* idx, hipStream_t s, int nblocks, const int* qlis
     pa.cand_val = idx->cand_val;
     pa.qlist = qlist;
     pa.stat = idx->stat_dev;
-    pa.cap = cap_now(idx);
+    pa.cap = ps.cap;
     pa.d = idx->dim;
-    pa.k = k;
+    pa.k = ps.k;
     pa.metric = idx->metric;
     pa.exact = exact;
     // (flags exist only for loose rows, and every loose row is counted: a corpus without any -- the usual case -- spares each
     // candidate the dependent flag8[row] load, one memory round trip of the prune's latency chain)
     // (a removed row carries the flag too -- its all-zero int8 image can pass a low threshold -- and is in no list: dead_n)
-    pa.flag8 = (use_i8(idx) && (idx->irr8_n > 0 || idx->dead_n > 0)) ? idx->flag8 : nullptr;
+    pa.flag8 = (ps.i8 && (idx->irr8_n > 0 || idx->dead_n > 0)) ? idx->flag8 : nullptr;
     pa.cscale = idx->metric == MI355DR_METRIC_IP ? idx->cmax : 1.0f;
     // int8 screen, cosine: candidates that survive the exact cut are screened once more on their bf16 shadow rows
     // (half the bytes of an fp32 row, a bound ~5x tighter) before the exact re-score
-    pa.shadow16 = (use_i8(idx) && idx->metric == 0 && !exact && idx->prefilter16) ? idx->shadow : nullptr;
+    pa.shadow16 = (ps.i8 && idx->metric == 0 && !exact && idx->prefilter16) ? idx->shadow : nullptr;
     pa.dpad = idx->dpad;
     pa.round_a = idx->round_a;
     // the general form walks the (usually empty) list of queries the one-wave form left, on a small grid
-    if (!exact && wide_now(idx)) {  // 33 <= k <= 128: the two-wave form alone (what it cannot hold is flagged for the re-screen)
+    if (!exact && ps.wide) {  // 33 <= k <= 128: the two-wave form alone (what it cannot hold is flagged for the re-screen)
         pa.shadow16 = nullptr;
         hipLaunchKernelGGL((k_prune_wide<2, 32>), dim3(nblocks), dim3(2 * kWave), prune_wide_lds_bytes(idx->dim, 2), s, pa);
         HIPCHECK(idx, hipGetLastError());
@@ -307,9 +322,9 @@ int launch_prune(mi355dr_index* idx, hipStream_t s, int nblocks, const int* qlis
     return MI355DR_OK;
 }
 
-int launch_prep(mi355dr_index* idx, hipStream_t s, int B, int Bpad, int metric, int cnt0 = 0) {
+int launch_prep(mi355dr_index* idx, hipStream_t s, int B, int Bpad, int metric, bool i8, int cnt0 = 0) {
     hipLaunchKernelGGL(k_prep_queries, dim3(Bpad), dim3(64), (size_t)idx->dim * sizeof(float), s, idx->qdev, B, idx->dim,
-                       idx->dpad, metric, idx->st, idx->dpad8, use_i8(idx) ? 1 : 0, idx->bf16_ec, idx->status_or_dev,
+                       idx->dpad, metric, idx->st, idx->dpad8, i8 ? 1 : 0, idx->bf16_ec, idx->status_or_dev,
                        idx->prune_skip, cnt0, idx->metric == MI355DR_METRIC_IP ? idx->cmax : 1.0f);
     idx->prune_parity = 0;
     HIPCHECK(idx, hipGetLastError());
@@ -323,12 +338,11 @@ constexpr int kRetryLevels = 2;  // re-screens of an overflowed query (bf16, gro
 
 // which kernel one screen launch over `rows` rows takes (launch_screen switches on it; mi355dr_debug_screen_hits reports it)
 enum ScreenKernel { kKernTile = 0, kKernStream = 1, kKern256c = 2, kKernRq = 3 };
-inline ScreenKernel screen_kernel_for(const mi355dr_index* idx, int B, int64_t rows, bool emit_all) {
+inline ScreenKernel screen_kernel_for(const mi355dr_index* idx, bool i8, int B, int64_t rows, bool emit_all) {
     // the emit-all first chunk always goes through the 128x128 kernel (k_screen256c and k_screen_rq have no emit-all epilogue)
     // ... and so do chunks of a few thousand rows: their thresholds are still so low that a good part of the tile is a
     // hit, which the per-lane global append of k_screen handles better than the small per-wave queues of k_screen256c and k_screen_rq
     const int tile = (emit_all || rows <= idx->small_chunk_rows) ? kTileM : screen_tile(B);
-    const bool i8 = use_i8(idx);
     const int row_bytes = i8 ? idx->dpad8 : idx->dpad * 2;
     const int ksteps = row_bytes / kRowB;
     // query operand resident in registers, 128-row tiles (k_screen_rq.h): int8 shadows of at most 768 bytes per row
@@ -339,12 +353,13 @@ inline ScreenKernel screen_kernel_for(const mi355dr_index* idx, int B, int64_t r
     return kKernTile;
 }
 
-// launch one screen pass over rows [r0, r_end) (r0 a multiple of the tile edge)
-int launch_screen(mi355dr_index* idx, hipStream_t s, int B, int64_t r0, int64_t r_end, int cap, int emit_mode) {
+// launch one screen pass over rows [r0, r_end) (r0 a multiple of the tile edge); flush_mask: k_screen_rq's common flush
+// period - 1 (-1: every wave on its own)
+int launch_screen(mi355dr_index* idx, hipStream_t s, bool i8, int B, int64_t r0, int64_t r_end, int cap, int emit_mode,
+                  int flush_mask) {
     const bool emit_all = emit_mode != 0;  // (both special epilogues live in k_screen)
-    const ScreenKernel kern = screen_kernel_for(idx, B, r_end - r0, emit_all);
+    const ScreenKernel kern = screen_kernel_for(idx, i8, B, r_end - r0, emit_all);
     const int tile = kern == kKern256c || kern == kKernRq ? kT2 : kTileM;
-    const bool i8 = use_i8(idx);
     ScreenArgs2 sa{};
     sa.status = idx->st.status;
     sa.shadow = i8 ? (const void*)idx->shadow8 : (const void*)idx->shadow;
@@ -387,7 +402,7 @@ int launch_screen(mi355dr_index* idx, hipStream_t s, int B, int64_t r0, int64_t 
         // pass for a sibling of this launch -- a stale word could only cost a capped wait, never a result)
         if (sa.epoch == 1) HIPCHECK(idx, hipMemsetAsync(idx->rq_progress, 0, kRqProgressWords * sizeof(int), s));
         sa.drift = idx->screen_drift;
-        sa.flush_mask = idx->flush_mask_now;
+        sa.flush_mask = flush_mask;
         sa.flush_alone = idx->screen_flush_alone;
         if (sa.ksteps == 6 && !idx->screen_rq_split_tests) {  // (A/B form, d = 768 only: every block test in one piece)
             hipLaunchKernelGGL((k_screen_rq<6, false, true>), dim3(g2), dim3(512), rq_lds(6), s, sa);
@@ -452,9 +467,11 @@ struct PassPlan {
     std::vector<int64_t> ends;   // chunk ends, ascending, last = n; the first chunk starts at 0 (starter) or is the emit-all one
     bool emit_all_first = false;
 };
-PassPlan plan_pass(const mi355dr_index* idx, int B, int k, double growth) {
+PassPlan plan_pass(const mi355dr_index* idx, const Pass& ps, int B, double growth) {
     PassPlan p;
     const int64_t n = idx->n;
+    const int k = ps.k, cap = ps.cap;
+    const bool wide = ps.wide;
     const int tile = screen_tile(B);
     int64_t seen = 0;  // rows whose k-th best the first planned chunk's threshold comes from
     // the starter leaves one candidate per 64-row slab of its sample in every query's list: the list must hold them
@@ -464,11 +481,9 @@ PassPlan plan_pass(const mi355dr_index* idx, int B, int k, double growth) {
     // (4096 <= n < 8192 with k in 17..32).  Either way: the emit-all ladder.
     // Round 6, 33 <= k <= 128 (two-wave prune): the same estimator over a 64 k-row sample -- 1024 slab maxima per query, of
     // which the prune re-scores the 128 best-looking; their k-th best exact score is (about) the k-th best of the sample.
-    const bool wide = wide_now(idx);
-    const int cap = cap_now(idx);
     const int64_t starter_rows = std::min<int64_t>(wide ? idx->starter_rows_wide : kStarterRows, n / 4) / kTileM * kTileM;
     const int64_t starter_slabs = (starter_rows + kSlabRows - 1) / kSlabRows;
-    if (idx->starter && (k <= kStarterKMax || wide) && idx->retry_level == 0 && idx->chunk0_set == 0 && n >= 4 * 1024 &&
+    if (idx->starter && (k <= kStarterKMax || wide) && ps.level == 0 && idx->chunk0_set == 0 && n >= 4 * 1024 &&
         starter_slabs <= cap && starter_slabs >= k) {
         p.sample = starter_rows;
         seen = p.sample;
@@ -518,23 +533,23 @@ PassPlan plan_pass(const mi355dr_index* idx, int B, int k, double growth) {
 
 inline int starter_count(const PassPlan& p) { return (int)((p.sample + kSlabRows - 1) / kSlabRows); }
 
-PassPlan make_plan(const mi355dr_index* idx, int B, int k) {
+PassPlan make_plan(const mi355dr_index* idx, const Pass& ps, int B) {
     // (measured round 3, N = 10 M, k = 10: a ratio of 4 per step -- 5 chunks -- 7.43 ms, the budget's 4.8 -- 4 chunks -- 7.54)
-    double growth = std::max(0.25, std::min((double)idx->chunk_growth, growth_budget(idx, k, use_i8(idx))));
+    const double budget = growth_budget(idx, ps.k, ps.i8);
+    double growth = std::max(0.25, std::min((double)idx->chunk_growth, budget));
     // small query blocks: a pass is one stream over the shadow rows plus one latency-bound re-score launch per chunk, and an
     // append costs nothing -- fewer, larger chunks (the k-dependent budget alone bounds the growth: x7 per step at k = 10)
-    if (B <= 64 && idx->retry_level == 0 && idx->chunk_growth_set == 0)
-        growth = std::max(growth, std::min(8.0, growth_budget(idx, k, use_i8(idx)) * kSmallBlockBudget));
-    if (idx->retry_level == 1) growth = std::max(0.25, growth * 0.5);
-    if (idx->retry_level >= 2) growth = 0.25;  // (every chunk then holds <= 20 % of the rows: a dense neighbourhood is split up)
-    return plan_pass(idx, B, k, growth);
+    if (B <= 64 && ps.level == 0 && idx->chunk_growth_set == 0) growth = std::max(growth, std::min(8.0, budget * kSmallBlockBudget));
+    if (ps.level == 1) growth = std::max(0.25, growth * 0.5);
+    if (ps.level >= 2) growth = 0.25;  // (every chunk then holds <= 20 % of the rows: a dense neighbourhood is split up)
+    return plan_pass(idx, ps, B, growth);
 }
 
 // screen path over all rows for the B queries prepared in idx->st / idx->qdev (candidate counts initialised to
 // starter_count(plan) by k_prep_queries when the plan has a starter)
-int run_screen(mi355dr_index* idx, hipStream_t s, int B, int k, const PassPlan& plan) {
+int run_screen(mi355dr_index* idx, hipStream_t s, const Pass& ps, int B, const PassPlan& plan) {
     int64_t kept_all_below = 0;  // rows the emit-all first chunk already turned into candidates
-    const bool i8 = use_i8(idx);
+    const bool i8 = ps.i8;
     const int side_n = i8 ? idx->irr8_n : idx->irr_n;  // rows this screen cannot see
     constexpr int kSideMerge = 32;
     bool side_done = false;
@@ -561,8 +576,9 @@ int run_screen(mi355dr_index* idx, hipStream_t s, int B, int k, const PassPlan& 
         return MI355DR_OK;
     };
     if (plan.sample > 0) {
-        CHECK(timed(false, plan.sample, [&] { return launch_screen(idx, s, B, 0, plan.sample, cap_now(idx), kEmitSlabMax); }));
-        CHECK(launch_prune(idx, s, B, nullptr, k, /*exact=*/0, /*thr_only=*/true, /*one_wave_only=*/true));
+        // (the flush mask: none of the slab-maximum epilogue's kernels reads it)
+        CHECK(timed(false, plan.sample, [&] { return launch_screen(idx, s, i8, B, 0, plan.sample, ps.cap, kEmitSlabMax, -1); }));
+        CHECK(launch_prune(idx, s, ps, B, nullptr, /*exact=*/0, /*thr_only=*/true, /*one_wave_only=*/true));
         idx->s_starters++;
     }
     int64_t done = 0;
@@ -572,41 +588,42 @@ int run_screen(mi355dr_index* idx, hipStream_t s, int B, int k, const PassPlan& 
         if (emit_all) kept_all_below = end;
         // the first chunk has no threshold yet: it keeps every row (direct stores) as long as it fits the buffer
         const bool big = !emit_all && end - done > idx->small_chunk_rows && screen_tile(B) == kT2;
-        {   // hit lanes a wave of k_screen_rq expects per tile (32 queries x 128 rows): rows above the threshold of `seen` rows
-            // ~ k x inflation / seen per row and query (inflation of the int8 bound ~8)
-            const int64_t seen = ci == 0 ? (plan.sample > 0 ? plan.sample : end) : done;
-            const double lanes = 8.0 * k * 4096.0 / (double)std::max<int64_t>(seen, 1);
-            int period = 1;
-            while (period < 64 && period * 2 * lanes <= idx->screen_flush_lanes) period *= 2;
-            idx->flush_mask_now = idx->screen_flush_sync ? period - 1 : -1;
-        }
-        CHECK(timed(big, end - done, [&] { return launch_screen(idx, s, B, done, end, cap_now(idx), emit_all ? kEmitAll : 0); }));
+        // hit lanes a wave of k_screen_rq expects per tile (32 queries x 128 rows): rows above the threshold of `seen` rows
+        // ~ k x inflation / seen per row and query (inflation of the int8 bound ~8)
+        const int64_t seen = ci == 0 ? (plan.sample > 0 ? plan.sample : end) : done;
+        const double lanes = 8.0 * ps.k * 4096.0 / (double)std::max<int64_t>(seen, 1);
+        int period = 1;
+        while (period < 64 && period * 2 * lanes <= idx->screen_flush_lanes) period *= 2;
+        const int flush_mask = idx->screen_flush_sync ? period - 1 : -1;
+        CHECK(timed(big, end - done, [&] { return launch_screen(idx, s, i8, B, done, end, ps.cap, emit_all ? kEmitAll : 0, flush_mask); }));
         idx->s_chunks++;
         if (end >= idx->n && side_n > 0 && side_n <= kSideMerge) {
             // rows this screen cannot see (irregular; for int8 also loose): a handful of them ride the LAST chunk's prune
             // as "no bound" candidates instead of costing a prune pass of their own (0.12 ms per block at N = 10 M)
             hipLaunchKernelGGL(k_emit_irregular, dim3(B), dim3(64), 0, s, i8 ? idx->irr8_rows : idx->irr_rows, side_n, idx->st,
-                               idx->cand_row, idx->cand_val, cap_now(idx), (int)kept_all_below);
+                               idx->cand_row, idx->cand_val, ps.cap, (int)kept_all_below);
             HIPCHECK(idx, hipGetLastError());
             side_done = true;
         }
         // every prune but the pass's last one carries its survivors over instead of re-scoring them (k_prune: defer_b)
         const bool last = end >= idx->n && (side_n == 0 || side_done);
-        CHECK(launch_prune(idx, s, B, nullptr, k, /*exact=*/0, false, lean, !last));
+        CHECK(launch_prune(idx, s, ps, B, nullptr, /*exact=*/0, false, lean, !last));
         done = end;
     }
     if (side_n > 0 && !side_done) {
         hipLaunchKernelGGL(k_emit_irregular, dim3(B), dim3(64), 0, s, i8 ? idx->irr8_rows : idx->irr_rows, side_n, idx->st,
-                           idx->cand_row, idx->cand_val, cap_now(idx), (int)kept_all_below);
+                           idx->cand_row, idx->cand_val, ps.cap, (int)kept_all_below);
         HIPCHECK(idx, hipGetLastError());
-        CHECK(launch_prune(idx, s, B, nullptr, k, 0, false, lean));
+        CHECK(launch_prune(idx, s, ps, B, nullptr, 0, false, lean));
     }
     idx->s_passes++;
     return MI355DR_OK;
 }
 
-// exact scan of rows [r0,r1) for the <= kScanQ queries in qlist_dev[off..off+nq), then exact prune
-int scan_range(mi355dr_index* idx, hipStream_t s, int off, int nq, int k, int64_t r0, int64_t r1) {
+// one exact-scan launch over rows [r0, r1) for the nq <= kScanQ queries of `qlist` (device memory).  ids != nullptr: the gathered
+// scan (mi355dr_search_subset) over list POSITIONS [r0, r1) of those local rows
+int launch_scan(mi355dr_index* idx, hipStream_t s, const int* qlist, int nq, int cap, int64_t r0, int64_t r1,
+                const int32_t* ids = nullptr) {
     ScanArgs sa{};
     sa.rows = idx->rows;
     sa.nrm2 = idx->nrm2;
@@ -614,38 +631,48 @@ int scan_range(mi355dr_index* idx, hipStream_t s, int off, int nq, int k, int64_
     sa.st = idx->st;
     sa.cand_row = idx->cand_row;
     sa.cand_val = idx->cand_val;
-    sa.qlist = idx->qlist_dev + off;
+    sa.qlist = qlist;
     sa.nq = nq;
-    sa.cap = cap_now(idx);
+    sa.cap = cap;
     sa.d = idx->dim;
     sa.metric = idx->metric;
     sa.row0 = r0;
     sa.row1 = r1;
-    const int64_t grid = (r1 - r0 + kScanThreads - 1) / kScanThreads;
-    if (idx->dim % kScan32PieceCols == 0 && idx->scan_dma)  // rows are whole 128-byte pieces: the LDS-DMA form
-        hipLaunchKernelGGL(k_scan32, dim3((unsigned)grid), dim3(kScanThreads), kScan32Lds, s, sa, idx->n);
-    else
-        hipLaunchKernelGGL(k_scan, dim3((unsigned)grid), dim3(kScanThreads), scan_lds_bytes(idx->dim, nq), s, sa);
+    const dim3 grid((unsigned)((r1 - r0 + kScanThreads - 1) / kScanThreads));
+    const ScanIdsArgs ia{sa, ids};
+    if (ids) hipLaunchKernelGGL(k_scan_ids, grid, dim3(kScanThreads), scan_ids_lds_bytes(idx->dim, nq), s, ia);
+    else if (idx->dim % kScan32PieceCols == 0 && idx->scan_dma)  // rows are whole 128-byte pieces: the LDS-DMA form
+        hipLaunchKernelGGL(k_scan32, grid, dim3(kScanThreads), kScan32Lds, s, sa, idx->n);
+    else hipLaunchKernelGGL(k_scan, grid, dim3(kScanThreads), scan_lds_bytes(idx->dim, nq), s, sa);
     HIPCHECK(idx, hipGetLastError());
-    return launch_prune(idx, s, nq, idx->qlist_dev + off, k, /*exact=*/1);
+    return MI355DR_OK;
 }
 
-// guaranteed exact path for the queries listed in `qs` (indices into the current block)
-int run_scan(mi355dr_index* idx, hipStream_t s, const std::vector<int>& qs, int k) {
+// that launch for the queries in qlist_dev[off..off+nq), then their exact prune
+int scan_range(mi355dr_index* idx, hipStream_t s, const Pass& ps, int off, int nq, int64_t r0, int64_t r1, const int32_t* ids) {
+    CHECK(launch_scan(idx, s, idx->qlist_dev + off, nq, ps.cap, r0, r1, ids));
+    return launch_prune(idx, s, ps, nq, idx->qlist_dev + off, /*exact=*/1);
+}
+
+// guaranteed exact path for the queries listed in `qs` (indices into the current block) over the index's `total` rows, or
+// (ids != nullptr) over the `total` positions of a sorted id list -- positions are in row order, and a sorted corpus is as
+// adversarial there as here.  The plain form returns without a synchronisation unless a chunk overflowed (asynchronous
+// blocks rely on that); the gathered form is complete on return.
+int run_scan(mi355dr_index* idx, hipStream_t s, const Pass& ps, const std::vector<int>& qs, int64_t total,
+             const int32_t* ids = nullptr) {
     if (qs.empty()) return MI355DR_OK;
     HIPCHECK(idx, hipMemcpyAsync(idx->qlist_dev, qs.data(), qs.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    const int nq_all = (int)qs.size();
+    const int nq_all = (int)qs.size(), cap = ps.cap;
     hipLaunchKernelGGL(k_reset_queries, dim3((nq_all + 255) / 256), dim3(256), 0, s, idx->st, idx->qlist_dev, nq_all);
     HIPCHECK(idx, hipGetLastError());
     const int per = kScanQ;  // queries per launch: one 32-column MFMA block (LDS use does not depend on the dimension)
     for (int off = 0; off < nq_all; off += per) {
         const int nq = std::min(per, nq_all - off);
         int64_t done = 0;
-        const int cap = cap_now(idx);
         int64_t chunk = std::min<int64_t>(idx->chunk0_rows, cap);
-        while (done < idx->n) {
-            const int64_t end = std::min<int64_t>(idx->n, done + chunk);
-            CHECK(scan_range(idx, s, off, nq, k, done, end));
+        while (done < total) {
+            const int64_t end = std::min<int64_t>(total, done + chunk);
+            CHECK(scan_range(idx, s, ps, off, nq, done, end, ids));
             if (end - done > cap) {  // only a chunk larger than the buffer can overflow
                 HIPCHECK(idx, hipMemcpyAsync(idx->status_host, idx->st.status, kQBlockMax * sizeof(int),
                                              hipMemcpyDeviceToHost, s));
@@ -665,7 +692,11 @@ int run_scan(mi355dr_index* idx, hipStream_t s, const std::vector<int>& qs, int 
                         HIPCHECK(idx, hipMemcpyAsync(idx->st.status + q, idx->status_host + q, sizeof(int),
                                                      hipMemcpyHostToDevice, s));
                     for (int64_t p = done; p < end; p += cap)
-                        CHECK(scan_range(idx, s, roff, (int)redo.size(), k, p, std::min<int64_t>(end, p + cap)));
+                        CHECK(scan_range(idx, s, ps, roff, (int)redo.size(), p, std::min<int64_t>(end, p + cap), ids));
+                    if (ids) {
+                        HIPCHECK(idx, hipStreamSynchronize(s));  // `redo` (pageable) was read by the copy
+                        idx->s_subset_rerun_queries += (int64_t)redo.size();
+                    }
                 }
             }
             done = end;
@@ -675,93 +706,28 @@ int run_scan(mi355dr_index* idx, hipStream_t s, const std::vector<int>& qs, int 
             chunk = std::max<int64_t>(chunk, done * (idx->chunk_growth_set ? idx->chunk_growth : 63));
         }
     }
-    idx->s_fallback_queries += nq_all;
-    return MI355DR_OK;
-}
-
-// ---- the gathered scan (mi355dr_search_subset) ------------------------------------------------------
-// exact scan of list positions [p0, p1) of idx->subset_ids for the <= kScanQ queries in qlist_dev[off..off+nq), then exact prune
-int scan_ids_range(mi355dr_index* idx, hipStream_t s, int off, int nq, int k, int64_t p0, int64_t p1) {
-    ScanIdsArgs ia{};
-    ia.ids = idx->subset_ids;
-    ia.s.rows = idx->rows;
-    ia.s.nrm2 = idx->nrm2;
-    ia.s.q = idx->qdev;
-    ia.s.st = idx->st;
-    ia.s.cand_row = idx->cand_row;
-    ia.s.cand_val = idx->cand_val;
-    ia.s.qlist = idx->qlist_dev + off;
-    ia.s.nq = nq;
-    ia.s.cap = cap_now(idx);
-    ia.s.d = idx->dim;
-    ia.s.metric = idx->metric;
-    ia.s.row0 = p0;
-    ia.s.row1 = p1;
-    const int64_t grid = (p1 - p0 + kScanThreads - 1) / kScanThreads;
-    hipLaunchKernelGGL(k_scan_ids, dim3((unsigned)grid), dim3(kScanThreads), scan_ids_lds_bytes(idx->dim, nq), s, ia);
-    HIPCHECK(idx, hipGetLastError());
-    return launch_prune(idx, s, nq, idx->qlist_dev + off, k, /*exact=*/1);
-}
-
-// run_scan's schedule over the m list POSITIONS instead of the index's rows, for the B prepared queries of the block: groups
-// of kScanQ queries, the chunk0_rows / x63 ladder, a chunk larger than the list re-run in list-sized pieces for the queries
-// it overflowed.  (The list is sorted: positions are in row order, and a sorted corpus is as adversarial here as there.)
-int run_scan_ids(mi355dr_index* idx, hipStream_t s, int B, int k, int64_t m) {
-    std::vector<int> qs(B);
-    for (int i = 0; i < B; ++i) qs[i] = i;
-    HIPCHECK(idx, hipMemcpyAsync(idx->qlist_dev, qs.data(), qs.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_reset_queries, dim3((B + 255) / 256), dim3(256), 0, s, idx->st, idx->qlist_dev, B);
-    HIPCHECK(idx, hipGetLastError());
-    const int cap = cap_now(idx);
-    for (int off = 0; off < B; off += kScanQ) {
-        const int nq = std::min(kScanQ, B - off);
-        int64_t done = 0;
-        int64_t chunk = std::min<int64_t>(idx->chunk0_rows, cap);
-        while (done < m) {
-            const int64_t end = std::min<int64_t>(m, done + chunk);
-            CHECK(scan_ids_range(idx, s, off, nq, k, done, end));
-            if (end - done > cap) {  // only a chunk larger than the buffer can overflow
-                HIPCHECK(idx, hipMemcpyAsync(idx->status_host, idx->st.status, kQBlockMax * sizeof(int), hipMemcpyDeviceToHost, s));
-                HIPCHECK(idx, hipStreamSynchronize(s));
-                std::vector<int> redo;
-                for (int j = 0; j < nq; ++j)
-                    if (idx->status_host[off + j] & kStOverflow) redo.push_back(off + j);
-                if (!redo.empty()) {
-                    // the overflowed queries alone, in buffer-sized pieces (cannot overflow); the others committed the chunk
-                    const int roff = kQBlockMax;  // (the tail of qlist_dev)
-                    HIPCHECK(idx, hipMemcpyAsync(idx->qlist_dev + roff, redo.data(), redo.size() * sizeof(int), hipMemcpyHostToDevice, s));
-                    for (int q : redo) idx->status_host[q] &= ~kStOverflow;  // (the prune did not commit the failed chunk: the kept list stands)
-                    for (int q : redo)
-                        HIPCHECK(idx, hipMemcpyAsync(idx->st.status + q, idx->status_host + q, sizeof(int), hipMemcpyHostToDevice, s));
-                    for (int64_t p = done; p < end; p += cap)
-                        CHECK(scan_ids_range(idx, s, roff, (int)redo.size(), k, p, std::min<int64_t>(end, p + cap)));
-                    HIPCHECK(idx, hipStreamSynchronize(s));  // `redo` (pageable) was read by the copy
-                    idx->s_subset_rerun_queries += (int64_t)redo.size();
-                }
-            }
-            done = end;
-            chunk = std::max<int64_t>(chunk, done * (idx->chunk_growth_set ? idx->chunk_growth : 63));
-        }
-    }
-    HIPCHECK(idx, hipStreamSynchronize(s));  // `qs` (pageable) was read by the copy
+    if (ids) HIPCHECK(idx, hipStreamSynchronize(s));  // `qs` (pageable) was read by the copy
+    else idx->s_fallback_queries += nq_all;
     return MI355DR_OK;
 }
 
 // one block of B <= kQBlockMax device-resident queries against the m uploaded ids -> device outputs [B,k], complete on return
 int subset_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, int k, int64_t m, double* out_dist_dev,
                  int64_t* out_rows_dev) {
-    idx->k_now = k;
-    idx->screening_now = false;  // (before the first launch: every kernel of the pass sees the exact path's list stride)
+    const Pass ps = decide_pass(idx, k, 0, /*force_scan=*/true);  // (it never screens: the exact path's list stride)
+    idx->last_pass_k = k;
     if (q_dev != idx->qdev)
         HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q_dev, (size_t)B * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
-    CHECK(launch_prep(idx, s, B, (int)round_up(B, screen_tile(B)), idx->metric));
-    if (m > 0) CHECK(run_scan_ids(idx, s, B, k, m));
+    CHECK(launch_prep(idx, s, B, (int)round_up(B, screen_tile(B)), idx->metric, ps.i8));
+    std::vector<int> all(B);
+    for (int i = 0; i < B; ++i) all[i] = i;
+    if (m > 0) CHECK(run_scan(idx, s, ps, all, m, idx->subset_ids));
     hipLaunchKernelGGL(k_finalize, dim3(B), dim3(64), 0, s, idx->st, k, idx->row_offset, idx->view_row_map.p, out_dist_dev,
                        out_rows_dev, idx->status_or_dev);
     HIPCHECK(idx, hipGetLastError());
     HIPCHECK(idx, hipMemcpyAsync(idx->status_host, idx->st.status, (size_t)kQBlockMax * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipStreamSynchronize(s));
-    // the scan re-runs every chunk that overflowed and clears the flag of each (complete_block, !used_screen): one left over is a lost chunk
+    // the scan re-runs every chunk that overflowed and clears the flag of each (complete_block, a pass that did not screen): one left over is a lost chunk
     for (int i = 0; i < B; ++i)
         if (idx->status_host[i] & kStOverflow)
             return fail(idx, MI355DR_E_INTERNAL, "subset scan: query " + std::to_string(i) + " lost a candidate chunk");
@@ -784,36 +750,32 @@ int pending_alloc(mi355dr_index* idx, Pending& p) {
     return MI355DR_OK;
 }
 
+// level / force_scan: 0 / false for a caller's block; complete_block's fix-up passes say theirs
 int enqueue_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, int k, double* out_dist_dev,
-                  int64_t* out_rows_dev, Pending& p) {
+                  int64_t* out_rows_dev, Pending& p, int level = 0, bool force_scan = false) {
     CHECK(ensure_qstate(idx));
     CHECK(pending_alloc(idx, p));
-    idx->k_now = k;
+    idx->last_pass_k = k;
     // a demoted int8 screen (AUTO) is on probation: first attempts at a demoted k count it down, then int8 gets another try
-    if (idx->retry_level == 0 && idx->screen_dtype == MI355DR_SCREEN_AUTO && k >= idx->i8_demoted_k && --idx->i8_probation <= 0)
+    if (level == 0 && idx->screen_dtype == MI355DR_SCREEN_AUTO && k >= idx->i8_demoted_k && --idx->i8_probation <= 0)
         idx->i8_demoted_k = INT_MAX;
     const int Bpad = (int)round_up(B, screen_tile(B));
-    if (idx->screen_dtype == MI355DR_SCREEN_I8 && !i8_available(idx) && idx->path != MI355DR_PATH_SCAN)
-        return fail(idx, MI355DR_E_UNSUPPORTED, "int8 screen unavailable: too many rows outside the residual limit");
-    // (inner product rides the same cosine screens: thresholds become cos >= dot_k / (|q| cmax), see k_prune)
-    const bool screen_possible = use_i8(idx) ? i8_available(idx) : idx->irr_n <= kIrrCap;
-    const bool use_screen = idx->n > 0 && screen_possible && idx->path != MI355DR_PATH_SCAN;
-    idx->screening_now = use_screen;  // (before the plan and the first launch: every kernel of the pass sees one list stride)
-    if (idx->path == MI355DR_PATH_SCREEN && !screen_possible && idx->n > 0)
-        return fail(idx, MI355DR_E_UNSUPPORTED, "screen path unavailable (metric or too many irregular rows)");
+    // (before the plan and the first launch: every kernel of the pass sees one screen type and one list stride)
+    const Pass ps = decide_pass(idx, k, level, force_scan, "screen path unavailable (metric or too many irregular rows)");
+    if (ps.refused) return fail(idx, MI355DR_E_UNSUPPORTED, ps.refused);
     if (q_dev != idx->qdev)
         HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q_dev, (size_t)B * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     PassPlan plan;
-    if (use_screen) plan = make_plan(idx, B, k);
+    if (ps.screening) plan = make_plan(idx, ps, B);
     // (also re-arms the status word and the prune's hand-over counters, and starts the lists at the starter's count)
-    CHECK(launch_prep(idx, s, B, Bpad, idx->metric, starter_count(plan)));
+    CHECK(launch_prep(idx, s, B, Bpad, idx->metric, ps.i8, starter_count(plan)));
     if (idx->n > 0) {
-        if (use_screen) {
-            CHECK(run_screen(idx, s, B, k, plan));
+        if (ps.screening) {
+            CHECK(run_screen(idx, s, ps, B, plan));
         } else {
             std::vector<int> all(B);
             for (int i = 0; i < B; ++i) all[i] = i;
-            CHECK(run_scan(idx, s, all, k));  // (blocks on the host only where a chunk larger than the buffer overflowed)
+            CHECK(run_scan(idx, s, ps, all, idx->n));  // (blocks on the host only where a chunk larger than the buffer overflowed)
         }
     }
     hipLaunchKernelGGL(k_finalize, dim3(B), dim3(64), 0, s, idx->st, k, idx->row_offset, idx->view_row_map.p, out_dist_dev,
@@ -826,24 +788,21 @@ int enqueue_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, 
     p.stream = s;
     p.q_dev = q_dev;
     p.B = B;
-    p.k = k;
+    p.pass = ps;
     p.out_dist = out_dist_dev;
     p.out_rows = out_rows_dev;
-    p.used_screen = use_screen;
-    p.was_i8 = use_screen && use_i8(idx);
-    p.level = idx->retry_level;
     return MI355DR_OK;
 }
 
 int search_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, int k, double* out_dist_dev,
-                 int64_t* out_rows_dev);
+                 int64_t* out_rows_dev, int level = 0, bool force_scan = false);
 
 int complete_block(mi355dr_index* idx, Pending& p) {
     if (!p.active) return MI355DR_OK;
     p.active = false;
     HIPCHECK(idx, hipEventSynchronize(p.done));
     drain_events(idx);
-    if (!p.used_screen) {
+    if (!p.pass.screening) {
         // the exact scan re-runs every chunk that overflowed (run_scan) and clears the flag of each: one left over is a lost chunk
         for (int i = 0; i < p.B; ++i)
             if (p.status_host[i] & kStOverflow)
@@ -853,7 +812,7 @@ int complete_block(mi355dr_index* idx, Pending& p) {
     if (p.status_host[kQBlockMax] == 0) return MI355DR_OK;
     // some query overflowed its candidate buffer or has an irregular norm
     hipStream_t s = p.stream;
-    const int B = p.B, k = p.k, level = p.level;
+    const int B = p.B, k = p.pass.k, level = p.pass.level;
     std::vector<int> sub;  // [todo ... | retry ...]
     int n_todo = 0;
     {
@@ -881,16 +840,8 @@ int complete_block(mi355dr_index* idx, Pending& p) {
     hipLaunchKernelGGL(k_gather_queries, dim3(n_sub), dim3(128), 0, s, p.q_dev, rb.map, idx->dim, rb.q);
     HIPCHECK(idx, hipGetLastError());
     HIPCHECK(idx, hipStreamSynchronize(s));  // `sub` (pageable) was read by the copy
-    const int saved_level = idx->retry_level, saved_path = idx->path;
-    int rc = MI355DR_OK;
-    if (n_todo > 0) {  // guaranteed exact path
-        idx->retry_level = level + 1;  // (buffers of the next level; the scan itself never re-screens)
-        idx->path = MI355DR_PATH_SCAN;
-        rc = search_block(idx, s, rb.q, n_todo, k, rb.dist, rb.rows);
-        idx->path = saved_path;
-        idx->retry_level = saved_level;
-        CHECK(rc);
-    }
+    // guaranteed exact path (a pass of the next level, for its buffers; the scan itself never re-screens)
+    if (n_todo > 0) CHECK(search_block(idx, s, rb.q, n_todo, k, rb.dist, rb.rows, level + 1, /*force_scan=*/true));
     if (n_retry > 0) {
         idx->s_retry_queries += n_retry;
         // AUTO gives the int8 screen up (from this k upwards) when more than 1 % of a block overflowed under its bound: the
@@ -900,16 +851,13 @@ int complete_block(mi355dr_index* idx, Pending& p) {
         // Not for ever -- a burst of queries into one dense neighbourhood must not cost a Gaussian-like corpus its int8 screen
         // (7.4 against 12.8 ms per block at the headline size): after 16 more blocks at such a k int8 gets another try, and the
         // wait doubles (up to 4096 blocks) whenever that try overflows again.
-        if (p.was_i8 && idx->screen_dtype == MI355DR_SCREEN_AUTO && n_retry * 100 > B) {
+        if (p.pass.i8 && idx->screen_dtype == MI355DR_SCREEN_AUTO && n_retry * 100 > B) {
             idx->i8_demoted_k = std::min(idx->i8_demoted_k, k);
             idx->i8_backoff = idx->i8_backoff == 0 ? 16 : std::min(idx->i8_backoff * 2, 4096);
             idx->i8_probation = idx->i8_backoff;
         }
-        idx->retry_level = level + 1;
-        rc = search_block(idx, s, rb.q + (size_t)n_todo * idx->dim, n_retry, k,
-                          rb.dist + (size_t)n_todo * k, rb.rows + (size_t)n_todo * k);
-        idx->retry_level = saved_level;
-        CHECK(rc);
+        CHECK(search_block(idx, s, rb.q + (size_t)n_todo * idx->dim, n_retry, k, rb.dist + (size_t)n_todo * k,
+                           rb.rows + (size_t)n_todo * k, level + 1));
     }
     hipLaunchKernelGGL(k_scatter_results, dim3(n_sub), dim3(128), 0, s, rb.dist, rb.rows, rb.map, k, p.out_dist, p.out_rows);
     HIPCHECK(idx, hipGetLastError());
@@ -932,9 +880,9 @@ int drain_pending(mi355dr_index* idx) { return complete_until(idx, idx->seq_next
 
 // one block of B <= kQBlockMax device-resident queries -> device outputs [B,k], complete on return
 int search_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, int k, double* out_dist_dev,
-                 int64_t* out_rows_dev) {
-    Pending& p = idx->sub_pend[std::min(idx->retry_level, kRetryLevels + 1)];
-    CHECK(enqueue_block(idx, s, q_dev, B, k, out_dist_dev, out_rows_dev, p));
+                 int64_t* out_rows_dev, int level, bool force_scan) {
+    Pending& p = idx->sub_pend[std::min(level, kRetryLevels + 1)];
+    CHECK(enqueue_block(idx, s, q_dev, B, k, out_dist_dev, out_rows_dev, p, level, force_scan));
     return complete_block(idx, p);
 }
 
@@ -968,7 +916,7 @@ int upload_and_prep(mi355dr_index* idx, const float* queries, int B, int metric)
     CHECK(drain_pending(idx));
     CHECK(ensure_qstate(idx));
     HIPCHECK(idx, hipMemcpyAsync(idx->qdev, queries, (size_t)B * idx->dim * sizeof(float), hipMemcpyHostToDevice, idx->stream));
-    return launch_prep(idx, idx->stream, B, (int)round_up(B, screen_tile(B)), metric);
+    return launch_prep(idx, idx->stream, B, (int)round_up(B, screen_tile(B)), metric, idle_i8(idx));
 }
 
 int check_search_args(mi355dr_index* idx, const void* q, int B, int k, const void* od, const void* orow) {
@@ -2035,8 +1983,8 @@ RangeState range_state(const mi355dr_index* idx, int R, int64_t pairs) {
 }
 
 // k_range_collect over the block's nq queries (qlist == nullptr: queries 0 .. nq-1) behind the launch that filled their lists
-int launch_range_collect(mi355dr_index* idx, hipStream_t s, const RangeState& rs, int form, int nq, const int* qlist, int cap,
-                         int span, int64_t row0) {
+int launch_range_collect(mi355dr_index* idx, hipStream_t s, const Pass& ps, const RangeState& rs, int form, int nq,
+                         const int* qlist, int span, int64_t row0) {
     RangeCollectArgs ca{};
     ca.rows = idx->rows;
     ca.nrm2 = idx->nrm2;
@@ -2046,8 +1994,8 @@ int launch_range_collect(mi355dr_index* idx, hipStream_t s, const RangeState& rs
     ca.cand_row = idx->cand_row;
     ca.cand_val = idx->cand_val;
     ca.qlist = qlist;
-    ca.flag8 = form != kRangeFormExact && use_i8(idx) ? idx->flag8.p : nullptr;
-    ca.cap = cap;
+    ca.flag8 = form != kRangeFormExact && ps.i8 ? idx->flag8.p : nullptr;
+    ca.cap = ps.cap;
     ca.d = idx->dim;
     ca.metric = idx->metric;
     ca.form = form;
@@ -2061,30 +2009,12 @@ int launch_range_collect(mi355dr_index* idx, hipStream_t s, const RangeState& rs
 
 // exact range scan of rows [r0, r1) for the queries in qlist_dev[0 .. nq_all): groups of kScanQ, the scan launches as they
 // are (their fixed thresholds were preset by k_range_prep), each followed by the exact form of k_range_collect
-int range_scan_span(mi355dr_index* idx, hipStream_t s, const RangeState& rs, int nq_all, int cap, int span, int64_t r0, int64_t r1) {
+int range_scan_span(mi355dr_index* idx, hipStream_t s, const Pass& ps, const RangeState& rs, int nq_all, int span, int64_t r0,
+                    int64_t r1) {
     for (int off = 0; off < nq_all; off += kScanQ) {
         const int nq = std::min(kScanQ, nq_all - off);
-        ScanArgs sa{};
-        sa.rows = idx->rows;
-        sa.nrm2 = idx->nrm2;
-        sa.q = idx->qdev;
-        sa.st = idx->st;
-        sa.cand_row = idx->cand_row;
-        sa.cand_val = idx->cand_val;
-        sa.qlist = idx->qlist_dev + off;
-        sa.nq = nq;
-        sa.cap = cap;
-        sa.d = idx->dim;
-        sa.metric = idx->metric;
-        sa.row0 = r0;
-        sa.row1 = r1;
-        const int64_t grid = (r1 - r0 + kScanThreads - 1) / kScanThreads;
-        if (idx->dim % kScan32PieceCols == 0 && idx->scan_dma)
-            hipLaunchKernelGGL(k_scan32, dim3((unsigned)grid), dim3(kScanThreads), kScan32Lds, s, sa, idx->n);
-        else
-            hipLaunchKernelGGL(k_scan, dim3((unsigned)grid), dim3(kScanThreads), scan_lds_bytes(idx->dim, nq), s, sa);
-        HIPCHECK(idx, hipGetLastError());
-        CHECK(launch_range_collect(idx, s, rs, kRangeFormExact, nq, idx->qlist_dev + off, cap, span, r0));
+        CHECK(launch_scan(idx, s, idx->qlist_dev + off, nq, ps.cap, r0, r1));
+        CHECK(launch_range_collect(idx, s, ps, rs, kRangeFormExact, nq, idx->qlist_dev + off, span, r0));
     }
     return MI355DR_OK;
 }
@@ -2092,28 +2022,12 @@ int range_scan_span(mi355dr_index* idx, hipStream_t s, const RangeState& rs, int
 // one block of nb <= kQBlockMax device-resident queries -> device outputs [nb, m] / [nb], complete on return
 int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, const double* radius, int m, double* od,
                 int64_t* orow, int64_t* ocount) {
-    // the screens' element type and the lists' stride follow k_now: 1 keeps the int8 screen wherever AUTO has it at all and
-    // the lists at option "cand_cap".  An ordinary search sets both words again before its first launch; they are put back
-    // all the same (stat "screen_dtype_active" reads k_now)
-    struct Restore {
-        mi355dr_index* idx;
-        int k_now;
-        bool screening_now;
-        ~Restore() {
-            idx->k_now = k_now;
-            idx->screening_now = screening_now;
-        }
-    } restore{idx, idx->k_now, idx->screening_now};
-    idx->k_now = 1;
-    idx->screening_now = false;
-    const int cap = cap_now(idx);
-    if (idx->screen_dtype == MI355DR_SCREEN_I8 && !i8_available(idx) && idx->path != MI355DR_PATH_SCAN)
-        return fail(idx, MI355DR_E_UNSUPPORTED, "int8 screen unavailable: too many rows outside the residual limit");
-    const bool i8 = use_i8(idx);
-    const bool screen_possible = i8 ? i8_available(idx) : idx->irr_n <= kIrrCap;
-    const bool use_screen = idx->n > 0 && screen_possible && idx->path != MI355DR_PATH_SCAN;
-    if (idx->path == MI355DR_PATH_SCREEN && !screen_possible && idx->n > 0)
-        return fail(idx, MI355DR_E_UNSUPPORTED, "screen path unavailable (too many irregular rows)");
+    // a pass decided as at k = 1: the int8 screen wherever AUTO has it at all, and (no two-wave prune at that k, screening or
+    // not) the lists at option "cand_cap".  It is no top-k pass: last_pass_k stands
+    const Pass ps = decide_pass(idx, 1, 0, false, "screen path unavailable (too many irregular rows)");
+    if (ps.refused) return fail(idx, MI355DR_E_UNSUPPORTED, ps.refused);
+    const int cap = ps.cap;
+    const bool i8 = ps.i8, use_screen = ps.screening;
     // the spans: chunks of option "range_chunk_rows" rows, whole 256-row tiles (a screen launch starts at a tile edge)
     const int64_t chunk = round_up(std::max<int64_t>(idx->range_chunk_rows, kT2), kT2);
     std::vector<RangeSpan> spans;
@@ -2125,7 +2039,7 @@ int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, c
     const RangeState rs = range_state(idx, R, pairs);
     if (q_dev != idx->qdev)
         HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q_dev, (size_t)nb * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
-    CHECK(launch_prep(idx, s, nb, (int)round_up(nb, screen_tile(nb)), idx->metric));
+    CHECK(launch_prep(idx, s, nb, (int)round_up(nb, screen_tile(nb)), idx->metric, i8));
     HIPCHECK(idx, hipMemcpyAsync(idx->rng.radius.p, radius, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHECK(idx, hipMemsetAsync(idx->rng.redo.p, 0, 2 * sizeof(int), s));
     HIPCHECK(idx, hipMemsetAsync(idx->rng.stat.p, 0, 2 * sizeof(unsigned long long), s));
@@ -2138,9 +2052,8 @@ int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, c
         for (int i = 0; i < n_main; ++i) {
             // k_screen_rq's common flush period: hits are rare under a fixed, tight threshold (a wave whose queue fills
             // faster still flushes on its own)
-            idx->flush_mask_now = idx->screen_flush_sync ? 15 : -1;
-            CHECK(launch_screen(idx, s, nb, spans[i].r0, spans[i].r1, cap, /*emit_mode=*/0));
-            CHECK(launch_range_collect(idx, s, rs, kRangeFormScreen, nb, nullptr, cap, i, spans[i].r0));
+            CHECK(launch_screen(idx, s, i8, nb, spans[i].r0, spans[i].r1, cap, /*emit_mode=*/0, idx->screen_flush_sync ? 15 : -1));
+            CHECK(launch_range_collect(idx, s, ps, rs, kRangeFormScreen, nb, nullptr, i, spans[i].r0));
         }
         // rows this screen cannot see (irregular; for int8 also loose), as a search pass feeds them: "no bound" candidates,
         // here in list-sized pieces with a collect step each, so that they cannot overflow a list
@@ -2150,11 +2063,11 @@ int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, c
             hipLaunchKernelGGL(k_emit_irregular, dim3(nb), dim3(64), 0, s, side + i0, std::min(cap, side_n - i0), idx->st,
                                idx->cand_row, idx->cand_val, cap, 0);
             HIPCHECK(idx, hipGetLastError());
-            CHECK(launch_range_collect(idx, s, rs, kRangeFormSide, nb, nullptr, cap, -1, 0));
+            CHECK(launch_range_collect(idx, s, ps, rs, kRangeFormSide, nb, nullptr, -1, 0));
         }
     } else if (n_main > 0) {
         HIPCHECK(idx, hipMemcpyAsync(idx->qlist_dev, all.data(), (size_t)nb * sizeof(int), hipMemcpyHostToDevice, s));
-        for (int i = 0; i < n_main; ++i) CHECK(range_scan_span(idx, s, rs, nb, cap, i, spans[i].r0, spans[i].r1));
+        for (int i = 0; i < n_main; ++i) CHECK(range_scan_span(idx, s, ps, rs, nb, i, spans[i].r0, spans[i].r1));
     }
     // ---- the recorded (query, span) pairs, on the exact path: a pair that came from the screen form runs its span whole; one
     // whose list overflowed under the exact scan runs it in pieces of `cap` rows, which cannot overflow
@@ -2184,10 +2097,10 @@ int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, c
             if (code & 1) {
                 for (int64_t p = sp.r0; p < sp.r1; p += cap) {
                     spans.push_back(RangeSpan{p, std::min(sp.r1, p + cap)});
-                    CHECK(range_scan_span(idx, s, rs, (int)qs.size(), cap, (int)spans.size() - 1, p, std::min(sp.r1, p + cap)));
+                    CHECK(range_scan_span(idx, s, ps, rs, (int)qs.size(), (int)spans.size() - 1, p, std::min(sp.r1, p + cap)));
                 }
             } else {
-                CHECK(range_scan_span(idx, s, rs, (int)qs.size(), cap, (int)(code >> 1), sp.r0, sp.r1));
+                CHECK(range_scan_span(idx, s, ps, rs, (int)qs.size(), (int)(code >> 1), sp.r0, sp.r1));
             }
         }
         HIPCHECK(idx, hipStreamSynchronize(s));  // (the query lists are pageable and leave with this round)
@@ -2220,7 +2133,9 @@ int range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, c
                            idx->dim, idx->rng.fb_q.p);
         HIPCHECK(idx, hipGetLastError());
         HIPCHECK(idx, hipStreamSynchronize(s));  // `fb` (pageable) was read by the copy
+        const int k_before = idx->last_pass_k;  // (the list of a range search: not the caller's most recent k)
         CHECK(search_block(idx, s, idx->rng.fb_q.p, nf, m, idx->rng.fb_dist.p, idx->rng.fb_rows.p));
+        idx->last_pass_k = k_before;
         hipLaunchKernelGGL(k_scatter_results, dim3(nf), dim3(128), 0, s, (const double*)idx->rng.fb_dist.p,
                            (const int64_t*)idx->rng.fb_rows.p, (const int*)idx->rng.fb_map.p, m, od, orow);
         HIPCHECK(idx, hipGetLastError());
@@ -2312,7 +2227,8 @@ int search_rows_impl(mi355dr_index* idx, const char* what, const int64_t* row_id
             HIPCHECK(idx, hipMemcpyAsync(idx->rowq.radius.p, rad.data(), (size_t)nb * sizeof(double), hipMemcpyHostToDevice, s));
             // every slot's distance to its own row, from the block's prepared queries: the bits a search returns for the pair
             HIPCHECK(idx, hipMemcpyAsync(idx->qdev, idx->rowq.q.p, (size_t)nb * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
-            CHECK(launch_prep(idx, s, nb, (int)round_up(nb, screen_tile(nb)), idx->metric));
+            // (the int8 flag does not matter: the re-score reads st.qn alone, and range_block prepares the block again)
+            CHECK(launch_prep(idx, s, nb, (int)round_up(nb, screen_tile(nb)), idx->metric, idle_i8(idx)));
             CHECK(launch_rescore(idx, s, idx->rowq.pair_q.p, idx->rowq.pair_row.p, nb, idx->rowq.self_dot.p, idx->rowq.self_dist.p));
             // the range pass of the gathered block (it prepares the block again; complete on return, `rad` has been read)
             CHECK(range_block(idx, s, idx->rowq.q.p, nb, rad.data(), stride, idx->rowq.cand_dist.p, idx->rowq.cand_rows.p,
@@ -2535,7 +2451,7 @@ const Stat kStats[] = {
     {"irregular_rows", nullptr, false, [](const Index* x) -> int64_t { return x->irr_n; }},
     {"loose_rows", nullptr, false, [](const Index* x) -> int64_t { return x->irr8_n; }},
     {"dead_rows", nullptr, false, [](const Index* x) -> int64_t { return x->dead_n; }},
-    {"screen_dtype_active", nullptr, false, [](const Index* x) -> int64_t { return use_i8(x) ? MI355DR_SCREEN_I8 : MI355DR_SCREEN_BF16; }},
+    {"screen_dtype_active", nullptr, false, [](const Index* x) -> int64_t { return idle_i8(x) ? MI355DR_SCREEN_I8 : MI355DR_SCREEN_BF16; }},
     {"hbm_bytes_resident", nullptr, false, [](const Index* x) -> int64_t {
          return x->cap_rows * ((int64_t)x->dim * 4 + (int64_t)x->dpad * 2 + (int64_t)x->dpad8 + 5) +
                 x->cap_rows / kI8GroupRows * (int64_t)sizeof(I8Group) + multivec_bytes(x) +
@@ -2661,7 +2577,8 @@ int mi355dr_debug_screen_dense(mi355dr_index* idx, const float* queries, int B, 
                     "debug_screen_dense: need 1<=B<=1024, 1<=n<=2048, row0 a multiple of the tile (128; 256 if B>128)");
     CHECK(upload_and_prep(idx, queries, B, /*metric=*/2));  // test hook: thresholds at -inf for every query
     hipStream_t s = idx->stream;
-    CHECK(launch_screen(idx, s, B, row0, row0 + n, kCandCap, /*emit_mode=*/0));
+    const bool i8 = idle_i8(idx);
+    CHECK(launch_screen(idx, s, i8, B, row0, row0 + n, kCandCap, /*emit_mode=*/0, /*flush_mask=*/-1));
     std::vector<int> cnt(B);
     std::vector<int32_t> crow((size_t)B * kCandCap);
     std::vector<float> cval((size_t)B * kCandCap);
@@ -2669,7 +2586,7 @@ int mi355dr_debug_screen_dense(mi355dr_index* idx, const float* queries, int B, 
     HIPCHECK(idx, hipMemcpyAsync(crow.data(), idx->cand_row, crow.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipMemcpyAsync(cval.data(), idx->cand_val, cval.size() * sizeof(float), hipMemcpyDeviceToHost, s));
     std::vector<uint8_t> flag(n, 0);  // int8 screen: rows outside the shadow carry a stale 0 (k_prune drops them)
-    if (use_i8(idx)) HIPCHECK(idx, hipMemcpyAsync(flag.data(), idx->flag8 + row0, n, hipMemcpyDeviceToHost, s));
+    if (i8) HIPCHECK(idx, hipMemcpyAsync(flag.data(), idx->flag8 + row0, n, hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipStreamSynchronize(s));
     for (int64_t i = 0; i < (int64_t)B * n; ++i) out_t[i] = NAN;
     for (int b = 0; b < B; ++b) {
@@ -2699,15 +2616,15 @@ int mi355dr_debug_screen_hits(mi355dr_index* idx, const float* queries, int B, i
     HIPCHECK(idx, hipMemcpyAsync(idx->st.thr, thr, (size_t)B * sizeof(float), hipMemcpyHostToDevice, s));
     // k_screen_rq's synchronised flushes: run_screen derives the period from k and the rows seen, neither of which exists
     // here -- two tiles, so that a workgroup of a few visits takes both the common flush and (at flush_alone) a wave's own
-    idx->flush_mask_now = idx->screen_flush_sync ? 1 : -1;
-    *out_kernel = (int)screen_kernel_for(idx, B, n, /*emit_all=*/false);
-    CHECK(launch_screen(idx, s, B, row0, row0 + n, cap, /*emit_mode=*/0));
+    const bool i8 = idle_i8(idx);
+    *out_kernel = (int)screen_kernel_for(idx, i8, B, n, /*emit_all=*/false);
+    CHECK(launch_screen(idx, s, i8, B, row0, row0 + n, cap, /*emit_mode=*/0, idx->screen_flush_sync ? 1 : -1));
     HIPCHECK(idx, hipMemcpyAsync(out_count, idx->st.cnt, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipMemcpyAsync(out_status, idx->st.status, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipMemcpyAsync(out_rows, idx->cand_row, (size_t)B * cap * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipMemcpyAsync(out_vals, idx->cand_val, (size_t)B * cap * sizeof(float), hipMemcpyDeviceToHost, s));
     std::vector<uint8_t> flag;  // int8 screen: rows outside the shadow carry a stale 0 (k_prune drops them)
-    if (use_i8(idx)) {
+    if (i8) {
         flag.resize((size_t)n);
         HIPCHECK(idx, hipMemcpyAsync(flag.data(), idx->flag8 + row0, (size_t)n, hipMemcpyDeviceToHost, s));
     }
@@ -2741,7 +2658,7 @@ int mi355dr_debug_i8_state(mi355dr_index* idx, const float* queries, int B, floa
     if (B <= 0 || B > kQBlockMax) return fail(idx, MI355DR_E_INVALID, "need 1<=B<=1024");
     if (g0 < 0 || n_groups < 0 || (g0 + n_groups) * kI8GroupRows > idx->cap_rows)
         return fail(idx, MI355DR_E_INVALID, "group range outside the index");
-    if (!use_i8(idx)) return fail(idx, MI355DR_E_UNSUPPORTED, "the int8 screen is not active");
+    if (!idle_i8(idx)) return fail(idx, MI355DR_E_UNSUPPORTED, "the int8 screen is not active");
     CHECK(upload_and_prep(idx, queries, B, idx->metric));
     hipStream_t s = idx->stream;
     HIPCHECK(idx, hipMemcpyAsync(out_sq, idx->st.sc, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, s));
