@@ -29,7 +29,9 @@ ABI_SYMBOLS = [
     "mi355dr_set_multivec", "mi355dr_set_multivec_device", "mi355dr_live_multivec",
     "mi355dr_gqr_refine_scores", "mi355dr_merge_topk_device", "mi355dr_pack_topk_device",
     "mi355dr_merge_topk_packed_device", "mi355dr_comm_unique_id", "mi355dr_comm_init", "mi355dr_comm_world", "mi355dr_comm_count", "mi355dr_comm_init_custom",
-    "mi355dr_search_sharded_device", "mi355dr_set_option", "mi355dr_get_stat",
+    "mi355dr_search_sharded_device", "mi355dr_search_range_sharded_device", "mi355dr_search_rows_sharded_device",
+    "mi355dr_search_range_rows_sharded_device", "mi355dr_search_mmr_sharded_device", "mi355dr_mmr_select_sharded",
+    "mi355dr_set_option", "mi355dr_get_stat",
     "mi355dr_reset_stats", "mi355dr_timer_start", "mi355dr_timer_stop", "mi355dr_synchronize",
     "mi355dr_dev_alloc", "mi355dr_dev_free", "mi355dr_dev_upload", "mi355dr_dev_download",
     "mi355dr_diag_mfma_stream",
@@ -209,6 +211,16 @@ def load() -> ctypes.CDLL:
     L.mi355dr_comm_count.argtypes = [vp, ctypes.POINTER(c_int)]
     L.mi355dr_search_sharded_device.restype = c_int
     L.mi355dr_search_sharded_device.argtypes = [vp, vp, c_int, c_int, vp, vp, vp]
+    L.mi355dr_search_range_sharded_device.restype = c_int
+    L.mi355dr_search_range_sharded_device.argtypes = [vp, vp, c_int, f64p, c_int, vp, vp, vp, vp]
+    L.mi355dr_search_rows_sharded_device.restype = c_int
+    L.mi355dr_search_rows_sharded_device.argtypes = [vp, i64p, c_int, c_int, c_int, vp, vp, vp]
+    L.mi355dr_search_range_rows_sharded_device.restype = c_int
+    L.mi355dr_search_range_rows_sharded_device.argtypes = [vp, i64p, c_int, f64p, c_int, c_int, vp, vp, vp, vp]
+    L.mi355dr_search_mmr_sharded_device.restype = c_int
+    L.mi355dr_search_mmr_sharded_device.argtypes = [vp, vp, c_int, c_int, c_int, ctypes.c_double, vp, vp, vp]
+    L.mi355dr_mmr_select_sharded.restype = c_int
+    L.mi355dr_mmr_select_sharded.argtypes = [vp, f32p, c_int, c_int, i64p, c_int, ctypes.c_double, f64p, i64p]
     L.mi355dr_set_option.restype = c_int
     L.mi355dr_set_option.argtypes = [vp, ctypes.c_char_p, i64]
     L.mi355dr_get_stat.restype = c_int

@@ -187,6 +187,15 @@ struct RowQueryBufs {
         return e;
     }
 };
+// row-sharded derived searches (mi355dr_search_*_sharded_device / mi355dr_mmr_select_sharded): this
+// rank's payload of an all-gather and the gathered payloads of all ranks (packed lists, query rows, host candidate lists: one
+// collective at a time, in stream order), the MMR candidate stage and its gathered form, the counter k_rows_gather's own
+// "outside this shard" count goes to (not a stat: rows_skipped counts slots NO rank owned)
+struct ShardBufs {
+    DevBuf<int64_t> send, recv;
+    DevBuf<float> stage, stage_all;
+    DevBuf<unsigned long long> local_skipped;
+};
 }  // namespace mi355
 
 struct mi355dr_index {
@@ -249,6 +258,7 @@ struct mi355dr_index {
     mi355::GroupBufs grp;
     mi355::RangeBufs rng;
     mi355::RowQueryBufs rowq;
+    mi355::ShardBufs shd;
     // a view (mi355dr_view_create; DESIGN.md "Views"): a read-only index built from listed rows / documents of a parent.  The
     // maps are null on every other index: the result-writing kernels then add row_offset instead
     bool is_view = false;
@@ -335,6 +345,9 @@ struct mi355dr_index {
     // what the finishing sort holds; never below the call's max_results)
     int64_t range_chunk_rows = (int64_t)1 << 21;
     int range_slots = mi355::kSortMax;
+    // mi355dr_search_mmr_sharded_device / mi355dr_mmr_select_sharded: most bytes of the GATHERED candidate-vector stage (option
+    // "shard_stage_bytes"; a block of queries is selected in sub-blocks sized to it, never below one query)
+    int64_t shard_stage_bytes = (int64_t)256 << 20;
     int64_t starter_rows_wide = 65536;  // the starter's sample at 33 <= k <= 128 (option "starter_rows_wide", tuning: 4096 ... 262144)
 
     // stats
@@ -375,6 +388,8 @@ struct mi355dr_index {
             s_range_redo_chunks = 0, s_range_fallback_queries = 0;
     // mi355dr_search_rows* / mi355dr_search_range_rows*: calls, slots, slots whose id was outside the shard or a removed row
     int64_t s_rows_searches = 0, s_rows_queries = 0, s_rows_skipped = 0;
+    // the row-sharded derived searches: calls per family, bytes this rank received through their all-gathers
+    int64_t s_shard_range_searches = 0, s_shard_rows_searches = 0, s_shard_mmr_searches = 0, s_shard_gather_bytes = 0;
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
     mi355::EventPairs ev_pool, ev_pending;
@@ -412,6 +427,9 @@ void multivec_destroy(mi355dr_index* idx);                       // mi355dr_maxs
 int multivec_reserve(mi355dr_index* idx, int64_t n_blocks, int64_t n_docs);  // mi355dr_maxsim.hip
 int64_t multivec_bytes(const mi355dr_index* idx);                // mi355dr_maxsim.hip: stat "hbm_bytes_resident"
 void comm_destroy(mi355dr_index* idx);                           // mi355dr_comm.hip
+// one all-gather over the index's communicator (RCCL, or the host's transport): bytes_per_rank (a multiple of 8) from every
+// rank's send_dev into recv_dev, rank-major; ordered on `stream` (a host transport may instead be complete on return)
+int comm_all_gather(mi355dr_index* idx, const void* send_dev, void* recv_dev, size_t bytes_per_rank, hipStream_t stream);  // mi355dr_comm.hip
 // read-only view of the multi-vector store for kernels outside mi355dr_maxsim.hip (GQR refinement)
 struct MultiVecView {
     const float* tok;             // [blocks*32, dpad] device

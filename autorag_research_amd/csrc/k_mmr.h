@@ -29,15 +29,32 @@ __host__ __device__ inline size_t mmr_lds_bytes(int d, int stride) {
 // "higher is better" image of a distance, in double: 1 - distance for cosine, -distance for inner product
 __device__ __forceinline__ double mmr_sim(int metric, double dist) { return metric == 0 ? 1.0 - dist : -dist; }
 
-// grid: one workgroup per query.  cand_rows / cand_dist: [B, stride], GLOBAL rows (row_offset is subtracted here; -1 = none).
-// out_dist / out_rows: [B, k].  pairs_scored: one counter, += the (picked, candidate) dots of this query.
-__global__ __launch_bounds__(kMmrThreads) void k_mmr_select(const int64_t* __restrict__ cand_rows,
-                                                            const double* __restrict__ cand_dist, int stride,
-                                                            const float* __restrict__ rows, const float* __restrict__ nrm2,
-                                                            int64_t n_rows, int64_t row_offset, int d, int metric, int k,
-                                                            double lambda, double* __restrict__ out_dist,
-                                                            int64_t* __restrict__ out_rows,
-                                                            unsigned long long* __restrict__ pairs_scored) {
+// Where the selection reads a candidate's fp32 vector and stored norm from.  locate(): is candidate i (global row r) a row the
+// source holds, and under which locator (kept in LDS, one int32 per candidate); vec() / nrm(): its vector and |row|^2.
+// This one: the index's own rows -- the locator is the local row.  k_shard.h has the other: the gathered stage of a row-sharded
+// index.  Both run mmr_select_body, so argmax, tie rule, staged_dot and distance_from cannot drift apart.
+struct MmrLocalRows {
+    const float* rows;
+    const float* nrm2;
+    int64_t n_rows, row_offset;
+    int d;
+    __device__ __forceinline__ bool locate(int, int64_t r, int32_t* loc) const {
+        if (r >= row_offset && r - row_offset < n_rows) {
+            *loc = (int32_t)(r - row_offset);
+            return true;
+        }
+        return false;
+    }
+    __device__ __forceinline__ const float* vec(int, int32_t loc) const { return rows + (int64_t)loc * d; }
+    __device__ __forceinline__ float nrm(int, int32_t loc) const { return nrm2[loc]; }
+};
+
+// one workgroup of kMmrThreads per query.  crow / cdist: this query's [stride] list, GLOBAL rows (-1 = none); od / orow: its
+// [k] picks.  pairs_scored: one counter, += the (picked, candidate) dots of this query.
+template <class Src>
+__device__ __forceinline__ void mmr_select_body(const Src& src, const int64_t* __restrict__ crow, const double* __restrict__ cdist,
+                                                int stride, int d, int metric, int k, double lambda, double* __restrict__ od,
+                                                int64_t* __restrict__ orow, unsigned long long* __restrict__ pairs_scored) {
     extern __shared__ __align__(16) unsigned char mmr_smem[];
     const int cap = mmr_cap(stride), dq = mmr_dq(d);
     float* tiles = (float*)mmr_smem;
@@ -52,20 +69,16 @@ __global__ __launch_bounds__(kMmrThreads) void k_mmr_select(const int64_t* __res
     unsigned char* sel = (unsigned char*)(n_elig + 4);
 
     const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6;
-    const int64_t qb = (int64_t)blockIdx.x;
-    const int64_t* crow = cand_rows + qb * stride;
-    const double* cdist = cand_dist + qb * stride;
-    double* od = out_dist + qb * k;
-    int64_t* orow = out_rows + qb * k;
 
-    // ---- the eligible prefix: a row of this index and a distance that is a number
+    // ---- the eligible prefix: a row the source holds and a distance that is a number
     if (tid == 0) n_elig[0] = stride;
     __syncthreads();
     for (int i = tid; i < stride; i += kMmrThreads) {
         const int64_t r = crow[i];
         const double dist = cdist[i];
-        if (r >= row_offset && r - row_offset < n_rows && dist == dist) {
-            lrow[i] = (int32_t)(r - row_offset);
+        int32_t loc = 0;
+        if (src.locate(i, r, &loc) && dist == dist) {
+            lrow[i] = loc;
             sq[i] = mmr_sim(metric, dist);
             sel[i] = 0;
         } else {
@@ -135,19 +148,19 @@ __global__ __launch_bounds__(kMmrThreads) void k_mmr_select(const int64_t* __res
         if (t == picks - 1) break;  // no update after the last pick
         // ---- the picked row becomes the LDS-resident vector
         const int32_t pr = lrow[cur];
-        const float* prow = rows + (int64_t)pr * d;
+        const float* prow = src.vec(cur, pr);
         for (int c = tid; c < dq; c += kMmrThreads) qv[c] = c < d ? prow[c] : 0.0f;
-        const float np = nrm2[pr];
+        const float np = src.nrm(cur, pr);
         __syncthreads();
         // ---- wave w scores candidates 64 (w + 4 round) + lane against it
         for (int r = 0; r < rounds; ++r) {
             const int i = kWave * (w + kMmrWaves * r) + lane;
             const bool live = i < n && !sel[i];
-            const float* rp = live ? rows + (int64_t)lrow[i] * d : nullptr;
+            const float* rp = live ? src.vec(i, lrow[i]) : nullptr;
             if (__builtin_amdgcn_ballot_w64(live) == 0) continue;  // (wave-uniform; staged_dot synchronises the wave only)
             const float dot = staged_dot(tiles + w * kStageFloats, rp, qv, d, lane);
             if (live) {
-                const double s = mmr_sim(metric, distance_from(metric, dot, np, nrm2[lrow[i]]));
+                const double s = mmr_sim(metric, distance_from(metric, dot, np, src.nrm(i, lrow[i])));
                 if (t == 0) ms[i] = s;
                 else if (s > ms[i]) ms[i] = s;  // (a NaN s is ignored)
             }
@@ -158,6 +171,21 @@ __global__ __launch_bounds__(kMmrThreads) void k_mmr_select(const int64_t* __res
         const unsigned long long p1 = (unsigned long long)(picks - 1);
         atomicAdd(pairs_scored, p1 * (unsigned long long)n - p1 * (unsigned long long)picks / 2);
     }
+}
+
+// grid: one workgroup per query.  cand_rows / cand_dist: [B, stride], GLOBAL rows (row_offset is subtracted here; -1 = none).
+// out_dist / out_rows: [B, k].
+__global__ __launch_bounds__(kMmrThreads) void k_mmr_select(const int64_t* __restrict__ cand_rows,
+                                                            const double* __restrict__ cand_dist, int stride,
+                                                            const float* __restrict__ rows, const float* __restrict__ nrm2,
+                                                            int64_t n_rows, int64_t row_offset, int d, int metric, int k,
+                                                            double lambda, double* __restrict__ out_dist,
+                                                            int64_t* __restrict__ out_rows,
+                                                            unsigned long long* __restrict__ pairs_scored) {
+    const int64_t qb = (int64_t)blockIdx.x;
+    const MmrLocalRows src{rows, nrm2, n_rows, row_offset, d};
+    mmr_select_body(src, cand_rows + qb * stride, cand_dist + qb * stride, stride, d, metric, k, lambda, out_dist + qb * k,
+                    out_rows + qb * k, pairs_scored);
 }
 
 }  // namespace mi355

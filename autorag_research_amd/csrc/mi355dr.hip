@@ -26,6 +26,7 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "k_groups.h"
 #include "k_range.h"
 #include "k_rows.h"
+#include "k_shard.h"
 
 using namespace mi355;
 
@@ -174,6 +175,8 @@ int ensure_qstate(mi355dr_index* idx) {
     if (mmr_lds_bytes(idx->dim, kMmrMax) > 160 * 1024)
         return fail(idx, MI355DR_E_UNSUPPORTED, "dim too large for the select kernels' LDS budget");
     HIPCHECK(idx, hipFuncSetAttribute((const void*)k_mmr_select, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)mmr_lds_bytes(idx->dim, kMmrMax)));
+    HIPCHECK(idx, hipFuncSetAttribute((const void*)k_shard_mmr_select, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)mmr_lds_bytes(idx->dim, kMmrMax)));
     HIPCHECK(idx, hipFuncSetAttribute((const void*)k_merge_groups, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)groups_lds_bytes(kSortMax)));
@@ -2275,6 +2278,366 @@ int mi355dr_search_range_rows_device(mi355dr_index* idx, const int64_t* row_ids,
                             out_count_dev, stream, /*host=*/false);
 }
 
+// ---- the derived searches over a row-sharded index (csrc/k_shard.h) ---------------------------------
+// One frame (begin_call) per call, so nothing below may call a public entry point: the inner "sharded block at width w" is
+// search_block straight into the packed planes, comm_all_gather, launch_merge with the rank stride.  Every rank enters every
+// collective of a call in the same order, an empty shard included (it contributes empty lists, zero counts, invalid slots).
+namespace {
+int check_comm(mi355dr_index* idx) {
+    if (!idx->comm && !idx->comm_custom) return fail(idx, MI355DR_E_INVALID, "mi355dr_comm_init has not been called on this index");
+    return MI355DR_OK;
+}
+// the merge sorts world x width entries per query
+int check_shard_width(mi355dr_index* idx, const std::string& what, int width) {
+    if ((int64_t)idx->comm_world * width > kSortMax)
+        return fail(idx, MI355DR_E_UNSUPPORTED, what + ": world*width exceeds 4096 (width " + std::to_string(width) + ")");
+    return MI355DR_OK;
+}
+
+// one all-gather of a call: the payload final and visible first (a host transport reads it with copies of its own, ordered
+// against the non-blocking stream by nothing), a transport error returned after the stream is drained
+int shard_gather(mi355dr_index* idx, hipStream_t s, const void* send, void* recv, size_t bytes_per_rank) {
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    const int rc = comm_all_gather(idx, send, recv, bytes_per_rank, s);
+    if (rc != MI355DR_OK) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    idx->s_shard_gather_bytes += (int64_t)idx->comm_world * (int64_t)bytes_per_rank;
+    return MI355DR_OK;
+}
+
+int shard_fill_lists(mi355dr_index* idx, hipStream_t s, double* dist, int64_t* rows, int64_t n_entries, int64_t* count, int nb) {
+    const int64_t n = std::max<int64_t>(n_entries, nb);
+    hipLaunchKernelGGL(k_shard_fill_lists, dim3((unsigned)((n + kShardThreads - 1) / kShardThreads)), dim3(kShardThreads), 0, s,
+                       dist, rows, n_entries, count, nb);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+// the send / receive buffers for a payload of `words` int64 per rank (before the block's first collective)
+int shard_reserve_words(mi355dr_index* idx, size_t words) {
+    HIPCHECK(idx, idx->shd.send.grow(words * sizeof(int64_t)));
+    HIPCHECK(idx, idx->shd.recv.grow(words * sizeof(int64_t) * (size_t)idx->comm_world));
+    return MI355DR_OK;
+}
+
+// the sharded search of one block of nb device queries at width w: this shard's list into the packed [2, nb, w] block (plane 0
+// the float8 distances, plane 1 global rows), one all-gather, the world*w -> w merge into od / orow [nb, w]
+int shard_topk_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, int w, double* od, int64_t* orow) {
+    const size_t plane = (size_t)nb * w, words = 2 * plane;
+    CHECK(shard_reserve_words(idx, words));
+    double* ld = (double*)idx->shd.send.p;
+    int64_t* lr = idx->shd.send.p + plane;
+    if (idx->n > 0) CHECK(search_block(idx, s, q_dev, nb, w, ld, lr));
+    else CHECK(shard_fill_lists(idx, s, ld, lr, (int64_t)plane, nullptr, 0));
+    CHECK(shard_gather(idx, s, idx->shd.send.p, idx->shd.recv.p, words * sizeof(int64_t)));
+    return launch_merge(idx, (const double*)idx->shd.recv.p, idx->shd.recv.p + plane, (int64_t)words, idx->comm_world, nb, w, od,
+                        orow, s);
+}
+
+// the sharded range pass of one block: this shard's first m in-range rows and its count into [2, nb, m] + [nb], one
+// all-gather (rank stride 2 nb m + nb), the merge of the lists and the sum of the counts
+int shard_range_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int nb, const double* radius, int m, double* od,
+                      int64_t* orow, int64_t* ocount) {
+    const size_t plane = (size_t)nb * m, words = 2 * plane + nb;
+    CHECK(shard_reserve_words(idx, words));
+    double* ld = (double*)idx->shd.send.p;
+    int64_t* lr = idx->shd.send.p + plane;
+    int64_t* lc = idx->shd.send.p + 2 * plane;
+    if (idx->n > 0) CHECK(range_block(idx, s, q_dev, nb, radius, m, ld, lr, lc));  // (complete on return)
+    else CHECK(shard_fill_lists(idx, s, ld, lr, (int64_t)plane, lc, nb));
+    CHECK(shard_gather(idx, s, idx->shd.send.p, idx->shd.recv.p, words * sizeof(int64_t)));
+    CHECK(launch_merge(idx, (const double*)idx->shd.recv.p, idx->shd.recv.p + plane, (int64_t)words, idx->comm_world, nb, m, od,
+                       orow, s));
+    hipLaunchKernelGGL(k_shard_count_fold, dim3((nb + kShardThreads - 1) / kShardThreads), dim3(kShardThreads), 0, s,
+                       (const int64_t*)idx->shd.recv.p, (int64_t)words, (int64_t)(2 * plane), idx->comm_world, nb, ocount);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+// queries per sub-block of the MMR selection: the gathered stage of the sub-block stays within option "shard_stage_bytes"
+int shard_mmr_sub(const mi355dr_index* idx, int nb, int stride) {
+    const int64_t per_q = (int64_t)idx->comm_world * stride * (idx->dim + 2) * (int64_t)sizeof(float);
+    int64_t qs = std::max<int64_t>(1, std::min<int64_t>(nb, idx->shard_stage_bytes / per_q));
+    while (qs > 1 && (int64_t)idx->comm_world * shard_stage_floats(qs * stride, idx->dim) * (int64_t)sizeof(float) > idx->shard_stage_bytes) --qs;
+    return (int)qs;
+}
+
+// the selection over nb merged lists [nb, stride] in idx->mmr.cand_*: per sub-block the owners stage their candidates'
+// vectors and norms, one all-gather, k_shard_mmr_select; asynchronous on the stream behind its last collective
+int shard_mmr_block(mi355dr_index* idx, hipStream_t s, int nb, int stride, int k, double lambda, double* out_dist_dev,
+                    int64_t* out_rows_dev) {
+    const int world = idx->comm_world, qs = shard_mmr_sub(idx, nb, stride);
+    const size_t cap_floats = (size_t)shard_stage_floats((int64_t)qs * stride, idx->dim);
+    HIPCHECK(idx, idx->shd.stage.grow(cap_floats * sizeof(float)));
+    HIPCHECK(idx, idx->shd.stage_all.grow(cap_floats * sizeof(float) * (size_t)world));
+    for (int q0 = 0; q0 < nb; q0 += qs) {
+        const int nq = std::min(qs, nb - q0);
+        const int64_t cnt = (int64_t)nq * stride, rank_floats = shard_stage_floats(cnt, idx->dim);
+        const int64_t* crow = idx->mmr.cand_rows.p + (int64_t)q0 * stride;
+        hipLaunchKernelGGL(k_shard_mmr_stage, dim3((unsigned)cnt), dim3(kWave), 0, s, crow, cnt, (const float*)idx->rows.p,
+                           (const float*)idx->nrm2.p, idx->n, idx->row_offset, idx->dim, idx->shd.stage.p);
+        HIPCHECK(idx, hipGetLastError());
+        CHECK(shard_gather(idx, s, idx->shd.stage.p, idx->shd.stage_all.p, (size_t)rank_floats * sizeof(float)));
+        hipLaunchKernelGGL(k_shard_mmr_select, dim3(nq), dim3(kMmrThreads), mmr_lds_bytes(idx->dim, stride), s, crow,
+                           (const double*)idx->mmr.cand_dist.p + (int64_t)q0 * stride, stride, (const float*)idx->shd.stage_all.p,
+                           rank_floats, world, cnt, idx->dim, idx->metric, k, lambda, out_dist_dev + (int64_t)q0 * k,
+                           out_rows_dev + (int64_t)q0 * k, idx->mmr.pairs_dev.p);
+        HIPCHECK(idx, hipGetLastError());
+    }
+    return MI355DR_OK;
+}
+
+// the call's last step of both MMR forms (the stream is idle): the selection's pair counter and the queries into the stats
+int shard_mmr_finish(mi355dr_index* idx, int B) {
+    unsigned long long pairs = 0;
+    HIPCHECK(idx, hipMemcpy(&pairs, idx->mmr.pairs_dev.p, sizeof(pairs), hipMemcpyDeviceToHost));
+    idx->s_shard_mmr_searches++;
+    idx->s_mmr_queries += B;
+    idx->s_mmr_pairs += (int64_t)pairs;
+    return MI355DR_OK;
+}
+
+// both by-row families over the shards (radius == nullptr: the top-k form), device outputs
+int search_rows_sharded_impl(mi355dr_index* idx, const char* what, const int64_t* row_ids, int B, const double* radius, bool range,
+                             int kout, int flags, double* out_dist, int64_t* out_rows, int64_t* out_count, void* stream) {
+    const bool include_self = (flags & MI355DR_ROWS_INCLUDE_SELF) != 0;
+    const int stride = kout + (include_self ? 0 : 1);  // the inner pass's list: room for the row itself
+    Call c;
+    CHECK(begin_call(idx, what, stream, kCallNoView | kCallDrain, c, [&]() -> int {
+        const std::string w(what);
+        CHECK(check_comm(idx));
+        if (B < 0) return fail(idx, MI355DR_E_INVALID, w + ": B must be >= 0");
+        if (kout < 1) return fail(idx, MI355DR_E_INVALID, w + (range ? ": max_results must be >= 1" : ": k must be > 0"));
+        if (flags & ~MI355DR_ROWS_INCLUDE_SELF) return fail(idx, MI355DR_E_INVALID, w + ": unknown flag bits");
+        if (B > 0 && (!row_ids || !out_dist || !out_rows || (range && (!radius || !out_count))))
+            return fail(idx, MI355DR_E_INVALID, w + ": null buffer");
+        if (range) CHECK(check_radii(idx, w, radius, B));
+        if (stride > kKMax)
+            return fail(idx, MI355DR_E_UNSUPPORTED, w + (range ? ": max_results" : ": k") + (include_self ? "" : " + 1 (the row itself)") + " exceeds 1024");
+        return check_shard_width(idx, w, stride);
+    }));
+    if (B == 0) return MI355DR_OK;
+    hipStream_t s = c.s;
+    const int d = idx->dim, world = idx->comm_world;
+    HIPCHECK(idx, idx->rowq.reserve(std::min(B, kQBlockMax), stride, d, /*range=*/true));
+    HIPCHECK(idx, grow_each(1, idx->shd.local_skipped));
+    HIPCHECK(idx, hipMemsetAsync(idx->rowq.skipped_dev.p, 0, sizeof(unsigned long long), s));
+    std::vector<double> rad;
+    std::vector<int> valid;
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        // this rank's payload: the owned vectors (zeros elsewhere), valid, the row-with-itself distances (range form; else zeros)
+        const int64_t qw = shard_rows_qwords(nb, d), vw = shard_rows_vwords(nb), words = shard_rows_words(nb, d);
+        const size_t lists = (size_t)2 * nb * stride + (range ? nb : 0);
+        CHECK(shard_reserve_words(idx, std::max((size_t)words, lists)));  // (the inner pass's payload too: nothing grows between the collectives)
+        float* pay_q = (float*)idx->shd.send.p;
+        int* pay_valid = (int*)(idx->shd.send.p + qw);
+        double* pay_self = (double*)(idx->shd.send.p + qw + vw);
+        HIPCHECK(idx, hipMemsetAsync(idx->shd.send.p, 0, (size_t)words * sizeof(int64_t), s));  // (the pads and an unused self_dist travel as zeros)
+        HIPCHECK(idx, hipMemcpyAsync(idx->rowq.ids.p, row_ids + b0, (size_t)nb * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_rows_gather, dim3(nb), dim3(kRowsThreads), 0, s, (const int64_t*)idx->rowq.ids.p, idx->row_offset,
+                           idx->n, (const float*)idx->rows.p, (const float*)idx->nrm2.p, d, pay_q, pay_valid, idx->rowq.pair_q.p,
+                           idx->rowq.pair_row.p, idx->shd.local_skipped.p);
+        HIPCHECK(idx, hipGetLastError());
+        if (range && idx->n > 0) {
+            // every slot's distance to its own row, on its owner: the bits a search returns for the pair (the others score row 0
+            // against zeros, and the fold never reads that)
+            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, pay_q, (size_t)nb * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+            CHECK(launch_prep(idx, s, nb, (int)round_up(nb, screen_tile(nb)), idx->metric, idle_i8(idx)));
+            CHECK(launch_rescore(idx, s, idx->rowq.pair_q.p, idx->rowq.pair_row.p, nb, idx->rowq.self_dot.p, pay_self));
+        }
+        CHECK(shard_gather(idx, s, idx->shd.send.p, idx->shd.recv.p, (size_t)words * sizeof(int64_t)));
+        hipLaunchKernelGGL(k_shard_rows_fold, dim3(nb), dim3(kShardThreads), 0, s, (const int64_t*)idx->shd.recv.p, words, world, nb,
+                           d, idx->rowq.q.p, idx->rowq.valid.p, idx->rowq.self_dist.p, idx->rowq.skipped_dev.p);
+        HIPCHECK(idx, hipGetLastError());
+        if (!range) {
+            CHECK(shard_topk_block(idx, s, idx->rowq.q.p, nb, stride, idx->rowq.cand_dist.p, idx->rowq.cand_rows.p));
+        } else {
+            // a slot nobody owns asks for nothing (its output is blanked below): no row is within -inf
+            valid.resize(nb);
+            HIPCHECK(idx, hipMemcpyAsync(valid.data(), idx->rowq.valid.p, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHECK(idx, hipStreamSynchronize(s));
+            rad.assign(radius + b0, radius + b0 + nb);
+            for (int b = 0; b < nb; ++b)
+                if (!valid[b]) rad[b] = -INFINITY;
+            HIPCHECK(idx, hipMemcpyAsync(idx->rowq.radius.p, rad.data(), (size_t)nb * sizeof(double), hipMemcpyHostToDevice, s));
+            CHECK(shard_range_block(idx, s, idx->rowq.q.p, nb, rad.data(), stride, idx->rowq.cand_dist.p, idx->rowq.cand_rows.p,
+                                    idx->rowq.cand_count.p));
+        }
+        hipLaunchKernelGGL(k_rows_drop, dim3(nb), dim3(kRowsThreads), 0, s, (const double*)idx->rowq.cand_dist.p,
+                           (const int64_t*)idx->rowq.cand_rows.p, stride, (const int64_t*)idx->rowq.ids.p,
+                           (const int*)idx->rowq.valid.p, kout, include_self ? 1 : 0,
+                           range ? (const int64_t*)idx->rowq.cand_count.p : nullptr, (const double*)idx->rowq.self_dist.p,
+                           (const double*)idx->rowq.radius.p, out_dist + (int64_t)b0 * kout, out_rows + (int64_t)b0 * kout,
+                           range ? out_count + b0 : nullptr);
+        HIPCHECK(idx, hipGetLastError());
+        HIPCHECK(idx, hipStreamSynchronize(s));  // (the next block reuses the id, query, list and payload buffers)
+    }
+    unsigned long long skipped = 0;
+    HIPCHECK(idx, hipMemcpy(&skipped, idx->rowq.skipped_dev.p, sizeof(skipped), hipMemcpyDeviceToHost));
+    idx->s_shard_rows_searches++;
+    idx->s_rows_queries += B;
+    idx->s_rows_skipped += (int64_t)skipped;
+    return MI355DR_OK;
+}
+}  // namespace
+
+int mi355dr_search_range_sharded_device(mi355dr_index* idx, const float* queries_dev, int B, const double* radius, int max_results,
+                                        double* out_dist_dev, int64_t* out_rows_dev, int64_t* out_count_dev, void* stream) {
+    const int m = max_results;
+    Call c;
+    CHECK(begin_call(idx, "search_range_sharded_device", stream, kCallNoView | kCallDrain, c, [&]() -> int {
+        CHECK(check_comm(idx));
+        if (B <= 0 || m < 1) return fail(idx, MI355DR_E_INVALID, "search_range_sharded_device: B and max_results must be >= 1");
+        if (m > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, "search_range_sharded_device: max_results exceeds 1024");
+        if (!queries_dev || !radius || !out_dist_dev || !out_rows_dev || !out_count_dev)
+            return fail(idx, MI355DR_E_INVALID, "search_range_sharded_device: null buffer");
+        CHECK(check_radii(idx, "search_range_sharded_device", radius, B));
+        return check_shard_width(idx, "search_range_sharded_device", m);
+    }));
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        CHECK(shard_range_block(idx, c.s, queries_dev + (int64_t)b0 * idx->dim, nb, radius + b0, m, out_dist_dev + (int64_t)b0 * m,
+                                out_rows_dev + (int64_t)b0 * m, out_count_dev + b0));
+        HIPCHECK(idx, hipStreamSynchronize(c.s));  // (the next block reuses the payload buffers)
+    }
+    idx->s_shard_range_searches++;
+    idx->s_range_queries += B;
+    return MI355DR_OK;
+}
+
+int mi355dr_search_rows_sharded_device(mi355dr_index* idx, const int64_t* row_ids, int B, int k, int flags, double* out_dist_dev,
+                                       int64_t* out_rows_dev, void* stream) {
+    return search_rows_sharded_impl(idx, "search_rows_sharded_device", row_ids, B, nullptr, false, k, flags, out_dist_dev,
+                                    out_rows_dev, nullptr, stream);
+}
+
+int mi355dr_search_range_rows_sharded_device(mi355dr_index* idx, const int64_t* row_ids, int B, const double* radius,
+                                             int max_results, int flags, double* out_dist_dev, int64_t* out_rows_dev,
+                                             int64_t* out_count_dev, void* stream) {
+    return search_rows_sharded_impl(idx, "search_range_rows_sharded_device", row_ids, B, radius, true, max_results, flags,
+                                    out_dist_dev, out_rows_dev, out_count_dev, stream);
+}
+
+int mi355dr_search_mmr_sharded_device(mi355dr_index* idx, const float* queries_dev, int B, int k, int fetch_k, double lambda,
+                                      double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
+    Call c;
+    CHECK(begin_call(idx, "search_mmr_sharded_device", stream, kCallNoView | kCallDrain, c, [&]() -> int {
+        CHECK(check_comm(idx));
+        CHECK(check_search_args(idx, queries_dev, B, k, out_dist_dev, out_rows_dev));
+        CHECK(check_mmr_lambda(idx, "search_mmr_sharded_device", lambda));
+        if (fetch_k < k) return fail(idx, MI355DR_E_INVALID, "search_mmr_sharded_device: fetch_k must be >= k");
+        if (fetch_k > kMmrMax) return fail(idx, MI355DR_E_UNSUPPORTED, "search_mmr_sharded_device: fetch_k exceeds 1024");
+        return check_shard_width(idx, "search_mmr_sharded_device", fetch_k);
+    }));
+    if (B == 0) return MI355DR_OK;
+    HIPCHECK(idx, idx->mmr.reserve(std::min(B, kQBlockMax), fetch_k));
+    HIPCHECK(idx, hipMemsetAsync(idx->mmr.pairs_dev.p, 0, sizeof(unsigned long long), c.s));
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        // the sharded search of the block at fetch_k, then the selection over the owners' staged vectors
+        CHECK(shard_topk_block(idx, c.s, queries_dev + (int64_t)b0 * idx->dim, nb, fetch_k, idx->mmr.cand_dist.p, idx->mmr.cand_rows.p));
+        CHECK(shard_mmr_block(idx, c.s, nb, fetch_k, k, lambda, out_dist_dev + (int64_t)b0 * k, out_rows_dev + (int64_t)b0 * k));
+        HIPCHECK(idx, hipStreamSynchronize(c.s));  // (the next block reuses the lists and the stage)
+    }
+    return shard_mmr_finish(idx, B);
+}
+
+int mi355dr_mmr_select_sharded(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* cand_rows, int m, double lambda,
+                               double* out_dist, int64_t* out_rows) {
+    Call c;
+    CHECK(begin_call(idx, "mmr_select_sharded", nullptr, kCallNoView | kCallDrain, c, [&]() -> int {
+        CHECK(check_comm(idx));
+        CHECK(check_search_args(idx, queries, B, k, out_dist, out_rows));
+        CHECK(check_mmr_lambda(idx, "mmr_select_sharded", lambda));
+        if (m < 0 || (B > 0 && m > 0 && !cand_rows)) return fail(idx, MI355DR_E_INVALID, "mmr_select_sharded: m must be >= 0 and cand_rows not null");
+        if (m > kMmrMax) return fail(idx, MI355DR_E_UNSUPPORTED, "mmr_select_sharded: m exceeds 1024");
+        return MI355DR_OK;
+    }));
+    if (B == 0) return MI355DR_OK;
+    for (int64_t i = 0; i < (int64_t)B * k; ++i) {
+        out_dist[i] = NAN;
+        out_rows[i] = -1;
+    }
+    hipStream_t s = c.s;
+    const int world = idx->comm_world;
+    HIPCHECK(idx, idx->mmr.reserve(std::min(B, kQBlockMax), std::max(m, 1)));
+    HIPCHECK(idx, hipMemsetAsync(idx->mmr.pairs_dev.p, 0, sizeof(unsigned long long), s));
+    const CallIO<> io{/*host=*/true, s, nullptr, {out_dist, out_rows, nullptr}, k};
+    std::vector<int32_t> pq;
+    std::vector<int64_t> pr, first, ordered_rows, mine, all;  // first[b]: query b's first owned pair
+    std::vector<double> got, ordered_dist;
+    std::vector<MmrCand> list;
+    PairBufs bufs;
+    for (int b0 = 0; b0 < B && m > 0; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        const size_t plane = (size_t)nb * m;
+        try {  // every query's list: the rows THIS shard holds, each once
+            pr.clear();
+            first.assign(1, 0);
+            for (int b = 0; b < nb; ++b) {
+                mmr_unique_rows(cand_rows + (int64_t)(b0 + b) * m, m, idx->row_offset, idx->n, pr);
+                first.push_back((int64_t)pr.size());
+            }
+            pq.resize(pr.size());
+            for (int b = 0; b < nb; ++b) std::fill(pq.begin() + first[b], pq.begin() + first[b + 1], b);
+            got.resize(pr.size());
+            mine.assign(2 * plane, -1);  // [2, nb, m]: global rows (-1: not mine / padding -- the flag), distance bits
+            all.resize(2 * plane * world);
+            ordered_dist.assign(plane, (double)NAN);
+            ordered_rows.assign(plane, -1);
+        } catch (const std::bad_alloc&) {
+            return fail(idx, MI355DR_E_NOMEM, "mmr_select_sharded: out of host memory for the candidate lists");
+        }
+        CHECK(shard_reserve_words(idx, 2 * plane));
+        const int64_t n_pairs = (int64_t)pr.size();
+        if (n_pairs > 0)
+            CHECK(rescore_host_pairs(idx, bufs, queries + (int64_t)b0 * idx->dim, nb, pq.data(), pr.data(), n_pairs, nullptr, got.data()));
+        for (int b = 0; b < nb; ++b)
+            for (int64_t i = first[b]; i < first[b + 1]; ++i) {
+                const size_t at = (size_t)b * m + (size_t)(i - first[b]);
+                mine[at] = pr[i] + idx->row_offset;
+                memcpy(&mine[plane + at], &got[i], sizeof(double));  // (a removed row, an undefined distance: the kernel's NaN, and still mine)
+            }
+        HIPCHECK(idx, hipMemcpyAsync(idx->shd.send.p, mine.data(), 2 * plane * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        CHECK(shard_gather(idx, s, idx->shd.send.p, idx->shd.recv.p, 2 * plane * sizeof(int64_t)));
+        HIPCHECK(idx, hipMemcpyAsync(all.data(), idx->shd.recv.p, 2 * plane * world * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipStreamSynchronize(s));
+        // every rank builds the same ordered lists: the union of the ranks' entries (shards are disjoint) in the total order
+        try {
+            for (int b = 0; b < nb; ++b) {
+                list.clear();
+                for (int r = 0; r < world; ++r) {
+                    const int64_t* rr = all.data() + (size_t)r * 2 * plane + (size_t)b * m;
+                    for (int j = 0; j < m && (int)list.size() < m; ++j) {
+                        if (rr[j] < 0) continue;
+                        double dist;
+                        memcpy(&dist, rr + plane + j, sizeof(double));
+                        list.push_back(MmrCand{dist, rr[j]});  // (global rows: the same order)
+                    }
+                }
+                mmr_order(list.data(), (int64_t)list.size());
+                for (size_t j = 0; j < list.size(); ++j) {
+                    ordered_dist[(size_t)b * m + j] = list[j].dist;
+                    ordered_rows[(size_t)b * m + j] = list[j].row;
+                }
+            }
+        } catch (const std::bad_alloc&) {
+            return fail(idx, MI355DR_E_NOMEM, "mmr_select_sharded: out of host memory for the candidate lists");
+        }
+        HIPCHECK(idx, hipMemcpyAsync(idx->mmr.cand_dist.p, ordered_dist.data(), plane * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(idx->mmr.cand_rows.p, ordered_rows.data(), plane * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        const BlockOut<int64_t> o = block_outputs(idx, io, b0);
+        CHECK(shard_mmr_block(idx, s, nb, m, k, lambda, o.dist, o.rows));
+        CHECK(block_return(idx, io, b0, nb, o));
+        HIPCHECK(idx, hipStreamSynchronize(s));  // (the ordered lists are pageable and are rewritten for the next block)
+    }
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    return shard_mmr_finish(idx, B);
+}
+
 int mi355dr_merge_topk_device(mi355dr_index* idx, const double* dist_all_dev, const int64_t* rows_all_dev, int world,
                               int B, int k, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
@@ -2382,6 +2745,7 @@ const Option kOptions[] = {
     {"view_slice_rows", &Index::view_slice_rows, 32, (int64_t)1 << 22},  // rows per staged slice of mi355dr_view_create on this index
     {"range_chunk_rows", &Index::range_chunk_rows, 256, (int64_t)1 << 31},  // rows per screen launch / exact span of mi355dr_search_range (rounded up to 256)
     {"range_slots", &Index::range_slots, 16, kSortMax},  // slots of a query's range result buffer (never below max_results)
+    {"shard_stage_bytes", &Index::shard_stage_bytes, 1},  // most bytes of the sharded MMR forms' gathered stage (never below one query's)
 };
 
 struct Stat {
@@ -2441,6 +2805,10 @@ const Stat kStats[] = {
     {"rows_searches", &Index::s_rows_searches, true},
     {"rows_queries", &Index::s_rows_queries, true},
     {"rows_skipped", &Index::s_rows_skipped, true},
+    {"sharded_range_searches", &Index::s_shard_range_searches, true},
+    {"sharded_rows_searches", &Index::s_shard_rows_searches, true},
+    {"sharded_mmr_searches", &Index::s_shard_mmr_searches, true},
+    {"shard_gather_bytes", &Index::s_shard_gather_bytes, true},
     {"compactions", &Index::s_compactions, true},
     {"compact_moved_rows", &Index::s_compact_moved_rows, true},
     {"view", nullptr, false, [](const Index* x) -> int64_t { return x->is_view ? 1 : 0; }},

@@ -90,6 +90,19 @@ void comm_destroy(mi355dr_index* idx) {
     idx->comm_stream = nullptr;
     idx->comm_cap = 0;
 }
+
+int comm_all_gather(mi355dr_index* idx, const void* send_dev, void* recv_dev, size_t bytes_per_rank, hipStream_t stream) {
+    if (bytes_per_rank % sizeof(int64_t) != 0) return fail(idx, MI355DR_E_INTERNAL, "all-gather payload is not a multiple of 8 bytes");
+    if (idx->comm_custom) {   // the host's transport (ordered on the stream, or complete on return)
+        const int rc = idx->comm_custom(send_dev, recv_dev, bytes_per_rank, (void*)stream, idx->comm_custom_user);
+        if (rc != 0) return fail(idx, MI355DR_E_HIP, "the host's all-gather failed with code " + std::to_string(rc));
+        return MI355DR_OK;
+    }
+    if (!idx->comm) return fail(idx, MI355DR_E_INVALID, "mi355dr_comm_init has not been called on this index");
+    const int rc = rccl().all_gather(send_dev, recv_dev, bytes_per_rank / sizeof(int64_t), kNcclInt64, idx->comm, stream);
+    if (rc != 0) return nccl_fail(idx, "ncclAllGather", rc);
+    return MI355DR_OK;
+}
 }  // namespace mi355
 
 extern "C" {
@@ -175,7 +188,6 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
     if ((int64_t)idx->comm_world * k > mi355::kSortMax) return mi355::fail(idx, MI355DR_E_UNSUPPORTED, "world*k exceeds 4096");
     if (B == 0) return MI355DR_OK;
     if (!queries_dev || !out_dist_dev || !out_rows_dev) return mi355::fail(idx, MI355DR_E_INVALID, "null buffer");
-    RcclApi& r = rccl();
     HIPCHECK(idx, hipSetDevice(idx->device));
     hipStream_t s = stream ? (hipStream_t)stream : idx->stream;
     const int world = idx->comm_world;
@@ -209,15 +221,8 @@ int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, 
         // complete on the host (the library re-does the rare flagged queries here): the packed block is final and visible
         CHECK(mi355dr_search_wait(idx, p.ticket));
         const size_t plane = (size_t)p.nb * k;
-        if (idx->comm_custom) {   // the host's transport (ordered on the communication stream, or complete on return)
-            const int rc = idx->comm_custom(idx->comm_packed[p.buf], idx->comm_packed_all[p.buf], 2 * plane * sizeof(int64_t),
-                                            (void*)idx->comm_stream, idx->comm_custom_user);
-            if (rc != 0) return mi355::fail(idx, MI355DR_E_HIP, "the host's all-gather failed with code " + std::to_string(rc));
-        } else {
-            const int rc = r.all_gather(idx->comm_packed[p.buf], idx->comm_packed_all[p.buf], 2 * plane, kNcclInt64, idx->comm,
-                                        idx->comm_stream);
-            if (rc != 0) return nccl_fail(idx, "ncclAllGather", rc);
-        }
+        CHECK(mi355::comm_all_gather(idx, idx->comm_packed[p.buf], idx->comm_packed_all[p.buf], 2 * plane * sizeof(int64_t),
+                                     idx->comm_stream));
         CHECK(mi355dr_merge_topk_packed_device(idx, idx->comm_packed_all[p.buf], world, p.nb, k, out_dist_dev + (int64_t)p.b0 * k,
                                                out_rows_dev + (int64_t)p.b0 * k, idx->comm_stream));
         HIPCHECK(idx, hipEventRecord(idx->comm_done[p.buf], idx->comm_stream));

@@ -548,6 +548,110 @@ class Mi355Index:
             self._h, ctypes.c_void_p(int(q_ptr)), int(B), int(k), ctypes.c_void_p(int(out_dist_ptr)),
             ctypes.c_void_p(int(out_rows_ptr)), _stream_arg(stream)))
 
+    # ---- the derived searches over the row-sharded index (include/mi355dr.h "the derived searches over a row-sharded index"):
+    # every rank passes the same arguments and receives what one index holding all rows would return; complete on return ----
+    def search_range_sharded_device(self, q_ptr: int, B: int, radius, max_results: int, out_dist_ptr: int, out_rows_ptr: int,
+                                    out_count_ptr: int, stream: int | None = None) -> None:
+        r = self._radius(radius, int(B))
+        check(self._h, self._lib.mi355dr_search_range_sharded_device(
+            self._h, ctypes.c_void_p(int(q_ptr)), int(B), ptr(r, ctypes.c_double), int(max_results),
+            ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)), ctypes.c_void_p(int(out_count_ptr)),
+            _stream_arg(stream)))
+
+    def search_rows_sharded_device(self, row_ids, k: int, out_dist_ptr: int, out_rows_ptr: int, include_self: bool = False,
+                                   stream: int | None = None) -> None:
+        ids = self._row_ids(row_ids)
+        check(self._h, self._lib.mi355dr_search_rows_sharded_device(
+            self._h, ptr(ids, ctypes.c_int64), ids.shape[0], int(k), 1 if include_self else 0, ctypes.c_void_p(int(out_dist_ptr)),
+            ctypes.c_void_p(int(out_rows_ptr)), _stream_arg(stream)))
+
+    def search_range_rows_sharded_device(self, row_ids, radius, max_results: int, out_dist_ptr: int, out_rows_ptr: int,
+                                         out_count_ptr: int, include_self: bool = False, stream: int | None = None) -> None:
+        ids = self._row_ids(row_ids)
+        r = self._radius(radius, ids.shape[0])
+        check(self._h, self._lib.mi355dr_search_range_rows_sharded_device(
+            self._h, ptr(ids, ctypes.c_int64), ids.shape[0], ptr(r, ctypes.c_double), int(max_results),
+            1 if include_self else 0, ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
+            ctypes.c_void_p(int(out_count_ptr)), _stream_arg(stream)))
+
+    def search_mmr_sharded_device(self, q_ptr: int, B: int, k: int, fetch_k: int, out_dist_ptr: int, out_rows_ptr: int,
+                                  lambda_mult: float = 0.5, stream: int | None = None) -> None:
+        check(self._h, self._lib.mi355dr_search_mmr_sharded_device(
+            self._h, ctypes.c_void_p(int(q_ptr)), int(B), int(k), int(fetch_k), float(lambda_mult),
+            ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)), _stream_arg(stream)))
+
+    def _device_results(self, B: int, width: int, with_count: bool, call):
+        """Device buffers [B, width] float64 / int64 (and [B] int64) for one call of a _sharded_device form, downloaded."""
+        dist = np.empty((B, width), dtype=np.float64)
+        rows = np.empty((B, width), dtype=np.int64)
+        count = np.empty(B, dtype=np.int64)
+        bufs = [self.dev_alloc(max(dist.nbytes, 8)), self.dev_alloc(max(rows.nbytes, 8)), self.dev_alloc(max(count.nbytes, 8))]
+        try:
+            call(*bufs)
+            if B and width:
+                self.dev_download(bufs[0], dist)
+                self.dev_download(bufs[1], rows)
+            if B and with_count:
+                self.dev_download(bufs[2], count)
+        finally:
+            for b in bufs:
+                self.dev_free(b)
+        return (dist, rows, count) if with_count else (dist, rows)
+
+    def _device_queries(self, queries) -> tuple[np.ndarray, int]:
+        q = self._queries_2d(queries)
+        p = self.dev_alloc(max(q.nbytes, 8))
+        if q.nbytes:
+            self.dev_upload(p, q)
+        return q, p
+
+    def search_range_sharded(self, queries, radius, max_results: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`search_range` over the shards: the merged list and the summed count, the same on every rank."""
+        q, qp = self._device_queries(queries)
+        try:
+            return self._device_results(q.shape[0], max(int(max_results), 0), True, lambda d, r, c: self.search_range_sharded_device(
+                qp, q.shape[0], radius, max_results, d, r, c))
+        finally:
+            self.dev_free(qp)
+
+    def search_mmr_sharded(self, queries, k: int, fetch_k: int, lambda_mult: float = 0.5) -> tuple[np.ndarray, np.ndarray]:
+        """`search_mmr` over the shards: the sharded search at `fetch_k`, then the picks over the owners' staged vectors."""
+        q, qp = self._device_queries(queries)
+        try:
+            return self._device_results(q.shape[0], max(int(k), 0), False, lambda d, r, _c: self.search_mmr_sharded_device(
+                qp, q.shape[0], k, fetch_k, d, r, lambda_mult))
+        finally:
+            self.dev_free(qp)
+
+    def search_rows_sharded(self, row_ids, k: int, include_self: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """`search_rows` over the shards: each id's vector comes from the rank that owns it."""
+        ids = self._row_ids(row_ids)
+        return self._device_results(ids.shape[0], max(int(k), 0), False, lambda d, r, _c: self.search_rows_sharded_device(
+            ids, k, d, r, include_self))
+
+    def search_range_rows_sharded(self, row_ids, radius, max_results: int,
+                                  include_self: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """`search_range_rows` over the shards."""
+        ids = self._row_ids(row_ids)
+        return self._device_results(ids.shape[0], max(int(max_results), 0), True,
+                                    lambda d, r, c: self.search_range_rows_sharded_device(ids, radius, max_results, d, r, c, include_self))
+
+    def mmr_select_sharded(self, queries, k: int, cand_rows, lambda_mult: float = 0.5) -> tuple[np.ndarray, np.ndarray]:
+        """`mmr_select` over the shards: cand_rows [B, m] global rows, the same on every rank."""
+        q = self._queries_2d(queries)
+        ids = np.ascontiguousarray(cand_rows, dtype=np.int64)
+        if ids.ndim == 1:
+            ids = ids[None, :]
+        if ids.ndim != 2 or ids.shape[0] != q.shape[0]:
+            raise ValueError(f"cand_rows must be [B, m] with B = {q.shape[0]}, got {ids.shape}")
+        B = q.shape[0]
+        dist = np.empty((B, k), dtype=np.float64)
+        rows = np.empty((B, k), dtype=np.int64)
+        check(self._h, self._lib.mi355dr_mmr_select_sharded(self._h, ptr(q, ctypes.c_float), B, int(k), ptr(ids, ctypes.c_int64),
+                                                            ids.shape[1], float(lambda_mult), ptr(dist, ctypes.c_double),
+                                                            ptr(rows, ctypes.c_int64)))
+        return dist, rows
+
     # ---- multi-vector ----
     def add_multivec(self, vecs, offsets) -> None:
         vecs = f32c(vecs)

@@ -378,6 +378,72 @@ class ShardedSearcher:
             out = np.where(np.isnan(out), g[r], out)
         return out
 
+    # ---- range, by-row and MMR search: inside the library, over ITS communicator (include/mi355dr.h "the derived searches
+    # over a row-sharded index") -- the query rows and the candidates' vectors are gathered and folded on the device ----
+    def _library_comm(self, method: str, entry: str) -> None:
+        """The index's own communicator, created on first use: RCCL under backend nccl (the unique id made on the group's rank
+        0 and broadcast over the group), the gloo all-gather as the library's transport plug-in under gloo."""
+        if not hasattr(self.index, entry):
+            raise NotImplementedError(f"ShardedSearcher.{method}: the index has no `{entry}` (no sharded form of {method})")
+        if getattr(self, "_lib_comm", False):
+            return
+        dist = self._dist
+        if self.backend == "nccl":
+            ids = [self.index.comm_unique_id() if self.rank == 0 else None]
+            src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
+            dist.broadcast_object_list(ids, src=src, group=self.group)
+            self.index.comm_init(self.rank, self.world, ids[0])
+        elif self.backend == "gloo" and hasattr(self.index, "comm_init_custom"):
+            self.index.comm_init_custom(self.rank, self.world, self._host_hop_all_gather)
+        else:
+            raise NotImplementedError(f"ShardedSearcher.{method}: needs a process group (nccl, or gloo with a native index)")
+        self._lib_comm = True
+
+    def _host_hop_all_gather(self, send_ptr: int, recv_ptr: int, nbytes: int, _stream: int) -> None:
+        """The library's transport over gloo: download, all-gather on the host, upload (complete on return)."""
+        import torch
+
+        mine = np.empty(nbytes // 8, dtype=np.int64)
+        self.index.dev_download(send_ptr, mine)
+        out = torch.empty(self.world * mine.size, dtype=torch.int64)
+        self._dist.all_gather_into_tensor(out, torch.from_numpy(mine), group=self.group)
+        self.index.dev_upload(recv_ptr, out.numpy())
+
+    def search_range(self, queries, radius, max_results: int):
+        """Mi355Index.search_range over the row-sharded corpus: (distance [B,m], rows [B,m], count [B]), the same on every rank."""
+        if self.world == 1 and not self.force_pipeline:
+            return self.index.search_range(queries, radius, max_results)
+        self._library_comm("search_range", "search_range_sharded")
+        return self.index.search_range_sharded(queries, radius, max_results)
+
+    def search_rows(self, row_ids, k: int, include_self: bool = False):
+        """Mi355Index.search_rows over the row-sharded corpus: each id's vector comes from the rank that owns it."""
+        if self.world == 1 and not self.force_pipeline:
+            return self.index.search_rows(row_ids, k, include_self)
+        self._library_comm("search_rows", "search_rows_sharded")
+        return self.index.search_rows_sharded(row_ids, k, include_self)
+
+    def search_range_rows(self, row_ids, radius, max_results: int, include_self: bool = False):
+        """Mi355Index.search_range_rows over the row-sharded corpus."""
+        if self.world == 1 and not self.force_pipeline:
+            return self.index.search_range_rows(row_ids, radius, max_results, include_self)
+        self._library_comm("search_range_rows", "search_range_rows_sharded")
+        return self.index.search_range_rows_sharded(row_ids, radius, max_results, include_self)
+
+    def search_mmr(self, queries, k: int, fetch_k: int, lambda_mult: float = 0.5):
+        """Mi355Index.search_mmr over the row-sharded corpus: the sharded search at fetch_k, the picks over the owners' vectors."""
+        if self.world == 1 and not self.force_pipeline:
+            return self.index.search_mmr(queries, k, fetch_k, lambda_mult)
+        self._library_comm("search_mmr", "search_mmr_sharded")
+        return self.index.search_mmr_sharded(queries, k, fetch_k, lambda_mult)
+
+    def mmr_select(self, queries, k: int, cand_rows, lambda_mult: float = 0.5):
+        """Mi355Index.mmr_select over the row-sharded corpus: the same pools (global rows) on every rank."""
+        if self.world == 1 and not self.force_pipeline:
+            return self.index.mmr_select(queries, k, cand_rows, lambda_mult)
+        self._library_comm("mmr_select", "mmr_select_sharded")
+        return self.index.mmr_select_sharded(queries, k, cand_rows, lambda_mult)
+
     # ---- multi-vector (MaxSim): docs sharded by cumulative token count, same gather + merge ----
     def add_local_multivec(self, vecs, offsets, global_doc0: int) -> None:
         """Add this rank's docs (ragged [sum_T, d] + offsets starting at 0); `global_doc0` = global index of its first doc."""
@@ -497,6 +563,7 @@ class ShardedSearcher:
         v.index = self.index.view(row_ids, doc_ids)
         v.overlapped_blocks = 0
         v._ms_stream = None
+        v._lib_comm = False   # (a view takes no communicator: the by-id and MMR forms are asked of the parent)
         return v
 
     def close(self) -> None:

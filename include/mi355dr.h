@@ -293,8 +293,8 @@ int mi355dr_search_groups_device(mi355dr_index* idx, const float* queries_dev, c
  *     "range_rescored" (screen path: candidates taken from the screens / of them re-scored), "range_redo_chunks" ((query, chunk)
  *     pairs run again on the exact path), "range_fallback_queries" (queries whose list the ordinary search served: that search
  *     moves the ordinary stats, nothing else of a range call does).
- *   Sharding is not built in, but the contract is shard-friendly: counts add across shards, and the lists -- global rows, the
- *     total order -- merge with mi355dr_merge_topk_device like any top-k lists. */
+ *   Row-sharded: mi355dr_search_range_sharded_device (below, "the derived searches over a row-sharded index") -- counts add
+ *     across shards, and the lists -- global rows, the total order -- merge like any top-k lists. */
 int mi355dr_search_range(mi355dr_index* idx, const float* queries, int B, const double* radius /* host [B] */,
                          int max_results, double* out_dist /* [B, max_results] */, int64_t* out_rows /* [B, max_results] */,
                          int64_t* out_count /* [B] */); /* all host */
@@ -339,8 +339,9 @@ int mi355dr_search_range_device(mi355dr_index* idx, const float* queries_dev, in
  *   Stats: "rows_searches" (calls), "rows_queries" (slots), "rows_skipped"; the ordinary and the range stats move as the inner
  *     pass moves them ("passes", "chunks", "range_in_range" -- the inner counts, the rows themselves included -- and so on; the
  *     call counters "range_searches" / "range_queries" belong to mi355dr_search_range* and stay).
- *   Not served: views (above); a row-sharded searcher or a process group -- the query row lives on one shard only, so its vector
- *     has to be broadcast first (mi355dr_get_rows on the owner, then the ordinary sharded search at k + 1). */
+ *   Not served: views (above).  Row-sharded: mi355dr_search_rows_sharded_device / mi355dr_search_range_rows_sharded_device
+ *     (below, "the derived searches over a row-sharded index") -- the query row lives on one shard only, so its vector is
+ *     gathered from the owner before the sharded pass at k + 1. */
 #define MI355DR_ROWS_INCLUDE_SELF 1 /* flags: the query row itself stays in the result (default 0: it is left out) */
 int mi355dr_search_rows(mi355dr_index* idx, const int64_t* row_ids /* HOST [B], global */, int B, int k, int flags,
                         double* out_dist /* [B, k] */, int64_t* out_rows /* [B, k] */); /* outputs on the host */
@@ -570,6 +571,54 @@ int mi355dr_comm_init_custom(mi355dr_index* idx, int rank, int world, mi355dr_al
  * on return `stream` has been made to wait for the last merge. */
 int mi355dr_search_sharded_device(mi355dr_index* idx, const float* queries_dev, int B, int k, double* out_dist_dev,
                                   int64_t* out_rows_dev, void* stream);
+
+/* ---- the derived searches over a row-sharded index: range, by stored row, MMR ----
+ * The contract of mi355dr_search_sharded_device: every rank passes the same arguments, and every rank receives what ONE index
+ * holding the rows of all shards would have returned from the local entry point of the same name -- float8 bits, global rows,
+ * NaN positions, NaN / -1 tails and counts.  All need a communicator (mi355dr_comm_init or mi355dr_comm_init_custom; else
+ * MI355DR_E_INVALID) and refuse a view (ask the parent); otherwise they carry the argument rules of their local forms.
+ *   mi355dr_search_range_sharded_device: the list and count of mi355dr_search_range on the union of the shards.  Each rank's
+ *     local list is its shard's first max_results in-range rows, so the world x max_results -> max_results merge under the
+ *     total order gives the global list; the counts add.  One all-gather per block of [2, nb, max_results] + [nb] int64.
+ *   mi355dr_search_rows_sharded_device / mi355dr_search_range_rows_sharded_device: the query of slot b is the stored vector of
+ *     row_ids[b] (HOST, global) on whichever rank owns it.  A slot nobody owns -- an id outside every shard, -1, a removed row
+ *     -- gives NaN / -1 and count 0 and adds one to "rows_skipped" on every rank.  Self-exclusion, MI355DR_ROWS_INCLUDE_SELF and
+ *     the range form's "was the row itself in range, decided from the row-with-itself distance" are as in the local forms (the
+ *     owner computes that distance).  Per block one all-gather of the slots' payloads -- nb x dim floats, nb int32 valid, nb
+ *     double self distances, each part padded to 8 bytes --, folded on the device (the lowest rank whose valid is set), then
+ *     the sharded pass at k + 1 / max_results + 1 (k / max_results with INCLUDE_SELF) and the local form's k_rows_drop.
+ *   mi355dr_search_mmr_sharded_device / mi355dr_mmr_select_sharded: the picks of mi355dr_search_mmr / mi355dr_mmr_select on the
+ *     union.  The candidate list is the sharded search at fetch_k, or the caller's pool (HOST, global rows, the hygiene of
+ *     mi355dr_mmr_select: every rank scores the listed rows it owns, one all-gather of [2, nb, m] int64 -- global row or -1
+ *     for "not mine", distance bits -- and every rank orders the union alike).  The similarity of two stored rows uses the
+ *     same fp32 fmaf chain and the same stored norms whichever GPUs the rows lie on: per sub-block of queries the owners stage
+ *     each candidate's vector, |row|^2 and an owned flag, one all-gather, and the selection of k_mmr_select reads candidate i
+ *     from its owner's stage.  Option "shard_stage_bytes" (default 256 MiB, any value >= 1; never below one query's worth)
+ *     caps the gathered stage: world x round_up4(queries x width x (dim + 2)) floats per sub-block.
+ *   MI355DR_E_UNSUPPORTED beyond the local rules: world x width > 4096 (the merge's sort), width = k + 1 / max_results + 1 (k /
+ *     max_results with INCLUDE_SELF), max_results for the range form, fetch_k for the MMR search.  A refused call changes
+ *     nothing and enters no collective; all checks run before the first collective and depend on the arguments and `world`
+ *     alone, so every rank refuses alike.  B == 0 is a valid no-op where the local form has it (not the range form).
+ *   Unlike mi355dr_search_sharded_device these calls are complete on return, like their local forms, and are not pipelined
+ *     across blocks; B above 1024 runs in internal blocks.  A rank whose shard is empty still enters every collective.  A
+ *     transport error returns MI355DR_E_HIP after the stream has been drained.  The transport plug-in's `fn` is called once
+ *     per all-gather with the call's stream; the payload is complete before it is called.
+ *   Stats: "sharded_range_searches" / "sharded_rows_searches" / "sharded_mmr_searches" (calls), "shard_gather_bytes" (bytes this
+ *     rank received through the all-gathers of these entry points: world x bytes_per_rank each).  The local stats move as the
+ *     inner work moves them: "range_queries", "range_in_range" (this shard's counts), "rows_queries", "rows_skipped" (slots NO
+ *     rank owned), "mmr_queries", "mmr_pairs_scored"; the call counters of the local entry points stay. */
+int mi355dr_search_range_sharded_device(mi355dr_index* idx, const float* queries_dev, int B, const double* radius /* HOST [B] */,
+                                        int max_results, double* out_dist_dev, int64_t* out_rows_dev, int64_t* out_count_dev,
+                                        void* stream);
+int mi355dr_search_rows_sharded_device(mi355dr_index* idx, const int64_t* row_ids /* HOST [B], global */, int B, int k, int flags,
+                                       double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+int mi355dr_search_range_rows_sharded_device(mi355dr_index* idx, const int64_t* row_ids /* HOST [B] */, int B,
+                                             const double* radius /* HOST [B] */, int max_results, int flags,
+                                             double* out_dist_dev, int64_t* out_rows_dev, int64_t* out_count_dev, void* stream);
+int mi355dr_search_mmr_sharded_device(mi355dr_index* idx, const float* queries_dev, int B, int k, int fetch_k, double lambda,
+                                      double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+int mi355dr_mmr_select_sharded(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* cand_rows /* host [B, m], global */,
+                               int m, double lambda, double* out_dist, int64_t* out_rows); /* all host */
 
 /* ---- options / stats / timing ----
  * options: "path" (MI355DR_PATH_*), "screen_dtype" (MI355DR_SCREEN_*), "row_offset", "profile" (0/1: HIP-event
