@@ -392,6 +392,12 @@ struct mi355dr_index {
     int64_t s_shard_range_searches = 0, s_shard_rows_searches = 0, s_shard_mmr_searches = 0, s_shard_gather_bytes = 0;
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
+    // which MaxSim screen launch ran last, written on the host next to the launch (mi355dr_debug_maxsim_pass reports it).
+    // family: MI355DR_MS_FORM_* (include/mi355dr.h); bps / pipe / now: the workgroup forms' blocks per stage, software pipeline,
+    // epilogue at once
+    struct MsScreenForm {
+        int family = 0, ncb = 0, waves = 0, bps = 0, pipe = 0, now = 0, grid = 0, reserved = 0;
+    } last_screen_form;
     mi355::EventPairs ev_pool, ev_pending;
     mi355::Event t0, t1;
 

@@ -1313,6 +1313,131 @@ int maxsim_subset_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_o
     return MI355DR_OK;
 }
 
+// ---- test hook: one pass of the search above, observed (mi355dr_debug_maxsim_pass, include/mi355dr.h) ----
+// what a pass counts and the one option the hook switches off for its own pass, put back on every way out
+struct MsDebugKeep {
+    mi355dr_index* idx;
+    int profile;
+    int64_t screened, candidates, fallbacks, cols, packed, ss, se, sf;
+    explicit MsDebugKeep(mi355dr_index* i)
+        : idx(i), profile(i->profile), screened(i->s_ms_screened), candidates(i->s_ms_candidates), fallbacks(i->s_ms_fallbacks),
+          cols(i->s_ms_screen_cols), packed(i->s_ms_packed_launches), ss(i->s_mss_screened), se(i->s_mss_exact), sf(i->s_mss_fallbacks) {
+        idx->profile = 0;  // (no events, no timing stats)
+    }
+    ~MsDebugKeep() {
+        idx->profile = profile;
+        idx->s_ms_screened = screened;
+        idx->s_ms_candidates = candidates;
+        idx->s_ms_fallbacks = fallbacks;
+        idx->s_ms_screen_cols = cols;
+        idx->s_ms_packed_launches = packed;
+        idx->s_mss_screened = ss;
+        idx->s_mss_exact = se;
+        idx->s_mss_fallbacks = sf;
+    }
+};
+
+int debug_maxsim_pass_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, int k, const int64_t* doc_ids,
+                           int64_t m_ids, int list_cap, int* out_live, float* out_screen, float* out_two_e, int32_t* out_lists,
+                           int* out_ctl, float* out_wide_sd, int* out_form, int* out_info) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return fail(idx, MI355DR_E_INVALID, "debug_maxsim_pass: not on a view");
+    if (B <= 0 || B > kPQ || k <= 0 || k > kKMax || !qtok || !q_offsets || m_ids < 0 || list_cap < 1 || !out_live || !out_screen ||
+        !out_two_e || !out_lists || !out_ctl || !out_wide_sd || !out_form || !out_info)
+        return fail(idx, MI355DR_E_INVALID, "bad debug_maxsim_pass arguments");
+    for (int b = 0; b < B; ++b)
+        if (q_offsets[b + 1] < q_offsets[b]) return fail(idx, MI355DR_E_INVALID, "q_offsets must be non-decreasing");
+    MultiVecStore* m = idx->mv;
+    if (!m || m->n_docs == 0) return fail(idx, MI355DR_E_INVALID, "debug_maxsim_pass: the index has no multi-vector store");
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    // a document list: what search_maxsim_subset_impl and search_maxsim_impl do with it before the first pass
+    std::vector<int32_t> list;
+    if (doc_ids) {
+        try {
+            subset_prepare_ids(doc_ids, m_ids, idx->row_offset, m->n_docs, list);
+        } catch (const std::bad_alloc&) {
+            return fail(idx, MI355DR_E_NOMEM, "debug_maxsim_pass: out of host memory for the document list");
+        }
+        const std::vector<int64_t>& off = m->blk_off_host;
+        list.erase(std::remove_if(list.begin(), list.end(), [&](int32_t d) { return off[(size_t)d + 1] <= off[(size_t)d]; }), list.end());
+        if (list.empty()) return fail(idx, MI355DR_E_INVALID, "debug_maxsim_pass: no listed document has vectors");
+        HIPCHECK(idx, m->sub_list.grow(list.size() * sizeof(int32_t)));
+        HIPCHECK(idx, m->sub_memb.grow((size_t)(m->cap_docs + 1) * sizeof(int64_t)));
+    }
+    MsDebugKeep keep(idx);
+    std::vector<float> res_d((size_t)B * k);  // the fast path's results: not reported
+    std::vector<int64_t> res_r((size_t)B * k);
+    MsSearch c{idx, m, idx->stream, qtok, q_offsets, B, k, res_d.data(), res_r.data(), false};
+    if (doc_ids) {
+        c.list = m->sub_list.p;
+        c.n_list = (int64_t)list.size();
+        c.list_screen = idx->maxsim_subset_screen > 0 || (idx->maxsim_subset_screen < 0 && c.n_list >= idx->maxsim_subset_screen_min);
+    }
+    CHECK(ms_search_prepare(c));
+    for (int b = 0; b < B; ++b)
+        if (q_offsets[b + 1] - q_offsets[b] > c.cols)
+            return fail(idx, MI355DR_E_INVALID, "debug_maxsim_pass: a query has more vectors than one launch stages");
+    if (doc_ids) {
+        HIPCHECK(idx, hipMemcpyAsync(m->sub_list.p, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, c.s));
+        if (c.list_screen && m->finite && c.lds16 <= 160 * 1024) {
+            hipLaunchKernelGGL(k_ms_membership, dim3((unsigned)((m->n_docs + 256) / 256)), dim3(256), 0, c.s, m->sub_list.p, c.n_list,
+                               m->n_docs, m->sub_memb.p);
+            HIPCHECK(idx, hipGetLastError());
+        }
+    }
+    HIPCHECK(idx, hipStreamSynchronize(c.s));
+    const MsPass p = ms_plan_pass(c, 0);
+    if (p.b_end < B) return fail(idx, MI355DR_E_INVALID, "debug_maxsim_pass: the queries do not fit one pass");
+    for (int b = 0; b < B; ++b) out_live[b] = -1;
+    for (int r = 0; r < p.n; ++r) out_live[p.b[r]] = r;
+    idx->last_screen_form = {};
+    out_info[0] = p.n;
+    out_info[1] = kMsCandCap;
+    out_info[2] = 0;
+    out_info[3] = kMsTightenMax;
+    for (int i = 0; i < 8; ++i) out_form[i] = 0;
+    for (int r = 0; r < p.n; ++r) {  // (the rounding of ms_fast_path / ms_slow_query; the fast path's device copy replaces it below)
+        out_two_e[r] = (float)p.two_e[r];
+        if ((double)out_two_e[r] < p.two_e[r]) out_two_e[r] = std::nextafter(out_two_e[r], INFINITY);
+    }
+    if (p.n == 0 || !p.screen) return MI355DR_OK;
+    const size_t img_cols = std::min<size_t>(kMsImgCols, (size_t)((p.total_col + 31) / 32 * 32 + 32));
+    HIPCHECK(idx, hipMemcpyAsync(m->qtok.p, c.qimg, img_cols * m->dpad * sizeof(float), hipMemcpyHostToDevice, c.s));
+    const size_t screen_bytes = (size_t)p.n * m->n_docs * sizeof(float);
+    HIPCHECK(idx, hipMemsetAsync(m->dist16.p, 0xFF, screen_bytes, c.s));
+    CHECK(ms_launch_screen(c, p));
+    HIPCHECK(idx, hipMemcpyAsync(out_screen, m->dist16.p, screen_bytes, hipMemcpyDeviceToHost, c.s));
+    HIPCHECK(idx, hipStreamSynchronize(c.s));
+    const auto& f = idx->last_screen_form;
+    const int form[8] = {f.family, f.ncb, f.waves, f.bps, f.pipe, f.now, f.grid, 0};
+    memcpy(out_form, form, sizeof(form));
+    if (k > kMsFastK) return MI355DR_OK;
+    bool handled[kPQ] = {};
+    CHECK(ms_fast_path(c, p, handled));
+    std::vector<int32_t> lists((size_t)3 * kPQ * kMsCandCap);
+    std::vector<float> sd((size_t)kPQ * kMsCandCap);
+    int ctl[3 * 2 * kPQ];
+    HIPCHECK(idx, hipMemcpy(lists.data(), m->cand_list.p, lists.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHECK(idx, hipMemcpy(sd.data(), m->cand_sd.p, sd.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHECK(idx, hipMemcpy(ctl, m->cand_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost));
+    HIPCHECK(idx, hipMemcpy(out_two_e, m->two_e_dev.p, p.n * sizeof(float), hipMemcpyDeviceToHost));
+    const bool tighten = idx->maxsim_tighten != 0;
+    for (int sec = 0; sec < 3; ++sec) {
+        const int src = sec == 2 && !tighten ? 0 : sec;  // (ms_fast_path: without the tightening the final list is the wide list)
+        for (int r = 0; r < p.n; ++r) {
+            const int cnt = ctl[(src * kPQ + r) * 2];
+            out_ctl[(sec * B + r) * 2] = cnt;
+            out_ctl[(sec * B + r) * 2 + 1] = ctl[(src * kPQ + r) * 2 + 1];
+            const size_t n = (size_t)std::min({cnt, kMsCandCap, list_cap});
+            memcpy(out_lists + ((size_t)sec * B + r) * list_cap, &lists[((size_t)src * kPQ + r) * kMsCandCap], n * sizeof(int32_t));
+            if (sec == 0 && tighten) memcpy(out_wide_sd + (size_t)r * list_cap, &sd[(size_t)r * kMsCandCap], n * sizeof(float));
+        }
+    }
+    out_info[2] = 1;
+    return MI355DR_OK;
+}
+
 }  // namespace
 
 namespace mi355 {
@@ -1387,6 +1512,13 @@ int mi355dr_maxsim_subset_ex(mi355dr_index* idx, const float* qtok, const int32_
                              int m_ids, int flags, float* out_dist) {
     if (flags & ~MI355DR_MAXSIM_CLAMP0) return fail(idx, MI355DR_E_INVALID, "unknown maxsim flag");
     return maxsim_subset_impl(idx, qtok, q_offsets, B, doc_ids, m_ids, (flags & MI355DR_MAXSIM_CLAMP0) ? 1 : 0, out_dist);
+}
+
+int mi355dr_debug_maxsim_pass(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, int k, const int64_t* doc_ids,
+                              int64_t m, int list_cap, int* out_live, float* out_screen, float* out_two_e, int32_t* out_lists,
+                              int* out_ctl, float* out_wide_sd, int* out_form, int* out_info) {
+    return debug_maxsim_pass_impl(idx, qtok, q_offsets, B, k, doc_ids, m, list_cap, out_live, out_screen, out_two_e, out_lists, out_ctl,
+                                  out_wide_sd, out_form, out_info);
 }
 
 }  // extern "C"

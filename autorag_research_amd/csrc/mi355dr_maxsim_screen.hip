@@ -398,6 +398,7 @@ int ms16_d128_launch(mi355dr_index* idx, hipStream_t s, int ncb, int64_t n_docs,
         // the granule-packed copy (k_maxsim_wg8.h): one workgroup per CU, each a contiguous range of documents with ~1/256 of the granules
         const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (pk->n_pblocks + 31) / 32));
         hipLaunchKernelGGL(mi355::k_maxsim16_wg8, dim3(grid), dim3(512), (size_t)mi355::mw_lds(4), s, sa, *pk, ncb);
+        idx->last_screen_form = {MI355DR_MS_FORM_WG_PACKED, ncb, 8, 4, 0, 0, (int)grid, 0};
         HIPCHECK(idx, hipGetLastError());
         return MI355DR_OK;
     }
@@ -405,6 +406,7 @@ int ms16_d128_launch(mi355dr_index* idx, hipStream_t s, int ncb, int64_t n_docs,
         const bool now = idx->maxsim_wg == 2;
         const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(256, (n_blocks + 31) / 32));
         hipLaunchKernelGGL(kMs16Wg8Kernels[now ? 1 : 0], dim3(grid), dim3(512), (size_t)mi355::mw_lds(4), s, sa, n_blocks);
+        idx->last_screen_form = {MI355DR_MS_FORM_WG, ncb, 8, 4, 1, now ? 1 : 0, (int)grid, 0};
         HIPCHECK(idx, hipGetLastError());
         return MI355DR_OK;
     }
@@ -417,6 +419,7 @@ int ms16_d128_launch(mi355dr_index* idx, hipStream_t s, int ncb, int64_t n_docs,
         const int bps = idx->maxsim_wg_bps == 2 ? 2 : 4;
         hipLaunchKernelGGL(kMs16WgKernels[bps == 4 ? (idx->maxsim_wg_pipe ? 2 : 1) : 0][now ? 1 : 0][ncb - 9], dim3(grid), dim3(512), (size_t)mi355::mw_lds(bps), s, sa,
                            n_blocks);
+        idx->last_screen_form = {MI355DR_MS_FORM_WG, ncb, 8, bps, bps == 4 && idx->maxsim_wg_pipe ? 1 : 0, now ? 1 : 0, (int)grid, 0};
         HIPCHECK(idx, hipGetLastError());
         return MI355DR_OK;
     }
@@ -428,12 +431,14 @@ int ms16_d128_launch(mi355dr_index* idx, hipStream_t s, int ncb, int64_t n_docs,
     const bool pk8 = pk && ncb <= kMs16PkMaxNcb;
     hipLaunchKernelGGL(pk8 ? kMs16PkKernels[ncb - 1] : kMs16Kernels[ncb - 1], dim3(grid), dim3(nw * 64), (size_t)ncb * 8 * 64 * sizeof(uint4), s, sa,
                        pk8 ? *pk : mi355::Ms16Pack{});
+    idx->last_screen_form = {pk8 ? MI355DR_MS_FORM_D128_PACKED : MI355DR_MS_FORM_D128, ncb, nw, 0, 0, 0, (int)grid, 0};
     HIPCHECK(idx, hipGetLastError());
     return MI355DR_OK;
 }
 
 int ms16_generic_launch(mi355dr_index* idx, hipStream_t s, unsigned grid, size_t lds16, const Ms16Args& sa) {
     hipLaunchKernelGGL(k_maxsim16<false>, dim3(grid), dim3(kMsThreads), lds16, s, sa);
+    idx->last_screen_form = {MI355DR_MS_FORM_GENERIC, 0, kMsThreads / 64, 0, 0, 0, (int)grid, 0};
     HIPCHECK(idx, hipGetLastError());
     return MI355DR_OK;
 }
@@ -448,6 +453,7 @@ int ms16_list_launch(mi355dr_index* idx, hipStream_t s, int ncb, size_t lds16, c
         hipLaunchKernelGGL(kMs16ListKernels[ncb - 1], dim3(grid), dim3(nw * 64), (size_t)ncb * 8 * 64 * sizeof(uint4), s, sa, mi355::Ms16Pack{});
     else
         hipLaunchKernelGGL(k_maxsim16<true>, dim3(grid), dim3(kMsThreads), lds16, s, sa);
+    idx->last_screen_form = {d128 ? MI355DR_MS_FORM_LIST_D128 : MI355DR_MS_FORM_LIST_GENERIC, d128 ? ncb : 0, nw, 0, 0, 0, (int)grid, 0};
     HIPCHECK(idx, hipGetLastError());
     return MI355DR_OK;
 }

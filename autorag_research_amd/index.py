@@ -909,6 +909,52 @@ class Mi355Index:
         return {"kernel": int(kernel.value), "count": count, "status": status, "dropped": flagged.sum(axis=1),
                 "q": np.nonzero(keep)[0].astype(np.int32), "row": rows[keep], "val": vals[keep]}
 
+    MS_FORMS = ("none", "generic", "d128", "d128_packed", "wg", "wg_packed", "list_generic", "list_d128")
+
+    def debug_maxsim_pass(self, qtok, q_offsets, k: int, doc_ids=None, list_cap: int = 8192) -> dict:
+        """ONE pass of `search_maxsim` (with `doc_ids`: of `search_maxsim_subset`) through the search's own functions, and what it
+        computed (mi355dr_debug_maxsim_pass).  Returns {"live" [B]: row of each query in the pass or -1, "screen" [n_live, n_docs]:
+        the screen distances as the kernel left them over rows poisoned with 0xFFFFFFFF, "two_e" [n_live], "form": {"family"
+        (MS_FORMS), "ncb", "waves", "bps", "pipe", "now", "grid"}, "cand_cap", "tighten_max", and for k <= 64 on a screened pass
+        "lists": {"wide" / "starter" / "final": per live query {"ids" (the entries held), "count", "overflow"}; wide also "sd"}
+        (else None)}.  NativeError (MI355DR_E_INVALID) when the queries are not one pass; the index stays usable."""
+        qtok = f32c(qtok).reshape(-1, self.dim)
+        q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int32)
+        B = q_offsets.shape[0] - 1
+        ids = None if doc_ids is None else self._row_ids(doc_ids)
+        n_docs = self.n_docs()
+        live = np.full(max(B, 1), -1, dtype=np.int32)
+        screen = np.empty((max(B, 1), max(n_docs, 1)), dtype=np.float32)
+        two_e = np.empty(max(B, 1), dtype=np.float32)
+        lists = np.full((3, max(B, 1), list_cap), -1, dtype=np.int32)
+        ctl = np.zeros((3, max(B, 1), 2), dtype=np.int32)
+        sd = np.full((max(B, 1), list_cap), np.nan, dtype=np.float32)
+        form = np.zeros(8, dtype=np.int32)
+        info = np.zeros(4, dtype=np.int32)
+        check(self._h, self._lib.mi355dr_debug_maxsim_pass(
+            self._h, ptr(qtok, ctypes.c_float), ptr(q_offsets, ctypes.c_int32), B, int(k),
+            None if ids is None else ptr(ids, ctypes.c_int64), 0 if ids is None else ids.shape[0], int(list_cap),
+            ptr(live, ctypes.c_int), ptr(screen, ctypes.c_float), ptr(two_e, ctypes.c_float), ptr(lists, ctypes.c_int32),
+            ptr(ctl, ctypes.c_int), ptr(sd, ctypes.c_float), ptr(form, ctypes.c_int), ptr(info, ctypes.c_int)))
+        n_live, cap = int(info[0]), int(info[1])
+        out = {"live": live[:B], "two_e": two_e[:n_live],
+               "screen": screen.reshape(-1)[:n_live * n_docs].reshape(n_live, n_docs),
+               "form": {"family": self.MS_FORMS[int(form[0])], "ncb": int(form[1]), "waves": int(form[2]), "bps": int(form[3]),
+                        "pipe": int(form[4]), "now": int(form[5]), "grid": int(form[6])},
+               "cand_cap": cap, "tighten_max": int(info[3]), "lists": None}
+        if info[2]:
+            out["lists"] = {}
+            for sec, name in enumerate(("wide", "starter", "final")):
+                rows = []
+                for r in range(n_live):
+                    held = min(int(ctl[sec, r, 0]), cap, list_cap)
+                    e = {"ids": lists[sec, r, :held].copy(), "count": int(ctl[sec, r, 0]), "overflow": int(ctl[sec, r, 1])}
+                    if sec == 0:
+                        e["sd"] = sd[r, :held].copy()
+                    rows.append(e)
+                out["lists"][name] = rows
+        return out
+
     def debug_i8_state(self, queries, g0: int, n_groups: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """int8 screen: (S_q [B], kq [B], S_g [n_groups], e_g [n_groups]) -- screen value = S_q S_g (q8.c8) + e_g kq."""
         q = f32c(queries)

@@ -709,6 +709,38 @@ int mi355dr_debug_screen_dense(mi355dr_index* idx, const float* queries, int B, 
  * (option screen_flush_sync = 0: none, as in a search). */
 int mi355dr_debug_screen_hits(mi355dr_index* idx, const float* queries, int B, int64_t row0, int64_t n, const float* thr,
                               int cap, int* out_count, int32_t* out_rows, float* out_vals, int* out_status, int* out_kernel);
+/* ONE pass of the MaxSim search, through the functions mi355dr_search_maxsim[_subset] itself calls, in their order (scratch and
+ * constants, the pass plan, the query upload, the screen launch and -- k <= 64 -- the fast path's selection, lists and re-score),
+ * handing back what the pass computed.  qtok / q_offsets / B / k as in mi355dr_search_maxsim; doc_ids / m as in
+ * mi355dr_search_maxsim_subset (doc_ids = NULL: every document).  Before the screen launch the pass's rows of the screen
+ * distances are filled with the bit pattern 0xFFFFFFFF: a word the screen did not write is recognisable.
+ * MI355DR_E_INVALID, the handle as it was: the queries do not all fit one pass (at most 16, at most 512 vectors together for
+ * dims <= 128, else the first group of four), a query has more vectors than one launch stages, the handle is a view or has no
+ * multi-vector store, no listed document has vectors.  Moves no statistic and no option.
+ * Outputs, all host:
+ *   out_live [B]          row of each query in the pass, -1 for a query without vectors; n_live = the rows
+ *   out_screen [B, n_docs] rows 0 .. n_live - 1: the screen distances as the kernel left them (row stride n_docs)
+ *   out_two_e [B]         rows 0 .. n_live - 1: 2E as handed to the device (float, rounded up)
+ *   out_lists [3, B, list_cap] / out_ctl [3, B, 2]: sections 0 = wide, 1 = starter, 2 = final list of each row and their
+ *                         (count, overflow flag), k <= 64 only; a list holds min(count, 8192) entries, the first
+ *                         min(.., list_cap) are copied.  With option maxsim_tighten = 0 there is no starter and the final list
+ *                         IS the wide list: section 2 then repeats section 0.
+ *   out_wide_sd [B, list_cap]  the screen distance stored with every entry of the wide list (maxsim_tighten = 1; else untouched)
+ *   out_form [8]          family (MI355DR_MS_FORM_*), column blocks (0: the generic forms), waves per workgroup, and for the
+ *                         workgroup forms blocks per stage, software-pipelined, epilogue at once; the grid; 0
+ *   out_info [4]          n_live, the lists' capacity (8192), 1 if the lists were produced (k <= 64 and the pass screened), the
+ *                         longest starter the tightening uses (1024) */
+#define MI355DR_MS_FORM_NONE 0         /* the pass was not screened: non-finite store or query, screen off, dim > 640 */
+#define MI355DR_MS_FORM_GENERIC 1      /* k_maxsim16<false> */
+#define MI355DR_MS_FORM_D128 2         /* k_maxsim16_d128<NCB, NW, false>: one wave per document */
+#define MI355DR_MS_FORM_D128_PACKED 3  /* k_maxsim16_d128<NCB, 4, true>: the same over the granule-packed copy */
+#define MI355DR_MS_FORM_WG 4           /* k_maxsim16_wg<NCB, DEFER, BPS, PIPE> */
+#define MI355DR_MS_FORM_WG_PACKED 5    /* k_maxsim16_wg8 */
+#define MI355DR_MS_FORM_LIST_GENERIC 6 /* k_maxsim16<true> */
+#define MI355DR_MS_FORM_LIST_D128 7    /* k_maxsim16_d128<NCB, NW, false, true> */
+int mi355dr_debug_maxsim_pass(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, int k, const int64_t* doc_ids,
+                              int64_t m, int list_cap, int* out_live, float* out_screen, float* out_two_e, int32_t* out_lists,
+                              int* out_ctl, float* out_wide_sd, int* out_form, int* out_info);
 /* the per-query screen bound E of the active screen dtype: exact cosine <= screen value + E  (bf16 screen: also
  * |screen value - exact cosine| <= E; int8 screen: the screen value already carries its row group's share of the bound) */
 int mi355dr_debug_screen_bound(mi355dr_index* idx, const float* queries, int B, float* out_E);
