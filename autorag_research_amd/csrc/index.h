@@ -78,6 +78,7 @@ struct EventPairs {
     }
 };
 struct MultiVecStore;  // mi355dr_maxsim.hip
+struct SparseStore;    // mi355dr_sparse.hip
 // What one search pass has decided, once, before its first launch (mi355dr.hip decide_pass): every function of the pass takes
 // it, or the field it needs, as a parameter -- none reads a decision from the handle
 struct Pass {
@@ -390,6 +391,12 @@ struct mi355dr_index {
     int64_t s_rows_searches = 0, s_rows_queries = 0, s_rows_skipped = 0;
     // the row-sharded derived searches: calls per family, bytes this rank received through their all-gathers
     int64_t s_shard_range_searches = 0, s_shard_rows_searches = 0, s_shard_mmr_searches = 0, s_shard_gather_bytes = 0;
+    // mi355dr_search_sparse* / mi355dr_search_bm25*: calls, queries, postings accumulated by k_sparse_score, (query, launch)
+    // candidate lists that overflowed and were run again in pieces
+    int64_t s_sparse_searches = 0, s_sparse_queries = 0, s_sparse_postings_scored = 0, s_sparse_overflows = 0;
+    int sparse_tile_docs = 2048;  // documents per LDS tile of k_sparse_score (option "sparse_tile_docs": a power of two, 256 .. 8192;
+                                  // 2048 was the fastest of 1024 .. 8192 at 3, 8 and 24 terms per query: DESIGN.md section 4.8j)
+    int sparse_cand_cap = 2048;   // slots of a query's sparse candidate list (option "sparse_cand_cap", 16 .. 2048)
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
     // which MaxSim screen launch ran last, written on the host next to the launch (mi355dr_debug_maxsim_pass reports it).
@@ -416,6 +423,8 @@ struct mi355dr_index {
 
     // multi-vector store (MaxSim), owned by mi355dr_maxsim.hip
     mi355::MultiVecStore* mv = nullptr;
+    // sparse store (tokenised documents, BM25), owned by mi355dr_sparse.hip
+    mi355::SparseStore* sp = nullptr;
 };
 
 
@@ -432,6 +441,11 @@ void multivec_destroy(mi355dr_index* idx);                       // mi355dr_maxs
 // room for n_blocks 32-token blocks and n_docs documents, the store created if there is none (mi355dr_view_create reserves once)
 int multivec_reserve(mi355dr_index* idx, int64_t n_blocks, int64_t n_docs);  // mi355dr_maxsim.hip
 int64_t multivec_bytes(const mi355dr_index* idx);                // mi355dr_maxsim.hip: stat "hbm_bytes_resident"
+void sparse_destroy(mi355dr_index* idx);                         // mi355dr_sparse.hip
+int64_t sparse_bytes(const mi355dr_index* idx);                  // mi355dr_sparse.hip: stat "hbm_bytes_resident"
+enum { kSparseStatDocs, kSparseStatTotalLen, kSparseStatPostings, kSparseStatVocab };
+int64_t sparse_stat(const mi355dr_index* idx, int which);        // mi355dr_sparse.hip: the store's own figures (0 without a store)
+int drain_searches(mi355dr_index* idx);                          // mi355dr.hip: blocks in flight finished (under the handle's mutex)
 void comm_destroy(mi355dr_index* idx);                           // mi355dr_comm.hip
 // one all-gather over the index's communicator (RCCL, or the host's transport): bytes_per_rank (a multiple of 8) from every
 // rank's send_dev into recv_dev, rank-major; ordered on `stream` (a host transport may instead be complete on return)

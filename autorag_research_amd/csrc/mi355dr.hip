@@ -1040,6 +1040,10 @@ int rescore_host_pairs(mi355dr_index* idx, PairBufs& bufs, const float* queries,
 
 }  // namespace
 
+namespace mi355 {
+int drain_searches(mi355dr_index* idx) { return drain_pending(idx); }
+}  // namespace mi355
+
 extern "C" {
 
 int mi355dr_version(void) { return 102; }
@@ -1096,6 +1100,7 @@ void mi355dr_destroy(mi355dr_index* idx) {
     (void)drain_pending(idx);
     if (idx->stream) (void)hipStreamSynchronize(idx->stream);
     multivec_destroy(idx);
+    sparse_destroy(idx);
     comm_destroy(idx);
     delete idx;  // every buffer and event goes with its owner, the stream with the handle's destructor (index.h)
 }
@@ -2745,6 +2750,8 @@ const Option kOptions[] = {
     {"view_slice_rows", &Index::view_slice_rows, 32, (int64_t)1 << 22},  // rows per staged slice of mi355dr_view_create on this index
     {"range_chunk_rows", &Index::range_chunk_rows, 256, (int64_t)1 << 31},  // rows per screen launch / exact span of mi355dr_search_range (rounded up to 256)
     {"range_slots", &Index::range_slots, 16, kSortMax},  // slots of a query's range result buffer (never below max_results)
+    {"sparse_tile_docs", &Index::sparse_tile_docs, 256, 8192},  // documents per LDS tile of k_sparse_score (a power of two: checked below)
+    {"sparse_cand_cap", &Index::sparse_cand_cap, 16, 2048},     // slots of a query's sparse candidate list
     {"shard_stage_bytes", &Index::shard_stage_bytes, 1},  // most bytes of the sharded MMR forms' gathered stage (never below one query's)
 };
 
@@ -2809,6 +2816,14 @@ const Stat kStats[] = {
     {"sharded_rows_searches", &Index::s_shard_rows_searches, true},
     {"sharded_mmr_searches", &Index::s_shard_mmr_searches, true},
     {"shard_gather_bytes", &Index::s_shard_gather_bytes, true},
+    {"sparse_searches", &Index::s_sparse_searches, true},
+    {"sparse_queries", &Index::s_sparse_queries, true},
+    {"sparse_postings_scored", &Index::s_sparse_postings_scored, true},
+    {"sparse_overflows", &Index::s_sparse_overflows, true},
+    {"sparse_docs", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatDocs); }},
+    {"sparse_total_len", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatTotalLen); }},
+    {"sparse_postings", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatPostings); }},
+    {"sparse_vocab", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatVocab); }},
     {"compactions", &Index::s_compactions, true},
     {"compact_moved_rows", &Index::s_compact_moved_rows, true},
     {"view", nullptr, false, [](const Index* x) -> int64_t { return x->is_view ? 1 : 0; }},
@@ -2823,7 +2838,8 @@ const Stat kStats[] = {
     {"hbm_bytes_resident", nullptr, false, [](const Index* x) -> int64_t {
          return x->cap_rows * ((int64_t)x->dim * 4 + (int64_t)x->dpad * 2 + (int64_t)x->dpad8 + 5) +
                 x->cap_rows / kI8GroupRows * (int64_t)sizeof(I8Group) + multivec_bytes(x) +
-                (int64_t)(x->view_row_map.bytes + x->view_doc_map.bytes);  // (a view's two id maps; none on a parent)
+                (int64_t)(x->view_row_map.bytes + x->view_doc_map.bytes) +  // (a view's two id maps; none on a parent)
+                sparse_bytes(x);
      }},
 };
 }  // namespace
@@ -2844,6 +2860,8 @@ int mi355dr_set_option(mi355dr_index* idx, const char* key, int64_t value) {
             if (o.gap_lo < o.gap_hi) range += ", not between " + std::to_string(o.gap_lo) + " and " + std::to_string(o.gap_hi);
             return fail(idx, MI355DR_E_INVALID, o.key + range);
         }
+        if (strcmp(key, "sparse_tile_docs") == 0 && (value & (value - 1)) != 0)
+            return fail(idx, MI355DR_E_INVALID, "sparse_tile_docs must be a power of two");
         o.field.set(idx, value);
         if (o.then) o.then(idx);
         return MI355DR_OK;

@@ -1,0 +1,493 @@
+// mi355dr_sparse.hip -- the sparse store of libmi355dr.so: tokenised documents, weighted / BM25 top-k.
+// The arithmetic is fixed by include/mi355dr.h ("sparse store"); no bit parity with VectorChord-BM25 is claimed.
+//
+// Host side: the documents as sorted (term, tf) pairs (6 bytes per posting) with their lengths and df -- what an add appends
+// to, what the BM25 weights are computed from, and what the term-major device layout is rebuilt from (counting sort + upload)
+// by the first search after an add.  Device side: term_off [vocab + 1], postings (doc int32, tf uint16) ascending by document
+// inside a term, document lengths, and the norms of the last (k1, b).  A search runs the document range in a few launches of
+// growing size (k_sparse.h): the first cannot overflow a candidate list, every later one appends only what beats the
+// query's k-th kept entry.
+#include "index.h"
+#include "k_sparse.h"
+
+#include <new>
+
+using namespace mi355;
+
+namespace mi355 {
+
+struct SparseStore {
+    // host
+    int64_t n_docs = 0, n_live = 0, total_len = 0, n_post = 0, vocab = 0;
+    std::vector<int32_t> doc_len;   // [n_docs]
+    std::vector<int64_t> doc_off;   // [n_docs + 1] into h_term / h_tf
+    std::vector<int32_t> h_term;    // per document: its distinct terms ascending ...
+    std::vector<uint16_t> h_tf;     // ... and their counts
+    std::vector<int64_t> df;        // [vocab]
+    // device layout (stale after an add until the next search)
+    bool stale = false;
+    DevBuf<int64_t> term_off;
+    DevBuf<int32_t> post_doc, len_dev;
+    DevBuf<uint16_t> post_tf;
+    DevBuf<double> norm;
+    bool norm_valid = false;
+    double norm_k1 = 0.0, norm_b = 0.0;
+    // one block's scratch
+    DevBuf<int32_t> q_terms, q_off, best_doc, cand_doc;
+    DevBuf<double> q_w, out_dist;
+    DevBuf<int64_t> out_rows;
+    DevBuf<uint64_t> best_key, cand_key;
+    DevBuf<unsigned> count;
+    DevBuf<int> flags, qlist;
+    DevBuf<unsigned long long> scored;
+    bool lds_registered = false;
+    SparseStore() { doc_off.push_back(0); }
+};
+
+void sparse_destroy(mi355dr_index* idx) {
+    delete idx->sp;
+    idx->sp = nullptr;
+}
+
+int64_t sparse_bytes(const mi355dr_index* idx) {
+    const SparseStore* s = idx->sp;
+    return s ? (int64_t)(s->term_off.bytes + s->post_doc.bytes + s->post_tf.bytes + s->len_dev.bytes + s->norm.bytes) : 0;
+}
+
+int64_t sparse_stat(const mi355dr_index* idx, int which) {
+    const SparseStore* s = idx->sp;
+    if (!s) return 0;
+    switch (which) {
+    case kSparseStatDocs: return s->n_live;
+    case kSparseStatTotalLen: return s->total_len;
+    case kSparseStatPostings: return s->n_post;
+    default: return s->vocab;
+    }
+}
+
+}  // namespace mi355
+
+namespace {
+
+constexpr int32_t kTermLimit = 1 << 20;
+constexpr int kTfMax = 4095;
+constexpr int64_t kDocsMax = 0x7FFFFFFEll;
+
+// the term-major layout from the host's documents: counting sort by term, documents ascending inside a term
+int sparse_upload(mi355dr_index* idx, SparseStore* sp) {
+    if (!sp->stale) return MI355DR_OK;
+    std::vector<int64_t> off;
+    std::vector<int32_t> pdoc;
+    std::vector<uint16_t> ptf;
+    try {
+        off.assign((size_t)sp->vocab + 1, 0);
+        pdoc.resize((size_t)sp->n_post);
+        ptf.resize((size_t)sp->n_post);
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, "sparse store: host memory for the term-major layout");
+    }
+    for (int64_t t = 0; t < sp->vocab; ++t) off[t + 1] = off[t] + sp->df[t];
+    {
+        std::vector<int64_t> cur;
+        try {
+            cur.assign(off.begin(), off.end() - 1);
+        } catch (const std::bad_alloc&) {
+            return fail(idx, MI355DR_E_NOMEM, "sparse store: host memory for the term-major layout");
+        }
+        for (int64_t d = 0; d < sp->n_docs; ++d)
+            for (int64_t p = sp->doc_off[d]; p < sp->doc_off[d + 1]; ++p) {
+                const int64_t at = cur[sp->h_term[p]]++;
+                pdoc[at] = (int32_t)d;
+                ptf[at] = sp->h_tf[p];
+            }
+    }
+    DevBuf<int64_t> term_off;
+    DevBuf<int32_t> post_doc, len_dev;
+    DevBuf<uint16_t> post_tf;
+    DevBuf<double> norm;
+    HIPCHECK(idx, term_off.grow(off.size() * sizeof(int64_t)));
+    HIPCHECK(idx, post_doc.grow(std::max<size_t>(pdoc.size(), 1) * sizeof(int32_t)));
+    HIPCHECK(idx, post_tf.grow(std::max<size_t>(ptf.size(), 1) * sizeof(uint16_t)));
+    HIPCHECK(idx, len_dev.grow(std::max<size_t>(sp->doc_len.size(), 1) * sizeof(int32_t)));
+    HIPCHECK(idx, norm.grow(std::max<size_t>(sp->doc_len.size(), 1) * sizeof(double)));
+    HIPCHECK(idx, hipMemcpy(term_off.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (!pdoc.empty()) {
+        HIPCHECK(idx, hipMemcpy(post_doc.p, pdoc.data(), pdoc.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHECK(idx, hipMemcpy(post_tf.p, ptf.data(), ptf.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    }
+    if (!sp->doc_len.empty())
+        HIPCHECK(idx, hipMemcpy(len_dev.p, sp->doc_len.data(), sp->doc_len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    sp->term_off.swap(term_off);
+    sp->post_doc.swap(post_doc);
+    sp->post_tf.swap(post_tf);
+    sp->len_dev.swap(len_dev);
+    sp->norm.swap(norm);
+    sp->norm_valid = false;
+    sp->stale = false;
+    return MI355DR_OK;
+}
+
+inline int pow2_at_least(int n) {
+    int p = 1;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+struct SparseOut {
+    double* dist;
+    int64_t* rows;
+    bool host;
+};
+
+// the launch plan of one block: document ranges [a, a') of growing size.  The first holds at most `cap` documents, so its
+// lists cannot overflow; after `seen` documents a random order lets about k * new / seen of the next `new` beat the k-th kept
+// entry, and the ratio keeps that at half a list.
+std::vector<int64_t> sparse_plan(int64_t n, int k, int cap) {
+    std::vector<int64_t> edges{0};
+    const int64_t ratio = std::min<int64_t>(16, std::max<int64_t>(1, cap / (2 * (int64_t)k)));
+    int64_t seen = std::min<int64_t>(n, cap);
+    edges.push_back(seen);
+    while (seen < n) {
+        seen = std::min(n, seen + seen * ratio);
+        edges.push_back(seen);
+    }
+    return edges;
+}
+
+int launch_score(mi355dr_index* idx, SparseStore* sp, hipStream_t s, const SparseStoreView& view, const SparseQueries& qs,
+                 const SparseLists& ls, int64_t a0, int64_t a1, int nq, double k1p1) {
+    const int T = idx->sparse_tile_docs;
+    const int64_t tiles = (a1 - 1) / T - a0 / T + 1;
+    hipLaunchKernelGGL(k_sparse_score, dim3((unsigned)tiles, (unsigned)nq), dim3(kSparseThreads), sparse_score_lds(T), s, view, qs, ls,
+                       a0, a1, T, k1p1, sp->scored.p);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+// Queries [0, B) as flat host arrays -- every query's terms ascending, distinct, inside [0, 2^20), at most kSparseTermsMax --
+// against the store; results to `out` ([B, k], host or device).  The handle's mutex is held.
+int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, const std::vector<double>& weights,
+                         const std::vector<int32_t>& offsets, int B, int k, double k1, double b, SparseOut out, hipStream_t s) {
+    idx->s_sparse_searches++;
+    idx->s_sparse_queries += B;
+    if (B == 0) return MI355DR_OK;
+    if (!idx->sp) {
+        idx->sp = new (std::nothrow) SparseStore();
+        if (!idx->sp) return fail(idx, MI355DR_E_NOMEM, "sparse store: host memory");
+    }
+    SparseStore* sp = idx->sp;
+    if (sp->n_live > 0) CHECK(sparse_upload(idx, sp));
+    const int cap = idx->sparse_cand_cap;
+    const int64_t n = sp->n_live > 0 ? sp->n_docs : 0;
+    if (!sp->lds_registered) {
+        HIPCHECK(idx, hipFuncSetAttribute((const void*)k_sparse_score, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)sparse_score_lds(kSparseTileMax)));
+        sp->lds_registered = true;
+    }
+    if (n > 0 && !(sp->norm_valid && sp->norm_k1 == k1 && sp->norm_b == b)) {
+        const double avgdl = (double)sp->total_len / (double)sp->n_live;
+        hipLaunchKernelGGL(k_sparse_norms, dim3((unsigned)((n + kSparseThreads - 1) / kSparseThreads)), dim3(kSparseThreads), 0, s,
+                           sp->len_dev.p, n, avgdl, k1, b, sp->norm.p);
+        HIPCHECK(idx, hipGetLastError());
+        sp->norm_valid = true;
+        sp->norm_k1 = k1;
+        sp->norm_b = b;
+    }
+    const std::vector<int64_t> edges = sparse_plan(n, k, cap);
+    const int n_chunks = n > 0 ? (int)edges.size() - 1 : 0;
+    const int nb_max = std::min(B, kQBlockMax);
+    const int np_max = pow2_at_least(k + cap);
+    // every buffer of the call before its first launch: a failure leaves the store as it was
+    HIPCHECK(idx, grow_each((size_t)nb_max * k, sp->best_key, sp->best_doc));
+    HIPCHECK(idx, grow_each((size_t)nb_max * cap, sp->cand_key, sp->cand_doc));
+    HIPCHECK(idx, grow_each((size_t)nb_max, sp->count));
+    HIPCHECK(idx, grow_each((size_t)nb_max + 1, sp->q_off));
+    HIPCHECK(idx, grow_each((size_t)nb_max * (std::max(n_chunks, 1) + 1), sp->flags, sp->qlist));
+    HIPCHECK(idx, grow_each(1, sp->scored));
+    if (out.host) HIPCHECK(idx, grow_each((size_t)nb_max * k, sp->out_dist, sp->out_rows));
+    HIPCHECK(idx, hipMemsetAsync(sp->scored.p, 0, sizeof(unsigned long long), s));
+
+    const SparseStoreView view{sp->term_off.p, sp->post_doc.p, sp->post_tf.p, sp->norm.p, (int)sp->vocab};
+    const double k1p1 = k1 + 1.0;
+    std::vector<int32_t> off_block;
+    std::vector<int> flags_host, redo_q;
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        const int32_t t_lo = offsets[b0], t_hi = offsets[b0 + nb];
+        const size_t nt = (size_t)(t_hi - t_lo);
+        off_block.resize((size_t)nb + 1);
+        for (int i = 0; i <= nb; ++i) off_block[i] = offsets[b0 + i] - t_lo;
+        HIPCHECK(idx, grow_each(std::max<size_t>(nt, 1), sp->q_terms));
+        HIPCHECK(idx, grow_each(std::max<size_t>(nt, 1), sp->q_w));
+        // (in stream order behind the previous block; the host vectors stay as they are until the block's last wait)
+        if (nt) {
+            HIPCHECK(idx, hipMemcpyAsync(sp->q_terms.p, terms.data() + t_lo, nt * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            HIPCHECK(idx, hipMemcpyAsync(sp->q_w.p, weights.data() + t_lo, nt * sizeof(double), hipMemcpyHostToDevice, s));
+        }
+        HIPCHECK(idx, hipMemcpyAsync(sp->q_off.p, off_block.data(), off_block.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+
+        SparseLists ls{sp->best_key.p, sp->best_doc.p, sp->cand_key.p, sp->cand_doc.p, sp->count.p, k, cap};
+        SparseQueries qs{sp->q_terms.p, sp->q_w.p, sp->q_off.p, nullptr};
+        const int64_t n_best = (int64_t)nb * k, n_flags = (int64_t)nb * (n_chunks + 1);
+        const int64_t n_reset = std::max(n_best, n_flags);
+        hipLaunchKernelGGL(k_sparse_reset, dim3((unsigned)((n_reset + kSparseThreads - 1) / kSparseThreads)), dim3(kSparseThreads), 0, s,
+                           sp->best_key.p, sp->best_doc.p, n_best, sp->count.p, (int64_t)nb, sp->flags.p, n_flags);
+        HIPCHECK(idx, hipGetLastError());
+        if (nt > 0) {
+            for (int c = 0; c < n_chunks; ++c) {
+                CHECK(launch_score(idx, sp, s, view, qs, ls, edges[c], edges[c + 1], nb, k1p1));
+                hipLaunchKernelGGL(k_sparse_merge, dim3((unsigned)nb), dim3(kSparseThreads), sparse_merge_lds(np_max), s, ls,
+                                   (const int*)nullptr, np_max, sp->flags.p + (size_t)c * nb);
+                HIPCHECK(idx, hipGetLastError());
+            }
+            if (n_chunks > 1) {  // (the first launch cannot overflow)
+                flags_host.resize((size_t)n_chunks * nb);
+                HIPCHECK(idx, hipMemcpyAsync(flags_host.data(), sp->flags.p, flags_host.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+                HIPCHECK(idx, hipStreamSynchronize(s));
+                int* spare = sp->flags.p + (size_t)n_chunks * nb;  // the pieces' flags: must stay zero
+                for (int c = 1; c < n_chunks; ++c) {
+                    redo_q.clear();
+                    for (int q = 0; q < nb; ++q)
+                        if (flags_host[(size_t)c * nb + q]) redo_q.push_back(q);
+                    if (redo_q.empty()) continue;
+                    idx->s_sparse_overflows += (int64_t)redo_q.size();
+                    int* ql = sp->qlist.p + (size_t)c * nb;
+                    HIPCHECK(idx, hipMemcpyAsync(ql, redo_q.data(), redo_q.size() * sizeof(int), hipMemcpyHostToDevice, s));
+                    SparseQueries qr = qs;
+                    qr.qlist = ql;
+                    for (int64_t a = edges[c]; a < edges[c + 1]; a += cap) {
+                        CHECK(launch_score(idx, sp, s, view, qr, ls, a, std::min<int64_t>(a + cap, edges[c + 1]), (int)redo_q.size(), k1p1));
+                        hipLaunchKernelGGL(k_sparse_merge, dim3((unsigned)redo_q.size()), dim3(kSparseThreads), sparse_merge_lds(np_max),
+                                           s, ls, (const int*)ql, np_max, spare);
+                        HIPCHECK(idx, hipGetLastError());
+                    }
+                    // a piece holds at most `cap` documents: a flag here is a defect, not an overflow
+                    HIPCHECK(idx, hipMemcpyAsync(flags_host.data(), spare, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
+                    HIPCHECK(idx, hipStreamSynchronize(s));
+                    for (int q = 0; q < nb; ++q)
+                        if (flags_host[q]) return fail(idx, MI355DR_E_INTERNAL, "sparse search: a piece of at most cap documents overflowed");
+                }
+            }
+        }
+        double* od = out.host ? sp->out_dist.p : out.dist + (int64_t)b0 * k;
+        int64_t* orow = out.host ? sp->out_rows.p : out.rows + (int64_t)b0 * k;
+        hipLaunchKernelGGL(k_sparse_final, dim3((unsigned)((n_best + kSparseThreads - 1) / kSparseThreads)), dim3(kSparseThreads), 0, s,
+                           sp->best_key.p, sp->best_doc.p, n_best, idx->row_offset, od, orow);
+        HIPCHECK(idx, hipGetLastError());
+        if (out.host) {
+            HIPCHECK(idx, hipMemcpyAsync(out.dist + (int64_t)b0 * k, od, (size_t)n_best * sizeof(double), hipMemcpyDeviceToHost, s));
+            HIPCHECK(idx, hipMemcpyAsync(out.rows + (int64_t)b0 * k, orow, (size_t)n_best * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHECK(idx, hipStreamSynchronize(s));
+    }
+    unsigned long long scored = 0;
+    HIPCHECK(idx, hipMemcpy(&scored, sp->scored.p, sizeof(scored), hipMemcpyDeviceToHost));
+    idx->s_sparse_postings_scored += (int64_t)scored;
+    return MI355DR_OK;
+}
+
+int check_common(mi355dr_index* idx, const int32_t* q_offsets, int B, int k, double k1, double b, const void* od, const void* orow) {
+    if (B < 0 || k <= 0) return fail(idx, MI355DR_E_INVALID, "sparse search: B must be >= 0 and k > 0");
+    if (k > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, "sparse search: k exceeds 1024");
+    if (!(k1 >= 0.0) || !std::isfinite(k1)) return fail(idx, MI355DR_E_INVALID, "sparse search: k1 must be finite and >= 0");
+    if (!(b >= 0.0 && b <= 1.0)) return fail(idx, MI355DR_E_INVALID, "sparse search: b must be in [0, 1]");
+    if (B > 0 && (!q_offsets || !od || !orow)) return fail(idx, MI355DR_E_INVALID, "sparse search: null buffer");
+    for (int i = 0; i < B; ++i)
+        if (q_offsets[i] < 0 || q_offsets[i + 1] < q_offsets[i])
+            return fail(idx, MI355DR_E_INVALID, "sparse search: q_offsets must start at >= 0 and never decrease");
+    return MI355DR_OK;
+}
+
+// the lock, the device, blocks in flight finished, the stream
+int sparse_begin(mi355dr_index* idx, std::unique_lock<std::mutex>& lock, void* stream, hipStream_t* s) {
+    lock = std::unique_lock<std::mutex>(idx->mu);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_searches(idx));
+    *s = stream ? (hipStream_t)stream : idx->stream;
+    return MI355DR_OK;
+}
+
+int search_sparse_impl(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B, int k,
+                       double k1, double b, SparseOut out, void* stream) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s = nullptr;
+    CHECK(sparse_begin(idx, lock, stream, &s));
+    CHECK(check_common(idx, q_offsets, B, k, k1, b, out.dist, out.rows));
+    std::vector<int32_t> terms, offsets;
+    std::vector<double> weights;
+    try {
+        offsets.assign((size_t)B + 1, 0);
+        std::vector<std::pair<int32_t, double>> one;
+        for (int q = 0; q < B; ++q) {
+            const int32_t lo = q_offsets[q], hi = q_offsets[q + 1];
+            if (hi > lo && (!q_terms || !q_weights)) return fail(idx, MI355DR_E_INVALID, "sparse search: null query");
+            if (hi - lo > kSparseTermsMax) return fail(idx, MI355DR_E_UNSUPPORTED, "sparse search: more than 1024 terms in one query");
+            one.clear();
+            for (int32_t p = lo; p < hi; ++p) {
+                const double w = q_weights[p];
+                if (q_terms[p] < 0 || q_terms[p] >= kTermLimit)
+                    return fail(idx, MI355DR_E_INVALID, "sparse search: term id outside [0, 2^20)");
+                if (!std::isfinite(w) || std::fabs(w) > 1e30)
+                    return fail(idx, MI355DR_E_INVALID, "sparse search: weights must be finite with |w| <= 1e30");
+                one.emplace_back(q_terms[p], w);
+            }
+            std::sort(one.begin(), one.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+            for (size_t i = 1; i < one.size(); ++i)
+                if (one[i].first == one[i - 1].first) return fail(idx, MI355DR_E_INVALID, "sparse search: a term is repeated in one query");
+            for (const auto& tw : one) {
+                terms.push_back(tw.first);
+                weights.push_back(tw.second);
+            }
+            offsets[(size_t)q + 1] = (int32_t)terms.size();
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, "sparse search: host memory");
+    }
+    return sparse_search_sorted(idx, terms, weights, offsets, B, k, k1, b, out, s);
+}
+
+int search_bm25_impl(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1, double b,
+                     SparseOut out, void* stream) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s = nullptr;
+    CHECK(sparse_begin(idx, lock, stream, &s));
+    CHECK(check_common(idx, q_offsets, B, k, k1, b, out.dist, out.rows));
+    const SparseStore* sp = idx->sp;
+    const int64_t N = sp ? sp->n_live : 0, vocab = sp ? sp->vocab : 0;
+    std::vector<int32_t> terms, offsets, one;
+    std::vector<double> weights;
+    try {
+        offsets.assign((size_t)B + 1, 0);
+        for (int q = 0; q < B; ++q) {
+            const int32_t lo = q_offsets[q], hi = q_offsets[q + 1];
+            if (hi > lo && !q_tokens) return fail(idx, MI355DR_E_INVALID, "bm25 search: null query");
+            one.assign(q_tokens + lo, q_tokens + hi);
+            std::sort(one.begin(), one.end());
+            one.erase(std::unique(one.begin(), one.end()), one.end());
+            if ((int64_t)one.size() > kSparseTermsMax)
+                return fail(idx, MI355DR_E_UNSUPPORTED, "bm25 search: more than 1024 distinct terms in one query");
+            for (const int32_t t : one) {
+                if (t < 0 || t >= vocab) continue;
+                const int64_t df = sp->df[t];
+                if (df == 0) continue;
+                terms.push_back(t);
+                weights.push_back(std::log(1.0 + (((double)(N - df) + 0.5) / ((double)df + 0.5))));
+            }
+            offsets[(size_t)q + 1] = (int32_t)terms.size();
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, "bm25 search: host memory");
+    }
+    return sparse_search_sorted(idx, terms, weights, offsets, B, k, k1, b, out, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi355dr_add_sparse(mi355dr_index* idx, const int32_t* terms, const int64_t* offsets, int64_t n_docs) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "add_sparse");
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_searches(idx));
+    if (n_docs < 0 || !offsets) return fail(idx, MI355DR_E_INVALID, "add_sparse: n_docs must be >= 0 and offsets not null");
+    if (offsets[0] < 0) return fail(idx, MI355DR_E_INVALID, "add_sparse: offsets must start at >= 0");
+    for (int64_t d = 0; d < n_docs; ++d) {
+        if (offsets[d + 1] < offsets[d]) return fail(idx, MI355DR_E_INVALID, "add_sparse: offsets must never decrease");
+        if (offsets[d + 1] - offsets[d] > INT32_MAX) return fail(idx, MI355DR_E_UNSUPPORTED, "add_sparse: a document of more than 2^31 - 1 tokens");
+    }
+    if (offsets[n_docs] > offsets[0] && !terms) return fail(idx, MI355DR_E_INVALID, "add_sparse: null terms");
+    const int64_t have = idx->sp ? idx->sp->n_docs : 0;
+    if (have + n_docs > kDocsMax) return fail(idx, MI355DR_E_UNSUPPORTED, "add_sparse: more than 2^31 - 2 documents");
+    if (n_docs == 0) return MI355DR_OK;
+    try {
+        // the new documents as sorted (term, tf) pairs, checked, before anything of the store changes
+        std::vector<int32_t> a_term, a_len, one;
+        std::vector<uint16_t> a_tf;
+        std::vector<int64_t> a_off;
+        a_off.reserve((size_t)n_docs);
+        a_len.reserve((size_t)n_docs);
+        int64_t max_term = -1, live = 0, total = 0;
+        for (int64_t d = 0; d < n_docs; ++d) {
+            one.assign(terms + offsets[d], terms + offsets[d + 1]);
+            std::sort(one.begin(), one.end());
+            if (!one.empty() && (one.front() < 0 || one.back() >= kTermLimit))
+                return fail(idx, MI355DR_E_INVALID, "add_sparse: term id outside [0, 2^20) in document " + std::to_string(d));
+            for (size_t i = 0; i < one.size();) {
+                size_t j = i;
+                while (j < one.size() && one[j] == one[i]) ++j;
+                if (j - i > (size_t)kTfMax)
+                    return fail(idx, MI355DR_E_UNSUPPORTED, "add_sparse: a term occurs more than 4095 times in document " + std::to_string(d));
+                a_term.push_back(one[i]);
+                a_tf.push_back((uint16_t)(j - i));
+                i = j;
+            }
+            a_off.push_back((int64_t)a_term.size());
+            a_len.push_back((int32_t)one.size());
+            if (!one.empty()) {
+                max_term = std::max<int64_t>(max_term, one.back());
+                ++live;
+                total += (int64_t)one.size();
+            }
+        }
+        if (!idx->sp) idx->sp = new SparseStore();
+        SparseStore* sp = idx->sp;
+        // room first: what follows cannot fail
+        sp->doc_len.reserve(sp->doc_len.size() + a_len.size());
+        sp->doc_off.reserve(sp->doc_off.size() + a_off.size());
+        sp->h_term.reserve(sp->h_term.size() + a_term.size());
+        sp->h_tf.reserve(sp->h_tf.size() + a_tf.size());
+        if (max_term + 1 > sp->vocab) sp->df.reserve((size_t)(max_term + 1));
+        if (max_term + 1 > sp->vocab) {
+            sp->df.resize((size_t)(max_term + 1), 0);
+            sp->vocab = max_term + 1;
+        }
+        const int64_t base = sp->n_post;
+        sp->doc_len.insert(sp->doc_len.end(), a_len.begin(), a_len.end());
+        for (const int64_t o : a_off) sp->doc_off.push_back(base + o);
+        sp->h_term.insert(sp->h_term.end(), a_term.begin(), a_term.end());
+        sp->h_tf.insert(sp->h_tf.end(), a_tf.begin(), a_tf.end());
+        for (const int32_t t : a_term) sp->df[t]++;
+        sp->n_docs += n_docs;
+        sp->n_live += live;
+        sp->total_len += total;
+        sp->n_post += (int64_t)a_term.size();
+        sp->stale = true;
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, "add_sparse: host memory");
+    }
+    return MI355DR_OK;
+}
+
+int64_t mi355dr_size_sparse(const mi355dr_index* idx) { return idx && idx->sp ? idx->sp->n_docs : 0; }
+
+int mi355dr_sparse_df(mi355dr_index* idx, const int32_t* terms, int64_t n, int64_t* out_df) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (n < 0 || (n > 0 && (!terms || !out_df))) return fail(idx, MI355DR_E_INVALID, "sparse_df: bad arguments");
+    const SparseStore* sp = idx->sp;
+    for (int64_t i = 0; i < n; ++i) out_df[i] = sp && terms[i] >= 0 && terms[i] < sp->vocab ? sp->df[terms[i]] : 0;
+    return MI355DR_OK;
+}
+
+int mi355dr_search_sparse(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B, int k,
+                          double k1, double b, double* out_dist, int64_t* out_rows) {
+    return search_sparse_impl(idx, q_terms, q_weights, q_offsets, B, k, k1, b, SparseOut{out_dist, out_rows, true}, nullptr);
+}
+int mi355dr_search_sparse_device(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B,
+                                 int k, double k1, double b, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
+    return search_sparse_impl(idx, q_terms, q_weights, q_offsets, B, k, k1, b, SparseOut{out_dist_dev, out_rows_dev, false}, stream);
+}
+int mi355dr_search_bm25(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1, double b,
+                        double* out_dist, int64_t* out_rows) {
+    return search_bm25_impl(idx, q_tokens, q_offsets, B, k, k1, b, SparseOut{out_dist, out_rows, true}, nullptr);
+}
+int mi355dr_search_bm25_device(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1, double b,
+                               double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
+    return search_bm25_impl(idx, q_tokens, q_offsets, B, k, k1, b, SparseOut{out_dist_dev, out_rows_dev, false}, stream);
+}
+
+}  // extern "C"

@@ -652,6 +652,77 @@ class Mi355Index:
                                                             ptr(rows, ctypes.c_int64)))
         return dist, rows
 
+    # ---- sparse store: tokenised documents, weighted / BM25 top-k (include/mi355dr.h "sparse store") ----
+    @staticmethod
+    def _ragged_i32(lists_or_flat, offsets, off_dtype) -> tuple[np.ndarray, np.ndarray]:
+        """(flat int32, offsets [n + 1]) from a list of token lists (offsets None) or from the flat pair itself."""
+        if offsets is None:
+            lists = [np.asarray(t, dtype=np.int64).reshape(-1) for t in lists_or_flat]
+            off = np.zeros(len(lists) + 1, dtype=np.int64)
+            if lists:
+                off[1:] = np.cumsum([t.shape[0] for t in lists])
+            flat = np.concatenate(lists) if lists else np.zeros(0, np.int64)
+        else:
+            flat = np.asarray(lists_or_flat, dtype=np.int64).reshape(-1)
+            off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+            if off.shape[0] < 1 or off[0] != 0 or off[-1] != flat.shape[0] or np.any(np.diff(off) < 0):
+                raise ValueError("offsets must start at 0, never decrease and end at the number of tokens")
+        if flat.size and (flat.min() < np.iinfo(np.int32).min or flat.max() > np.iinfo(np.int32).max):
+            raise ValueError("token ids must fit int32")
+        if off[-1] > np.iinfo(off_dtype).max:
+            raise ValueError("too many tokens for one call")
+        return np.ascontiguousarray(flat, dtype=np.int32), np.ascontiguousarray(off, dtype=off_dtype)
+
+    def add_sparse(self, token_lists, offsets=None) -> None:
+        """Append tokenised documents: a list of int token lists, or (terms, offsets [n_docs + 1]).  A document without tokens
+        takes an id and never matches.  A term id outside [0, 2^20) or a term more than 4095 times in one document: NativeError,
+        nothing changes."""
+        terms, off = self._ragged_i32(token_lists, offsets, np.int64)
+        check(self._h, self._lib.mi355dr_add_sparse(self._h, ptr(terms, ctypes.c_int32), ptr(off, ctypes.c_int64), off.shape[0] - 1))
+
+    def size_sparse(self) -> int:
+        """Stored sparse documents, with or without tokens."""
+        return int(self._lib.mi355dr_size_sparse(self._h))
+
+    def sparse_df(self, terms) -> np.ndarray:
+        """Document frequency of each term (0 for unseen and out-of-range ids)."""
+        t = np.ascontiguousarray(np.asarray(terms, dtype=np.int64).reshape(-1).clip(-1, 2**31 - 1), dtype=np.int32)
+        out = np.zeros(t.shape[0], dtype=np.int64)
+        check(self._h, self._lib.mi355dr_sparse_df(self._h, ptr(t, ctypes.c_int32), t.shape[0], ptr(out, ctypes.c_int64)))
+        return out
+
+    def _sparse_call(self, B: int, k: int, device_out: bool, host_call, device_call) -> tuple[np.ndarray, np.ndarray]:
+        if device_out:  # the _device form into buffers of this call, downloaded
+            return self._device_results(B, max(int(k), 0), False, lambda d, r, _c: check(self._h, device_call(
+                ctypes.c_void_p(d), ctypes.c_void_p(r), _stream_arg(None))))
+        dist = np.empty((B, max(int(k), 0)), dtype=np.float64)
+        rows = np.empty((B, max(int(k), 0)), dtype=np.int64)
+        check(self._h, host_call(ptr(dist, ctypes.c_double), ptr(rows, ctypes.c_int64)))
+        return dist, rows
+
+    def search_sparse(self, terms, weights, offsets, k: int, k1: float = 1.2, b: float = 0.75,
+                      device_out: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """Weighted sparse top-k: query j is terms[offsets[j]:offsets[j + 1]] (distinct) with the weights alongside.  Returns
+        (distance float64 [B, k] = -score, ids int64 [B, k]); NaN / -1 behind the matches."""
+        t, off = self._ragged_i32(terms, offsets, np.int32)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != t.shape[0]:
+            raise ValueError("weights must have one entry per term")
+        B = off.shape[0] - 1
+        a = (self._h, ptr(t, ctypes.c_int32), ptr(w, ctypes.c_double), ptr(off, ctypes.c_int32), B, int(k), float(k1), float(b))
+        return self._sparse_call(B, k, device_out, lambda d, r: self._lib.mi355dr_search_sparse(*a, d, r),
+                                 lambda d, r, s: self._lib.mi355dr_search_sparse_device(*a, d, r, s))
+
+    def search_bm25(self, token_lists, k: int, k1: float = 1.2, b: float = 0.75, device_out: bool = False,
+                    offsets=None) -> tuple[np.ndarray, np.ndarray]:
+        """BM25 top-k of raw token queries (repeats count once, unseen terms are dropped; idf by libm's log on the host).
+        Returns (distance float64 [B, k] = -score, ids int64 [B, k]).  `device_out`: through the _device form."""
+        t, off = self._ragged_i32(token_lists, offsets, np.int32)
+        B = off.shape[0] - 1
+        a = (self._h, ptr(t, ctypes.c_int32), ptr(off, ctypes.c_int32), B, int(k), float(k1), float(b))
+        return self._sparse_call(B, k, device_out, lambda d, r: self._lib.mi355dr_search_bm25(*a, d, r),
+                                 lambda d, r, s: self._lib.mi355dr_search_bm25_device(*a, d, r, s))
+
     # ---- multi-vector ----
     def add_multivec(self, vecs, offsets) -> None:
         vecs = f32c(vecs)

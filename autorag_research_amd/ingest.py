@@ -141,7 +141,8 @@ class StoreTarget:
         return out
 
     def populate_bm25_tokens(self, entity: str, tokenizer: str, batch_size: int) -> int:
-        """The in-memory tables have no `bm25_tokens` column (BM25 is the reference's own SQL: out of scope); nothing to do."""
+        """The in-memory tables have no `bm25_tokens` column: the service tokenises `contents` itself when it builds a unit's
+        sparse store (service._UnitIndex.ensure_sparse, bm25.py); nothing to do."""
         return 0
 
     def set_embeddings(self, entity: str, emb_type: str, ids: list, embeddings: list) -> int:

@@ -182,6 +182,10 @@ class _UnitIndex:
         # refresh compacts by itself once dead / size reaches this fraction, or the head of the index is dead (None: never)
         self.compact_dead_fraction = compact_dead_fraction
         self._pos_of_id = self._stored_row_of_pos = None   # (dict) caches of pos_of_id() / stored_row_of_pos(): see _forget_maps
+        # the sparse store of `table.contents` under one tokenizer (BM25): document id = table position.  It is replicated, not
+        # sharded, and rebuilt whole when the contents it was built from are no longer the table's (`ensure_sparse`)
+        self.sparse: Mi355Index | None = None
+        self._sparse_of: tuple[Any, list] | None = None    # (tokenizer key, the contents list it was built from)
 
     def _not_null_positions(self) -> np.ndarray:
         emb = self.table.embedding
@@ -245,11 +249,35 @@ class _UnitIndex:
             self.multi_rows = np.arange(off.shape[0] - 1)
         return self.multi
 
+    def ensure_sparse(self, tokenizer: Any) -> Mi355Index:
+        """The sparse store of the table's contents under `tokenizer` (a name or a callable, bm25.get_tokenizer): one document
+        per table position, None = a document without tokens, so ids stay positions.  Built on first use; a refresh that
+        changed the contents, or another tokenizer, rebuilds it whole."""
+        from .bm25 import get_tokenizer, tokenizer_key  # noqa: PLC0415
+
+        key, contents = tokenizer_key(tokenizer), self.table.contents
+        if self.sparse is not None and self._sparse_of is not None and self._sparse_of[0] == key:
+            if self._sparse_of[1] is contents:
+                return self.sparse
+            if self._sparse_of[1] == contents:   # a newer export with the same contents: remember its list, compare once
+                self._sparse_of = (key, contents)
+                return self.sparse
+        if self.sparse is not None:
+            self.sparse.close()
+            self.sparse = None
+        tok = get_tokenizer(tokenizer)
+        docs = [[] if c is None else tok(c if isinstance(c, str) else bytes(c).decode("utf-8", "replace")) for c in contents]
+        ix = Mi355Index(8, "cosine", self.device)  # (the handle's dense side stays empty)
+        ix.add_sparse(docs)
+        self.sparse, self._sparse_of = ix, (key, contents)
+        return ix
+
     def close(self) -> None:
-        for ix in (self.single, self.multi, self.single_sharded, self.multi_sharded):
+        for ix in (self.single, self.multi, self.single_sharded, self.multi_sharded, self.sparse):
             if ix is not None:
                 ix.close()
-        self.single = self.multi = self.single_sharded = self.multi_sharded = None
+        self.single = self.multi = self.single_sharded = self.multi_sharded = self.sparse = None
+        self._sparse_of = None
         self._start_over(self.table)
 
     # ---- primary key -> table position -> index row (the GQR pools and the candidate scorer name chunks by key) ----
@@ -640,6 +668,36 @@ class Mi355RetrievalService:
             return self.maxsim_search_by_embeddings([q.embeddings for q in queries], top_k, unit, within=within)
         Q = np.stack([q.embedding for q in queries]).astype(np.float32, copy=False)
         return self._single_block(Q, top_k, unit, within, mmr_fetch_k, mmr_lambda)
+
+    # ---- BM25: the lexical leg, over the unit's sparse store (reference retrieval_pipeline.py:398-465) ----
+    def _bm25_block(self, texts: list[str], top_k: int, tokenizer: Any, k1: float, b: float) -> list[list[dict]]:
+        """A page of query texts as one block.  Under a process group every rank holds the whole sparse store and computes the
+        same lists.  score = -distance: positive, higher is better, as the reference negates the operator's (chunk.py:236)."""
+        from .bm25 import get_tokenizer  # noqa: PLC0415
+
+        u = self._unit("chunk")
+        ix = u.ensure_sparse(tokenizer)
+        tok = get_tokenizer(tokenizer)
+        dist, rows = ix.search_bm25([tok(t) for t in texts], top_k, k1=k1, b=b)
+        return self._results_from_block(u.table, np.arange(len(u.table.ids)), rows, -dist, True)
+
+    def bm25_search(self, query_ids: list[int | str], top_k: int = 10, tokenizer: Any = "simple",
+                    index_name: str = "idx_chunk_bm25", k1: float = 1.2, b: float = 0.75) -> list[list[dict]]:
+        """BM25 top-k for every query id, scored as one block (reference bm25_search, :425-465; `index_name` is recorded by the
+        pipeline and unused here).  Raises ValueError exactly like the reference."""
+        texts = []
+        for qid, q in zip(query_ids, self.get_queries(list(query_ids)), strict=True):
+            if q is None:
+                raise ValueError(f"Query {qid} not found")  # noqa: TRY003
+            texts.append(q.contents or "")
+        if not texts:
+            return []
+        return self._bm25_block(texts, top_k, tokenizer, k1, b)
+
+    def bm25_search_by_text(self, query_text: str, top_k: int = 10, tokenizer: Any = "simple",
+                            index_name: str = "idx_chunk_bm25", k1: float = 1.2, b: float = 0.75) -> list[dict]:
+        """BM25 top-k of a raw query text, no query row needed (reference bm25_search_by_text, :398-423)."""
+        return self._bm25_block([query_text], top_k, tokenizer, k1, b)[0]
 
     def _check_mmr(self, search_mode: str, mmr_fetch_k: int | None) -> None:
         """MMR is a single-vector, single-GPU selection: it scores stored rows against each other, and under row shards the

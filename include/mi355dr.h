@@ -505,6 +505,60 @@ int mi355dr_search_maxsim_subset_device(mi355dr_index* idx, const float* qtok_de
                                         const int64_t* doc_ids, int64_t m, float* out_dist_dev, int64_t* out_rows_dev,
                                         void* stream); /* doc_ids and q_offsets stay on the HOST */
 
+/* ---- sparse store: tokenised documents, weighted / BM25 top-k scored on the device ----
+ * The lexical leg of the hybrid pipelines (the reference's BM25RetrievalPipeline is one SQL statement against
+ * VectorChord-BM25).  That extension's float4 arithmetic and pg_tokenizer's vocabularies cannot be pinned without a
+ * PostgreSQL, so THIS HEADER FIXES THE ARITHMETIC ITSELF; agreement with the reference is claimed on the interface only
+ * (signatures, the sign and order of scores, result dicts), never on score bits.
+ *
+ * Store.  Document i is a sequence of int32 term ids, any order, repeats allowed; tf(i,t) = occurrences of t in i, L_i = the
+ *   sequence's length.  Ids are dense in insertion order and stable; a returned id is the local id + option "row_offset".  A
+ *   document without tokens is stored and takes an id, but is not a document for the statistics and never matches.
+ *   N = documents with tokens, total_len = sum of L_i, df(t) = documents with tf(i,t) > 0.
+ * Limits.  A term id outside [0, 2^20): MI355DR_E_INVALID.  tf(i,t) > 4095: MI355DR_E_UNSUPPORTED.  At most 2^31 - 2
+ *   documents.  A refused add changes nothing.  Several adds answer exactly as one add of the concatenation.
+ * Weighted score (mi355dr_search_sparse*).  Query j is q_terms[q_offsets[j] .. q_offsets[j+1]) with weights alongside: DISTINCT
+ *   terms in [0, 2^20), finite weights with |w| <= 1e30 (else E_INVALID; more than 1024 terms: E_UNSUPPORTED).  The library
+ *   sorts a query's terms ascending.  Everything is IEEE double, one rounding per operation, no fused multiply-add:
+ *       avgdl  = (double)total_len / (double)N
+ *       norm_i = k1 * ((1.0 - b) + b * ((double)L_i / avgdl))
+ *       score  = +0.0;  for t in the query's terms, ASCENDING term id, with tf = tf(i,t) > 0:
+ *                    frac  = ((double)tf * (k1 + 1.0)) / ((double)tf + norm_i)
+ *                    score = score + (w_t * frac)
+ *       distance(i) = -score
+ *   Document i MATCHES iff it holds at least one query term (a score of zero or below still matches).  A result line is the
+ *   first k matches under (distance asc, NaN last, id asc), NaN / -1 behind them; a query with no term, or none that occurs,
+ *   and every query over an empty store give an all NaN / -1 line.  k1 >= 0 finite and b in [0, 1], else E_INVALID; k > 1024:
+ *   E_UNSUPPORTED; B above 1024 runs in internal blocks.
+ * BM25 (mi355dr_search_bm25*).  A query is a raw token sequence: repeats count once, terms with df = 0 (or outside
+ *   [0, 2^20)) are dropped, and the weights are computed ON THE HOST with libm's log,
+ *       w_t = log(1.0 + (((double)(N - df) + 0.5) / ((double)df + 0.5)))
+ *   then the weighted search runs.  No transcendental runs on the device.
+ * Calls run under the handle's mutex, first complete whatever search is in flight, and are complete on return.  The _device
+ *   forms take the QUERY on the host and write the results to device memory on `stream` (null: the handle's).  A failed
+ *   allocation returns E_NOMEM with nothing changed.  The term-major device layout is rebuilt by the first search after an add
+ *   (host counting sort + upload); the host keeps the documents as sorted (term, tf) pairs, 6 bytes per posting.
+ * Options: "sparse_tile_docs" (documents per LDS tile, a power of two 256 .. 8192, default 2048), "sparse_cand_cap" (slots of a
+ *   query's candidate list, 16 .. 2048 [default]; a list that overflows is dropped whole and its document range run again in
+ *   pieces that cannot overflow -- same results).  Stats: "sparse_docs" (N), "sparse_total_len", "sparse_postings" (distinct
+ *   (doc, term) pairs), "sparse_vocab" (largest term id + 1), "sparse_searches" (calls), "sparse_queries",
+ *   "sparse_postings_scored", "sparse_overflows" ((query, launch) lists run again); the store's device bytes are part of
+ *   "hbm_bytes_resident".
+ * Views: a view has an empty sparse store and refuses mi355dr_add_sparse; mi355dr_compact does not touch the sparse store.
+ * Out of scope: update / remove / compact of sparse documents, views over the store, a row-sharded sparse search (it needs
+ *   global df / avgdl), a key filter, fusion on the device, any claim of bit parity with VectorChord-BM25. */
+int mi355dr_add_sparse(mi355dr_index* idx, const int32_t* terms, const int64_t* offsets /* [n_docs + 1] */, int64_t n_docs); /* host */
+int64_t mi355dr_size_sparse(const mi355dr_index* idx); /* stored documents, with or without tokens */
+int mi355dr_sparse_df(mi355dr_index* idx, const int32_t* terms, int64_t n, int64_t* out_df); /* 0 for unseen / out-of-range terms */
+int mi355dr_search_sparse(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets /* [B + 1] */,
+                          int B, int k, double k1, double b, double* out_dist /* [B, k] */, int64_t* out_rows /* [B, k] */);
+int mi355dr_search_sparse_device(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets,
+                                 int B, int k, double k1, double b, double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+int mi355dr_search_bm25(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets /* [B + 1] */, int B, int k, double k1,
+                        double b, double* out_dist, int64_t* out_rows);
+int mi355dr_search_bm25_device(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1,
+                               double b, double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+
 /* ---- Guided Query Refinement of candidate pools (GQR hybrid pipeline) ----
  * Replaces the per-query numpy loops of autorag_research/pipelines/retrieval/gqr_hybrid.py: `_optimize_query_embedding`
  * (:321-340), `_optimize_query_multi_embedding` (:342-362), `_optimize_in_score_space` (:306-319).  Float64 throughout
