@@ -26,6 +26,7 @@ static_assert(kSortMax >= kKMax + kCandCap, "the general prune's sort must hold 
 // status bits per query
 constexpr int kStOverflow = 1;   // candidate buffer overflowed in some chunk -> result must be recomputed
 constexpr int kStIrregular = 2;  // query norm is zero / non-finite / out of the screen's range
+constexpr int kStSpecMiss = 4;   // speculative pass: the pass's own k-th best does not justify the threshold its screen ran at
 
 // per-query search state (device arrays, one slot per query of the current block)
 struct QueryState {
@@ -46,6 +47,24 @@ struct QueryState {
     float* kq;          // [Bpad] int8 screen: factor on a row group's residual norm, 1.0001 + 3 e_q
     int8_t* qhat8;      // [Bpad, dpad8] int8 quantised normalised queries
     int* carry;         // [Bpad] candidates at the head of the list that an earlier prune of this pass carried over (k_prune, defer_b)
+    float* thr_used;    // [Bpad] speculative pass: the threshold its one screen launch ran at (-inf: nothing to verify)
+};
+
+// ---- the speculative one-chunk pass ----
+// m(k): rows the model threshold expects above it, from tools/spec_model.py's rule (the smallest m whose mean miss margin is
+// 5 of its standard deviations at n = 2^20 and n = 10^7, d = 768); 0 = no m inside the one-wave prune's budget,
+// kSpecInflation * m <= 0.75 * (1024 - k): such a k never speculates.  tests/test_spec_model.py holds the table to the rule.
+constexpr int kSpecKMax = 32;
+constexpr int kSpecSlabsMax = 256;  // slabs of the starter's sample at these k (16 384 rows): the moment scratch is 2 MB
+constexpr int kSpecInflation = 10;  // candidates per row expected above the threshold: what the schedule budgets for the int8 bound
+constexpr int kSpecM[kSpecKMax + 1] = {0,  0,  74, 58, 54, 53, 53, 54, 55, 57, 58, 60, 62, 64, 66, 68, 70,
+                                       71, 73, 75, 0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0,  0};
+inline int spec_m_of(int k) { return k >= 1 && k <= kSpecKMax ? kSpecM[k] : 0; }  // (host)
+// what the starter's prune needs for the model threshold t = mean + sd * zq of a query's sampled screen values
+struct SpecModel {
+    const float* moments;  // [Bpad, slabs, 2] per query and 64-row slab of the sample: sum and sum of squares (nullptr: no model)
+    int slabs, rows;       // slabs per query; rows the sums run over
+    float zq;              // Phi^-1(1 - m / n) + the lab shift, from the host
 };
 
 // bf16 value (upper 16 bits) back to fp32

@@ -88,6 +88,12 @@ struct Pass {
     bool i8 = false;         // the screen's element type: int8, else bf16 (also what k_prep_queries quantises for)
     bool wide = false;       // its prunes take the two-wave form (screening passes at 33 <= k <= 128)
     int cap = 0;             // candidate slots per query = the lists' stride
+    // one screen launch over all rows at a threshold the starter's sample PREDICTS, verified against the pass's own k-th best
+    // (DESIGN.md 4.3): a first attempt that screens behind the starter, at a k with an admissible m(k), on a corpus of at least
+    // spec_min_rows rows, with option "speculate" on and the index not on speculation probation
+    bool speculative = false;
+    bool spec_eligible = false;  // ... all of that but the probation
+    int spec_m = 0;         // rows the model threshold expects above it (dev_common.h kSpecM)
     const char* refused = nullptr;  // not null: no pass may run, MI355DR_E_UNSUPPORTED with this text
 };
 // one block between enqueue_block() and complete_block() (mi355dr.hip)
@@ -273,6 +279,13 @@ struct mi355dr_index {
     int screen_dtype = 0;  // MI355DR_SCREEN_AUTO
     int i8_backoff = 0, i8_probation = 0;  // demotion is not for ever: after i8_probation more blocks at such a k AUTO tries int8 again;
                                            // the wait doubles (16 ... 4096 blocks) every time that try overflows again
+    // speculative passes (Pass::speculative): a block of which more than 1 % missed or overflowed suspends them for spec_probation
+    // first attempts -- 16 at first, doubling up to 4096 with every block that fails again; option "speculate" re-arms
+    int speculate = 1;
+    int64_t spec_min_rows = (int64_t)1 << 20;  // 64 samples: smaller corpora keep the ladder
+    int spec_shift_milli = 0;  // lab: added to zq in thousandths of the sample's standard deviation (makes the model wrong on purpose)
+    int spec_backoff = 0, spec_probation = 0;
+    mi355::DevBuf<float> spec_moments;  // [kQBlockMax, kSpecSlabsMax, 2] the starter's per-slab sums (screen_hits.h)
     int i8_demoted_k = INT_MAX;  // AUTO saw the int8 bound overflow on this corpus' score distribution at this k: bf16 from there up
     double i8_min_budget = 0.25;  // AUTO keeps the int8 screen while growth_budget(k, int8) stays above this (k <= 133)
     mi355::RetryBufs retry[3];  // one set per level: the nested call owns the next
@@ -362,6 +375,8 @@ struct mi355dr_index {
     mi355::DevBuf<int> rq_progress;  // [kRqProgressWords] the limiter's progress words
     int rq_epoch = 0;            // launch stamp of the last k_screen_rq launch (1 ... 4095)
     int64_t s_rq_launches = 0;  // of them: k_screen_rq launches (stat "screen_rq_launches")
+    // speculative passes, and their queries that missed the verification / overflowed a list (both also count as retry_queries)
+    int64_t s_spec_passes = 0, s_spec_miss_queries = 0, s_spec_overflow_queries = 0;
     int64_t s_retry_queries = 0;  // queries whose candidate list overflowed and that were re-screened with the bf16 bound
     int64_t s_ms_screened = 0, s_ms_candidates = 0, s_ms_fallbacks = 0;  // MaxSim: queries screened, docs re-scored, full re-runs
     // option "profile": HIP-event time of the MaxSim screen launches (k_maxsim16*) and of the exact launches on candidate lists

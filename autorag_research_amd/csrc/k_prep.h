@@ -223,6 +223,7 @@ __global__ __launch_bounds__(64) void k_prep_queries(const float* __restrict__ q
             st.thr[b] = __builtin_inff();
             st.cnt[b] = 0;
             st.carry[b] = 0;
+            st.thr_used[b] = -__builtin_inff();
             st.best_n[b] = 0;
             st.thr_key[b] = 0;
             st.thr_row[b] = -1;
@@ -297,6 +298,7 @@ __global__ __launch_bounds__(64) void k_prep_queries(const float* __restrict__ q
         st.thr[b] = (regular || metric == 2) ? -__builtin_inff() : __builtin_inff();
         st.cnt[b] = cnt0;  // (> 0: the starter writes one candidate per slab at fixed slots)
         st.carry[b] = 0;
+        st.thr_used[b] = -__builtin_inff();  // (a speculative pass's starter prune says what its screen runs at)
         st.best_n[b] = 0;
         st.thr_key[b] = kKeyNaN;
         st.thr_row[b] = 0x7FFFFFFF;

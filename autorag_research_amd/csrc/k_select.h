@@ -50,6 +50,11 @@ struct PruneArgs {
     // cut.  The threshold a deferring prune publishes comes from kept U round A alone: any k exact scores bound the k-th
     // best from below.  One-wave form only (the general form re-scores everything it is handed).
     int defer_b;
+    // starter of a speculative pass (thr_only): behind the rigorous threshold the wave reduces its query's slab
+    // sums (the starter's epilogue, screen_hits.h) to the sample's mean and standard deviation and publishes
+    // max(rigorous, threshold of t = mean + sd * zq) in st.thr AND st.thr_used -- a PREDICTION, which k_finalize verifies
+    // against the pass's own k-th best.  A query without a rigorous threshold keeps what it has.
+    SpecModel spec;
 };                         // (the screen bound is per query: st.E[q])
 
 // Similarity of an exact key in the SCREEN's units: the cosine itself, or dot / |q| (the inner-product shadows hold the rows
@@ -433,6 +438,25 @@ __device__ __forceinline__ void prune_body(const PruneArgs& a, char* smem) {
                     bkey[i] = K2[i];
                     brow[i] = R2[i];
                 }
+            float t_model = -__builtin_inff();  // speculative pass: the sample's mean + sd * zq, in the screen's units
+            if (a.thr_only && a.spec.moments != nullptr) {
+                const float* mo = a.spec.moments + (int64_t)q * a.spec.slabs * 2;
+                double s1 = 0.0, s2 = 0.0;
+                for (int i = lane; i < a.spec.slabs; i += kWave) {
+                    s1 += (double)mo[2 * i];
+                    s2 += (double)mo[2 * i + 1];
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    s1 += __shfl_xor(s1, o, kWave);
+                    s2 += __shfl_xor(s2, o, kWave);
+                }
+                // (the divisor is the sample's size: the few values the sums leave out -- NaN images of irregular rows, at most
+                // kIrrCap of them -- are not counted, which pulls mean and variance towards 0 by their share.  An estimate.)
+                const double mean = s1 / (double)a.spec.rows;
+                const double var = s2 / (double)a.spec.rows - mean * mean;
+                t_model = (float)(mean + sqrt(var > 0.0 ? var : 0.0) * (double)a.spec.zq);
+            }
             if (lane == 0) {
                 if (!a.thr_only) a.st.best_n[q] = n_keep;
                 a.st.cnt[q] = carried;  // (the next chunk's appends go behind the carried survivors)
@@ -443,8 +467,17 @@ __device__ __forceinline__ void prune_body(const PruneArgs& a, char* smem) {
                         a.st.thr_key[q] = wk;
                         a.st.thr_row[q] = R2[a.k - 1];
                     }
-                    if (wk != kKeyNaN && !(a.st.status[q] & kStIrregular))
-                        a.st.thr[q] = screen_threshold(a.metric, key_to_dist(wk), E, nq);
+                    if (wk != kKeyNaN && !(a.st.status[q] & kStIrregular)) {
+                        float thr = screen_threshold(a.metric, key_to_dist(wk), E, nq);
+                        if (a.thr_only && a.spec.moments != nullptr) {
+                            // the distance a row of screen value t would have: 1 - t (cosine), -t |q| (inner product)
+                            const double dist_t = a.metric == 0 ? 1.0 - (double)t_model : -(double)t_model * sqrt((double)nq);
+                            const float thr_model = screen_threshold(a.metric, dist_t, E, nq);
+                            if (thr_model > thr && thr_model < __builtin_inff()) thr = thr_model;  // (NaN, +inf: the rigorous one)
+                            a.st.thr_used[q] = thr;
+                        }
+                        a.st.thr[q] = thr;
+                    }
                 }
             }
             return;
@@ -597,9 +630,21 @@ __global__ __launch_bounds__(64) void k_emit_irregular(const int32_t* __restrict
 // grid: B blocks of 64 threads.  row_map (a view: mi355dr_view_create) names the global id of every stored row; else it is
 // row + row_offset
 __global__ __launch_bounds__(64) void k_finalize(QueryState st, int k, int64_t row_offset, const int64_t* __restrict__ row_map,
-                                                  double* out_dist, int64_t* out_rows, int* status_or) {
+                                                  double* out_dist, int64_t* out_rows, int* status_or, int spec_metric) {
     const int q = blockIdx.x;
     const int n = st.best_n[q];
+    // Verification of a speculative pass (spec_metric = its metric, else -1): the screen ran at thr_used, a
+    // prediction.  If the threshold the k-th kept exact distance allows is at or above it, every row that reaches the true
+    // k-th best had a bound at or above thr_used and was a candidate: the kept top-k is the corpus's.  Otherwise (or with
+    // fewer than k kept) the query is flagged and done again by the ladder.  An irregular query is recomputed anyway.
+    if (threadIdx.x == 0 && spec_metric >= 0 && !(st.status[q] & kStIrregular)) {
+        float thr_final = -__builtin_inff();
+        if (n >= k) {
+            const uint64_t wk = st.best_key[(int64_t)q * kKMax + k - 1];
+            if (wk != kKeyNaN) thr_final = screen_threshold(spec_metric, key_to_dist(wk), st.E[q], st.qn[q]);
+        }
+        if (n < k || thr_final < st.thr_used[q]) st.status[q] |= kStSpecMiss;
+    }
     for (int s = threadIdx.x; s < k; s += blockDim.x) {
         // (a kept entry with row kRowNone is a removed row that filled a slot no live row claimed: "no result")
         if (s < n && st.best_row[(int64_t)q * kKMax + s] != kRowNone) {

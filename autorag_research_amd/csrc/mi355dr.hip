@@ -121,6 +121,8 @@ int ensure_qstate(mi355dr_index* idx) {
     HIPCHECK(idx, hipMemset(idx->rq_progress, 0, kRqProgressWords * sizeof(int)));
     HIPCHECK(idx, own(idx->st.qhat8, B * idx->dpad8));
     HIPCHECK(idx, own(idx->st.carry, B * sizeof(int)));
+    HIPCHECK(idx, own(idx->st.thr_used, B * sizeof(float)));
+    HIPCHECK(idx, idx->spec_moments.grow(B * kSpecSlabsMax * 2 * sizeof(float)));
     HIPCHECK(idx, idx->qdev.grow(B * idx->dim * sizeof(float)));
     HIPCHECK(idx, idx->cand_row.grow(B * kCandCapWide * sizeof(int32_t)));
     HIPCHECK(idx, idx->cand_val.grow(B * kCandCapWide * sizeof(float)));
@@ -246,6 +248,18 @@ inline double growth_budget(const mi355dr_index* idx, int k, bool i8) {
 // Which screen: int8 needs a corpus that quantised within the limit and (in AUTO) a k small enough that its wider bound still
 // allows chunks to grow (k <= 133 at the default budget line); larger k keeps bf16.
 inline bool i8_available(const mi355dr_index* idx) { return idx->irr8_n <= kIrrCap; }
+constexpr int kStarterKMax = 32;          // the starter's round A re-scores max(32, 2k) <= 64 rows: one batch of the one-wave form
+constexpr int64_t kStarterRows = 16384;   // sample size (256 slabs); a corpus must hold at least 4 samples
+static_assert(kStarterRows / kSlabRows <= kSpecSlabsMax, "the moment scratch holds one entry per slab of the starter's sample");
+// rows the starter of a pass samples, 0 if the pass takes the emit-all ladder (the reasons: plan_pass)
+int64_t starter_sample_rows(const mi355dr_index* idx, const Pass& ps) {
+    const int64_t n = idx->n;
+    const int64_t rows = std::min<int64_t>(ps.wide ? idx->starter_rows_wide : kStarterRows, n / 4) / kTileM * kTileM;
+    const int64_t slabs = (rows + kSlabRows - 1) / kSlabRows;
+    const bool take = idx->starter && (ps.k <= kStarterKMax || ps.wide) && ps.level == 0 && idx->chunk0_set == 0 && n >= 4 * 1024 &&
+                      slabs <= ps.cap && slabs >= ps.k;
+    return take ? rows : 0;
+}
 Pass decide_pass(const mi355dr_index* idx, int k, int level, bool force_scan, const char* no_screen = nullptr) {
     Pass ps;
     ps.k = k;
@@ -268,14 +282,23 @@ Pass decide_pass(const mi355dr_index* idx, int k, int level, bool force_scan, co
     if (idx->screen_dtype == MI355DR_SCREEN_I8 && !i8_available(idx) && path != MI355DR_PATH_SCAN)
         ps.refused = "int8 screen unavailable: too many rows outside the residual limit";
     else if (path == MI355DR_PATH_SCREEN && !screen_possible && idx->n > 0) ps.refused = no_screen;
+    // speculative one-chunk pass: m(k) inside the one-wave prune's budget (the compiled-in table holds only such k: the
+    // inequality is tools/spec_model.py's, checked again here for a list stride the caller shrank)
+    ps.spec_m = spec_m_of(k);
+    // (spec_eligible: everything but the probation -- enqueue_block counts a suspension down on exactly these passes)
+    ps.spec_eligible = level == 0 && ps.screening && !ps.wide && ps.spec_m > 0 && idx->speculate && idx->n >= idx->spec_min_rows &&
+                       kSpecInflation * ps.spec_m * 4 <= 3 * (std::min(kPruneSmallSort, ps.cap) - k) &&
+                       starter_sample_rows(idx, ps) > 0;
+    ps.speculative = ps.spec_eligible && idx->spec_probation <= 0;
     return ps;
 }
 // between searches (stat "screen_dtype_active", the debug entry points): the screen a first attempt at the last k would take
 inline bool idle_i8(const mi355dr_index* idx) { return decide_pass(idx, idx->last_pass_k, 0, false).i8; }
 
 int launch_prune(mi355dr_index* idx, hipStream_t s, const Pass& ps, int nblocks, const int* qlist, int exact,
-                 bool thr_only = false, bool one_wave_only = false, bool defer_b = false) {
+                 bool thr_only = false, bool one_wave_only = false, bool defer_b = false, const SpecModel* spec = nullptr) {
     PruneArgs pa{};
+    if (spec) pa.spec = *spec;  // (the starter's prune of a speculative pass)
     pa.thr_only = thr_only ? 1 : 0;
     pa.one_wave_only = one_wave_only ? 1 : 0;
     pa.defer_b = defer_b && idx->defer_round_b ? 1 : 0;
@@ -359,7 +382,7 @@ inline ScreenKernel screen_kernel_for(const mi355dr_index* idx, bool i8, int B, 
 // launch one screen pass over rows [r0, r_end) (r0 a multiple of the tile edge); flush_mask: k_screen_rq's common flush
 // period - 1 (-1: every wave on its own)
 int launch_screen(mi355dr_index* idx, hipStream_t s, bool i8, int B, int64_t r0, int64_t r_end, int cap, int emit_mode,
-                  int flush_mask) {
+                  int flush_mask, int moment_slabs = 0) {
     const bool emit_all = emit_mode != 0;  // (both special epilogues live in k_screen)
     const ScreenKernel kern = screen_kernel_for(idx, i8, B, r_end - r0, emit_all);
     const int tile = kern == kKern256c || kern == kKernRq ? kT2 : kTileM;
@@ -384,6 +407,10 @@ int launch_screen(mi355dr_index* idx, hipStream_t s, bool i8, int B, int64_t r0,
     sa.row_end = r_end;
     sa.row0 = r0;
     sa.emit_all = emit_mode;
+    if (moment_slabs > 0) {  // the starter of a speculative pass: per-slab sums behind the slab maxima
+        sa.moments = idx->spec_moments;
+        sa.moment_slabs = moment_slabs;
+    }
     const int64_t grid = round_up(sa.n_ctiles, 8) * sa.n_qtiles;
     switch (kern) {
     case kKernRq: {
@@ -462,9 +489,10 @@ int launch_screen(mi355dr_index* idx, hipStream_t s, bool i8, int B, int64_t r0,
 //    chunk) to the end, then one uniform ratio (N / S)^(1/n) -- no short last chunk with a prune of its own.
 //  * (Option prune_companion = 0: no general-form launch behind the one-wave prune, what it cannot hold is flagged and
 //    re-screened -- measured slower: see index.h.)
-constexpr int kStarterKMax = 32;          // the starter's round A re-scores max(32, 2k) <= 64 rows: one batch of the one-wave form
-constexpr int64_t kStarterRows = 16384;   // sample size (256 slabs); a corpus must hold at least 4 samples
-// (a pass at 33 <= k <= 128 samples idx->starter_rows_wide rows: 65536 = 1024 slabs by default)
+// (kStarterKMax, kStarterRows: above decide_pass; a pass at 33 <= k <= 128 samples idx->starter_rows_wide rows: 65536 = 1024 slabs
+// by default)
+//  * SPECULATIVE passes (Pass::speculative): the starter, then ONE chunk over all rows at the threshold the
+//    starter's prune predicts from the sample's moments; k_finalize verifies it, complete_block re-runs what it rejects.
 struct PassPlan {
     int64_t sample = 0;          // > 0: starter over rows [0, sample)
     std::vector<int64_t> ends;   // chunk ends, ascending, last = n; the first chunk starts at 0 (starter) or is the emit-all one
@@ -473,7 +501,7 @@ struct PassPlan {
 PassPlan plan_pass(const mi355dr_index* idx, const Pass& ps, int B, double growth) {
     PassPlan p;
     const int64_t n = idx->n;
-    const int k = ps.k, cap = ps.cap;
+    const int cap = ps.cap;
     const bool wide = ps.wide;
     const int tile = screen_tile(B);
     int64_t seen = 0;  // rows whose k-th best the first planned chunk's threshold comes from
@@ -484,12 +512,14 @@ PassPlan plan_pass(const mi355dr_index* idx, const Pass& ps, int B, double growt
     // (4096 <= n < 8192 with k in 17..32).  Either way: the emit-all ladder.
     // Round 6, 33 <= k <= 128 (two-wave prune): the same estimator over a 64 k-row sample -- 1024 slab maxima per query, of
     // which the prune re-scores the 128 best-looking; their k-th best exact score is (about) the k-th best of the sample.
-    const int64_t starter_rows = std::min<int64_t>(wide ? idx->starter_rows_wide : kStarterRows, n / 4) / kTileM * kTileM;
-    const int64_t starter_slabs = (starter_rows + kSlabRows - 1) / kSlabRows;
-    if (idx->starter && (k <= kStarterKMax || wide) && ps.level == 0 && idx->chunk0_set == 0 && n >= 4 * 1024 &&
-        starter_slabs <= cap && starter_slabs >= k) {
+    const int64_t starter_rows = starter_sample_rows(idx, ps);
+    if (starter_rows > 0) {
         p.sample = starter_rows;
         seen = p.sample;
+        if (ps.speculative) {  // one chunk: its threshold does not come from rows seen before
+            p.ends.push_back(n);
+            return p;
+        }
     } else {
         const int64_t c0 = std::min<int64_t>(n, round_up(std::max<int64_t>(tile, std::min<int64_t>(idx->chunk0_rows, cap)), tile));
         p.emit_all_first = c0 <= cap;
@@ -536,6 +566,17 @@ PassPlan plan_pass(const mi355dr_index* idx, const Pass& ps, int B, double growt
 
 inline int starter_count(const PassPlan& p) { return (int)((p.sample + kSlabRows - 1) / kSlabRows); }
 
+// Phi^-1(p), 0 < p < 1, by bisection on erfc (host, once per speculative pass; tools/spec_model.py does the same)
+inline double normal_quantile(double p) {
+    double lo = -40.0, hi = 40.0;
+    for (int i = 0; i < 200; ++i) {
+        const double mid = 0.5 * (lo + hi);
+        if (0.5 * std::erfc(-mid / std::sqrt(2.0)) < p) lo = mid;
+        else hi = mid;
+    }
+    return 0.5 * (lo + hi);
+}
+
 PassPlan make_plan(const mi355dr_index* idx, const Pass& ps, int B) {
     // (measured round 3, N = 10 M, k = 10: a ratio of 4 per step -- 5 chunks -- 7.43 ms, the budget's 4.8 -- 4 chunks -- 7.54)
     const double budget = growth_budget(idx, ps.k, ps.i8);
@@ -580,8 +621,21 @@ int run_screen(mi355dr_index* idx, hipStream_t s, const Pass& ps, int B, const P
     };
     if (plan.sample > 0) {
         // (the flush mask: none of the slab-maximum epilogue's kernels reads it)
-        CHECK(timed(false, plan.sample, [&] { return launch_screen(idx, s, i8, B, 0, plan.sample, ps.cap, kEmitSlabMax, -1); }));
-        CHECK(launch_prune(idx, s, ps, B, nullptr, /*exact=*/0, /*thr_only=*/true, /*one_wave_only=*/true));
+        SpecModel sm{};
+        if (ps.speculative) {
+            // zq = Phi^-1(1 - m / n): the Gaussian quantile above which m of the n rows are expected (no inverse error function
+            // on the device); the lab shift makes the model wrong on purpose
+            sm.moments = idx->spec_moments;
+            sm.slabs = starter_count(plan);
+            sm.rows = (int)plan.sample;
+            sm.zq = (float)(normal_quantile(1.0 - (double)ps.spec_m / (double)idx->n) + idx->spec_shift_milli / 1000.0);
+            idx->s_spec_passes++;
+        }
+        CHECK(timed(false, plan.sample, [&] {
+            return launch_screen(idx, s, i8, B, 0, plan.sample, ps.cap, kEmitSlabMax, -1, ps.speculative ? sm.slabs : 0);
+        }));
+        CHECK(launch_prune(idx, s, ps, B, nullptr, /*exact=*/0, /*thr_only=*/true, /*one_wave_only=*/true, false,
+                           ps.speculative ? &sm : nullptr));
         idx->s_starters++;
     }
     int64_t done = 0;
@@ -594,7 +648,9 @@ int run_screen(mi355dr_index* idx, hipStream_t s, const Pass& ps, int B, const P
         // hit lanes a wave of k_screen_rq expects per tile (32 queries x 128 rows): rows above the threshold of `seen` rows
         // ~ k x inflation / seen per row and query (inflation of the int8 bound ~8)
         const int64_t seen = ci == 0 ? (plan.sample > 0 ? plan.sample : end) : done;
-        const double lanes = 8.0 * ps.k * 4096.0 / (double)std::max<int64_t>(seen, 1);
+        // (a speculative pass's one chunk: kSpecInflation x m candidates expected over all n rows, whatever was seen before)
+        const double lanes = ps.speculative ? (double)kSpecInflation * ps.spec_m * 4096.0 / (double)idx->n
+                                            : 8.0 * ps.k * 4096.0 / (double)std::max<int64_t>(seen, 1);
         int period = 1;
         while (period < 64 && period * 2 * lanes <= idx->screen_flush_lanes) period *= 2;
         const int flush_mask = idx->screen_flush_sync ? period - 1 : -1;
@@ -726,7 +782,7 @@ int subset_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, i
     for (int i = 0; i < B; ++i) all[i] = i;
     if (m > 0) CHECK(run_scan(idx, s, ps, all, m, idx->subset_ids));
     hipLaunchKernelGGL(k_finalize, dim3(B), dim3(64), 0, s, idx->st, k, idx->row_offset, idx->view_row_map.p, out_dist_dev,
-                       out_rows_dev, idx->status_or_dev);
+                       out_rows_dev, idx->status_or_dev, /*spec_metric=*/-1);
     HIPCHECK(idx, hipGetLastError());
     HIPCHECK(idx, hipMemcpyAsync(idx->status_host, idx->st.status, (size_t)kQBlockMax * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHECK(idx, hipStreamSynchronize(s));
@@ -766,6 +822,8 @@ int enqueue_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, 
     // (before the plan and the first launch: every kernel of the pass sees one screen type and one list stride)
     const Pass ps = decide_pass(idx, k, level, force_scan, "screen path unavailable (metric or too many irregular rows)");
     if (ps.refused) return fail(idx, MI355DR_E_UNSUPPORTED, ps.refused);
+    // suspended speculation: passes that would have speculated count the probation down (this one takes the ladder)
+    if (idx->spec_probation > 0 && ps.spec_eligible) idx->spec_probation--;
     if (q_dev != idx->qdev)
         HIPCHECK(idx, hipMemcpyAsync(idx->qdev, q_dev, (size_t)B * idx->dim * sizeof(float), hipMemcpyDeviceToDevice, s));
     PassPlan plan;
@@ -781,8 +839,9 @@ int enqueue_block(mi355dr_index* idx, hipStream_t s, const float* q_dev, int B, 
             CHECK(run_scan(idx, s, ps, all, idx->n));  // (blocks on the host only where a chunk larger than the buffer overflowed)
         }
     }
+    // (a speculative pass is verified here: queries whose own k-th best does not justify the threshold they ran at are flagged)
     hipLaunchKernelGGL(k_finalize, dim3(B), dim3(64), 0, s, idx->st, k, idx->row_offset, idx->view_row_map.p, out_dist_dev,
-                       out_rows_dev, idx->status_or_dev);
+                       out_rows_dev, idx->status_or_dev, ps.speculative && idx->n > 0 ? idx->metric : -1);
     HIPCHECK(idx, hipGetLastError());
     // (one copy: the per-query words and, behind them, their OR)
     HIPCHECK(idx, hipMemcpyAsync(p.status_host, idx->st.status, (size_t)(kQBlockMax + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -823,6 +882,10 @@ int complete_block(mi355dr_index* idx, Pending& p) {
         for (int i = 0; i < B; ++i) {
             const int st = p.status_host[i];
             if (st == 0) continue;
+            if (p.pass.speculative && !(st & kStIrregular)) {  // (a speculative pass is level 0: these are re-run by the ladder)
+                if (st & kStOverflow) idx->s_spec_overflow_queries++;
+                else if (st & kStSpecMiss) idx->s_spec_miss_queries++;
+            }
             // an overflow at the first attempt is re-screened with the tighter bound and slower growth; whatever
             // overflows again, and every query the screen cannot rank (irregular norm), is recomputed exactly
             if (level < kRetryLevels && !(st & kStIrregular)) retry.push_back(i);
@@ -854,7 +917,18 @@ int complete_block(mi355dr_index* idx, Pending& p) {
         // Not for ever -- a burst of queries into one dense neighbourhood must not cost a Gaussian-like corpus its int8 screen
         // (7.4 against 12.8 ms per block at the headline size): after 16 more blocks at such a k int8 gets another try, and the
         // wait doubles (up to 4096 blocks) whenever that try overflows again.
-        if (p.pass.i8 && idx->screen_dtype == MI355DR_SCREEN_AUTO && n_retry * 100 > B) {
+        // A speculative pass's misses and overflows speak of the MODEL, not of the int8 bound: they do not demote the screen.
+        // More than 1 % of a block suspends speculation instead, the same way -- 16 first attempts, doubling up to 4096 with
+        // every block that fails again, re-armed by option "speculate" -- so a corpus the model is wrong about costs one failed
+        // block per probation period.  (Blocks already in flight finish as they were enqueued.)
+        if (p.pass.speculative) {
+            // (while suspended, a failing block is one that was in flight when the suspension began: the same verdict, not a
+            // second one -- four blocks of one burst do not take the wait from 16 to 128)
+            if (n_retry * 100 > B && idx->spec_probation <= 0) {
+                idx->spec_backoff = idx->spec_backoff == 0 ? 16 : std::min(idx->spec_backoff * 2, 4096);
+                idx->spec_probation = idx->spec_backoff;
+            }
+        } else if (p.pass.i8 && idx->screen_dtype == MI355DR_SCREEN_AUTO && n_retry * 100 > B) {
             idx->i8_demoted_k = std::min(idx->i8_demoted_k, k);
             idx->i8_backoff = idx->i8_backoff == 0 ? 16 : std::min(idx->i8_backoff * 2, 4096);
             idx->i8_probation = idx->i8_backoff;
@@ -1362,6 +1436,7 @@ int mi355dr_compact(mi355dr_index* idx, int64_t* new_of_old) {
     // setting "screen_dtype" does
     idx->i8_demoted_k = INT_MAX;
     idx->i8_backoff = idx->i8_probation = 0;
+    idx->spec_backoff = idx->spec_probation = 0;  // (so was a suspended speculation: the sample is of other rows now)
     idx->s_compactions += n_moved > 0;  // (a call that only dropped a dead tail moved nothing)
     idx->s_compact_moved_rows += n_moved;
     if (new_of_old) {
@@ -2727,6 +2802,9 @@ const Option kOptions[] = {
     {"chunk0_rows", &Index::chunk0_rows, 1, INT64_MAX, [](Index* x) { x->chunk0_set = 1; }},
     {"starter", {&Index::starter, kSwitch}},
     {"prune_companion", {&Index::prune_companion, kSwitch}},
+    {"speculate", {&Index::speculate, kSwitch}, INT64_MIN, INT64_MAX, [](Index* x) { x->spec_backoff = x->spec_probation = 0; }},  // (re-arms)
+    {"spec_min_rows", &Index::spec_min_rows, 0},
+    {"spec_shift_milli", &Index::spec_shift_milli, -20000, 20000},  // lab: makes the model threshold wrong by this many thousandths of a standard deviation
     {"scan_dma", {&Index::scan_dma, kSwitch}},
     {"defer_round_b", {&Index::defer_round_b, kSwitch}},
     {"chunk_growth", &Index::chunk_growth, 1, INT64_MAX, [](Index* x) { x->chunk_growth_set = 1; }},
@@ -2774,6 +2852,10 @@ const Stat kStats[] = {
     {"passes", &Index::s_passes, true},
     {"starters", &Index::s_starters, true},
     {"retry_queries", &Index::s_retry_queries, true},
+    {"spec_passes", &Index::s_spec_passes, true},
+    {"spec_miss_queries", &Index::s_spec_miss_queries, true},
+    {"spec_overflow_queries", &Index::s_spec_overflow_queries, true},
+    {"spec_suspended", nullptr, false, [](const Index* x) -> int64_t { return x->spec_probation > 0 ? 1 : 0; }},
     {"maxsim_screened", &Index::s_ms_screened, true},
     {"maxsim_candidates", &Index::s_ms_candidates, true},
     {"maxsim_fallbacks", &Index::s_ms_fallbacks, true},
@@ -2843,6 +2925,8 @@ const Stat kStats[] = {
      }},
 };
 }  // namespace
+
+int mi355dr_debug_spec_m(int k) { return spec_m_of(k); }  // (no index, no device: tests/test_spec_model.py holds it to the rule)
 
 int mi355dr_set_option(mi355dr_index* idx, const char* key, int64_t value) {
     if (!idx || !key) return fail(idx, MI355DR_E_INVALID, "null argument");

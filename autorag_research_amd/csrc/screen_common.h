@@ -38,6 +38,8 @@ struct ScreenArgs {
     int64_t row0;     // first row of this chunk
     int emit_all;     // 1 = first chunk: every (query,row) is a candidate -> direct store at slot row-row0, no atomics;
                       // 2 = starter (k_screen only): per query and 64-row slab ONLY the largest value, at slot (slab index)
+    float* moments;   // starter of a speculative pass (else nullptr): [Bpad, moment_slabs, 2] sum and sum of squares of the
+    int moment_slabs; // slab's screen values, per query -- the sample the model threshold is predicted from (k_select.h)
 };
 constexpr int kEmitAll = 1, kEmitSlabMax = 2;
 constexpr int kSlabRows = 64;  // rows of one wave's sub-tile in k_screen: the starter keeps one candidate per slab and query

@@ -92,6 +92,39 @@ __device__ __forceinline__ void screen_emit_slab_max(const ScreenArgs& a, const 
                                                      int lane, const I8Blk (&blk)[2]) {
     float best = -__builtin_inff();
     int64_t best_row = slab_row0;
+    if (a.moments != nullptr) {  // wave-uniform: a speculative pass's sample moments (no atomics: one writer per query and slab)
+        // sum and sum of squares of the screen's ESTIMATE of the similarity, over the slab's rows below row_end: the bf16 value
+        // itself; int8: S_q S_g acc WITHOUT the group's share e_g kq of the bound, which the compared value carries on top.  The
+        // model threshold is verified against exact similarities (k_finalize), so it has to be predicted in their units: with
+        // e_g kq left in (0.28 of a standard deviation at d = 768) the prediction sits that much too high, and a sixth of the
+        // headline's queries missed.  NaN images (bf16, irregular rows) are left out; stale zeros of rows outside the int8
+        // shadow stay in: nothing rigorous reads this
+        float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int64_t rb = slab_row0 + 32 * i + 4 * (lane >> 5);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float v;
+                if constexpr (I8) v = (float)__builtin_bit_cast(i32x16, acc[i])[r] * blk[i].m;
+                else v = acc[i][r];
+                if (rb + (r & 3) + 8 * (r >> 2) < a.row_end && v == v) {
+                    s1 += v;
+                    s2 = __builtin_fmaf(v, v, s2);
+                }
+            }
+        }
+        s1 += __shfl_xor(s1, 32, kWave);
+        s2 += __shfl_xor(s2, 32, kWave);
+        if (lane < 32) {
+            const int64_t slot = (slab_row0 - a.row0) / kSlabRows;
+            if (slot < a.moment_slabs) {
+                float* mo = a.moments + ((int64_t)q * a.moment_slabs + slot) * 2;
+                mo[0] = s1;
+                mo[1] = s2;
+            }
+        }
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int64_t rbase = slab_row0 + 32 * i + 4 * (lane >> 5);

@@ -707,8 +707,17 @@ int mi355dr_mmr_select_sharded(mi355dr_index* idx, const float* queries, int B, 
  *          rounded up to 8-token granules instead of 32-token blocks, built on the first such pass and extended by the next one after an add -- -1
  *          [default]: when it has at least 5 % fewer blocks than the padded copy and its memory is there, 1: always, 0: never;
  *          identical results); "range_chunk_rows" and "range_slots" (mi355dr_search_range, described there).
+ *          The speculative one-chunk pass (identical results): "speculate" (1 [default]: a first attempt at a
+ *          k with an admissible m(k) -- 2 <= k <= 19 -- on a corpus of at least "spec_min_rows" [1048576] rows screens all rows
+ *          in ONE launch at a threshold predicted from the starter's sample and verifies it against its own k-th best; 0: the
+ *          chunk ladder; setting it also ends a suspension), "spec_shift_milli" (lab option, [-20000, 20000], default 0: moves
+ *          the predicted threshold by value / 1000 standard deviations of the sample, so that a test can make it wrong).
  * stats:   "screen_launches", "screen_ns" (profile=1), "screen_rows" (all screen launches) and their k_screen256 share
  *          "screen256_launches", "screen256_ns", "screen256_rows"; "candidates", "rescored",
+ *          "spec_passes" (speculative passes), "spec_miss_queries" / "spec_overflow_queries" (their queries whose k-th best did
+ *          not justify the threshold / whose candidate list overflowed: re-run by the ladder, counted in "retry_queries" too,
+ *          never held against the int8 screen), "spec_suspended" (1 while speculation is suspended: more than 1 % of a block
+ *          failed; 16 passes that would have speculated, doubling up to 4096 with every later block that fails),
  *          "fallback_queries" (queries recomputed by the exact scan), "retry_queries" (queries whose candidate list
  *          overflowed and that were re-screened with the bf16 bound and slower chunk growth first), "i8_demoted" (AUTO
  *          gave up the int8 screen for this index after > 1 % of a block overflowed -- from "i8_demoted_k", the k of that
@@ -802,6 +811,9 @@ int mi355dr_debug_screen_bound(mi355dr_index* idx, const float* queries, int B, 
  * step S_g and the measured residual norm e_g.  Screen value of (query, row) = S_q S_g (q8 . c8) + e_g kq. */
 int mi355dr_debug_i8_state(mi355dr_index* idx, const float* queries, int B, float* out_sq, float* out_kq, int64_t g0,
                            int64_t n_groups, float* out_step, float* out_err);
+/* m(k) of the speculative pass as compiled in: the rows its predicted threshold expects above it; 0 = this k never
+ * speculates.  Needs no index and no device. */
+int mi355dr_debug_spec_m(int k);
 /* exact fp32 chain + distance for explicit (query,row) pairs, computed by the re-score device code */
 int mi355dr_debug_rescore(mi355dr_index* idx, const float* queries, int B, const int32_t* pair_q,
                           const int64_t* pair_row, int64_t n_pairs, float* out_dot, double* out_dist);
