@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "mi355dr_search_maxsim", "mi355dr_search_maxsim_device", "mi355dr_search_maxsim_subset", "mi355dr_search_maxsim_subset_device", "mi355dr_maxsim_subset", "mi355dr_maxsim_subset_ex", "mi355dr_add_multivec_device", "mi355dr_gqr_refine", "mi355dr_gqr_refine_maxsim",
     "mi355dr_set_multivec", "mi355dr_set_multivec_device", "mi355dr_live_multivec",
     "mi355dr_add_sparse", "mi355dr_size_sparse", "mi355dr_sparse_df", "mi355dr_search_sparse", "mi355dr_search_sparse_device",
-    "mi355dr_search_bm25", "mi355dr_search_bm25_device",
+    "mi355dr_search_bm25", "mi355dr_search_bm25_device", "mi355dr_set_sparse", "mi355dr_remove_sparse", "mi355dr_live_sparse",
     "mi355dr_gqr_refine_scores", "mi355dr_merge_topk_device", "mi355dr_pack_topk_device",
     "mi355dr_merge_topk_packed_device", "mi355dr_comm_unique_id", "mi355dr_comm_init", "mi355dr_comm_world", "mi355dr_comm_count", "mi355dr_comm_init_custom",
     "mi355dr_search_sharded_device", "mi355dr_search_range_sharded_device", "mi355dr_search_rows_sharded_device",
@@ -193,6 +193,12 @@ def load() -> ctypes.CDLL:
     L.mi355dr_add_sparse.argtypes = [vp, i32p, i64p, i64]
     L.mi355dr_size_sparse.restype = i64
     L.mi355dr_size_sparse.argtypes = [vp]
+    L.mi355dr_set_sparse.restype = c_int
+    L.mi355dr_set_sparse.argtypes = [vp, i64p, i32p, i64p, i64]
+    L.mi355dr_remove_sparse.restype = c_int
+    L.mi355dr_remove_sparse.argtypes = [vp, i64p, i64]
+    L.mi355dr_live_sparse.restype = i64
+    L.mi355dr_live_sparse.argtypes = [vp]
     L.mi355dr_sparse_df.restype = c_int
     L.mi355dr_sparse_df.argtypes = [vp, i32p, i64, i64p]
     L.mi355dr_search_sparse.restype = c_int

@@ -412,6 +412,14 @@ struct mi355dr_index {
     int sparse_tile_docs = 2048;  // documents per LDS tile of k_sparse_score (option "sparse_tile_docs": a power of two, 256 .. 8192;
                                   // 2048 was the fastest of 1024 .. 8192 at 3, 8 and 24 terms per query: DESIGN.md section 4.8j)
     int sparse_cand_cap = 2048;   // slots of a query's sparse candidate list (option "sparse_cand_cap", 16 .. 2048)
+    // the first search after add / set / remove of sparse documents rebuilds the overlay alone while the moved documents'
+    // postings are at most this many percent of the base layout's, else the whole layout (option "sparse_overlay_max_pct",
+    // 0 .. 100; 0: always the whole layout).  25: the largest size measured, where the overlay build still cost a quarter of
+    // the full build's time and the steady block time was below an untouched store's; above it
+    // nothing was measured
+    int sparse_overlay_max_pct = 25;
+    // layout builds of the sparse store by kind, and documents given to mi355dr_set_sparse / mi355dr_remove_sparse
+    int64_t s_sparse_full_builds = 0, s_sparse_overlay_builds = 0, s_sparse_sets = 0;
     int64_t s_ms_screen_cols = 0;  // query-vector columns (whole blocks of 32) the screen launches multiplied every token by
     mi355::Event ms_ev[4];
     // which MaxSim screen launch ran last, written on the host next to the launch (mi355dr_debug_maxsim_pass reports it).
@@ -458,7 +466,7 @@ int multivec_reserve(mi355dr_index* idx, int64_t n_blocks, int64_t n_docs);  // 
 int64_t multivec_bytes(const mi355dr_index* idx);                // mi355dr_maxsim.hip: stat "hbm_bytes_resident"
 void sparse_destroy(mi355dr_index* idx);                         // mi355dr_sparse.hip
 int64_t sparse_bytes(const mi355dr_index* idx);                  // mi355dr_sparse.hip: stat "hbm_bytes_resident"
-enum { kSparseStatDocs, kSparseStatTotalLen, kSparseStatPostings, kSparseStatVocab };
+enum { kSparseStatDocs, kSparseStatTotalLen, kSparseStatPostings, kSparseStatVocab, kSparseStatOverlayPostings, kSparseStatDeadPostings };
 int64_t sparse_stat(const mi355dr_index* idx, int which);        // mi355dr_sparse.hip: the store's own figures (0 without a store)
 int drain_searches(mi355dr_index* idx);                          // mi355dr.hip: blocks in flight finished (under the handle's mutex)
 void comm_destroy(mi355dr_index* idx);                           // mi355dr_comm.hip

@@ -4,7 +4,9 @@
 // sum taken over the query's terms in ASCENDING term id.  Three kernels serve one block of <= kQBlockMax queries:
 //   k_sparse_norms   norm_i = k1 * ((1 - b) + b * (L_i / avgdl)) for every document, once per (k1, b, store state)
 //   k_sparse_score   one workgroup per (tile of T documents, query): term-at-a-time into LDS accumulators, then the touched
-//                    documents that can still enter the query's top-k are appended to its candidate list
+//                    documents that can still enter the query's top-k are appended to its candidate list.  <false>: one
+//                    layout, the store as the last full build left it.  <true>: a mutated store -- the base layout minus the
+//                    `moved` documents, plus the overlay layout that holds those documents' current postings
 //   k_sparse_merge   one workgroup per query: kept top-k + candidate list sorted under (distance asc, NaN last, id asc)
 //   k_sparse_final   the kept lists written out as (distance, id + row_offset), NaN / -1 behind the matches
 // The candidate list is the one bounded buffer: appends count past its end, the merge sees the count, drops the WHOLE list of
@@ -23,9 +25,14 @@ constexpr int kSparseCapMax = 2048;     // candidate slots per query: kKMax kept
 static_assert(kKMax + kSparseCapMax <= kSortMax, "the merge sorts the kept list and a full candidate list together");
 
 // LDS of k_sparse_score: acc[T] doubles | slice start [kSparseTermsMax] int64 | slice length [kSparseTermsMax] int32 |
-// touched bitmap [T / 32] | postings counter
-__host__ __device__ inline size_t sparse_score_lds(int T) {
-    return (size_t)T * sizeof(double) + (size_t)kSparseTermsMax * (sizeof(int64_t) + sizeof(int32_t)) + (size_t)(T / 32) * 4 + 16;
+// touched bitmap [T / 32] | postings counter.  With an overlay: a second slice table behind the first and the tile's `moved`
+// bits behind `touched` -- acc | start | overlay start | length | overlay length | touched | moved | counter -- and both
+// tables hold `terms_cap` entries, the most terms of a query of the block (even, <= kSparseTermsMax), not kSparseTermsMax:
+// two full tables would cost 24 KiB and leave three workgroups per CU at T = 2048 where the one-layout kernel has five
+__host__ __device__ inline size_t sparse_score_lds(int T, bool overlay = false, int terms_cap = kSparseTermsMax) {
+    const size_t per_term = sizeof(int64_t) + sizeof(int32_t), bits = (size_t)(T / 32) * 4;
+    if (!overlay) return (size_t)T * sizeof(double) + (size_t)kSparseTermsMax * per_term + bits + 16;
+    return (size_t)T * sizeof(double) + 2 * (size_t)terms_cap * per_term + 2 * bits + 16;
 }
 __host__ __device__ inline size_t sparse_merge_lds(int np) { return (size_t)np * (sizeof(uint64_t) + sizeof(int32_t)); }
 
@@ -60,6 +67,17 @@ struct SparseStoreView {
     const double* norm;       // [n_docs]
     int vocab;
 };
+// what a mutated store adds to the base layout: one bit per document whose postings in the base are no longer its content,
+// and a second term-major layout of the same format with the current postings of those documents
+struct SparseOverlayView {
+    const unsigned* moved;    // [moved_words] bit d & 31 of word d >> 5
+    const int64_t* term_off;  // [vocab + 1]
+    const int32_t* post_doc;  // ascending inside a term; every document here has its moved bit set
+    const uint16_t* post_tf;
+    int64_t moved_words;
+    int vocab;
+    int terms_cap;            // entries of each LDS slice table: >= the terms of every query of the launch, even
+};
 struct SparseQueries {
     const int32_t* terms;    // each query's terms ascending, distinct, inside [0, vocab)
     const double* weights;
@@ -77,15 +95,23 @@ struct SparseLists {
 
 // grid: (tiles of the launch, queries of the launch).  The launch covers documents [a0, a1); tile x covers
 // [(a0 / T + x) * T, + T) cut to [a0, a1).  T: a power of two, 256 .. kSparseTileMax.
-__global__ __launch_bounds__(kSparseThreads) void k_sparse_score(SparseStoreView st, SparseQueries qs, SparseLists ls, int64_t a0,
-                                                                 int64_t a1, int T, double k1p1,
+// kOverlay: `ov` is read (else it is ignored and the kernel is the one-layout kernel).  Within one term the base postings that
+// survive (document not moved) and the overlay's postings (documents moved) name disjoint documents, so the accumulation stays
+// plain read-add-writes; a skipped posting is neither added nor counted, so an emptied document is never touched.
+template <bool kOverlay>
+__global__ __launch_bounds__(kSparseThreads) void k_sparse_score(SparseStoreView st, SparseOverlayView ov, SparseQueries qs,
+                                                                 SparseLists ls, int64_t a0, int64_t a1, int T, double k1p1,
                                                                  unsigned long long* __restrict__ postings_scored) {
     extern __shared__ __align__(16) unsigned char sparse_smem[];
     double* acc = (double*)sparse_smem;
     int64_t* s_lo = (int64_t*)(acc + T);
-    int32_t* s_n = (int32_t*)(s_lo + kSparseTermsMax);
-    unsigned* touched = (unsigned*)(s_n + kSparseTermsMax);
-    unsigned* s_scored = touched + T / 32;
+    const int terms_cap = kOverlay ? ov.terms_cap : kSparseTermsMax;
+    int64_t* o_lo = s_lo + (kOverlay ? terms_cap : 0);
+    int32_t* s_n = (int32_t*)(o_lo + terms_cap);
+    int32_t* o_n = s_n + (kOverlay ? terms_cap : 0);
+    unsigned* touched = (unsigned*)(o_n + terms_cap);
+    unsigned* moved = touched + (kOverlay ? T / 32 : 0);
+    unsigned* s_scored = moved + T / 32;
 
     const int tid = threadIdx.x;
     const int q = qs.qlist ? qs.qlist[blockIdx.y] : (int)blockIdx.y;
@@ -94,27 +120,55 @@ __global__ __launch_bounds__(kSparseThreads) void k_sparse_score(SparseStoreView
     const int64_t d1 = t0 + T < a1 ? t0 + T : a1;
     const int qo = qs.offsets[q];
     int nt = qs.offsets[q + 1] - qo;
-    if (nt > kSparseTermsMax) nt = kSparseTermsMax;  // (the host refuses such a query)
+    if (nt > terms_cap) nt = terms_cap;  // (the host refuses a query of more than kSparseTermsMax terms and sizes terms_cap)
 
     // ---- 1: every term's posting slice inside [d0, d1)
     int any = 0;
-    for (int i = tid; i < nt; i += kSparseThreads) {
-        const int t = qs.terms[qo + i];
-        int64_t lo = 0, hi = 0;
-        if (t >= 0 && t < st.vocab && d0 < d1) {
-            const int64_t p0 = st.term_off[t], p1 = st.term_off[t + 1];
-            lo = sparse_lower_bound(st.post_doc, p0, p1, d0);
-            hi = sparse_lower_bound(st.post_doc, lo, p1, d1);
+    if constexpr (kOverlay) {
+        // the two layouts side by side: waves 0 and 1 search the base while waves 2 and 3 search the overlay, so the chain of
+        // dependent loads a lane waits for is as long as with one layout
+        constexpr int kHalf = kSparseThreads / 2;
+        const bool in_ov = tid >= kHalf;  // (wave-uniform)
+        const int64_t* __restrict__ term_off = in_ov ? ov.term_off : st.term_off;
+        const int32_t* __restrict__ post_doc = in_ov ? ov.post_doc : st.post_doc;
+        const int vocab = in_ov ? ov.vocab : st.vocab;
+        int64_t* out_lo = in_ov ? o_lo : s_lo;
+        int32_t* out_n = in_ov ? o_n : s_n;
+        for (int i = tid & (kHalf - 1); i < nt; i += kHalf) {
+            const int t = qs.terms[qo + i];
+            int64_t lo = 0, hi = 0;
+            if (t >= 0 && t < vocab && d0 < d1) {
+                const int64_t p0 = term_off[t], p1 = term_off[t + 1];
+                lo = sparse_lower_bound(post_doc, p0, p1, d0);
+                hi = sparse_lower_bound(post_doc, lo, p1, d1);
+            }
+            out_lo[i] = lo;
+            out_n[i] = (int32_t)(hi - lo);  // <= T
+            any |= hi > lo;
         }
-        s_lo[i] = lo;
-        s_n[i] = (int32_t)(hi - lo);  // <= T
-        any |= hi > lo;
+    } else {
+        for (int i = tid; i < nt; i += kSparseThreads) {
+            const int t = qs.terms[qo + i];
+            int64_t lo = 0, hi = 0;
+            if (t >= 0 && t < st.vocab && d0 < d1) {
+                const int64_t p0 = st.term_off[t], p1 = st.term_off[t + 1];
+                lo = sparse_lower_bound(st.post_doc, p0, p1, d0);
+                hi = sparse_lower_bound(st.post_doc, lo, p1, d1);
+            }
+            s_lo[i] = lo;
+            s_n[i] = (int32_t)(hi - lo);  // <= T
+            any |= hi > lo;
+        }
     }
     if (!__syncthreads_or(any)) return;  // (block-uniform) nothing of this query in this tile
 
     // ---- 2: accumulators at +0.0, nothing touched
     for (int j = tid; j < T; j += kSparseThreads) acc[j] = 0.0;
     for (int j = tid; j < T / 32; j += kSparseThreads) touched[j] = 0u;
+    if constexpr (kOverlay) {
+        const int64_t w0 = t0 >> 5;  // (t0 is a multiple of T >= 256)
+        for (int j = tid; j < T / 32; j += kSparseThreads) moved[j] = w0 + j < ov.moved_words ? ov.moved[w0 + j] : 0u;
+    }
     if (tid == 0) *s_scored = 0u;
     __syncthreads();
 
@@ -123,17 +177,33 @@ __global__ __launch_bounds__(kSparseThreads) void k_sparse_score(SparseStoreView
     unsigned scored = 0;
     for (int i = 0; i < nt; ++i) {
         const int n = s_n[i];  // (block-uniform)
-        if (n == 0) continue;
+        const int m = kOverlay ? o_n[i] : 0;
+        if (n == 0 && m == 0) continue;
         const int64_t lo = s_lo[i];
         const double w = qs.weights[qo + i];
         for (int p = tid; p < n; p += kSparseThreads) {
             const int64_t doc = st.post_doc[lo + p];
             const double tf = (double)st.post_tf[lo + p];
             const int j = (int)(doc - t0);
+            if constexpr (kOverlay) {
+                if (moved[j >> 5] >> (j & 31) & 1u) continue;  // a dead posting: the document's content is in the overlay
+            }
             const double frac = (tf * k1p1) / (tf + st.norm[doc]);
             acc[j] = acc[j] + (w * frac);
             atomicOr(&touched[j >> 5], 1u << (j & 31));
             ++scored;
+        }
+        if constexpr (kOverlay) {
+            const int64_t olo = o_lo[i];
+            for (int p = tid; p < m; p += kSparseThreads) {
+                const int64_t doc = ov.post_doc[olo + p];
+                const double tf = (double)ov.post_tf[olo + p];
+                const int j = (int)(doc - t0);
+                const double frac = (tf * k1p1) / (tf + st.norm[doc]);
+                acc[j] = acc[j] + (w * frac);
+                atomicOr(&touched[j >> 5], 1u << (j & 31));
+                ++scored;
+            }
         }
         __syncthreads();
     }

@@ -2830,6 +2830,7 @@ const Option kOptions[] = {
     {"range_slots", &Index::range_slots, 16, kSortMax},  // slots of a query's range result buffer (never below max_results)
     {"sparse_tile_docs", &Index::sparse_tile_docs, 256, 8192},  // documents per LDS tile of k_sparse_score (a power of two: checked below)
     {"sparse_cand_cap", &Index::sparse_cand_cap, 16, 2048},     // slots of a query's sparse candidate list
+    {"sparse_overlay_max_pct", &Index::sparse_overlay_max_pct, 0, 100},  // overlay build while moved postings <= this % of the base's (0: never)
     {"shard_stage_bytes", &Index::shard_stage_bytes, 1},  // most bytes of the sharded MMR forms' gathered stage (never below one query's)
 };
 
@@ -2902,6 +2903,11 @@ const Stat kStats[] = {
     {"sparse_queries", &Index::s_sparse_queries, true},
     {"sparse_postings_scored", &Index::s_sparse_postings_scored, true},
     {"sparse_overflows", &Index::s_sparse_overflows, true},
+    {"sparse_full_builds", &Index::s_sparse_full_builds, true},
+    {"sparse_overlay_builds", &Index::s_sparse_overlay_builds, true},
+    {"sparse_sets", &Index::s_sparse_sets, true},
+    {"sparse_overlay_postings", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatOverlayPostings); }},
+    {"sparse_dead_postings", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatDeadPostings); }},
     {"sparse_docs", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatDocs); }},
     {"sparse_total_len", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatTotalLen); }},
     {"sparse_postings", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatPostings); }},

@@ -1,12 +1,14 @@
-// mi355dr_sparse.hip -- the sparse store of libmi355dr.so: tokenised documents, weighted / BM25 top-k (DESIGN.md section 4.9).
+// mi355dr_sparse.hip -- the sparse store of libmi355dr.so: tokenised documents, weighted / BM25 top-k (DESIGN.md section 4.8j).
 // The arithmetic is fixed by include/mi355dr.h ("sparse store"); no bit parity with VectorChord-BM25 is claimed.
 //
 // Host side: the documents as sorted (term, tf) pairs (6 bytes per posting) with their lengths and df -- what an add appends
-// to, what the BM25 weights are computed from, and what the term-major device layout is rebuilt from (counting sort + upload)
-// by the first search after an add.  Device side: term_off [vocab + 1], postings (doc int32, tf uint16) ascending by document
-// inside a term, document lengths, and the norms of the last (k1, b).  A search runs the document range in a few launches of
-// growing size (k_sparse.h): the first cannot overflow a candidate list, every later one appends only what beats the
-// query's k-th kept entry.
+// to, what a set / remove replaces a document's slice of, what the BM25 weights are computed from, and what the term-major
+// device layout is rebuilt from (counting sort + upload) by the first search after a mutation.  Device side: term_off
+// [vocab + 1], postings (doc int32, tf uint16) ascending by document inside a term, document lengths, and the norms of the last
+// (k1, b) -- once as the base (the last full build) and, while documents have been replaced, emptied or appended since, a
+// `moved` bit per document and an overlay of the same format with those documents' current postings.  A search runs the
+// document range in a few launches of growing size (k_sparse.h): the first cannot overflow a candidate list, every later one
+// appends only what beats the query's k-th kept entry.
 #include "index.h"
 #include "k_sparse.h"
 
@@ -17,18 +19,34 @@ using namespace mi355;
 namespace mi355 {
 
 struct SparseStore {
-    // host
-    int64_t n_docs = 0, n_live = 0, total_len = 0, n_post = 0, vocab = 0;
+    // host.  Document d is the pairs [doc_at[d], + doc_cnt[d]) of the arena (h_term ascending inside a document, h_tf alongside).
+    // The arena is append-only: a set writes the new pairs at its end and leaves the old ones behind; every full layout build
+    // squeezes it back to n_post pairs in document order.
+    int64_t n_docs = 0, n_live = 0, total_len = 0, n_post = 0;
+    int64_t vocab = 0;              // largest term id with df > 0, plus one (df may be longer: zeros behind it)
     std::vector<int32_t> doc_len;   // [n_docs]
-    std::vector<int64_t> doc_off;   // [n_docs + 1] into h_term / h_tf
-    std::vector<int32_t> h_term;    // per document: its distinct terms ascending ...
-    std::vector<uint16_t> h_tf;     // ... and their counts
-    std::vector<int64_t> df;        // [vocab]
-    // device layout (stale after an add until the next search)
+    std::vector<int64_t> doc_at;    // [n_docs]
+    std::vector<int32_t> doc_cnt;   // [n_docs] distinct terms
+    std::vector<int32_t> h_term;
+    std::vector<uint16_t> h_tf;
+    std::vector<int64_t> df;
+    // what the device's base layout holds (the last full build), and what has left it since
+    bool has_base = false;
+    int64_t base_post = 0;
+    int base_vocab = 0;
+    std::vector<unsigned> moved;    // [(n_docs + 31) / 32] documents whose content is no longer the base's (appended ones too)
+    int64_t moved_post = 0;         // postings the moved documents hold now: the overlay's size once it is built
+    int64_t dead_post = 0;          // postings the moved documents have in the base
+    // device layout (stale after an add / set / remove until the next search)
     bool stale = false;
-    DevBuf<int64_t> term_off;
-    DevBuf<int32_t> post_doc, len_dev;
-    DevBuf<uint16_t> post_tf;
+    DevBuf<int64_t> term_off, ov_term_off;
+    DevBuf<int32_t> post_doc, ov_post_doc, len_dev;
+    DevBuf<uint16_t> post_tf, ov_post_tf;
+    DevBuf<unsigned> moved_dev;
+    int64_t moved_words_dev = 0;
+    int ov_vocab = 0;
+    bool ov_active = false;         // the layout on the device has moved documents: searches launch k_sparse_score<true>
+    int64_t ov_post_dev = 0, dead_post_dev = 0;  // the overlay's postings and the base's dead ones, as built
     DevBuf<double> norm;
     bool norm_valid = false;
     double norm_k1 = 0.0, norm_b = 0.0;
@@ -41,7 +59,6 @@ struct SparseStore {
     DevBuf<int> flags, qlist;
     DevBuf<unsigned long long> scored;
     bool lds_registered = false;
-    SparseStore() { doc_off.push_back(0); }
 };
 
 void sparse_destroy(mi355dr_index* idx) {
@@ -51,7 +68,9 @@ void sparse_destroy(mi355dr_index* idx) {
 
 int64_t sparse_bytes(const mi355dr_index* idx) {
     const SparseStore* s = idx->sp;
-    return s ? (int64_t)(s->term_off.bytes + s->post_doc.bytes + s->post_tf.bytes + s->len_dev.bytes + s->norm.bytes) : 0;
+    return s ? (int64_t)(s->term_off.bytes + s->post_doc.bytes + s->post_tf.bytes + s->len_dev.bytes + s->norm.bytes +
+                         s->ov_term_off.bytes + s->ov_post_doc.bytes + s->ov_post_tf.bytes + s->moved_dev.bytes)
+             : 0;
 }
 
 int64_t sparse_stat(const mi355dr_index* idx, int which) {
@@ -61,6 +80,8 @@ int64_t sparse_stat(const mi355dr_index* idx, int which) {
     case kSparseStatDocs: return s->n_live;
     case kSparseStatTotalLen: return s->total_len;
     case kSparseStatPostings: return s->n_post;
+    case kSparseStatOverlayPostings: return s->ov_post_dev;
+    case kSparseStatDeadPostings: return s->dead_post_dev;
     default: return s->vocab;
     }
 }
@@ -73,54 +94,137 @@ constexpr int32_t kTermLimit = 1 << 20;
 constexpr int kTfMax = 4095;
 constexpr int64_t kDocsMax = 0x7FFFFFFEll;
 
-// the term-major layout from the host's documents: counting sort by term, documents ascending inside a term
-int sparse_upload(mi355dr_index* idx, SparseStore* sp) {
-    if (!sp->stale) return MI355DR_OK;
+template <class F>
+void for_each_moved(const SparseStore* sp, F f) {  // ascending
+    for (size_t w = 0; w < sp->moved.size(); ++w)
+        for (unsigned bits = sp->moved[w]; bits; bits &= bits - 1) f((int64_t)w * 32 + __builtin_ctz(bits));
+}
+
+// a term-major layout (counting sort by term, documents ascending inside a term) in host vectors: of every document, or of
+// the moved ones alone
+struct HostLayout {
     std::vector<int64_t> off;
     std::vector<int32_t> pdoc;
     std::vector<uint16_t> ptf;
+};
+void sparse_sort(const SparseStore* sp, bool moved_only, int vocab, int64_t n_post, HostLayout* out) {
+    out->off.assign((size_t)vocab + 1, 0);
+    out->pdoc.resize((size_t)n_post);
+    out->ptf.resize((size_t)n_post);
+    if (moved_only)
+        for_each_moved(sp, [&](int64_t d) {
+            for (int64_t p = sp->doc_at[d]; p < sp->doc_at[d] + sp->doc_cnt[d]; ++p) out->off[(size_t)sp->h_term[p] + 1]++;
+        });
+    else
+        for (int t = 0; t < vocab; ++t) out->off[(size_t)t + 1] = sp->df[t];
+    for (int t = 0; t < vocab; ++t) out->off[(size_t)t + 1] += out->off[t];
+    std::vector<int64_t> cur(out->off.begin(), out->off.end() - 1);
+    const auto place = [&](int64_t d) {
+        for (int64_t p = sp->doc_at[d]; p < sp->doc_at[d] + sp->doc_cnt[d]; ++p) {
+            const int64_t at = cur[sp->h_term[p]]++;
+            out->pdoc[at] = (int32_t)d;
+            out->ptf[at] = sp->h_tf[p];
+        }
+    };
+    if (moved_only) for_each_moved(sp, place);
+    else
+        for (int64_t d = 0; d < sp->n_docs; ++d) place(d);
+}
+
+// the arena back to n_post pairs in document order (nothing changes when memory fails: the old arena stays)
+void sparse_squeeze(SparseStore* sp) {
+    if ((int64_t)sp->h_term.size() == sp->n_post) return;
+    std::vector<int32_t> term;
+    std::vector<uint16_t> tf;
+    term.reserve((size_t)(sp->n_post + sp->n_post / 8));  // (the slack of arena_reserve: the next set need not move it)
+    tf.reserve((size_t)(sp->n_post + sp->n_post / 8));
+    for (int64_t d = 0; d < sp->n_docs; ++d) {
+        term.insert(term.end(), sp->h_term.begin() + sp->doc_at[d], sp->h_term.begin() + sp->doc_at[d] + sp->doc_cnt[d]);
+        tf.insert(tf.end(), sp->h_tf.begin() + sp->doc_at[d], sp->h_tf.begin() + sp->doc_at[d] + sp->doc_cnt[d]);
+    }
+    int64_t at = 0;
+    for (int64_t d = 0; d < sp->n_docs; ++d) {
+        sp->doc_at[d] = at;
+        at += sp->doc_cnt[d];
+    }
+    sp->h_term.swap(term);
+    sp->h_tf.swap(tf);
+}
+
+// The device layout brought up to the host's documents by the first search after a mutation.  While the moved documents'
+// postings are at most `sparse_overlay_max_pct` percent of the base's, the base stays and the overlay alone is sorted and
+// uploaded; else a full build, after which nothing is moved.  Both upload doc_len and `moved` whole and take a fresh norm
+// buffer (avgdl changed).  Every allocation comes before the first swap: a failure leaves the store as it was.
+int sparse_upload(mi355dr_index* idx, SparseStore* sp) {
+    if (!sp->stale) return MI355DR_OK;
+    const bool overlay = sp->has_base && idx->sparse_overlay_max_pct > 0 &&
+                         sp->moved_post * 100 <= (int64_t)idx->sparse_overlay_max_pct * sp->base_post;
+    HostLayout lay;
+    int vocab = (int)sp->vocab;
     try {
-        off.assign((size_t)sp->vocab + 1, 0);
-        pdoc.resize((size_t)sp->n_post);
-        ptf.resize((size_t)sp->n_post);
+        if (overlay) {
+            vocab = 0;
+            for_each_moved(sp, [&](int64_t d) {
+                if (sp->doc_cnt[d]) vocab = std::max(vocab, sp->h_term[sp->doc_at[d] + sp->doc_cnt[d] - 1] + 1);
+            });
+            sparse_sort(sp, true, vocab, sp->moved_post, &lay);
+        } else {
+            sparse_squeeze(sp);
+            sparse_sort(sp, false, vocab, sp->n_post, &lay);
+        }
     } catch (const std::bad_alloc&) {
         return fail(idx, MI355DR_E_NOMEM, "sparse store: host memory for the term-major layout");
-    }
-    for (int64_t t = 0; t < sp->vocab; ++t) off[t + 1] = off[t] + sp->df[t];
-    {
-        std::vector<int64_t> cur;
-        try {
-            cur.assign(off.begin(), off.end() - 1);
-        } catch (const std::bad_alloc&) {
-            return fail(idx, MI355DR_E_NOMEM, "sparse store: host memory for the term-major layout");
-        }
-        for (int64_t d = 0; d < sp->n_docs; ++d)
-            for (int64_t p = sp->doc_off[d]; p < sp->doc_off[d + 1]; ++p) {
-                const int64_t at = cur[sp->h_term[p]]++;
-                pdoc[at] = (int32_t)d;
-                ptf[at] = sp->h_tf[p];
-            }
     }
     DevBuf<int64_t> term_off;
     DevBuf<int32_t> post_doc, len_dev;
     DevBuf<uint16_t> post_tf;
+    DevBuf<unsigned> moved_dev;
     DevBuf<double> norm;
-    HIPCHECK(idx, term_off.grow(off.size() * sizeof(int64_t)));
-    HIPCHECK(idx, post_doc.grow(std::max<size_t>(pdoc.size(), 1) * sizeof(int32_t)));
-    HIPCHECK(idx, post_tf.grow(std::max<size_t>(ptf.size(), 1) * sizeof(uint16_t)));
+    HIPCHECK(idx, term_off.grow(lay.off.size() * sizeof(int64_t)));
+    HIPCHECK(idx, post_doc.grow(std::max<size_t>(lay.pdoc.size(), 1) * sizeof(int32_t)));
+    HIPCHECK(idx, post_tf.grow(std::max<size_t>(lay.ptf.size(), 1) * sizeof(uint16_t)));
     HIPCHECK(idx, len_dev.grow(std::max<size_t>(sp->doc_len.size(), 1) * sizeof(int32_t)));
+    HIPCHECK(idx, moved_dev.grow(std::max<size_t>(sp->moved.size(), 1) * sizeof(unsigned)));
     HIPCHECK(idx, norm.grow(std::max<size_t>(sp->doc_len.size(), 1) * sizeof(double)));
-    HIPCHECK(idx, hipMemcpy(term_off.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (!pdoc.empty()) {
-        HIPCHECK(idx, hipMemcpy(post_doc.p, pdoc.data(), pdoc.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHECK(idx, hipMemcpy(post_tf.p, ptf.data(), ptf.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    HIPCHECK(idx, hipMemcpy(term_off.p, lay.off.data(), lay.off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (!lay.pdoc.empty()) {
+        HIPCHECK(idx, hipMemcpy(post_doc.p, lay.pdoc.data(), lay.pdoc.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHECK(idx, hipMemcpy(post_tf.p, lay.ptf.data(), lay.ptf.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     }
-    if (!sp->doc_len.empty())
+    if (!sp->doc_len.empty()) {
         HIPCHECK(idx, hipMemcpy(len_dev.p, sp->doc_len.data(), sp->doc_len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    sp->term_off.swap(term_off);
-    sp->post_doc.swap(post_doc);
-    sp->post_tf.swap(post_tf);
+        if (overlay) HIPCHECK(idx, hipMemcpy(moved_dev.p, sp->moved.data(), sp->moved.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+        else HIPCHECK(idx, hipMemset(moved_dev.p, 0, sp->moved.size() * sizeof(unsigned)));
+    }
+    if (overlay) {
+        sp->ov_term_off.swap(term_off);
+        sp->ov_post_doc.swap(post_doc);
+        sp->ov_post_tf.swap(post_tf);
+        sp->ov_vocab = vocab;
+        sp->ov_active = true;
+        sp->ov_post_dev = sp->moved_post;
+        sp->dead_post_dev = sp->dead_post;
+        idx->s_sparse_overlay_builds++;
+    } else {
+        sp->term_off.swap(term_off);
+        sp->post_doc.swap(post_doc);
+        sp->post_tf.swap(post_tf);
+        sp->ov_term_off.release();
+        sp->ov_post_doc.release();
+        sp->ov_post_tf.release();
+        std::fill(sp->moved.begin(), sp->moved.end(), 0u);
+        sp->has_base = true;
+        sp->base_post = sp->n_post;
+        sp->base_vocab = vocab;
+        sp->moved_post = sp->dead_post = 0;
+        sp->ov_vocab = 0;
+        sp->ov_active = false;
+        sp->ov_post_dev = sp->dead_post_dev = 0;
+        idx->s_sparse_full_builds++;
+    }
     sp->len_dev.swap(len_dev);
+    sp->moved_dev.swap(moved_dev);
+    sp->moved_words_dev = (int64_t)sp->moved.size();
     sp->norm.swap(norm);
     sp->norm_valid = false;
     sp->stale = false;
@@ -154,12 +258,18 @@ std::vector<int64_t> sparse_plan(int64_t n, int k, int cap) {
     return edges;
 }
 
-int launch_score(mi355dr_index* idx, SparseStore* sp, hipStream_t s, const SparseStoreView& view, const SparseQueries& qs,
-                 const SparseLists& ls, int64_t a0, int64_t a1, int nq, double k1p1) {
+// the block and its overflow pieces launch the same instantiation: <true> exactly while the device layout has moved documents
+int launch_score(mi355dr_index* idx, SparseStore* sp, hipStream_t s, const SparseStoreView& view, const SparseOverlayView& ov,
+                 const SparseQueries& qs, const SparseLists& ls, int64_t a0, int64_t a1, int nq, double k1p1) {
     const int T = idx->sparse_tile_docs;
     const int64_t tiles = (a1 - 1) / T - a0 / T + 1;
-    hipLaunchKernelGGL(k_sparse_score, dim3((unsigned)tiles, (unsigned)nq), dim3(kSparseThreads), sparse_score_lds(T), s, view, qs, ls,
-                       a0, a1, T, k1p1, sp->scored.p);
+    const dim3 grid((unsigned)tiles, (unsigned)nq);
+    if (sp->ov_active)
+        hipLaunchKernelGGL(k_sparse_score<true>, grid, dim3(kSparseThreads), sparse_score_lds(T, true, ov.terms_cap), s, view, ov, qs, ls, a0, a1, T,
+                           k1p1, sp->scored.p);
+    else
+        hipLaunchKernelGGL(k_sparse_score<false>, grid, dim3(kSparseThreads), sparse_score_lds(T), s, view, ov, qs, ls, a0, a1, T, k1p1,
+                           sp->scored.p);
     HIPCHECK(idx, hipGetLastError());
     return MI355DR_OK;
 }
@@ -180,8 +290,10 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
     const int cap = idx->sparse_cand_cap;
     const int64_t n = sp->n_live > 0 ? sp->n_docs : 0;
     if (!sp->lds_registered) {
-        HIPCHECK(idx, hipFuncSetAttribute((const void*)k_sparse_score, hipFuncAttributeMaxDynamicSharedMemorySize,
+        HIPCHECK(idx, hipFuncSetAttribute((const void*)k_sparse_score<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)sparse_score_lds(kSparseTileMax)));
+        HIPCHECK(idx, hipFuncSetAttribute((const void*)k_sparse_score<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)sparse_score_lds(kSparseTileMax, true)));
         sp->lds_registered = true;
     }
     if (n > 0 && !(sp->norm_valid && sp->norm_k1 == k1 && sp->norm_b == b)) {
@@ -207,7 +319,8 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
     if (out.host) HIPCHECK(idx, grow_each((size_t)nb_max * k, sp->out_dist, sp->out_rows));
     HIPCHECK(idx, hipMemsetAsync(sp->scored.p, 0, sizeof(unsigned long long), s));
 
-    const SparseStoreView view{sp->term_off.p, sp->post_doc.p, sp->post_tf.p, sp->norm.p, (int)sp->vocab};
+    const SparseStoreView view{sp->term_off.p, sp->post_doc.p, sp->post_tf.p, sp->norm.p, sp->base_vocab};
+    SparseOverlayView ov{sp->moved_dev.p, sp->ov_term_off.p, sp->ov_post_doc.p, sp->ov_post_tf.p, sp->moved_words_dev, sp->ov_vocab, 2};
     const double k1p1 = k1 + 1.0;
     std::vector<int32_t> off_block;
     std::vector<int> flags_host, redo_q;
@@ -217,6 +330,8 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
         const size_t nt = (size_t)(t_hi - t_lo);
         off_block.resize((size_t)nb + 1);
         for (int i = 0; i <= nb; ++i) off_block[i] = offsets[b0 + i] - t_lo;
+        ov.terms_cap = 2;  // the block's longest query, even: the size of k_sparse_score<true>'s two LDS slice tables
+        for (int i = 0; i < nb; ++i) ov.terms_cap = std::max(ov.terms_cap, (offsets[b0 + i + 1] - offsets[b0 + i] + 1) & ~1);
         HIPCHECK(idx, grow_each(std::max<size_t>(nt, 1), sp->q_terms));
         HIPCHECK(idx, grow_each(std::max<size_t>(nt, 1), sp->q_w));
         // (in stream order behind the previous block; the host vectors stay as they are until the block's last wait)
@@ -235,7 +350,7 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
         HIPCHECK(idx, hipGetLastError());
         if (nt > 0) {
             for (int c = 0; c < n_chunks; ++c) {
-                CHECK(launch_score(idx, sp, s, view, qs, ls, edges[c], edges[c + 1], nb, k1p1));
+                CHECK(launch_score(idx, sp, s, view, ov, qs, ls, edges[c], edges[c + 1], nb, k1p1));
                 hipLaunchKernelGGL(k_sparse_merge, dim3((unsigned)nb), dim3(kSparseThreads), sparse_merge_lds(np_max), s, ls,
                                    (const int*)nullptr, np_max, sp->flags.p + (size_t)c * nb);
                 HIPCHECK(idx, hipGetLastError());
@@ -256,7 +371,7 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
                     SparseQueries qr = qs;
                     qr.qlist = ql;
                     for (int64_t a = edges[c]; a < edges[c + 1]; a += cap) {
-                        CHECK(launch_score(idx, sp, s, view, qr, ls, a, std::min<int64_t>(a + cap, edges[c + 1]), (int)redo_q.size(), k1p1));
+                        CHECK(launch_score(idx, sp, s, view, ov, qr, ls, a, std::min<int64_t>(a + cap, edges[c + 1]), (int)redo_q.size(), k1p1));
                         hipLaunchKernelGGL(k_sparse_merge, dim3((unsigned)redo_q.size()), dim3(kSparseThreads), sparse_merge_lds(np_max),
                                            s, ls, (const int*)ql, np_max, spare);
                         HIPCHECK(idx, hipGetLastError());
@@ -383,6 +498,130 @@ int search_bm25_impl(mi355dr_index* idx, const int32_t* q_tokens, const int32_t*
     return sparse_search_sorted(idx, terms, weights, offsets, B, k, k1, b, out, s);
 }
 
+// documents [0, n) of a call as terms[offsets[j] .. offsets[j + 1]); offsets null: n documents without tokens
+int check_ragged(mi355dr_index* idx, const std::string& what, const int32_t* terms, const int64_t* offsets, int64_t n) {
+    if (!offsets) return MI355DR_OK;
+    if (offsets[0] < 0) return fail(idx, MI355DR_E_INVALID, what + ": offsets must start at >= 0");
+    for (int64_t d = 0; d < n; ++d) {
+        if (offsets[d + 1] < offsets[d]) return fail(idx, MI355DR_E_INVALID, what + ": offsets must never decrease");
+        if (offsets[d + 1] - offsets[d] > INT32_MAX) return fail(idx, MI355DR_E_UNSUPPORTED, what + ": a document of more than 2^31 - 1 tokens");
+    }
+    if (offsets[n] > offsets[0] && !terms) return fail(idx, MI355DR_E_INVALID, what + ": null terms");
+    return MI355DR_OK;
+}
+
+// the documents of a call as sorted (term, tf) pairs: document j is [end[j - 1], end[j]) of term / tf, len[j] its tokens
+struct SparseDigest {
+    std::vector<int32_t> term, len;
+    std::vector<uint16_t> tf;
+    std::vector<int64_t> end;
+    int64_t max_term = -1;
+};
+int sparse_digest(mi355dr_index* idx, const std::string& what, const int32_t* terms, const int64_t* offsets, int64_t n, SparseDigest* a) {
+    std::vector<int32_t> one;
+    a->end.reserve((size_t)n);
+    a->len.reserve((size_t)n);
+    for (int64_t d = 0; d < n; ++d) {
+        one.clear();
+        if (offsets) one.assign(terms + offsets[d], terms + offsets[d + 1]);
+        std::sort(one.begin(), one.end());
+        if (!one.empty() && (one.front() < 0 || one.back() >= kTermLimit))
+            return fail(idx, MI355DR_E_INVALID, what + ": term id outside [0, 2^20) in document " + std::to_string(d));
+        for (size_t i = 0; i < one.size();) {
+            size_t j = i;
+            while (j < one.size() && one[j] == one[i]) ++j;
+            if (j - i > (size_t)kTfMax)
+                return fail(idx, MI355DR_E_UNSUPPORTED, what + ": a term occurs more than 4095 times in document " + std::to_string(d));
+            a->term.push_back(one[i]);
+            a->tf.push_back((uint16_t)(j - i));
+            i = j;
+        }
+        a->end.push_back((int64_t)a->term.size());
+        a->len.push_back((int32_t)one.size());
+        if (!one.empty()) a->max_term = std::max<int64_t>(a->max_term, one.back());
+    }
+    return MI355DR_OK;
+}
+
+// room for `more` pairs behind the arena.  When it has to move it takes an eighth more than asked for, and at least half as
+// much again as it holds: an exact reserve would copy the whole arena at every call
+void arena_reserve(SparseStore* sp, size_t more) {
+    const size_t need = sp->h_term.size() + more;
+    if (need <= sp->h_term.capacity() && need <= sp->h_tf.capacity()) return;
+    const size_t want = std::max(need + need / 8, sp->h_term.size() + sp->h_term.size() / 2);
+    sp->h_term.reserve(want);
+    sp->h_tf.reserve(want);
+}
+
+// Document d becomes document j of the digest; the room (arena, df) is there, so this cannot fail.  Its old pairs stay behind
+// in the arena.  False: it had no tokens and gets none -- nothing changes.
+bool sparse_put(SparseStore* sp, int64_t d, const SparseDigest& a, int64_t j) {
+    const int64_t lo = j ? a.end[(size_t)j - 1] : 0, cnt = a.end[(size_t)j] - lo;
+    const int64_t old_at = sp->doc_at[d], old_cnt = sp->doc_cnt[d];
+    if (old_cnt == 0 && cnt == 0) return false;
+    unsigned& word = sp->moved[(size_t)(d >> 5)];
+    const unsigned bit = 1u << (d & 31);
+    if (word & bit) {
+        sp->moved_post -= old_cnt;
+    } else {  // until now its content was the base's (a document appended since the base was built has none there)
+        word |= bit;
+        sp->dead_post += old_cnt;
+    }
+    for (int64_t p = old_at; p < old_at + old_cnt; ++p) sp->df[sp->h_term[p]]--;
+    sp->n_post -= old_cnt;
+    sp->total_len -= sp->doc_len[d];
+    sp->n_live -= sp->doc_len[d] > 0;
+    sp->doc_at[d] = (int64_t)sp->h_term.size();
+    sp->doc_cnt[d] = (int32_t)cnt;
+    sp->doc_len[d] = a.len[(size_t)j];
+    sp->h_term.insert(sp->h_term.end(), a.term.begin() + lo, a.term.begin() + lo + cnt);
+    sp->h_tf.insert(sp->h_tf.end(), a.tf.begin() + lo, a.tf.begin() + lo + cnt);
+    for (int64_t p = lo; p < lo + cnt; ++p) sp->df[a.term[(size_t)p]]++;
+    sp->n_post += cnt;
+    sp->moved_post += cnt;
+    sp->total_len += a.len[(size_t)j];
+    sp->n_live += a.len[(size_t)j] > 0;
+    if (cnt) sp->vocab = std::max<int64_t>(sp->vocab, (int64_t)a.term[(size_t)(lo + cnt - 1)] + 1);
+    while (sp->vocab > 0 && sp->df[(size_t)sp->vocab - 1] == 0) --sp->vocab;
+    return true;
+}
+
+// mi355dr_set_sparse, and mi355dr_remove_sparse as the set of n empty sequences (offsets null)
+int set_sparse_impl(mi355dr_index* idx, const std::string& what, const int64_t* doc_ids, const int32_t* terms, const int64_t* offsets,
+                    int64_t n) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, what.c_str());
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_searches(idx));
+    const bool removing = what == "remove_sparse";
+    if (n < 0) return fail(idx, MI355DR_E_INVALID, what + ": n must be >= 0");
+    if (n == 0) return MI355DR_OK;
+    if (!doc_ids || (!removing && !offsets)) return fail(idx, MI355DR_E_INVALID, what + ": null buffer");
+    CHECK(check_ragged(idx, what, terms, offsets, n));
+    SparseStore* sp = idx->sp;
+    const int64_t have = sp ? sp->n_docs : 0;
+    try {
+        std::vector<int64_t> ids(doc_ids, doc_ids + n);
+        std::sort(ids.begin(), ids.end());
+        if (ids.front() < 0 || ids.back() >= have)
+            return fail(idx, MI355DR_E_INVALID, what + ": a document id outside [0, " + std::to_string(have) + ")");
+        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end())
+            return fail(idx, MI355DR_E_INVALID, what + ": a document id is listed twice");
+        SparseDigest a;
+        CHECK(sparse_digest(idx, what, terms, offsets, n, &a));
+        // room first: what follows cannot fail
+        arena_reserve(sp, a.term.size());
+        if ((size_t)(a.max_term + 1) > sp->df.size()) sp->df.resize((size_t)(a.max_term + 1), 0);
+        for (int64_t j = 0; j < n; ++j)
+            if (sparse_put(sp, doc_ids[j], a, j)) sp->stale = true;
+        idx->s_sparse_sets += n;
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, what + ": host memory");
+    }
+    return MI355DR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -394,73 +633,47 @@ int mi355dr_add_sparse(mi355dr_index* idx, const int32_t* terms, const int64_t* 
     HIPCHECK(idx, hipSetDevice(idx->device));
     CHECK(drain_searches(idx));
     if (n_docs < 0 || !offsets) return fail(idx, MI355DR_E_INVALID, "add_sparse: n_docs must be >= 0 and offsets not null");
-    if (offsets[0] < 0) return fail(idx, MI355DR_E_INVALID, "add_sparse: offsets must start at >= 0");
-    for (int64_t d = 0; d < n_docs; ++d) {
-        if (offsets[d + 1] < offsets[d]) return fail(idx, MI355DR_E_INVALID, "add_sparse: offsets must never decrease");
-        if (offsets[d + 1] - offsets[d] > INT32_MAX) return fail(idx, MI355DR_E_UNSUPPORTED, "add_sparse: a document of more than 2^31 - 1 tokens");
-    }
-    if (offsets[n_docs] > offsets[0] && !terms) return fail(idx, MI355DR_E_INVALID, "add_sparse: null terms");
+    CHECK(check_ragged(idx, "add_sparse", terms, offsets, n_docs));
     const int64_t have = idx->sp ? idx->sp->n_docs : 0;
     if (have + n_docs > kDocsMax) return fail(idx, MI355DR_E_UNSUPPORTED, "add_sparse: more than 2^31 - 2 documents");
     if (n_docs == 0) return MI355DR_OK;
     try {
         // the new documents as sorted (term, tf) pairs, checked, before anything of the store changes
-        std::vector<int32_t> a_term, a_len, one;
-        std::vector<uint16_t> a_tf;
-        std::vector<int64_t> a_off;
-        a_off.reserve((size_t)n_docs);
-        a_len.reserve((size_t)n_docs);
-        int64_t max_term = -1, live = 0, total = 0;
-        for (int64_t d = 0; d < n_docs; ++d) {
-            one.assign(terms + offsets[d], terms + offsets[d + 1]);
-            std::sort(one.begin(), one.end());
-            if (!one.empty() && (one.front() < 0 || one.back() >= kTermLimit))
-                return fail(idx, MI355DR_E_INVALID, "add_sparse: term id outside [0, 2^20) in document " + std::to_string(d));
-            for (size_t i = 0; i < one.size();) {
-                size_t j = i;
-                while (j < one.size() && one[j] == one[i]) ++j;
-                if (j - i > (size_t)kTfMax)
-                    return fail(idx, MI355DR_E_UNSUPPORTED, "add_sparse: a term occurs more than 4095 times in document " + std::to_string(d));
-                a_term.push_back(one[i]);
-                a_tf.push_back((uint16_t)(j - i));
-                i = j;
-            }
-            a_off.push_back((int64_t)a_term.size());
-            a_len.push_back((int32_t)one.size());
-            if (!one.empty()) {
-                max_term = std::max<int64_t>(max_term, one.back());
-                ++live;
-                total += (int64_t)one.size();
-            }
-        }
+        SparseDigest a;
+        CHECK(sparse_digest(idx, "add_sparse", terms, offsets, n_docs, &a));
         if (!idx->sp) idx->sp = new SparseStore();
         SparseStore* sp = idx->sp;
         // room first: what follows cannot fail
-        sp->doc_len.reserve(sp->doc_len.size() + a_len.size());
-        sp->doc_off.reserve(sp->doc_off.size() + a_off.size());
-        sp->h_term.reserve(sp->h_term.size() + a_term.size());
-        sp->h_tf.reserve(sp->h_tf.size() + a_tf.size());
-        if (max_term + 1 > sp->vocab) sp->df.reserve((size_t)(max_term + 1));
-        if (max_term + 1 > sp->vocab) {
-            sp->df.resize((size_t)(max_term + 1), 0);
-            sp->vocab = max_term + 1;
+        const size_t docs = (size_t)(sp->n_docs + n_docs);
+        sp->doc_len.reserve(docs);
+        sp->doc_at.reserve(docs);
+        sp->doc_cnt.reserve(docs);
+        sp->moved.reserve((docs + 31) / 32);
+        arena_reserve(sp, a.term.size());
+        if ((size_t)(a.max_term + 1) > sp->df.size()) sp->df.resize((size_t)(a.max_term + 1), 0);
+        sp->moved.resize((docs + 31) / 32, 0u);
+        for (int64_t j = 0; j < n_docs; ++j) {  // (an appended document is not in the base: it rides the overlay or waits for a full build)
+            sp->doc_len.push_back(0);
+            sp->doc_at.push_back(0);
+            sp->doc_cnt.push_back(0);
+            sparse_put(sp, sp->n_docs++, a, j);
         }
-        const int64_t base = sp->n_post;
-        sp->doc_len.insert(sp->doc_len.end(), a_len.begin(), a_len.end());
-        for (const int64_t o : a_off) sp->doc_off.push_back(base + o);
-        sp->h_term.insert(sp->h_term.end(), a_term.begin(), a_term.end());
-        sp->h_tf.insert(sp->h_tf.end(), a_tf.begin(), a_tf.end());
-        for (const int32_t t : a_term) sp->df[t]++;
-        sp->n_docs += n_docs;
-        sp->n_live += live;
-        sp->total_len += total;
-        sp->n_post += (int64_t)a_term.size();
         sp->stale = true;
     } catch (const std::bad_alloc&) {
         return fail(idx, MI355DR_E_NOMEM, "add_sparse: host memory");
     }
     return MI355DR_OK;
 }
+
+int mi355dr_set_sparse(mi355dr_index* idx, const int64_t* doc_ids, const int32_t* terms, const int64_t* offsets, int64_t n) {
+    return set_sparse_impl(idx, "set_sparse", doc_ids, terms, offsets, n);
+}
+
+int mi355dr_remove_sparse(mi355dr_index* idx, const int64_t* doc_ids, int64_t n) {
+    return set_sparse_impl(idx, "remove_sparse", doc_ids, nullptr, nullptr, n);
+}
+
+int64_t mi355dr_live_sparse(const mi355dr_index* idx) { return idx && idx->sp ? idx->sp->n_live : 0; }
 
 int64_t mi355dr_size_sparse(const mi355dr_index* idx) { return idx && idx->sp ? idx->sp->n_docs : 0; }
 

@@ -680,6 +680,36 @@ class Mi355Index:
         terms, off = self._ragged_i32(token_lists, offsets, np.int64)
         check(self._h, self._lib.mi355dr_add_sparse(self._h, ptr(terms, ctypes.c_int32), ptr(off, ctypes.c_int64), off.shape[0] - 1))
 
+    @staticmethod
+    def _sparse_ids(doc_ids) -> np.ndarray:
+        ids = np.asarray(doc_ids)
+        if ids.size and not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError("doc_ids must be integers")
+        return np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+
+    def set_sparse(self, doc_ids, token_lists, offsets=None) -> None:
+        """Document doc_ids[j] becomes token_lists[j] (or terms[offsets[j]:offsets[j + 1]], the flat form of `add_sparse`): later
+        searches, `sparse_df` and the stats answer as a fresh store given one `add_sparse` of the current documents.  No tokens
+        removes the document (it keeps its id and never matches), tokens revive a removed one.  Ids are local (no `row_offset`).
+        An id out of range or listed twice, a term id outside [0, 2^20), a term more than 4095 times in one document:
+        NativeError, nothing changes."""
+        ids = self._sparse_ids(doc_ids)
+        terms, off = self._ragged_i32(token_lists, offsets, np.int64)
+        if off.shape[0] - 1 != ids.shape[0]:
+            raise ValueError(f"{ids.shape[0]} doc_ids for {off.shape[0] - 1} token lists")
+        check(self._h, self._lib.mi355dr_set_sparse(self._h, ptr(ids, ctypes.c_int64), ptr(terms, ctypes.c_int32),
+                                                    ptr(off, ctypes.c_int64), ids.shape[0]))
+
+    def remove_sparse(self, doc_ids) -> None:
+        """The documents lose their tokens: stored, holding their ids, never matching, no part of N, total_len or df.  Removing a
+        document without tokens changes nothing."""
+        ids = self._sparse_ids(doc_ids)
+        check(self._h, self._lib.mi355dr_remove_sparse(self._h, ptr(ids, ctypes.c_int64), ids.shape[0]))
+
+    def live_sparse(self) -> int:
+        """Sparse documents with tokens: N of the statistics (`size_sparse` minus the documents without tokens)."""
+        return int(self._lib.mi355dr_live_sparse(self._h))
+
     def size_sparse(self) -> int:
         """Stored sparse documents, with or without tokens."""
         return int(self._lib.mi355dr_size_sparse(self._h))

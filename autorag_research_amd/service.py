@@ -183,7 +183,7 @@ class _UnitIndex:
         self.compact_dead_fraction = compact_dead_fraction
         self._pos_of_id = self._stored_row_of_pos = None   # (dict) caches of pos_of_id() / stored_row_of_pos(): see _forget_maps
         # the sparse store of `table.contents` under one tokenizer (BM25): document id = table position.  It is replicated, not
-        # sharded, and rebuilt whole when the contents it was built from are no longer the table's (`ensure_sparse`)
+        # sharded, and brought up to the table's contents when they are no longer what it was built from (`ensure_sparse`)
         self.sparse: Mi355Index | None = None
         self._sparse_of: tuple[Any, list] | None = None    # (tokenizer key, the contents list it was built from)
 
@@ -251,8 +251,10 @@ class _UnitIndex:
 
     def ensure_sparse(self, tokenizer: Any) -> Mi355Index:
         """The sparse store of the table's contents under `tokenizer` (a name or a callable, bm25.get_tokenizer): one document
-        per table position, None = a document without tokens, so ids stay positions.  Built on first use; a refresh that
-        changed the contents, or another tokenizer, rebuilds it whole."""
+        per table position, None = a document without tokens, so ids stay positions.  Built on first use.  A refresh that
+        changed cells or appended rows is applied as the difference (`set_sparse` of the changed positions, `add_sparse` of the
+        tail: only those are tokenised); a shorter table, another tokenizer, or a store object without `set_sparse` rebuilds it
+        whole."""
         from .bm25 import get_tokenizer, tokenizer_key  # noqa: PLC0415
 
         key, contents = tokenizer_key(tokenizer), self.table.contents
@@ -262,11 +264,27 @@ class _UnitIndex:
             if self._sparse_of[1] == contents:   # a newer export with the same contents: remember its list, compare once
                 self._sparse_of = (key, contents)
                 return self.sparse
+        tok = get_tokenizer(tokenizer)
+
+        def tokens(c):
+            return [] if c is None else tok(c if isinstance(c, str) else bytes(c).decode("utf-8", "replace"))
+
+        if (self.sparse is not None and self._sparse_of is not None and self._sparse_of[0] == key
+                and len(self._sparse_of[1]) <= len(contents) and hasattr(self.sparse, "set_sparse")):
+            # the table kept its positions and grew at the end at most: the difference alone -- one set of the cells that
+            # changed, one add of the tail (under a process group every rank applies the same difference)
+            old = self._sparse_of[1]
+            changed = [i for i, c in enumerate(old) if c != contents[i]]
+            if changed:
+                self.sparse.set_sparse(changed, [tokens(contents[i]) for i in changed])
+            if len(contents) > len(old):
+                self.sparse.add_sparse([tokens(c) for c in contents[len(old):]])
+            self._sparse_of = (key, contents)
+            return self.sparse
         if self.sparse is not None:
             self.sparse.close()
             self.sparse = None
-        tok = get_tokenizer(tokenizer)
-        docs = [[] if c is None else tok(c if isinstance(c, str) else bytes(c).decode("utf-8", "replace")) for c in contents]
+        docs = [tokens(c) for c in contents]
         ix = Mi355Index(8, "cosine", self.device)  # (the handle's dense side stays empty)
         ix.add_sparse(docs)
         self.sparse, self._sparse_of = ix, (key, contents)

@@ -536,19 +536,42 @@ int mi355dr_search_maxsim_subset_device(mi355dr_index* idx, const float* qtok_de
  *   then the weighted search runs.  No transcendental runs on the device.
  * Calls run under the handle's mutex, first complete whatever search is in flight, and are complete on return.  The _device
  *   forms take the QUERY on the host and write the results to device memory on `stream` (null: the handle's).  A failed
- *   allocation returns E_NOMEM with nothing changed.  The term-major device layout is rebuilt by the first search after an add
- *   (host counting sort + upload); the host keeps the documents as sorted (term, tf) pairs, 6 bytes per posting.
+ *   allocation returns E_NOMEM with nothing changed.  The term-major device layout is brought up to date by the first search
+ *   after an add / set / remove (host counting sort + upload); the host keeps the documents as sorted (term, tf) pairs, 6 bytes
+ *   per posting.
+ * Replace and remove (mi355dr_set_sparse, mi355dr_remove_sparse).  set: document doc_ids[j] becomes the token sequence
+ *   terms[offsets[j] .. offsets[j+1]), under the limits of the add.  remove: a set with an empty sequence -- the document stays
+ *   stored and keeps its id, never matches and leaves N, total_len and df; a later set with tokens revives it.  Ids and
+ *   mi355dr_size_sparse never change; mi355dr_live_sparse is N.  doc_ids are LOCAL ids (no "row_offset"), each in
+ *   [0, mi355dr_size_sparse) and listed once per call; else, and for a null buffer with n > 0 or decreasing offsets,
+ *   E_INVALID and nothing changes.  n = 0 is a no-op; a view refuses both.  CONTRACT: after any sequence of add / set / remove
+ *   every search (all distance bits, ids, tails), mi355dr_sparse_df and the stats "sparse_docs", "sparse_total_len",
+ *   "sparse_postings", "sparse_vocab" (the largest term id with df > 0, plus one: it can shrink) equal those of a fresh handle
+ *   given ONE mi355dr_add_sparse of the current documents.
+ *   On the device the store is the BASE (the layout of the last full build), one `moved` bit per document whose content is no
+ *   longer the base's (replaced, emptied, or appended since), and the OVERLAY, a second layout of the same format with the
+ *   current postings of the moved documents.  The first search after a mutation rebuilds the overlay alone while its postings
+ *   are at most "sparse_overlay_max_pct" percent of the base's, else the whole layout (the overlay is then empty).  A store
+ *   without moved documents is scored by the same kernel as before these calls existed.
  * Options: "sparse_tile_docs" (documents per LDS tile, a power of two 256 .. 8192, default 2048), "sparse_cand_cap" (slots of a
  *   query's candidate list, 16 .. 2048 [default]; a list that overflows is dropped whole and its document range run again in
- *   pieces that cannot overflow -- same results).  Stats: "sparse_docs" (N), "sparse_total_len", "sparse_postings" (distinct
+ *   pieces that cannot overflow -- same results), "sparse_overlay_max_pct" (0 .. 100, default 25; 0: every mutation takes a
+ *   full build).  Stats: "sparse_docs" (N), "sparse_total_len", "sparse_postings" (distinct
  *   (doc, term) pairs), "sparse_vocab" (largest term id + 1), "sparse_searches" (calls), "sparse_queries",
- *   "sparse_postings_scored", "sparse_overflows" ((query, launch) lists run again); the store's device bytes are part of
- *   "hbm_bytes_resident".
- * Views: a view has an empty sparse store and refuses mi355dr_add_sparse; mi355dr_compact does not touch the sparse store.
- * Out of scope: update / remove / compact of sparse documents, views over the store, a row-sharded sparse search (it needs
+ *   "sparse_postings_scored", "sparse_overflows" ((query, launch) lists run again), "sparse_full_builds",
+ *   "sparse_overlay_builds", "sparse_overlay_postings" (the overlay's size as last built), "sparse_dead_postings" (base postings
+ *   of moved documents, as last built), "sparse_sets" (documents set or removed); the store's device bytes, overlay and
+ *   `moved` included, are part of "hbm_bytes_resident".
+ * Views: a view has an empty sparse store and refuses mi355dr_add_sparse / _set_sparse / _remove_sparse; mi355dr_compact does
+ *   not touch the sparse store.
+ * Out of scope: compaction / renumbering of sparse documents (ids are table positions in the service), views over the store, a row-sharded sparse search (it needs
  *   global df / avgdl), a key filter, fusion on the device, any claim of bit parity with VectorChord-BM25. */
 int mi355dr_add_sparse(mi355dr_index* idx, const int32_t* terms, const int64_t* offsets /* [n_docs + 1] */, int64_t n_docs); /* host */
 int64_t mi355dr_size_sparse(const mi355dr_index* idx); /* stored documents, with or without tokens */
+int mi355dr_set_sparse(mi355dr_index* idx, const int64_t* doc_ids /* HOST [n] */, const int32_t* terms,
+                       const int64_t* offsets /* HOST [n + 1] */, int64_t n);
+int mi355dr_remove_sparse(mi355dr_index* idx, const int64_t* doc_ids /* HOST [n] */, int64_t n);
+int64_t mi355dr_live_sparse(const mi355dr_index* idx); /* documents with tokens = N of the statistics */
 int mi355dr_sparse_df(mi355dr_index* idx, const int32_t* terms, int64_t n, int64_t* out_df); /* 0 for unseen / out-of-range terms */
 int mi355dr_search_sparse(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets /* [B + 1] */,
                           int B, int k, double k1, double b, double* out_dist /* [B, k] */, int64_t* out_rows /* [B, k] */);

@@ -27,6 +27,21 @@ sys.path.insert(0, str(ROOT / "tests"))
 SPARSE_STATS = ["sparse_docs", "sparse_total_len", "sparse_postings", "sparse_vocab", "sparse_postings_scored", "sparse_overflows"]
 
 
+def zipf_corpus(rng, n: int, vocab: int, doc_len: int):
+    """(terms int32 flat, offsets int64 [n + 1], lengths): lengths uniform in [1, 2 * doc_len), tokens Zipf (p ~ 1 / rank)"""
+    lengths = rng.integers(1, 2 * doc_len, size=n)
+    offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    cdf = np.cumsum(1.0 / np.arange(1, vocab + 1))
+    terms = np.searchsorted(cdf / cdf[-1], rng.random(int(offsets[-1]))).astype(np.int32).clip(0, vocab - 1)
+    return terms, offsets, lengths
+
+
+def doc_queries(rng, terms, offsets, lengths, B: int, query_terms: int) -> list:
+    """B queries of `query_terms` tokens of one random document each"""
+    picks = rng.integers(0, len(lengths), size=B)
+    return [terms[offsets[d] + rng.integers(0, lengths[d], size=query_terms)].tolist() for d in picks]
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_000_000)
@@ -46,12 +61,8 @@ def main() -> None:
 
     rng = np.random.default_rng(a.seed)
     n, B = a.docs, a.queries
-    lengths = rng.integers(1, 2 * a.doc_len, size=n)
-    offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-    cdf = np.cumsum(1.0 / np.arange(1, a.vocab + 1))
-    terms = np.searchsorted(cdf / cdf[-1], rng.random(int(offsets[-1]))).astype(np.int32).clip(0, a.vocab - 1)
-    picks = rng.integers(0, n, size=B)
-    queries = [terms[offsets[d] + rng.integers(0, lengths[d], size=a.query_terms)].tolist() for d in picks]
+    terms, offsets, lengths = zipf_corpus(rng, n, a.vocab, a.doc_len)
+    queries = doc_queries(rng, terms, offsets, lengths, B, a.query_terms)
 
     out = {"docs": n, "vocab": a.vocab, "tokens": int(offsets[-1]), "queries": B, "query_terms": a.query_terms, "k": a.k,
            "repeats": a.repeats, "sparse_tile_docs": a.tile_docs or "default"}
