@@ -29,6 +29,8 @@ ABI_SYMBOLS = [
     "mi355dr_set_multivec", "mi355dr_set_multivec_device", "mi355dr_live_multivec",
     "mi355dr_add_sparse", "mi355dr_size_sparse", "mi355dr_sparse_df", "mi355dr_search_sparse", "mi355dr_search_sparse_device",
     "mi355dr_search_bm25", "mi355dr_search_bm25_device", "mi355dr_set_sparse", "mi355dr_remove_sparse", "mi355dr_live_sparse",
+    "mi355dr_search_sparse_subset", "mi355dr_search_sparse_subset_device", "mi355dr_search_bm25_subset",
+    "mi355dr_search_bm25_subset_device", "mi355dr_score_sparse_subset", "mi355dr_score_bm25_subset",
     "mi355dr_gqr_refine_scores", "mi355dr_merge_topk_device", "mi355dr_pack_topk_device",
     "mi355dr_merge_topk_packed_device", "mi355dr_comm_unique_id", "mi355dr_comm_init", "mi355dr_comm_world", "mi355dr_comm_count", "mi355dr_comm_init_custom",
     "mi355dr_search_sharded_device", "mi355dr_search_range_sharded_device", "mi355dr_search_rows_sharded_device",
@@ -209,6 +211,18 @@ def load() -> ctypes.CDLL:
     L.mi355dr_search_bm25.argtypes = [vp, i32p, i32p, c_int, c_int, c_double, c_double, f64p, i64p]
     L.mi355dr_search_bm25_device.restype = c_int
     L.mi355dr_search_bm25_device.argtypes = [vp, i32p, i32p, c_int, c_int, c_double, c_double, vp, vp, vp]
+    L.mi355dr_search_sparse_subset.restype = c_int
+    L.mi355dr_search_sparse_subset.argtypes = [vp, i32p, f64p, i32p, c_int, c_int, c_double, c_double, i64p, i64, f64p, i64p]
+    L.mi355dr_search_sparse_subset_device.restype = c_int
+    L.mi355dr_search_sparse_subset_device.argtypes = [vp, i32p, f64p, i32p, c_int, c_int, c_double, c_double, i64p, i64, vp, vp, vp]
+    L.mi355dr_search_bm25_subset.restype = c_int
+    L.mi355dr_search_bm25_subset.argtypes = [vp, i32p, i32p, c_int, c_int, c_double, c_double, i64p, i64, f64p, i64p]
+    L.mi355dr_search_bm25_subset_device.restype = c_int
+    L.mi355dr_search_bm25_subset_device.argtypes = [vp, i32p, i32p, c_int, c_int, c_double, c_double, i64p, i64, vp, vp, vp]
+    L.mi355dr_score_sparse_subset.restype = c_int
+    L.mi355dr_score_sparse_subset.argtypes = [vp, i32p, f64p, i32p, c_int, c_double, c_double, i64p, c_int, f64p]
+    L.mi355dr_score_bm25_subset.restype = c_int
+    L.mi355dr_score_bm25_subset.argtypes = [vp, i32p, i32p, c_int, c_double, c_double, i64p, c_int, f64p]
     L.mi355dr_gqr_refine.restype = c_int
     L.mi355dr_gqr_refine.argtypes = [vp, f64p, c_int, i64p, c_int, f64p, c_int, c_double, c_double, c_double, f64p]
     L.mi355dr_gqr_refine_maxsim.restype = c_int

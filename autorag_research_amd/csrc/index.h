@@ -412,6 +412,15 @@ struct mi355dr_index {
     int sparse_tile_docs = 2048;  // documents per LDS tile of k_sparse_score (option "sparse_tile_docs": a power of two, 256 .. 8192;
                                   // 2048 was the fastest of 1024 .. 8192 at 3, 8 and 24 terms per query: DESIGN.md section 4.8j)
     int sparse_cand_cap = 2048;   // slots of a query's sparse candidate list (option "sparse_cand_cap", 16 .. 2048)
+    // mi355dr_search_*_subset: a list of at most this many local documents (and at most sparse_cand_cap) is looked up pair by
+    // pair (k_sparse_pairs), a longer one runs the filtered tile pass (option "sparse_subset_pairs_max", 0 .. sparse_cand_cap;
+    // 0: always the tile pass).  2048: the largest list measured and the largest the candidate list admits -- at 1 M documents
+    // and 8-term queries the pair pass took 0.88 / 0.93 / 1.15 / 1.40 ms per block at m = 64 / 256 / 1024 / 2048 where the
+    // tile pass took 1.57 / 3.06 / 6.56 / 8.51 ("Within a listed subset")
+    int64_t sparse_subset_pairs_max = 2048;
+    // the *_subset forms: calls of the four searches, calls of the two score forms, (query, document) pairs given to
+    // k_sparse_pairs, tiles launched by the filtered k_sparse_score (grid.x, summed over launches)
+    int64_t s_sparse_subset_searches = 0, s_sparse_subset_scores = 0, s_sparse_subset_pairs = 0, s_sparse_subset_tiles = 0;
     // the first search after add / set / remove of sparse documents rebuilds the overlay alone while the moved documents'
     // postings are at most this many percent of the base layout's, else the whole layout (option "sparse_overlay_max_pct",
     // 0 .. 100; 0: always the whole layout).  25: the largest size measured, where the overlay build still cost a quarter of

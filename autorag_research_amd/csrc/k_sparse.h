@@ -7,6 +7,10 @@
 //                    documents that can still enter the query's top-k are appended to its candidate list.  <false>: one
 //                    layout, the store as the last full build left it.  <true>: a mutated store -- the base layout minus the
 //                    `moved` documents, plus the overlay layout that holds those documents' current postings
+//                    <*, true>: the same two within a listed subset -- the launch's tiles come from a list, and a posting of
+//                    a document whose `allowed` bit is clear is skipped
+//   k_sparse_pairs   one thread per (query, listed document): the document looked up in each of the query's term slices --
+//                    the exact scores of a pool, or the matches of a short list appended to the candidate lists
 //   k_sparse_merge   one workgroup per query: kept top-k + candidate list sorted under (distance asc, NaN last, id asc)
 //   k_sparse_final   the kept lists written out as (distance, id + row_offset), NaN / -1 behind the matches
 // The candidate list is the one bounded buffer: appends count past its end, the merge sees the count, drops the WHOLE list of
@@ -33,6 +37,12 @@ __host__ __device__ inline size_t sparse_score_lds(int T, bool overlay = false, 
     const size_t per_term = sizeof(int64_t) + sizeof(int32_t), bits = (size_t)(T / 32) * 4;
     if (!overlay) return (size_t)T * sizeof(double) + (size_t)kSparseTermsMax * per_term + bits + 16;
     return (size_t)T * sizeof(double) + 2 * (size_t)terms_cap * per_term + 2 * bits + 16;
+}
+// the filtered instantiations: the tile's `allowed` bits behind `touched` / `moved`, and slice tables of `terms_cap` entries in
+// both (acc | start | [overlay start] | length | [overlay length] | touched | [moved] | allowed | counter)
+__host__ __device__ inline size_t sparse_score_lds_filtered(int T, bool overlay, int terms_cap) {
+    const size_t per_term = sizeof(int64_t) + sizeof(int32_t), bits = (size_t)(T / 32) * 4;
+    return (size_t)T * sizeof(double) + (overlay ? 2 : 1) * (size_t)terms_cap * per_term + (overlay ? 3 : 2) * bits + 16;
 }
 __host__ __device__ inline size_t sparse_merge_lds(int np) { return (size_t)np * (sizeof(uint64_t) + sizeof(int32_t)); }
 
@@ -78,6 +88,12 @@ struct SparseOverlayView {
     int vocab;
     int terms_cap;            // entries of each LDS slice table: >= the terms of every query of the launch, even
 };
+// a search within a listed subset (kFilter): the launch's tiles and one bit per document that is listed
+struct SparseFilterView {
+    const int32_t* tiles;     // [gridDim.x] tile indices, ascending: tile x of the launch covers [tiles[x] * T, + T)
+    const unsigned* allowed;  // [allowed_words] bit d & 31 of word d >> 5
+    int64_t allowed_words;
+};
 struct SparseQueries {
     const int32_t* terms;    // each query's terms ascending, distinct, inside [0, vocab)
     const double* weights;
@@ -98,24 +114,30 @@ struct SparseLists {
 // kOverlay: `ov` is read (else it is ignored and the kernel is the one-layout kernel).  Within one term the base postings that
 // survive (document not moved) and the overlay's postings (documents moved) name disjoint documents, so the accumulation stays
 // plain read-add-writes; a skipped posting is neither added nor counted, so an emptied document is never touched.
-template <bool kOverlay>
+// kFilter: `flt` is read (else it is ignored).  Tile x is tile flt.tiles[x], cut to [a0, a1) as before; a posting of a
+// document that is not allowed is skipped like a dead one; the slice tables hold ov.terms_cap entries with or without an
+// overlay (of `ov`, <false, true> reads terms_cap alone).
+template <bool kOverlay, bool kFilter = false>
 __global__ __launch_bounds__(kSparseThreads) void k_sparse_score(SparseStoreView st, SparseOverlayView ov, SparseQueries qs,
                                                                  SparseLists ls, int64_t a0, int64_t a1, int T, double k1p1,
-                                                                 unsigned long long* __restrict__ postings_scored) {
+                                                                 unsigned long long* __restrict__ postings_scored, SparseFilterView flt) {
     extern __shared__ __align__(16) unsigned char sparse_smem[];
     double* acc = (double*)sparse_smem;
     int64_t* s_lo = (int64_t*)(acc + T);
-    const int terms_cap = kOverlay ? ov.terms_cap : kSparseTermsMax;
+    const int terms_cap = kOverlay || kFilter ? ov.terms_cap : kSparseTermsMax;
     int64_t* o_lo = s_lo + (kOverlay ? terms_cap : 0);
     int32_t* s_n = (int32_t*)(o_lo + terms_cap);
     int32_t* o_n = s_n + (kOverlay ? terms_cap : 0);
     unsigned* touched = (unsigned*)(o_n + terms_cap);
     unsigned* moved = touched + (kOverlay ? T / 32 : 0);
-    unsigned* s_scored = moved + T / 32;
+    unsigned* allowed = moved + (kFilter ? T / 32 : 0);
+    unsigned* s_scored = allowed + T / 32;
 
     const int tid = threadIdx.x;
     const int q = qs.qlist ? qs.qlist[blockIdx.y] : (int)blockIdx.y;
-    const int64_t t0 = (a0 / T + (int64_t)blockIdx.x) * T;
+    int64_t t0;
+    if constexpr (kFilter) t0 = (int64_t)flt.tiles[blockIdx.x] * T;
+    else t0 = (a0 / T + (int64_t)blockIdx.x) * T;
     const int64_t d0 = t0 > a0 ? t0 : a0;
     const int64_t d1 = t0 + T < a1 ? t0 + T : a1;
     const int qo = qs.offsets[q];
@@ -169,6 +191,10 @@ __global__ __launch_bounds__(kSparseThreads) void k_sparse_score(SparseStoreView
         const int64_t w0 = t0 >> 5;  // (t0 is a multiple of T >= 256)
         for (int j = tid; j < T / 32; j += kSparseThreads) moved[j] = w0 + j < ov.moved_words ? ov.moved[w0 + j] : 0u;
     }
+    if constexpr (kFilter) {
+        const int64_t w0 = t0 >> 5;
+        for (int j = tid; j < T / 32; j += kSparseThreads) allowed[j] = w0 + j < flt.allowed_words ? flt.allowed[w0 + j] : 0u;
+    }
     if (tid == 0) *s_scored = 0u;
     __syncthreads();
 
@@ -188,6 +214,9 @@ __global__ __launch_bounds__(kSparseThreads) void k_sparse_score(SparseStoreView
             if constexpr (kOverlay) {
                 if (moved[j >> 5] >> (j & 31) & 1u) continue;  // a dead posting: the document's content is in the overlay
             }
+            if constexpr (kFilter) {
+                if (!(allowed[j >> 5] >> (j & 31) & 1u)) continue;  // not listed
+            }
             const double frac = (tf * k1p1) / (tf + st.norm[doc]);
             acc[j] = acc[j] + (w * frac);
             atomicOr(&touched[j >> 5], 1u << (j & 31));
@@ -199,6 +228,9 @@ __global__ __launch_bounds__(kSparseThreads) void k_sparse_score(SparseStoreView
                 const int64_t doc = ov.post_doc[olo + p];
                 const double tf = (double)ov.post_tf[olo + p];
                 const int j = (int)(doc - t0);
+                if constexpr (kFilter) {
+                    if (!(allowed[j >> 5] >> (j & 31) & 1u)) continue;
+                }
                 const double frac = (tf * k1p1) / (tf + st.norm[doc]);
                 acc[j] = acc[j] + (w * frac);
                 atomicOr(&touched[j >> 5], 1u << (j & 31));
@@ -225,6 +257,85 @@ __global__ __launch_bounds__(kSparseThreads) void k_sparse_score(SparseStoreView
     }
     __syncthreads();
     if (tid == 0 && *s_scored) atomicAdd(postings_scored, (unsigned long long)*s_scored);
+}
+
+constexpr int kSparsePairTerms = kSparseThreads;  // terms whose slice bounds one round stages in LDS, one per thread
+
+struct SparsePairs {
+    const int32_t* ids;  // local documents, -1: skipped.  row_stride = 0: [m], one list for every query; else [queries, row_stride]
+    int64_t m;           // pairs per query
+    int64_t row_stride;
+    double* out_dist;    // [queries, m]: -score, NaN where skipped or unmatched.  null: the matches go to the candidate lists
+    int q0;              // query blockIdx.y + q0 of the block
+    int overlay;         // the layout has moved documents: `ov` is read
+};
+
+// grid: (ceil(m / kSparseThreads), queries of the launch), one thread per (query, listed document).  The document is looked
+// up by binary search in the slice of each of the query's terms, ASCENDING: the base's slice while its `moved` bit is clear,
+// the overlay's when it is set.  The operations and their order are k_sparse_score's, so the bits are too.  The chain of a
+// thread is one dependent load per halving of a slice and nothing else: the slice bounds and weights of kSparsePairTerms
+// terms at a time are staged in LDS by the block (they are the same for its threads), 10 KiB and few registers, so eight
+// waves per SIMD hide each other's loads.  With lists, every match is appended: the caller keeps m <= ls.cap.
+__global__ __launch_bounds__(kSparseThreads) void k_sparse_pairs(SparseStoreView st, SparseOverlayView ov, SparseQueries qs,
+                                                                 SparseLists ls, SparsePairs pr, double k1p1,
+                                                                 unsigned long long* __restrict__ postings_scored) {
+    __shared__ int64_t s_p0[2][kSparsePairTerms], s_p1[2][kSparsePairTerms];
+    __shared__ double s_w[kSparsePairTerms];
+    __shared__ unsigned s_scored;
+    const int tid = threadIdx.x;
+    const int q = pr.q0 + (int)blockIdx.y;
+    const int64_t j = (int64_t)blockIdx.x * kSparseThreads + tid;
+    const int qo = qs.offsets[q];
+    const int nt = qs.offsets[q + 1] - qo;  // (block-uniform)
+    const int64_t d = j < pr.m ? (int64_t)pr.ids[(int64_t)blockIdx.y * pr.row_stride + j] : -1;
+    int in_ov = 0;
+    if (d >= 0 && pr.overlay && (d >> 5) < ov.moved_words) in_ov = (int)(ov.moved[d >> 5] >> (d & 31) & 1u);
+    const int32_t* __restrict__ post_doc = in_ov ? ov.post_doc : st.post_doc;
+    const uint16_t* __restrict__ post_tf = in_ov ? ov.post_tf : st.post_tf;
+    const double norm = d >= 0 ? st.norm[d] : 0.0;
+    if (tid == 0) s_scored = 0u;
+
+    double score = 0.0;
+    bool hit = false;
+    unsigned scored = 0;
+    for (int i0 = 0; i0 < nt; i0 += kSparsePairTerms) {
+        const int ni = nt - i0 < kSparsePairTerms ? nt - i0 : kSparsePairTerms;
+        __syncthreads();  // (the round before has been read)
+        if (tid < ni) {
+            const int t = qs.terms[qo + i0 + tid];
+            s_w[tid] = qs.weights[qo + i0 + tid];
+            const bool in_base = t >= 0 && t < st.vocab, in_over = pr.overlay && t >= 0 && t < ov.vocab;
+            s_p0[0][tid] = in_base ? st.term_off[t] : 0;
+            s_p1[0][tid] = in_base ? st.term_off[t + 1] : 0;
+            s_p0[1][tid] = in_over ? ov.term_off[t] : 0;
+            s_p1[1][tid] = in_over ? ov.term_off[t + 1] : 0;
+        }
+        __syncthreads();
+        for (int i = 0; d >= 0 && i < ni; ++i) {
+            const int64_t p0 = s_p0[in_ov][i], p1 = s_p1[in_ov][i];
+            if (p0 == p1) continue;
+            const int64_t p = sparse_lower_bound(post_doc, p0, p1, d);
+            if (p == p1 || (int64_t)post_doc[p] != d) continue;
+            const double tf = (double)post_tf[p];
+            const double frac = (tf * k1p1) / (tf + norm);
+            score = score + (s_w[i] * frac);
+            hit = true;
+            ++scored;
+        }
+    }
+    if (pr.out_dist) {
+        if (j < pr.m) pr.out_dist[(int64_t)blockIdx.y * pr.m + j] = hit ? -score : __longlong_as_double(0x7FF8000000000000ll);
+    } else if (hit) {
+        const unsigned slot = atomicAdd(&ls.count[q], 1u);
+        if (slot < (unsigned)ls.cap) {
+            ls.cand_key[(int64_t)q * ls.cap + slot] = dist_to_key(-score);
+            ls.cand_doc[(int64_t)q * ls.cap + slot] = (int32_t)d;
+        }
+    }
+    __syncthreads();  // (s_scored is zero for everyone, also when the query has no term)
+    if (scored) atomicAdd(&s_scored, scored);
+    __syncthreads();
+    if (tid == 0 && s_scored) atomicAdd(postings_scored, (unsigned long long)s_scored);
 }
 
 __device__ __forceinline__ void bitonic_asc_sparse(uint64_t* key, int32_t* row, int n) {

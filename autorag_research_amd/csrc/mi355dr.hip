@@ -2831,6 +2831,7 @@ const Option kOptions[] = {
     {"sparse_tile_docs", &Index::sparse_tile_docs, 256, 8192},  // documents per LDS tile of k_sparse_score (a power of two: checked below)
     {"sparse_cand_cap", &Index::sparse_cand_cap, 16, 2048},     // slots of a query's sparse candidate list
     {"sparse_overlay_max_pct", &Index::sparse_overlay_max_pct, 0, 100},  // overlay build while moved postings <= this % of the base's (0: never)
+    {"sparse_subset_pairs_max", &Index::sparse_subset_pairs_max, 0, 2048},  // longest listed subset looked up pair by pair (<= sparse_cand_cap: checked below)
     {"shard_stage_bytes", &Index::shard_stage_bytes, 1},  // most bytes of the sharded MMR forms' gathered stage (never below one query's)
 };
 
@@ -2906,6 +2907,10 @@ const Stat kStats[] = {
     {"sparse_full_builds", &Index::s_sparse_full_builds, true},
     {"sparse_overlay_builds", &Index::s_sparse_overlay_builds, true},
     {"sparse_sets", &Index::s_sparse_sets, true},
+    {"sparse_subset_searches", &Index::s_sparse_subset_searches, true},
+    {"sparse_subset_scores", &Index::s_sparse_subset_scores, true},
+    {"sparse_subset_pairs", &Index::s_sparse_subset_pairs, true},
+    {"sparse_subset_tiles", &Index::s_sparse_subset_tiles, true},
     {"sparse_overlay_postings", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatOverlayPostings); }},
     {"sparse_dead_postings", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatDeadPostings); }},
     {"sparse_docs", nullptr, false, [](const Index* x) -> int64_t { return sparse_stat(x, kSparseStatDocs); }},
@@ -2952,6 +2957,8 @@ int mi355dr_set_option(mi355dr_index* idx, const char* key, int64_t value) {
         }
         if (strcmp(key, "sparse_tile_docs") == 0 && (value & (value - 1)) != 0)
             return fail(idx, MI355DR_E_INVALID, "sparse_tile_docs must be a power of two");
+        if (strcmp(key, "sparse_subset_pairs_max") == 0 && value > idx->sparse_cand_cap)
+            return fail(idx, MI355DR_E_INVALID, "sparse_subset_pairs_max must not exceed sparse_cand_cap");
         o.field.set(idx, value);
         if (o.then) o.then(idx);
         return MI355DR_OK;

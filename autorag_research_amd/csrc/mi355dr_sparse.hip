@@ -8,9 +8,13 @@
 // (k1, b) -- once as the base (the last full build) and, while documents have been replaced, emptied or appended since, a
 // `moved` bit per document and an overlay of the same format with those documents' current postings.  A search runs the
 // document range in a few launches of growing size (k_sparse.h): the first cannot overflow a candidate list, every later one
-// appends only what beats the query's k-th kept entry.
+// appends only what beats the query's k-th kept entry.  Within a listed subset (the *_subset forms; sparse_subset.h) a long list
+// runs the same launches over the tiles that hold a listed document, filtered by a bitmap; a short one, and the score forms,
+// look every (query, document) pair up directly (k_sparse_pairs).
 #include "index.h"
 #include "k_sparse.h"
+#include "sparse_subset.h"
+#include "subset_ids.h"
 
 #include <new>
 
@@ -58,6 +62,10 @@ struct SparseStore {
     DevBuf<unsigned> count;
     DevBuf<int> flags, qlist;
     DevBuf<unsigned long long> scored;
+    // a call within a listed subset: the `allowed` bitmap, the launches' tile lists, the local ids and the score forms' distances
+    DevBuf<unsigned> sub_bits;
+    DevBuf<int32_t> sub_tiles, sub_ids;
+    DevBuf<double> pair_dist;
     bool lds_registered = false;
 };
 
@@ -69,7 +77,8 @@ void sparse_destroy(mi355dr_index* idx) {
 int64_t sparse_bytes(const mi355dr_index* idx) {
     const SparseStore* s = idx->sp;
     return s ? (int64_t)(s->term_off.bytes + s->post_doc.bytes + s->post_tf.bytes + s->len_dev.bytes + s->norm.bytes +
-                         s->ov_term_off.bytes + s->ov_post_doc.bytes + s->ov_post_tf.bytes + s->moved_dev.bytes)
+                         s->ov_term_off.bytes + s->ov_post_doc.bytes + s->ov_post_tf.bytes + s->moved_dev.bytes +
+                         s->sub_bits.bytes + s->sub_tiles.bytes + s->sub_ids.bytes + s->pair_dist.bytes)
              : 0;
 }
 
@@ -243,57 +252,57 @@ struct SparseOut {
     bool host;
 };
 
-// the launch plan of one block: document ranges [a, a') of growing size.  The first holds at most `cap` documents, so its
-// lists cannot overflow; after `seen` documents a random order lets about k * new / seen of the next `new` beat the k-th kept
-// entry, and the ratio keeps that at half a list.
-std::vector<int64_t> sparse_plan(int64_t n, int k, int cap) {
-    std::vector<int64_t> edges{0};
-    const int64_t ratio = std::min<int64_t>(16, std::max<int64_t>(1, cap / (2 * (int64_t)k)));
-    int64_t seen = std::min<int64_t>(n, cap);
-    edges.push_back(seen);
-    while (seen < n) {
-        seen = std::min(n, seen + seen * ratio);
-        edges.push_back(seen);
-    }
-    return edges;
-}
-
-// the block and its overflow pieces launch the same instantiation: <true> exactly while the device layout has moved documents
+// the block and its overflow pieces launch the same instantiation: <true> exactly while the device layout has moved documents,
+// <*, true> exactly for a launch with a tile list (a search within a listed subset)
 int launch_score(mi355dr_index* idx, SparseStore* sp, hipStream_t s, const SparseStoreView& view, const SparseOverlayView& ov,
-                 const SparseQueries& qs, const SparseLists& ls, int64_t a0, int64_t a1, int nq, double k1p1) {
+                 const SparseQueries& qs, const SparseLists& ls, const SparseLaunch& l, int nq, double k1p1) {
     const int T = idx->sparse_tile_docs;
-    const int64_t tiles = (a1 - 1) / T - a0 / T + 1;
+    if (l.n_tiles >= 0) {
+        const SparseFilterView flt{sp->sub_tiles.p + l.tile_at, sp->sub_bits.p, (sp->n_docs + 31) / 32};
+        const dim3 grid((unsigned)l.n_tiles, (unsigned)nq);
+        const size_t lds = sparse_score_lds_filtered(T, sp->ov_active, ov.terms_cap);
+        if (sp->ov_active)
+            hipLaunchKernelGGL((k_sparse_score<true, true>), grid, dim3(kSparseThreads), lds, s, view, ov, qs, ls, l.a0, l.a1, T, k1p1,
+                               sp->scored.p, flt);
+        else
+            hipLaunchKernelGGL((k_sparse_score<false, true>), grid, dim3(kSparseThreads), lds, s, view, ov, qs, ls, l.a0, l.a1, T, k1p1,
+                               sp->scored.p, flt);
+        idx->s_sparse_subset_tiles += l.n_tiles;
+        HIPCHECK(idx, hipGetLastError());
+        return MI355DR_OK;
+    }
+    const int64_t tiles = (l.a1 - 1) / T - l.a0 / T + 1;
     const dim3 grid((unsigned)tiles, (unsigned)nq);
+    const SparseFilterView none{nullptr, nullptr, 0};
     if (sp->ov_active)
-        hipLaunchKernelGGL(k_sparse_score<true>, grid, dim3(kSparseThreads), sparse_score_lds(T, true, ov.terms_cap), s, view, ov, qs, ls, a0, a1, T,
-                           k1p1, sp->scored.p);
+        hipLaunchKernelGGL(k_sparse_score<true>, grid, dim3(kSparseThreads), sparse_score_lds(T, true, ov.terms_cap), s, view, ov, qs, ls, l.a0,
+                           l.a1, T, k1p1, sp->scored.p, none);
     else
-        hipLaunchKernelGGL(k_sparse_score<false>, grid, dim3(kSparseThreads), sparse_score_lds(T), s, view, ov, qs, ls, a0, a1, T, k1p1,
-                           sp->scored.p);
+        hipLaunchKernelGGL(k_sparse_score<false>, grid, dim3(kSparseThreads), sparse_score_lds(T), s, view, ov, qs, ls, l.a0, l.a1, T, k1p1,
+                           sp->scored.p, none);
     HIPCHECK(idx, hipGetLastError());
     return MI355DR_OK;
 }
 
-// Queries [0, B) as flat host arrays -- every query's terms ascending, distinct, inside [0, 2^20), at most kSparseTermsMax --
-// against the store; results to `out` ([B, k], host or device).  The handle's mutex is held.
-int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, const std::vector<double>& weights,
-                         const std::vector<int32_t>& offsets, int B, int k, double k1, double b, SparseOut out, hipStream_t s) {
-    idx->s_sparse_searches++;
-    idx->s_sparse_queries += B;
-    if (B == 0) return MI355DR_OK;
+// the store of the handle (created when there is none), its device layout and the norms of (k1, b) brought up to date; *n: the
+// documents a search runs over (0 while no document has tokens)
+int sparse_ready(mi355dr_index* idx, double k1, double b, hipStream_t s, int64_t* n_out) {
     if (!idx->sp) {
         idx->sp = new (std::nothrow) SparseStore();
         if (!idx->sp) return fail(idx, MI355DR_E_NOMEM, "sparse store: host memory");
     }
     SparseStore* sp = idx->sp;
     if (sp->n_live > 0) CHECK(sparse_upload(idx, sp));
-    const int cap = idx->sparse_cand_cap;
     const int64_t n = sp->n_live > 0 ? sp->n_docs : 0;
     if (!sp->lds_registered) {
         HIPCHECK(idx, hipFuncSetAttribute((const void*)k_sparse_score<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)sparse_score_lds(kSparseTileMax)));
         HIPCHECK(idx, hipFuncSetAttribute((const void*)k_sparse_score<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)sparse_score_lds(kSparseTileMax, true)));
+        HIPCHECK(idx, hipFuncSetAttribute((const void*)k_sparse_score<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)sparse_score_lds_filtered(kSparseTileMax, false, kSparseTermsMax)));
+        HIPCHECK(idx, hipFuncSetAttribute((const void*)k_sparse_score<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)sparse_score_lds_filtered(kSparseTileMax, true, kSparseTermsMax)));
         sp->lds_registered = true;
     }
     if (n > 0 && !(sp->norm_valid && sp->norm_k1 == k1 && sp->norm_b == b)) {
@@ -305,11 +314,81 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
         sp->norm_k1 = k1;
         sp->norm_b = b;
     }
-    const std::vector<int64_t> edges = sparse_plan(n, k, cap);
-    const int n_chunks = n > 0 ? (int)edges.size() - 1 : 0;
+    *n_out = n;
+    return MI355DR_OK;
+}
+
+// queries [b0, b0 + nb) of the call to the device, in stream order behind the previous block (the host vectors stay as they
+// are until the block's last wait); *terms_cap: the block's longest query, even -- the size of the LDS slice tables of every
+// k_sparse_score but <false>
+int sparse_put_queries(mi355dr_index* idx, SparseStore* sp, const std::vector<int32_t>& terms, const std::vector<double>& weights,
+                       const std::vector<int32_t>& offsets, int b0, int nb, hipStream_t s, std::vector<int32_t>& off_block,
+                       int* terms_cap, size_t* nt_out) {
+    const int32_t t_lo = offsets[b0], t_hi = offsets[b0 + nb];
+    const size_t nt = (size_t)(t_hi - t_lo);
+    off_block.resize((size_t)nb + 1);
+    for (int i = 0; i <= nb; ++i) off_block[i] = offsets[b0 + i] - t_lo;
+    *terms_cap = 2;
+    for (int i = 0; i < nb; ++i) *terms_cap = std::max(*terms_cap, (offsets[b0 + i + 1] - offsets[b0 + i] + 1) & ~1);
+    HIPCHECK(idx, grow_each(std::max<size_t>(nt, 1), sp->q_terms));
+    HIPCHECK(idx, grow_each(std::max<size_t>(nt, 1), sp->q_w));
+    if (nt) {
+        HIPCHECK(idx, hipMemcpyAsync(sp->q_terms.p, terms.data() + t_lo, nt * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHECK(idx, hipMemcpyAsync(sp->q_w.p, weights.data() + t_lo, nt * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    HIPCHECK(idx, hipMemcpyAsync(sp->q_off.p, off_block.data(), off_block.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    *nt_out = nt;
+    return MI355DR_OK;
+}
+
+// the lists of a call within a listed subset
+struct SparseSubsetArg {
+    const int64_t* doc_ids;  // HOST, global ids
+    int64_t m;
+};
+
+// Queries [0, B) as flat host arrays -- every query's terms ascending, distinct, inside [0, 2^20), at most kSparseTermsMax --
+// against the store; results to `out` ([B, k], host or device).  The handle's mutex is held.  `sub`: null, or the list the
+// search is restricted to -- its local documents run through k_sparse_pairs when they are at most "sparse_subset_pairs_max",
+// else through the launches of sparse_plan_subset with a tile list each.
+int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, const std::vector<double>& weights,
+                         const std::vector<int32_t>& offsets, int B, int k, double k1, double b, SparseOut out, hipStream_t s,
+                         const SparseSubsetArg* sub = nullptr) {
+    if (sub) idx->s_sparse_subset_searches++;
+    else idx->s_sparse_searches++;
+    idx->s_sparse_queries += B;
+    if (B == 0) return MI355DR_OK;
+    int64_t n = 0;
+    CHECK(sparse_ready(idx, k1, b, s, &n));
+    SparseStore* sp = idx->sp;
+    const int cap = idx->sparse_cand_cap;
+    std::vector<int32_t> listed;  // the list's local documents, ascending, each once
+    std::vector<unsigned> bits;
+    SparseLaunchPlan plan;
+    bool pairs = false;
+    try {
+        if (sub) {
+            // a list that may take the pair pass is short: sort it; a longer one goes through the bitmap it needs anyway
+            const int64_t pairs_max = std::min<int64_t>(idx->sparse_subset_pairs_max, cap);
+            if (sub->m <= pairs_max || n == 0) subset_prepare_ids(sub->doc_ids, sub->m, idx->row_offset, n, listed);
+            else sparse_subset_scan(sub->doc_ids, sub->m, idx->row_offset, n, listed, bits);
+            pairs = (int64_t)listed.size() <= pairs_max;  // (duplicates may have made a longer list short)
+            if (pairs) bits.clear();
+            else plan = sparse_plan_subset(listed, k, cap, idx->sparse_tile_docs);
+        } else {
+            plan = sparse_plan_all(n, k, cap);
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, "sparse search: host memory for the launch plan");
+    }
+    if (listed.empty()) pairs = false;  // (nothing to look up: every line is NaN / -1)
+    const int n_chunks = pairs ? 1 : (int)plan.ranges.size();
     const int nb_max = std::min(B, kQBlockMax);
     const int np_max = pow2_at_least(k + cap);
     // every buffer of the call before its first launch: a failure leaves the store as it was
+    if (pairs) HIPCHECK(idx, grow_each(listed.size(), sp->sub_ids));
+    if (!bits.empty()) HIPCHECK(idx, grow_each(bits.size(), sp->sub_bits));
+    if (!plan.tiles.empty()) HIPCHECK(idx, grow_each(plan.tiles.size(), sp->sub_tiles));
     HIPCHECK(idx, grow_each((size_t)nb_max * k, sp->best_key, sp->best_doc));
     HIPCHECK(idx, grow_each((size_t)nb_max * cap, sp->cand_key, sp->cand_doc));
     HIPCHECK(idx, grow_each((size_t)nb_max, sp->count));
@@ -318,6 +397,11 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
     HIPCHECK(idx, grow_each(1, sp->scored));
     if (out.host) HIPCHECK(idx, grow_each((size_t)nb_max * k, sp->out_dist, sp->out_rows));
     HIPCHECK(idx, hipMemsetAsync(sp->scored.p, 0, sizeof(unsigned long long), s));
+    // (the list's device forms stay as they are for every block of the call; the host vectors until the first block's wait)
+    if (pairs) HIPCHECK(idx, hipMemcpyAsync(sp->sub_ids.p, listed.data(), listed.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (!bits.empty()) HIPCHECK(idx, hipMemcpyAsync(sp->sub_bits.p, bits.data(), bits.size() * sizeof(unsigned), hipMemcpyHostToDevice, s));
+    if (!plan.tiles.empty())
+        HIPCHECK(idx, hipMemcpyAsync(sp->sub_tiles.p, plan.tiles.data(), plan.tiles.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
 
     const SparseStoreView view{sp->term_off.p, sp->post_doc.p, sp->post_tf.p, sp->norm.p, sp->base_vocab};
     SparseOverlayView ov{sp->moved_dev.p, sp->ov_term_off.p, sp->ov_post_doc.p, sp->ov_post_tf.p, sp->moved_words_dev, sp->ov_vocab, 2};
@@ -326,20 +410,8 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
     std::vector<int> flags_host, redo_q;
     for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
         const int nb = std::min(kQBlockMax, B - b0);
-        const int32_t t_lo = offsets[b0], t_hi = offsets[b0 + nb];
-        const size_t nt = (size_t)(t_hi - t_lo);
-        off_block.resize((size_t)nb + 1);
-        for (int i = 0; i <= nb; ++i) off_block[i] = offsets[b0 + i] - t_lo;
-        ov.terms_cap = 2;  // the block's longest query, even: the size of k_sparse_score<true>'s two LDS slice tables
-        for (int i = 0; i < nb; ++i) ov.terms_cap = std::max(ov.terms_cap, (offsets[b0 + i + 1] - offsets[b0 + i] + 1) & ~1);
-        HIPCHECK(idx, grow_each(std::max<size_t>(nt, 1), sp->q_terms));
-        HIPCHECK(idx, grow_each(std::max<size_t>(nt, 1), sp->q_w));
-        // (in stream order behind the previous block; the host vectors stay as they are until the block's last wait)
-        if (nt) {
-            HIPCHECK(idx, hipMemcpyAsync(sp->q_terms.p, terms.data() + t_lo, nt * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            HIPCHECK(idx, hipMemcpyAsync(sp->q_w.p, weights.data() + t_lo, nt * sizeof(double), hipMemcpyHostToDevice, s));
-        }
-        HIPCHECK(idx, hipMemcpyAsync(sp->q_off.p, off_block.data(), off_block.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        size_t nt = 0;
+        CHECK(sparse_put_queries(idx, sp, terms, weights, offsets, b0, nb, s, off_block, &ov.terms_cap, &nt));
 
         SparseLists ls{sp->best_key.p, sp->best_doc.p, sp->cand_key.p, sp->cand_doc.p, sp->count.p, k, cap};
         SparseQueries qs{sp->q_terms.p, sp->q_w.p, sp->q_off.p, nullptr};
@@ -348,9 +420,18 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
         hipLaunchKernelGGL(k_sparse_reset, dim3((unsigned)((n_reset + kSparseThreads - 1) / kSparseThreads)), dim3(kSparseThreads), 0, s,
                            sp->best_key.p, sp->best_doc.p, n_best, sp->count.p, (int64_t)nb, sp->flags.p, n_flags);
         HIPCHECK(idx, hipGetLastError());
-        if (nt > 0) {
+        if (nt > 0 && pairs) {  // (at most cap listed documents: the lists cannot overflow)
+            const SparsePairs pr{sp->sub_ids.p, (int64_t)listed.size(), 0, nullptr, 0, sp->ov_active ? 1 : 0};
+            hipLaunchKernelGGL(k_sparse_pairs, dim3((unsigned)((listed.size() + kSparseThreads - 1) / kSparseThreads), (unsigned)nb),
+                               dim3(kSparseThreads), 0, s, view, ov, qs, ls, pr, k1p1, sp->scored.p);
+            HIPCHECK(idx, hipGetLastError());
+            idx->s_sparse_subset_pairs += (int64_t)nb * (int64_t)listed.size();
+            hipLaunchKernelGGL(k_sparse_merge, dim3((unsigned)nb), dim3(kSparseThreads), sparse_merge_lds(np_max), s, ls,
+                               (const int*)nullptr, np_max, sp->flags.p);
+            HIPCHECK(idx, hipGetLastError());
+        } else if (nt > 0) {
             for (int c = 0; c < n_chunks; ++c) {
-                CHECK(launch_score(idx, sp, s, view, ov, qs, ls, edges[c], edges[c + 1], nb, k1p1));
+                CHECK(launch_score(idx, sp, s, view, ov, qs, ls, plan.ranges[c], nb, k1p1));
                 hipLaunchKernelGGL(k_sparse_merge, dim3((unsigned)nb), dim3(kSparseThreads), sparse_merge_lds(np_max), s, ls,
                                    (const int*)nullptr, np_max, sp->flags.p + (size_t)c * nb);
                 HIPCHECK(idx, hipGetLastError());
@@ -370,8 +451,8 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
                     HIPCHECK(idx, hipMemcpyAsync(ql, redo_q.data(), redo_q.size() * sizeof(int), hipMemcpyHostToDevice, s));
                     SparseQueries qr = qs;
                     qr.qlist = ql;
-                    for (int64_t a = edges[c]; a < edges[c + 1]; a += cap) {
-                        CHECK(launch_score(idx, sp, s, view, ov, qr, ls, a, std::min<int64_t>(a + cap, edges[c + 1]), (int)redo_q.size(), k1p1));
+                    for (const SparseLaunch& piece : plan.pieces[c]) {
+                        CHECK(launch_score(idx, sp, s, view, ov, qr, ls, piece, (int)redo_q.size(), k1p1));
                         hipLaunchKernelGGL(k_sparse_merge, dim3((unsigned)redo_q.size()), dim3(kSparseThreads), sparse_merge_lds(np_max),
                                            s, ls, (const int*)ql, np_max, spare);
                         HIPCHECK(idx, hipGetLastError());
@@ -422,15 +503,17 @@ int sparse_begin(mi355dr_index* idx, std::unique_lock<std::mutex>& lock, void* s
     return MI355DR_OK;
 }
 
-int search_sparse_impl(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B, int k,
-                       double k1, double b, SparseOut out, void* stream) {
-    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
-    std::unique_lock<std::mutex> lock;
-    hipStream_t s = nullptr;
-    CHECK(sparse_begin(idx, lock, stream, &s));
-    CHECK(check_common(idx, q_offsets, B, k, k1, b, out.dist, out.rows));
+// the queries of a call as sparse_search_sorted takes them
+struct SortedQueries {
     std::vector<int32_t> terms, offsets;
     std::vector<double> weights;
+};
+
+// the weighted forms' queries, checked, each one's terms sorted ascending
+int weighted_queries(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B,
+                     SortedQueries* out) {
+    std::vector<int32_t>&terms = out->terms, &offsets = out->offsets;
+    std::vector<double>& weights = out->weights;
     try {
         offsets.assign((size_t)B + 1, 0);
         std::vector<std::pair<int32_t, double>> one;
@@ -459,20 +542,16 @@ int search_sparse_impl(mi355dr_index* idx, const int32_t* q_terms, const double*
     } catch (const std::bad_alloc&) {
         return fail(idx, MI355DR_E_NOMEM, "sparse search: host memory");
     }
-    return sparse_search_sorted(idx, terms, weights, offsets, B, k, k1, b, out, s);
+    return MI355DR_OK;
 }
 
-int search_bm25_impl(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1, double b,
-                     SparseOut out, void* stream) {
-    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
-    std::unique_lock<std::mutex> lock;
-    hipStream_t s = nullptr;
-    CHECK(sparse_begin(idx, lock, stream, &s));
-    CHECK(check_common(idx, q_offsets, B, k, k1, b, out.dist, out.rows));
+// the BM25 forms' queries: raw tokens -> the terms that occur, each once, ascending, weighted by the store's N and df
+int bm25_queries(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, SortedQueries* out) {
     const SparseStore* sp = idx->sp;
     const int64_t N = sp ? sp->n_live : 0, vocab = sp ? sp->vocab : 0;
-    std::vector<int32_t> terms, offsets, one;
-    std::vector<double> weights;
+    std::vector<int32_t>&terms = out->terms, &offsets = out->offsets;
+    std::vector<int32_t> one;
+    std::vector<double>& weights = out->weights;
     try {
         offsets.assign((size_t)B + 1, 0);
         for (int q = 0; q < B; ++q) {
@@ -495,7 +574,99 @@ int search_bm25_impl(mi355dr_index* idx, const int32_t* q_tokens, const int32_t*
     } catch (const std::bad_alloc&) {
         return fail(idx, MI355DR_E_NOMEM, "bm25 search: host memory");
     }
-    return sparse_search_sorted(idx, terms, weights, offsets, B, k, k1, b, out, s);
+    return MI355DR_OK;
+}
+
+// the eight search forms: weighted (q_terms, q_weights) or BM25 (q_terms are raw tokens), host or device results, the whole
+// store or a listed subset
+int search_impl(mi355dr_index* idx, bool bm25, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B, int k,
+                double k1, double b, SparseOut out, void* stream, const SparseSubsetArg* sub = nullptr) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s = nullptr;
+    CHECK(sparse_begin(idx, lock, stream, &s));
+    CHECK(check_common(idx, q_offsets, B, k, k1, b, out.dist, out.rows));
+    if (sub && (sub->m < 0 || (sub->m > 0 && !sub->doc_ids)))
+        return fail(idx, MI355DR_E_INVALID, "sparse search within a subset: m must be >= 0 and doc_ids not null");
+    SortedQueries q;
+    CHECK(bm25 ? bm25_queries(idx, q_terms, q_offsets, B, &q) : weighted_queries(idx, q_terms, q_weights, q_offsets, B, &q));
+    return sparse_search_sorted(idx, q.terms, q.weights, q.offsets, B, k, k1, b, out, s, sub);
+}
+
+constexpr int64_t kPairsLaunchMax = (int64_t)1 << 22;  // (query, document) pairs of one k_sparse_pairs launch of the score forms
+
+// mi355dr_score_sparse_subset / mi355dr_score_bm25_subset: every query against its own row of doc_ids, through k_sparse_pairs in
+// launches of whole rows (or, for a row longer than a launch, parts of one row) staged in buffers of at most kPairsLaunchMax
+int score_impl(mi355dr_index* idx, bool bm25, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B,
+               double k1, double b, const int64_t* doc_ids, int m, double* out_dist) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s = nullptr;
+    CHECK(sparse_begin(idx, lock, nullptr, &s));
+    CHECK(check_common(idx, q_offsets, B, 1, k1, b, idx, idx));  // (no k and no result lists here: the buffers are checked below)
+    if (m < 0) return fail(idx, MI355DR_E_INVALID, "sparse scores: m must be >= 0");
+    if (B > 0 && m > 0 && (!doc_ids || !out_dist)) return fail(idx, MI355DR_E_INVALID, "sparse scores: null buffer");
+    if ((int64_t)B * m > INT32_MAX) return fail(idx, MI355DR_E_UNSUPPORTED, "sparse scores: B * m must be below 2^31");
+    SortedQueries q;
+    CHECK(bm25 ? bm25_queries(idx, q_terms, q_offsets, B, &q) : weighted_queries(idx, q_terms, q_weights, q_offsets, B, &q));
+    idx->s_sparse_subset_scores++;
+    if (B == 0 || m == 0) return MI355DR_OK;
+    int64_t n = 0;
+    CHECK(sparse_ready(idx, k1, b, s, &n));
+    SparseStore* sp = idx->sp;
+    if (n == 0) {  // no document matches anything
+        std::fill(out_dist, out_dist + (int64_t)B * m, std::nan(""));
+        return MI355DR_OK;
+    }
+    const int nb_max = std::min(B, kQBlockMax);
+    const int rows_per = m <= kPairsLaunchMax ? (int)std::min<int64_t>(nb_max, kPairsLaunchMax / m) : 1;
+    const int64_t cols = std::min<int64_t>(m, kPairsLaunchMax);
+    std::vector<int32_t> ids_host, off_block;
+    try {
+        ids_host.resize((size_t)(rows_per * cols));
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, "sparse scores: host memory");
+    }
+    HIPCHECK(idx, grow_each(ids_host.size(), sp->sub_ids, sp->pair_dist));
+    HIPCHECK(idx, grow_each((size_t)nb_max + 1, sp->q_off));
+    HIPCHECK(idx, grow_each(1, sp->scored));
+    HIPCHECK(idx, hipMemsetAsync(sp->scored.p, 0, sizeof(unsigned long long), s));
+
+    const SparseStoreView view{sp->term_off.p, sp->post_doc.p, sp->post_tf.p, sp->norm.p, sp->base_vocab};
+    const SparseLists no_lists{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    SparseOverlayView ov{sp->moved_dev.p, sp->ov_term_off.p, sp->ov_post_doc.p, sp->ov_post_tf.p, sp->moved_words_dev, sp->ov_vocab, 2};
+    const double k1p1 = k1 + 1.0;
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        size_t nt = 0;
+        CHECK(sparse_put_queries(idx, sp, q.terms, q.weights, q.offsets, b0, nb, s, off_block, &ov.terms_cap, &nt));
+        const SparseQueries qs{sp->q_terms.p, sp->q_w.p, sp->q_off.p, nullptr};
+        for (int q0 = 0; q0 < nb; q0 += rows_per) {
+            const int nq = std::min(rows_per, nb - q0);
+            for (int64_t j0 = 0; j0 < m; j0 += cols) {
+                const int64_t mm = std::min<int64_t>(cols, m - j0);
+                for (int r = 0; r < nq; ++r) {
+                    const int64_t* row = doc_ids + (int64_t)(b0 + q0 + r) * m + j0;
+                    for (int64_t j = 0; j < mm; ++j) ids_host[(size_t)(r * mm + j)] = (int32_t)subset_local_row(row[j], idx->row_offset, n);
+                }
+                const size_t n_pairs = (size_t)(nq * mm);
+                HIPCHECK(idx, hipMemcpyAsync(sp->sub_ids.p, ids_host.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
+                const SparsePairs pr{sp->sub_ids.p, mm, mm, sp->pair_dist.p, q0, sp->ov_active ? 1 : 0};
+                hipLaunchKernelGGL(k_sparse_pairs, dim3((unsigned)((mm + kSparseThreads - 1) / kSparseThreads), (unsigned)nq),
+                                   dim3(kSparseThreads), 0, s, view, ov, qs, no_lists, pr, k1p1, sp->scored.p);
+                HIPCHECK(idx, hipGetLastError());
+                idx->s_sparse_subset_pairs += (int64_t)n_pairs;
+                // (rows of the launch are whole, or it is part of one row: contiguous in out_dist either way)
+                HIPCHECK(idx, hipMemcpyAsync(out_dist + (int64_t)(b0 + q0) * m + j0, sp->pair_dist.p, n_pairs * sizeof(double),
+                                             hipMemcpyDeviceToHost, s));
+                HIPCHECK(idx, hipStreamSynchronize(s));  // (ids_host and the two device buffers are free again)
+            }
+        }
+    }
+    unsigned long long scored = 0;
+    HIPCHECK(idx, hipMemcpy(&scored, sp->scored.p, sizeof(scored), hipMemcpyDeviceToHost));
+    idx->s_sparse_postings_scored += (int64_t)scored;
+    return MI355DR_OK;
 }
 
 // documents [0, n) of a call as terms[offsets[j] .. offsets[j + 1]); offsets null: n documents without tokens
@@ -688,19 +859,50 @@ int mi355dr_sparse_df(mi355dr_index* idx, const int32_t* terms, int64_t n, int64
 
 int mi355dr_search_sparse(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B, int k,
                           double k1, double b, double* out_dist, int64_t* out_rows) {
-    return search_sparse_impl(idx, q_terms, q_weights, q_offsets, B, k, k1, b, SparseOut{out_dist, out_rows, true}, nullptr);
+    return search_impl(idx, false, q_terms, q_weights, q_offsets, B, k, k1, b, SparseOut{out_dist, out_rows, true}, nullptr);
 }
 int mi355dr_search_sparse_device(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B,
                                  int k, double k1, double b, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
-    return search_sparse_impl(idx, q_terms, q_weights, q_offsets, B, k, k1, b, SparseOut{out_dist_dev, out_rows_dev, false}, stream);
+    return search_impl(idx, false, q_terms, q_weights, q_offsets, B, k, k1, b, SparseOut{out_dist_dev, out_rows_dev, false}, stream);
 }
 int mi355dr_search_bm25(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1, double b,
                         double* out_dist, int64_t* out_rows) {
-    return search_bm25_impl(idx, q_tokens, q_offsets, B, k, k1, b, SparseOut{out_dist, out_rows, true}, nullptr);
+    return search_impl(idx, true, q_tokens, nullptr, q_offsets, B, k, k1, b, SparseOut{out_dist, out_rows, true}, nullptr);
 }
 int mi355dr_search_bm25_device(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1, double b,
                                double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
-    return search_bm25_impl(idx, q_tokens, q_offsets, B, k, k1, b, SparseOut{out_dist_dev, out_rows_dev, false}, stream);
+    return search_impl(idx, true, q_tokens, nullptr, q_offsets, B, k, k1, b, SparseOut{out_dist_dev, out_rows_dev, false}, stream);
+}
+
+int mi355dr_search_sparse_subset(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B,
+                                 int k, double k1, double b, const int64_t* doc_ids, int64_t m, double* out_dist, int64_t* out_rows) {
+    const SparseSubsetArg sub{doc_ids, m};
+    return search_impl(idx, false, q_terms, q_weights, q_offsets, B, k, k1, b, SparseOut{out_dist, out_rows, true}, nullptr, &sub);
+}
+int mi355dr_search_sparse_subset_device(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets,
+                                        int B, int k, double k1, double b, const int64_t* doc_ids, int64_t m, double* out_dist_dev,
+                                        int64_t* out_rows_dev, void* stream) {
+    const SparseSubsetArg sub{doc_ids, m};
+    return search_impl(idx, false, q_terms, q_weights, q_offsets, B, k, k1, b, SparseOut{out_dist_dev, out_rows_dev, false}, stream, &sub);
+}
+int mi355dr_search_bm25_subset(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1, double b,
+                               const int64_t* doc_ids, int64_t m, double* out_dist, int64_t* out_rows) {
+    const SparseSubsetArg sub{doc_ids, m};
+    return search_impl(idx, true, q_tokens, nullptr, q_offsets, B, k, k1, b, SparseOut{out_dist, out_rows, true}, nullptr, &sub);
+}
+int mi355dr_search_bm25_subset_device(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1,
+                                      double b, const int64_t* doc_ids, int64_t m, double* out_dist_dev, int64_t* out_rows_dev,
+                                      void* stream) {
+    const SparseSubsetArg sub{doc_ids, m};
+    return search_impl(idx, true, q_tokens, nullptr, q_offsets, B, k, k1, b, SparseOut{out_dist_dev, out_rows_dev, false}, stream, &sub);
+}
+int mi355dr_score_sparse_subset(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B,
+                                double k1, double b, const int64_t* doc_ids, int m, double* out_dist) {
+    return score_impl(idx, false, q_terms, q_weights, q_offsets, B, k1, b, doc_ids, m, out_dist);
+}
+int mi355dr_score_bm25_subset(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, double k1, double b,
+                              const int64_t* doc_ids, int m, double* out_dist) {
+    return score_impl(idx, true, q_tokens, nullptr, q_offsets, B, k1, b, doc_ids, m, out_dist);
 }
 
 }  // extern "C"

@@ -753,6 +753,72 @@ class Mi355Index:
         return self._sparse_call(B, k, device_out, lambda d, r: self._lib.mi355dr_search_bm25(*a, d, r),
                                  lambda d, r, s: self._lib.mi355dr_search_bm25_device(*a, d, r, s))
 
+    # within a listed subset: a filter, not a view -- the statistics (N, avgdl, df) stay those of the whole store, so a listed
+    # document's distance is bit for bit the unrestricted search's.  doc_ids are GLOBAL ids (local id + `row_offset`); ids
+    # outside the store (negative ones and -1 padding included) are skipped
+    def search_sparse_subset(self, terms, weights, offsets, k: int, doc_ids, k1: float = 1.2, b: float = 0.75,
+                             device_out: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """`search_sparse` among the listed documents (one list for every query, duplicates count once, any order): the
+        unrestricted ranking with the unlisted documents struck out, cut to k, NaN / -1 behind."""
+        t, off = self._ragged_i32(terms, offsets, np.int32)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != t.shape[0]:
+            raise ValueError("weights must have one entry per term")
+        ids = self._sparse_ids(doc_ids)
+        B = off.shape[0] - 1
+        a = (self._h, ptr(t, ctypes.c_int32), ptr(w, ctypes.c_double), ptr(off, ctypes.c_int32), B, int(k), float(k1), float(b),
+             ptr(ids, ctypes.c_int64), ids.shape[0])
+        return self._sparse_call(B, k, device_out, lambda d, r: self._lib.mi355dr_search_sparse_subset(*a, d, r),
+                                 lambda d, r, s: self._lib.mi355dr_search_sparse_subset_device(*a, d, r, s))
+
+    def search_bm25_subset(self, token_lists, k: int, doc_ids, k1: float = 1.2, b: float = 0.75, device_out: bool = False,
+                           offsets=None) -> tuple[np.ndarray, np.ndarray]:
+        """`search_bm25` among the listed documents; the idf weights come from the WHOLE store's N and df."""
+        t, off = self._ragged_i32(token_lists, offsets, np.int32)
+        ids = self._sparse_ids(doc_ids)
+        B = off.shape[0] - 1
+        a = (self._h, ptr(t, ctypes.c_int32), ptr(off, ctypes.c_int32), B, int(k), float(k1), float(b), ptr(ids, ctypes.c_int64),
+             ids.shape[0])
+        return self._sparse_call(B, k, device_out, lambda d, r: self._lib.mi355dr_search_bm25_subset(*a, d, r),
+                                 lambda d, r, s: self._lib.mi355dr_search_bm25_subset_device(*a, d, r, s))
+
+    def _sparse_pool(self, doc_ids, B: int) -> np.ndarray:
+        ids = np.asarray(doc_ids)
+        if ids.size and not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError("doc_ids must be integers")
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        if ids.ndim == 1 and B == 1:
+            ids = ids[None, :]
+        if ids.ndim != 2 or ids.shape[0] != B:
+            raise ValueError(f"doc_ids must be [B, m] with B = {B}, got {ids.shape}")
+        return ids
+
+    def score_sparse_subset(self, terms, weights, offsets, doc_ids, k1: float = 1.2, b: float = 0.75) -> np.ndarray:
+        """Exact distances (-score) of every query to ITS OWN candidates: doc_ids [B, m] -> float64 [B, m], NaN where the id is
+        skipped or the document does not match the query; a duplicate is scored in every position."""
+        t, off = self._ragged_i32(terms, offsets, np.int32)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != t.shape[0]:
+            raise ValueError("weights must have one entry per term")
+        B = off.shape[0] - 1
+        ids = self._sparse_pool(doc_ids, B)
+        out = np.empty(ids.shape, dtype=np.float64)
+        check(self._h, self._lib.mi355dr_score_sparse_subset(self._h, ptr(t, ctypes.c_int32), ptr(w, ctypes.c_double),
+                                                             ptr(off, ctypes.c_int32), B, float(k1), float(b),
+                                                             ptr(ids, ctypes.c_int64), ids.shape[1], ptr(out, ctypes.c_double)))
+        return out
+
+    def score_bm25_subset(self, token_lists, doc_ids, k1: float = 1.2, b: float = 0.75, offsets=None) -> np.ndarray:
+        """`score_sparse_subset` of raw token queries under the BM25 weights of the whole store."""
+        t, off = self._ragged_i32(token_lists, offsets, np.int32)
+        B = off.shape[0] - 1
+        ids = self._sparse_pool(doc_ids, B)
+        out = np.empty(ids.shape, dtype=np.float64)
+        check(self._h, self._lib.mi355dr_score_bm25_subset(self._h, ptr(t, ctypes.c_int32), ptr(off, ctypes.c_int32), B, float(k1),
+                                                           float(b), ptr(ids, ctypes.c_int64), ids.shape[1],
+                                                           ptr(out, ctypes.c_double)))
+        return out
+
     # ---- multi-vector ----
     def add_multivec(self, vecs, offsets) -> None:
         vecs = f32c(vecs)

@@ -688,21 +688,63 @@ class Mi355RetrievalService:
         return self._single_block(Q, top_k, unit, within, mmr_fetch_k, mmr_lambda)
 
     # ---- BM25: the lexical leg, over the unit's sparse store (reference retrieval_pipeline.py:398-465) ----
-    def _bm25_block(self, texts: list[str], top_k: int, tokenizer: Any, k1: float, b: float) -> list[list[dict]]:
+    def _bm25_block(self, texts: list[str], top_k: int, tokenizer: Any, k1: float, b: float,
+                    within: list | None = None) -> list[list[dict]]:
         """A page of query texts as one block.  Under a process group every rank holds the whole sparse store and computes the
-        same lists.  score = -distance: positive, higher is better, as the reference negates the operator's (chunk.py:236)."""
+        same lists.  score = -distance: positive, higher is better, as the reference negates the operator's (chunk.py:236).
+        `within`: among the listed keys only -- a filter under the whole store's statistics, as the reference's statement
+        with `AND id = ANY(:ids)` behaves; unknown keys are left out."""
         from .bm25 import get_tokenizer  # noqa: PLC0415
 
         u = self._unit("chunk")
         ix = u.ensure_sparse(tokenizer)
         tok = get_tokenizer(tokenizer)
-        dist, rows = ix.search_bm25([tok(t) for t in texts], top_k, k1=k1, b=b)
+        queries = [tok(t) for t in texts]
+        if within is None:
+            dist, rows = ix.search_bm25(queries, top_k, k1=k1, b=b)
+        else:
+            dist, rows = self._bm25_within(u, ix, queries, top_k, k1, b, within)
         return self._results_from_block(u.table, np.arange(len(u.table.ids)), rows, -dist, True)
 
+    @staticmethod
+    def _bm25_within(u: _UnitIndex, ix: Any, queries: list, top_k: int, k1: float, b: float, within: list):
+        """`search_bm25` among the listed keys (sparse id = table position).  One `search_bm25_subset` call where the store has
+        it; a store object without it searches everything (k = size_sparse()) and the host strikes out the rest: the same
+        lists."""
+        pos = u.pos_of_id()
+        docs = np.array(sorted({pos[pk] for pk in within if pk in pos}), dtype=np.int64)
+        dist = np.full((len(queries), top_k), np.nan, dtype=np.float64)
+        rows = np.full((len(queries), top_k), -1, dtype=np.int64)
+        if docs.size and hasattr(ix, "search_bm25_subset"):
+            return ix.search_bm25_subset(queries, top_k, docs, k1=k1, b=b)
+        if docs.size and ix.size_sparse() > 0:
+            d, r = ix.search_bm25(queries, ix.size_sparse(), k1=k1, b=b)
+            for j in range(len(queries)):
+                keep = np.flatnonzero(np.isin(r[j], docs) & (r[j] >= 0))[:top_k]
+                dist[j, :keep.size], rows[j, :keep.size] = d[j, keep], r[j, keep]
+        return dist, rows
+
+    def bm25_score_candidates(self, query_text: str, doc_ids: list, tokenizer: Any = "simple", k1: float = 1.2,
+                              b: float = 0.75) -> dict:
+        """BM25 score of explicit candidates: {doc_id: positive score}, the score `bm25_search_by_text` gives the same chunk.
+        Ids unknown to the table and candidates that hold no query term are left out (as `maxsim_score_candidates` does)."""
+        from .bm25 import get_tokenizer  # noqa: PLC0415
+
+        u = self._unit("chunk")
+        ix = u.ensure_sparse(tokenizer)
+        pos = u.pos_of_id()
+        known = [(pk, pos[pk]) for pk in doc_ids if pk in pos]
+        if not known:
+            return {}
+        rows = np.array([[p for _, p in known]], dtype=np.int64)
+        dist = ix.score_bm25_subset([get_tokenizer(tokenizer)(query_text)], rows, k1=k1, b=b)[0]
+        return {pk: -float(dv) for (pk, _), dv in zip(known, dist) if dv == dv}
+
     def bm25_search(self, query_ids: list[int | str], top_k: int = 10, tokenizer: Any = "simple",
-                    index_name: str = "idx_chunk_bm25", k1: float = 1.2, b: float = 0.75) -> list[list[dict]]:
+                    index_name: str = "idx_chunk_bm25", k1: float = 1.2, b: float = 0.75,
+                    within: list | None = None) -> list[list[dict]]:
         """BM25 top-k for every query id, scored as one block (reference bm25_search, :425-465; `index_name` is recorded by the
-        pipeline and unused here).  Raises ValueError exactly like the reference."""
+        pipeline and unused here).  Raises ValueError exactly like the reference.  `within`: among the listed chunk ids only."""
         texts = []
         for qid, q in zip(query_ids, self.get_queries(list(query_ids)), strict=True):
             if q is None:
@@ -710,12 +752,14 @@ class Mi355RetrievalService:
             texts.append(q.contents or "")
         if not texts:
             return []
-        return self._bm25_block(texts, top_k, tokenizer, k1, b)
+        return self._bm25_block(texts, top_k, tokenizer, k1, b, within)
 
     def bm25_search_by_text(self, query_text: str, top_k: int = 10, tokenizer: Any = "simple",
-                            index_name: str = "idx_chunk_bm25", k1: float = 1.2, b: float = 0.75) -> list[dict]:
-        """BM25 top-k of a raw query text, no query row needed (reference bm25_search_by_text, :398-423)."""
-        return self._bm25_block([query_text], top_k, tokenizer, k1, b)[0]
+                            index_name: str = "idx_chunk_bm25", k1: float = 1.2, b: float = 0.75,
+                            within: list | None = None) -> list[dict]:
+        """BM25 top-k of a raw query text, no query row needed (reference bm25_search_by_text, :398-423).  `within`: among the
+        listed chunk ids only."""
+        return self._bm25_block([query_text], top_k, tokenizer, k1, b, within)[0]
 
     def _check_mmr(self, search_mode: str, mmr_fetch_k: int | None) -> None:
         """MMR is a single-vector, single-GPU selection: it scores stored rows against each other, and under row shards the

@@ -562,10 +562,35 @@ int mi355dr_search_maxsim_subset_device(mi355dr_index* idx, const float* qtok_de
  *   "sparse_overlay_builds", "sparse_overlay_postings" (the overlay's size as last built), "sparse_dead_postings" (base postings
  *   of moved documents, as last built), "sparse_sets" (documents set or removed); the store's device bytes, overlay and
  *   `moved` included, are part of "hbm_bytes_resident".
+ * Within a listed subset (mi355dr_search_sparse_subset*, mi355dr_search_bm25_subset*, mi355dr_score_sparse_subset,
+ *   mi355dr_score_bm25_subset).  A FILTER, NOT A VIEW: N, total_len, avgdl, df, and so every BM25 weight and every norm_i, are
+ *   those of the WHOLE store -- a listed document's distance is bit for bit the distance the unrestricted search computes for
+ *   it.  doc_ids are GLOBAL ids as the searches return them (local id + option "row_offset"), on the HOST, under the rule of
+ *   mi355dr_search_subset: values outside [row_offset, row_offset + mi355dr_size_sparse) are skipped (negative values and -1
+ *   padding included), a value listed twice counts once, order never matters.  A listed document without tokens never matches.
+ *   search_*_subset: one list [m] shared by all B queries.  A result line is the unrestricted ranking -- ALL matches under
+ *     (distance asc, NaN last, id asc) -- with the unlisted documents struck out, cut to k, NaN / -1 behind.  Queries, k / k1 / b,
+ *     blocks, mutex, drain, stream and the _device convention (query and list on the host, results on the device, complete on
+ *     return) are those of mi355dr_search_sparse / _bm25.  m == 0, no listed document in range, or an empty store (a view's):
+ *     every line all NaN / -1.  m < 0, or a null list with m > 0: E_INVALID.
+ *   score_*_subset: every query has its OWN list, row q of doc_ids [B, m]; out_dist[q, j] (HOST) is the distance (-score) of
+ *     query q to doc_ids[q, j], NaN where the id is skipped or the document does not match the query.  A duplicate in a row is
+ *     scored in every position it occupies.  m == 0 or B == 0: no-op.  B * m must be below 2^31 (else E_UNSUPPORTED).
+ *   Two exact paths serve a mutated store as well as an untouched one.  A list of at most "sparse_subset_pairs_max" local
+ *     documents (option, 0 .. "sparse_cand_cap", default 2048; 0: never; above the cap: E_INVALID; a cap lowered afterwards
+ *     bounds it), and every score form, looks each (query, document) pair up by binary search in the query's term slices.  A
+ *     longer list runs the search's own launches over the tiles that hold a listed document, filtered by a bitmap, planned in
+ *     LISTED documents (the first launch holds at most "sparse_cand_cap" of them, an overflowed one is run again in pieces of
+ *     at most that many).  Same bits on both paths.
+ *   Stats: "sparse_subset_searches" (calls of the four search forms; they count in "sparse_queries", not in
+ *     "sparse_searches"), "sparse_subset_scores" (calls of the two score forms), "sparse_subset_pairs" ((query, document) pairs
+ *     looked up), "sparse_subset_tiles" (tiles launched by the filtered pass, summed over launches).  "sparse_postings_scored"
+ *     counts on both paths exactly the (query term, listed document) postings that were added (for a score form: per position).
+ *     The list's device buffers belong to the store and are part of "hbm_bytes_resident".
  * Views: a view has an empty sparse store and refuses mi355dr_add_sparse / _set_sparse / _remove_sparse; mi355dr_compact does
  *   not touch the sparse store.
  * Out of scope: compaction / renumbering of sparse documents (ids are table positions in the service), views over the store, a row-sharded sparse search (it needs
- *   global df / avgdl), a key filter, fusion on the device, any claim of bit parity with VectorChord-BM25. */
+ *   global df / avgdl), fusion on the device, any claim of bit parity with VectorChord-BM25. */
 int mi355dr_add_sparse(mi355dr_index* idx, const int32_t* terms, const int64_t* offsets /* [n_docs + 1] */, int64_t n_docs); /* host */
 int64_t mi355dr_size_sparse(const mi355dr_index* idx); /* stored documents, with or without tokens */
 int mi355dr_set_sparse(mi355dr_index* idx, const int64_t* doc_ids /* HOST [n] */, const int32_t* terms,
@@ -581,6 +606,22 @@ int mi355dr_search_bm25(mi355dr_index* idx, const int32_t* q_tokens, const int32
                         double b, double* out_dist, int64_t* out_rows);
 int mi355dr_search_bm25_device(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1,
                                double b, double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+int mi355dr_search_sparse_subset(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets,
+                                 int B, int k, double k1, double b, const int64_t* doc_ids /* HOST [m] */, int64_t m,
+                                 double* out_dist /* [B, k] */, int64_t* out_rows /* [B, k] */);
+int mi355dr_search_sparse_subset_device(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets,
+                                        int B, int k, double k1, double b, const int64_t* doc_ids /* HOST [m] */, int64_t m,
+                                        double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+int mi355dr_search_bm25_subset(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1,
+                               double b, const int64_t* doc_ids /* HOST [m] */, int64_t m, double* out_dist, int64_t* out_rows);
+int mi355dr_search_bm25_subset_device(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1,
+                                      double b, const int64_t* doc_ids /* HOST [m] */, int64_t m, double* out_dist_dev,
+                                      int64_t* out_rows_dev, void* stream);
+int mi355dr_score_sparse_subset(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets,
+                                int B, double k1, double b, const int64_t* doc_ids /* HOST [B, m] */, int m,
+                                double* out_dist /* HOST [B, m] */);
+int mi355dr_score_bm25_subset(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, double k1, double b,
+                              const int64_t* doc_ids /* HOST [B, m] */, int m, double* out_dist /* HOST [B, m] */);
 
 /* ---- Guided Query Refinement of candidate pools (GQR hybrid pipeline) ----
  * Replaces the per-query numpy loops of autorag_research/pipelines/retrieval/gqr_hybrid.py: `_optimize_query_embedding`
