@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "mi355dr_dev_alloc", "mi355dr_dev_free", "mi355dr_dev_upload", "mi355dr_dev_download",
     "mi355dr_diag_mfma_stream",
     "mi355dr_debug_screen_dense", "mi355dr_debug_screen_hits", "mi355dr_debug_screen_bound", "mi355dr_debug_i8_state", "mi355dr_debug_rescore",
-    "mi355dr_debug_maxsim_pass", "mi355dr_debug_spec_m",
+    "mi355dr_debug_maxsim_pass", "mi355dr_debug_spec_m", "mi355dr_debug_spec_model",
 ]
 
 
@@ -291,6 +291,9 @@ def load() -> ctypes.CDLL:
     L.mi355dr_debug_rescore.argtypes = [vp, f32p, c_int, i32p, i64p, i64, f32p, f64p]
     L.mi355dr_debug_spec_m.restype = c_int
     L.mi355dr_debug_spec_m.argtypes = [c_int]
+    L.mi355dr_debug_spec_model.restype = c_int
+    L.mi355dr_debug_spec_model.argtypes = [vp, f32p, c_int, c_int, f32p, f32p, f32p, ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     L.mi355dr_debug_maxsim_pass.restype = c_int
     L.mi355dr_debug_maxsim_pass.argtypes = [vp, f32p, i32p, c_int, c_int, i64p, i64, c_int, ctypes.POINTER(c_int), f32p, f32p, i32p,
                                             ctypes.POINTER(c_int), f32p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]

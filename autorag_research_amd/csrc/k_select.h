@@ -473,7 +473,7 @@ __device__ __forceinline__ void prune_body(const PruneArgs& a, char* smem) {
                             // the distance a row of screen value t would have: 1 - t (cosine), -t |q| (inner product)
                             const double dist_t = a.metric == 0 ? 1.0 - (double)t_model : -(double)t_model * sqrt((double)nq);
                             const float thr_model = screen_threshold(a.metric, dist_t, E, nq);
-                            if (thr_model > thr && thr_model < __builtin_inff()) thr = thr_model;  // (NaN, +inf: the rigorous one)
+                            if (thr_model > thr && thr_model < __builtin_inff()) thr = thr_model;  // (NaN: the rigorous one; an infinite t arrives as FLT_MAX -- float_below -- and passes: DESIGN.md 4.3)
                             a.st.thr_used[q] = thr;
                         }
                         a.st.thr[q] = thr;

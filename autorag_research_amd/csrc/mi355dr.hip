@@ -577,6 +577,21 @@ inline double normal_quantile(double p) {
     return 0.5 * (lo + hi);
 }
 
+// what the starter's prune of a speculative pass predicts from (run_screen; mi355dr_debug_spec_model).  zq = Phi^-1(1 - m / n):
+// the Gaussian quantile above which m of the n rows are expected (no inverse error function on the device); the lab shift
+// makes the model wrong on purpose.  n counts removed rows, and the sums run over the sample's rows, removed ones included
+// (DESIGN.md 4.3 "On a mutated index").  *zq_out: the quantile before its rounding to float.
+SpecModel spec_model(const mi355dr_index* idx, const Pass& ps, const PassPlan& plan, double* zq_out = nullptr) {
+    SpecModel sm{};
+    sm.moments = idx->spec_moments;
+    sm.slabs = starter_count(plan);
+    sm.rows = (int)plan.sample;
+    const double zq = normal_quantile(1.0 - (double)ps.spec_m / (double)idx->n) + idx->spec_shift_milli / 1000.0;
+    sm.zq = (float)zq;
+    if (zq_out) *zq_out = zq;
+    return sm;
+}
+
 PassPlan make_plan(const mi355dr_index* idx, const Pass& ps, int B) {
     // (measured round 3, N = 10 M, k = 10: a ratio of 4 per step -- 5 chunks -- 7.43 ms, the budget's 4.8 -- 4 chunks -- 7.54)
     const double budget = growth_budget(idx, ps.k, ps.i8);
@@ -623,12 +638,7 @@ int run_screen(mi355dr_index* idx, hipStream_t s, const Pass& ps, int B, const P
         // (the flush mask: none of the slab-maximum epilogue's kernels reads it)
         SpecModel sm{};
         if (ps.speculative) {
-            // zq = Phi^-1(1 - m / n): the Gaussian quantile above which m of the n rows are expected (no inverse error function
-            // on the device); the lab shift makes the model wrong on purpose
-            sm.moments = idx->spec_moments;
-            sm.slabs = starter_count(plan);
-            sm.rows = (int)plan.sample;
-            sm.zq = (float)(normal_quantile(1.0 - (double)ps.spec_m / (double)idx->n) + idx->spec_shift_milli / 1000.0);
+            sm = spec_model(idx, ps, plan);
             idx->s_spec_passes++;
         }
         CHECK(timed(false, plan.sample, [&] {
@@ -3154,6 +3164,57 @@ int mi355dr_debug_i8_state(mi355dr_index* idx, const float* queries, int B, floa
         out_step[i] = gr[(size_t)i].step;
         out_err[i] = gr[(size_t)i].err;
     }
+    return MI355DR_OK;
+}
+
+int mi355dr_debug_spec_model(mi355dr_index* idx, const float* queries, int B, int k, float* out_moments, float* out_thr_rigorous,
+                             float* out_thr_used, double* out_zq, int64_t* out_sample_rows, int* out_slabs, int* out_i8) {
+    if (!idx || !queries || !out_moments || !out_thr_rigorous || !out_thr_used || !out_zq || !out_sample_rows || !out_slabs ||
+        !out_i8)
+        return fail(idx, MI355DR_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (B <= 0 || B > kQBlockMax || k <= 0 || k > kKMax) return fail(idx, MI355DR_E_INVALID, "need 1<=B<=1024, 1<=k<=1024");
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    CHECK(drain_pending(idx));
+    CHECK(ensure_qstate(idx));
+    const Pass ps = decide_pass(idx, k, 0, false, "screen path unavailable (metric or too many irregular rows)");
+    if (ps.refused) return fail(idx, MI355DR_E_UNSUPPORTED, ps.refused);
+    if (!ps.speculative) return fail(idx, MI355DR_E_UNSUPPORTED, "debug_spec_model: a pass at this k would not speculate");
+    idx->last_pass_k = k;  // (as a search at k leaves it: the other hooks then read the screen this pass took)
+    hipStream_t s = idx->stream;
+    const PassPlan plan = make_plan(idx, ps, B);
+    const SpecModel sm = spec_model(idx, ps, plan, out_zq);
+    const int Bpad = (int)round_up(B, screen_tile(B));
+    // the prunes count candidates and re-scored rows per query on the device (stats "candidates", "rescored"): the hook hands
+    // the words back as it found them, also where a launch below fails
+    std::vector<unsigned long long> stat_before(2 * (size_t)kQBlockMax);
+    const size_t stat_bytes = stat_before.size() * sizeof(unsigned long long);
+    HIPCHECK(idx, hipMemcpyAsync(stat_before.data(), idx->stat_dev, stat_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    // the head of run_screen, twice: the plain starter (what the rigorous threshold is), then the speculative pass's
+    const auto heads = [&]() -> int {
+        for (int model = 0; model < 2; ++model) {
+            HIPCHECK(idx, hipMemcpyAsync(idx->qdev, queries, (size_t)B * idx->dim * sizeof(float), hipMemcpyHostToDevice, s));
+            CHECK(launch_prep(idx, s, B, Bpad, idx->metric, ps.i8, starter_count(plan)));
+            CHECK(launch_screen(idx, s, ps.i8, B, 0, plan.sample, ps.cap, kEmitSlabMax, -1, model ? sm.slabs : 0));
+            CHECK(launch_prune(idx, s, ps, B, nullptr, /*exact=*/0, /*thr_only=*/true, /*one_wave_only=*/true, false,
+                               model ? &sm : nullptr));
+            if (!model)
+                HIPCHECK(idx, hipMemcpyAsync(out_thr_rigorous, idx->st.thr, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHECK(idx, hipMemcpyAsync(out_thr_used, idx->st.thr_used, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIPCHECK(idx, hipMemcpyAsync(out_moments, idx->spec_moments, (size_t)B * sm.slabs * 2 * sizeof(float), hipMemcpyDeviceToHost, s));
+        return MI355DR_OK;
+    };
+    const int rc = heads();
+    const hipError_t put_back = hipMemcpyAsync(idx->stat_dev, stat_before.data(), stat_bytes, hipMemcpyHostToDevice, s);
+    const hipError_t done = hipStreamSynchronize(s);
+    CHECK(rc);
+    HIPCHECK(idx, put_back);
+    HIPCHECK(idx, done);
+    *out_sample_rows = plan.sample;
+    *out_slabs = sm.slabs;
+    *out_i8 = ps.i8 ? 1 : 0;
     return MI355DR_OK;
 }
 

@@ -1142,6 +1142,27 @@ class Mi355Index:
                                                             ptr(out, ctypes.c_float)))
         return out
 
+    def debug_spec_model(self, queries, k: int) -> dict:
+        """The head of a speculative pass at `k` (mi355dr_debug_spec_model): {"moments" [B, slabs, 2]: per-slab sum and sum of
+        squares of the sample's screen estimates, "thr_rigorous" [B], "thr_used" [B], "zq", "sample_rows", "i8"}.
+        NativeError (MI355DR_E_UNSUPPORTED) where a first attempt at `k` would not speculate."""
+        q = f32c(queries)
+        B = q.shape[0]
+        moments = np.empty((B, 256, 2), dtype=np.float32)
+        rigorous = np.empty(B, dtype=np.float32)
+        used = np.empty(B, dtype=np.float32)
+        zq = ctypes.c_double(0.0)
+        rows = ctypes.c_int64(0)
+        slabs = ctypes.c_int(0)
+        i8 = ctypes.c_int(0)
+        check(self._h, self._lib.mi355dr_debug_spec_model(self._h, ptr(q, ctypes.c_float), B, int(k), ptr(moments, ctypes.c_float),
+                                                          ptr(rigorous, ctypes.c_float), ptr(used, ctypes.c_float),
+                                                          ctypes.byref(zq), ctypes.byref(rows), ctypes.byref(slabs),
+                                                          ctypes.byref(i8)))
+        n = int(slabs.value)
+        return {"moments": moments.reshape(-1)[:B * n * 2].reshape(B, n, 2).copy(), "thr_rigorous": rigorous, "thr_used": used,
+                "zq": float(zq.value), "sample_rows": int(rows.value), "i8": bool(i8.value)}
+
     def debug_rescore(self, queries, pair_q, pair_row) -> tuple[np.ndarray, np.ndarray]:
         q = f32c(queries)
         pq = np.ascontiguousarray(pair_q, dtype=np.int32)

@@ -878,6 +878,22 @@ int mi355dr_debug_i8_state(mi355dr_index* idx, const float* queries, int B, floa
 /* m(k) of the speculative pass as compiled in: the rows its predicted threshold expects above it; 0 = this k never
  * speculates.  Needs no index and no device. */
 int mi355dr_debug_spec_m(int k);
+/* The head of a speculative pass at k for B <= 1024 host queries, observed: prepare, the starter screen, the thr_only prune --
+ * the launches a search puts in front of its one chunk, decided as a search decides them -- once without the model (the
+ * rigorous threshold the sample's k-th best gives) and once with it.  MI355DR_E_UNSUPPORTED where a first attempt at k would
+ * not speculate now (k outside the table, fewer than spec_min_rows rows, option speculate off, speculation suspended, no
+ * screen).  Host only: it launches the search's kernels and changes none.  Like a search at k it sets the k the other hooks
+ * take their screen type from; it moves no statistic (the per-query words behind "candidates" / "rescored", which its prunes
+ * count in, are put back as they were) and no probation counter.  Outputs, all host:
+ *   out_moments [B, 256, 2]  filled as [B, *out_slabs, 2]: per query and 64-row slab of the sample the sum and the sum of
+ *                            squares of the screen's estimate (int8: without the group's share of the bound)
+ *   out_thr_rigorous [B]     st.thr behind the plain starter (+inf for a query the screen cannot rank)
+ *   out_thr_used [B]         the threshold the one chunk would run at: max(rigorous, model); -inf where there is no rigorous one
+ *   *out_zq                  Phi^-1(1 - m(k) / size) + spec_shift_milli / 1000, before its rounding to float
+ *   *out_sample_rows, *out_slabs   rows the sums run over (the divisor), slabs per query
+ *   *out_i8                  1 if the int8 screen served */
+int mi355dr_debug_spec_model(mi355dr_index* idx, const float* queries, int B, int k, float* out_moments, float* out_thr_rigorous,
+                             float* out_thr_used, double* out_zq, int64_t* out_sample_rows, int* out_slabs, int* out_i8);
 /* exact fp32 chain + distance for explicit (query,row) pairs, computed by the re-score device code */
 int mi355dr_debug_rescore(mi355dr_index* idx, const float* queries, int B, const int32_t* pair_q,
                           const int64_t* pair_row, int64_t n_pairs, float* out_dot, double* out_dist);

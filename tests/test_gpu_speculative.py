@@ -5,6 +5,9 @@ oracle: ids and the bits of the float64 distances.  Corpora are the smallest the
 
 import numpy as np
 import pytest
+from spec_common import index as _index
+from spec_common import planted_corpus
+from spec_common import same as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -16,24 +19,6 @@ def pkg(native_built):
     import autorag_research_amd as p
 
     return p
-
-
-def _same(got, want):
-    (dist, rows), (rd, rr) = got, want
-    assert np.array_equal(rows, rr)
-    assert np.array_equal(np.isnan(dist), np.isnan(rd))  # NaN payload/sign is not part of the contract
-    ok = ~np.isnan(rd)
-    assert np.array_equal(dist[ok].view(np.uint64), rd[ok].view(np.uint64))
-
-
-def _index(pkg, C, metric="cosine"):
-    idx = pkg.Mi355Index(C.shape[1], metric)
-    idx.add(C)
-    idx.set_option("spec_min_rows", len(C))
-    # four samples of rows are ONE step of the default ladder as well (ratio 4): chunk ratios of at most 2 make every pass
-    # that is not speculative recognisable by its two chunks.  A speculative pass has no ratio to grow by.
-    idx.set_option("chunk_growth", 1)
-    return idx
 
 
 # ---- Gaussian rows: the model holds ---------------------------------------------------------------------------------------
@@ -148,17 +133,7 @@ def hard(oracle):
     out = {}
     # (a) the best rows of some queries inside the sample, each with an exact duplicate at the far end (tie: lower row first);
     # zero rows; a row the int8 shadow cannot hold; a zero query and a NaN query
-    rng = np.random.default_rng(21)
-    C = rng.standard_normal((N, D2)).astype(np.float32)
-    Q = rng.standard_normal((48, D2)).astype(np.float32)
-    for i in range(8):
-        C[100 + 37 * i] = Q[i] * np.float32(1.5)
-        C[N - 1 - i] = C[100 + 37 * i]
-    C[[5, 20000, N - 20]] = 0.0
-    C[30000] = 0.01 * C[30000]
-    C[30000, 3] = 9.0   # (one dominant component: outside the int8 shadow)
-    Q[20] = 0.0
-    Q[21, 7] = np.nan
+    C, Q = planted_corpus()
     out["planted"] = (C, Q)
     # (b) a dense cluster of 3000 rows around 8 queries, behind the sample
     rng = np.random.default_rng(22)

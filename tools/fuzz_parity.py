@@ -2,7 +2,9 @@
 
 Runs random shapes / data modes / option settings for a wall-clock budget and stops at the first mismatch, printing the
 seed of the failing case.  Test infrastructure (it uses oracle/), meant for a GPU box:
-    python tools/fuzz_parity.py --seconds 300 [--seed 1] [--only single|maxsim|session|gqr]
+    python tools/fuzz_parity.py --seconds 300 [--seed 1] [--only single|maxsim|session|gqr|mutated]
+(`mutated` -- an index that is appended to, updated, thinned and compacted between searches -- is drawn only when asked for:
+the case numbers of the other kinds replay what they always did.)
 """
 import argparse
 import sys
@@ -378,7 +380,137 @@ def check_gqr(rng, case):
     return desc + f" d={d} docs={n_docs}"
 
 
-CHECKS = {"maxsim": check_maxsim, "single": check_single, "session": check_session, "gqr": check_gqr}
+def check_mutated(rng, case):
+    """one index of 20 000 .. 70 000 rows that is appended to, updated, thinned, compacted and re-configured, mirrored step by
+    step in tests/helpers.py MutableOracleIndex; after every step one of search / search_rows / search_mmr / search_range
+    against the references of tests/ over the mirror's live rows, bit for bit.  Half the cases lower spec_min_rows to the size:
+    k = 2, 10, 19 then take the speculative one-chunk pass on a sample with dead and rewritten rows."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import mmr_ref  # noqa: E402
+    import range_ref  # noqa: E402
+    import rows_ref  # noqa: E402
+    from helpers import MutableOracleIndex  # noqa: E402
+
+    n = int(rng.integers(20_000, 70_001))
+    d = int(rng.choice([16, 64, 128]))
+    mode = str(rng.choice(["gauss", "scaled", "clustered", "dups", "spiky", "dirty"]))
+    metric = "ip" if rng.random() < IP_PROB else "cosine"
+    spec = bool(rng.random() < 0.5)
+    desc = f"mutated n={n} d={d} mode={mode} metric={metric} spec_min_rows={'size' if spec else 'default'}"
+    mo = MutableOracleIndex(d, metric)
+    spec_stats = ("spec_passes", "spec_miss_queries", "spec_overflow_queries", "retry_queries", "fallback_queries")
+
+    def live_part():
+        live = np.flatnonzero(mo._live)
+        return live, np.ascontiguousarray(mo._rows[live])
+
+    def same(got, exp, what):
+        for g, e in zip(got, exp):
+            g, e = np.asarray(g), np.asarray(e)
+            if g.dtype.kind == "f":
+                ok = np.array_equal(np.isnan(g), np.isnan(e)) and np.array_equal(
+                    np.ascontiguousarray(g[~np.isnan(g)]).view(np.uint64), np.ascontiguousarray(e[~np.isnan(e)]).view(np.uint64))
+            else:
+                ok = np.array_equal(g, e)
+            if not ok:
+                bad = np.argwhere(~((g == e) | ((g != g) & (e != e))))[:3].tolist()
+                st = {s: idx.stat(s) for s in spec_stats + ("screen_dtype_active", "spec_suspended")}
+                raise AssertionError(f"MISMATCH {desc} | {what} stats={st} first bad={bad}")
+
+    def check_one():
+        nonlocal desc
+        form = str(rng.choice(["search", "rows", "mmr", "range"]))
+        k = int(rng.choice([2, 10, 19, 20, 40]))
+        B = int(rng.choice([1, 8, 48]))
+        live, Cl = live_part()
+        Q = rng.standard_normal((B, d)).astype(np.float32)
+        if mode in ("clustered", "dups") and len(live):
+            Q[: max(1, B // 2)] = Cl[rng.integers(0, len(live), size=max(1, B // 2))] + (
+                0.01 * rng.standard_normal((max(1, B // 2), d))).astype(np.float32)
+        idx.reset_stats()
+        if form == "search":
+            what = f"search B={B} k={k}"
+            same(idx.search(Q, k), mo.search(Q, k), what)
+        elif form == "rows":
+            ids = rng.integers(-2, len(mo) + 3, size=B).astype(np.int64)
+            inc = bool(rng.random() < 0.3)
+            what = f"search_rows B={B} k={k} include_self={inc}"
+            # (over the live rows alone, ids renumbered: the reference's depth grows with the number of dead rows otherwise)
+            new_of_old = np.where(mo._live, np.cumsum(mo._live) - 1, -1)
+            local = np.where((ids >= 0) & (ids < len(mo)), new_of_old[np.clip(ids, 0, len(mo) - 1)], -1)
+            ed, er = rows_ref.search_rows(cpu_ref, Cl, local, k, metric=metric, include_self=inc)
+            same(idx.search_rows(ids, k, include_self=inc), (ed, np.where(er >= 0, live[np.maximum(er, 0)], -1)), what)
+        elif form == "mmr":
+            lam = float(rng.choice([0.0, 0.5, 1.0]))
+            what = f"search_mmr B={B} k={min(k, 5)} fetch_k={k} lambda={lam}"
+            ed, er, _ = mmr_ref.search_mmr(cpu_ref, Cl, Q, min(k, 5), k, lam, metric=metric)
+            same(idx.search_mmr(Q, min(k, 5), k, lam), (ed, np.where(er >= 0, live[np.maximum(er, 0)], -1)), what)
+        else:
+            ds, rs = range_ref.oracle_sorted(cpu_ref, Cl, Q, metric, depth=3 * k + 8)
+            radius, _ = range_ref.radius_admitting(ds, rs, rng.integers(0, 3 * k, size=B))
+            what = f"search_range B={B} max_results={k}"
+            if not range_ref.covers(ds, radius):   # (ties deeper than the reference looked: duplicates)
+                desc += f" | {what} (skipped: ties)"
+                return
+            ed, er, ec = range_ref.search_range(ds, rs, radius, k)
+            same(idx.search_range(Q, radius, k), (ed, np.where(er >= 0, live[np.maximum(er, 0)], -1), ec), what)
+        desc += f" | {what} {[idx.stat(s) for s in spec_stats[:4]]}"
+
+    with pkg.Mi355Index(d, metric) as idx:
+        C = corpus(rng, n, d, mode)
+        idx.add(C)
+        mo.add(C)
+        if spec:
+            idx.set_option("spec_min_rows", n)
+        for step in range(int(rng.integers(4, 9))):
+            op = str(rng.choice(["append", "update", "remove", "remove_head", "compact", "option"]))
+            live = np.flatnonzero(mo._live)
+            if op == "append":
+                more = corpus(rng, int(rng.integers(1, 3000)), d, str(rng.choice(["gauss", "clustered", "dups"])))
+                idx.add(more)
+                mo.add(more)
+                desc += f" | add {more.shape[0]}"
+            elif op == "update":
+                ids = rng.choice(len(mo), size=int(rng.integers(1, min(500, len(mo)) + 1)), replace=False)
+                new = corpus(rng, len(ids), d, "gauss")
+                new[: len(ids) // 4] = mo._rows[ids[: len(ids) // 4]] * np.float32(rng.choice([0.1, 7.5]))   # rescaled
+                if rng.random() < 0.5:
+                    new[-1] = 0.0
+                idx.update_rows(ids, new)
+                mo.update_rows(ids, new)
+                desc += f" | update {len(ids)}"
+            elif op == "remove" and len(live) > 1000:
+                ids = rng.choice(live, size=int(rng.integers(1, 501)), replace=False)
+                idx.remove_rows(ids)
+                mo.remove_rows(ids)
+                desc += f" | remove {len(ids)}"
+            elif op == "remove_head" and len(live) > 30_000:
+                ids = live[live < int(rng.choice([100, 5000, 16384, 20000]))]
+                if len(ids) == 0:
+                    continue
+                idx.remove_rows(ids)
+                mo.remove_rows(ids)
+                desc += f" | remove head {len(ids)}"
+            elif op == "compact":
+                got, exp = idx.compact(), mo.compact()
+                if not np.array_equal(got, exp):
+                    raise AssertionError(f"MISMATCH {desc} | compact: new_of_old differs")
+                desc += f" | compact -> {len(mo)}"
+            elif op == "option":
+                key, val = [("screen_dtype", str(rng.choice(["auto", "bf16"]))), ("cand_cap", int(rng.choice([300, 1024, 2048]))),
+                            ("chunk_growth", int(rng.choice([1, 3]))), ("speculate", int(rng.integers(0, 2))),
+                            ("spec_min_rows", len(mo)), ("range_slots", int(rng.choice([16, 1024])))][int(rng.integers(0, 6))]
+                idx.set_option(key, val)
+                desc += f" | {key}={val}"
+            else:
+                continue
+            if len(idx) != len(mo) or idx.live_rows != mo.live_rows:
+                raise AssertionError(f"MISMATCH {desc}: size {len(idx)} / {len(mo)}, live {idx.live_rows} / {mo.live_rows}")
+            check_one()
+    return desc
+
+
+CHECKS = {"maxsim": check_maxsim, "single": check_single, "session": check_session, "gqr": check_gqr, "mutated": check_mutated}
 
 
 def pick_kind(u: float) -> str:
@@ -406,14 +538,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--only", choices=["single", "maxsim", "session", "gqr"], default=None)
+    ap.add_argument("--only", choices=["single", "maxsim", "session", "gqr", "mutated"], default=None)
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--start", type=int, default=0, help="first case number (cases are seeded by number)")
     ap.add_argument("--poison", default=None, help="hex byte (e.g. ff, 7f) or 'random': dirty the device memory first")
     a = ap.parse_args()
     if a.poison:
         poison_device_memory(a.poison)
-    t0, case, counts = time.time(), a.start, {"single": 0, "maxsim": 0, "session": 0, "gqr": 0}
+    t0, case, counts = time.time(), a.start, {"single": 0, "maxsim": 0, "session": 0, "gqr": 0, "mutated": 0}
     while time.time() - t0 < a.seconds:
         seed = a.seed * 1_000_003 + case
         rng = np.random.default_rng(seed)
