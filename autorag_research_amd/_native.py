@@ -23,7 +23,7 @@ ABI_SYMBOLS = [
     "mi355dr_add_rows", "mi355dr_add_rows_device", "mi355dr_size", "mi355dr_dim", "mi355dr_get_rows",
     "mi355dr_update_rows", "mi355dr_update_rows_device", "mi355dr_remove_rows", "mi355dr_live_rows", "mi355dr_compact",
     "mi355dr_search", "mi355dr_search_device", "mi355dr_search_device_async", "mi355dr_search_wait",
-    "mi355dr_search_subset", "mi355dr_search_subset_device", "mi355dr_score_subset", "mi355dr_search_mmr", "mi355dr_search_mmr_device", "mi355dr_mmr_select", "mi355dr_merge_groups_device", "mi355dr_search_groups", "mi355dr_search_groups_device", "mi355dr_search_range", "mi355dr_search_range_device",
+    "mi355dr_search_subset", "mi355dr_search_subset_device", "mi355dr_score_subset", "mi355dr_search_mmr", "mi355dr_search_mmr_device", "mi355dr_mmr_select", "mi355dr_merge_groups_device", "mi355dr_search_groups", "mi355dr_search_groups_device", "mi355dr_fuse_lists", "mi355dr_fuse_lists_device", "mi355dr_search_range", "mi355dr_search_range_device",
     "mi355dr_search_rows", "mi355dr_search_rows_device", "mi355dr_search_range_rows", "mi355dr_search_range_rows_device", "mi355dr_view_create", "mi355dr_add_multivec", "mi355dr_size_multivec",
     "mi355dr_search_maxsim", "mi355dr_search_maxsim_device", "mi355dr_search_maxsim_subset", "mi355dr_search_maxsim_subset_device", "mi355dr_maxsim_subset", "mi355dr_maxsim_subset_ex", "mi355dr_add_multivec_device", "mi355dr_gqr_refine", "mi355dr_gqr_refine_maxsim",
     "mi355dr_set_multivec", "mi355dr_set_multivec_device", "mi355dr_live_multivec",
@@ -46,6 +46,13 @@ ABI_SYMBOLS = [
 
 # mi355dr_allgather_fn (include/mi355dr.h): (send_dev, recv_dev, bytes_per_rank, stream, user) -> 0 on success
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p)
+
+
+class FuseOpts(ctypes.Structure):
+    """mi355dr_fuse_opts (include/mi355dr.h "hybrid fusion")."""
+
+    _fields_ = [("method", ctypes.c_int), ("mode_1", ctypes.c_int), ("mode_2", ctypes.c_int), ("rrf_k", ctypes.c_int),
+                ("fetch_k", ctypes.c_int), ("weight", ctypes.c_double), ("min_1", ctypes.c_double), ("min_2", ctypes.c_double)]
 
 
 class NativeError(RuntimeError):
@@ -152,6 +159,11 @@ def load() -> ctypes.CDLL:
     L.mi355dr_search_groups.argtypes = [vp, f32p, i32p, c_int, c_int, c_int, f64p, i64p, i32p]
     L.mi355dr_search_groups_device.restype = c_int
     L.mi355dr_search_groups_device.argtypes = [vp, vp, i32p, c_int, c_int, c_int, vp, vp, vp, vp]
+    fuse_p = ctypes.POINTER(FuseOpts)
+    L.mi355dr_fuse_lists_device.restype = c_int
+    L.mi355dr_fuse_lists_device.argtypes = [vp, vp, vp, c_int, vp, i64, vp, vp, c_int, vp, i64, c_int, c_int, fuse_p, vp, vp, vp, vp]
+    L.mi355dr_fuse_lists.restype = c_int
+    L.mi355dr_fuse_lists.argtypes = [vp, f64p, i64p, c_int, i64p, i64, f64p, i64p, c_int, i64p, i64, c_int, c_int, fuse_p, f64p, i64p, i32p]
     L.mi355dr_search_range.restype = c_int
     L.mi355dr_search_range.argtypes = [vp, f32p, c_int, f64p, c_int, f64p, i64p, i64p]
     L.mi355dr_search_range_device.restype = c_int

@@ -153,6 +153,23 @@ struct GroupBufs {
         return e;
     }
 };
+// hybrid fusion (mi355dr_fuse_lists): the host form's staging -- both lists [B, w_l], their maps and
+// the results [B, k_out] / [B] (B unbounded: not block-shaped, so it grows here).  The device form needs none of it
+struct FuseBufs {
+    DevBuf<double> vals[2], out_vals;
+    DevBuf<int64_t> ids[2], map[2], out_ids;
+    DevBuf<int32_t> count;
+    hipError_t reserve(size_t B, const int* w, const int64_t* map_len, size_t k_out) {
+        hipError_t e = hipSuccess;
+        for (int l = 0; l < 2 && !e; ++l) {
+            e = grow_each(B * (size_t)w[l], vals[l], ids[l]);
+            if (!e) e = grow_each((size_t)map_len[l], map[l]);
+        }
+        if (!e) e = grow_each(B * k_out, out_vals, out_ids);
+        if (!e) e = grow_each(B, count);
+        return e;
+    }
+};
 // range search (mi355dr_search_range*): one block's result buffers [nb, R slots] with their per-query
 // words, the radii, the redo list of `pairs` pairs, the two device counters and the sub-block of the queries the ordinary
 // search serves (fb_*: map, gathered queries, lists [nb, m])
@@ -263,6 +280,7 @@ struct mi355dr_index {
     mi355::DevBuf<int32_t> subset_ids;  // the listed rows of the mi355dr_search_subset call in progress: local, ascending, unique
     mi355::MmrBufs mmr;      // per-family scratch of the derived searches (above): grown by each family's reserve()
     mi355::GroupBufs grp;
+    mi355::FuseBufs fuse;
     mi355::RangeBufs rng;
     mi355::RowQueryBufs rowq;
     mi355::ShardBufs shd;
@@ -398,6 +416,8 @@ struct mi355dr_index {
     int64_t s_mmr_searches = 0, s_mmr_queries = 0, s_mmr_pairs = 0;
     // mi355dr_search_groups*: calls, sub-queries; groups merged by them and by mi355dr_merge_groups_device
     int64_t s_group_searches = 0, s_group_subqueries = 0, s_groups_merged = 0;
+    // mi355dr_fuse_lists*: calls, queries
+    int64_t s_fuse_calls = 0, s_fuse_queries = 0;
     // mi355dr_search_range*: calls, queries, rows in range (the counts, summed); screen path: candidates taken from the screens
     // and of them re-scored; (query, chunk) pairs run again on the exact path; queries whose list the ordinary search served
     int64_t s_range_searches = 0, s_range_queries = 0, s_range_in_range = 0, s_range_candidates = 0, s_range_rescored = 0,

@@ -24,6 +24,7 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "k_mmr.h"
 #include "mmr_order.h"
 #include "k_groups.h"
+#include "k_fuse.h"
 #include "k_range.h"
 #include "k_rows.h"
 #include "k_shard.h"
@@ -2038,6 +2039,136 @@ int mi355dr_search_groups_device(mi355dr_index* idx, const float* queries_dev, c
                               stream, /*host=*/false);
 }
 
+// ---- hybrid fusion: two ranked lists per query fused into one (csrc/k_fuse.h) -----------------------
+namespace {
+struct FuseLists {  // one call's inputs and outputs, all on the device or all on the host
+    const double* vals[2];
+    const int64_t* ids[2];
+    const int64_t* map[2];
+    int64_t map_len[2];
+    int w[2];
+    double* out_vals;
+    int64_t* out_ids;
+    int32_t* out_count;
+};
+
+// the call's shape and options; fills everything of *a but the pointers.  Nothing has been touched when this fails.
+int check_fuse(mi355dr_index* idx, const char* what, const FuseLists& io, int B, int k_out, const mi355dr_fuse_opts* o, FuseArgs* a) {
+    const std::string w(what);
+    if (B < 0) return fail(idx, MI355DR_E_INVALID, w + ": B must be >= 0");
+    if (io.w[0] <= 0 || io.w[1] <= 0 || k_out <= 0) return fail(idx, MI355DR_E_INVALID, w + ": the list widths and k_out must be > 0");
+    if (!o) return fail(idx, MI355DR_E_INVALID, w + ": opts is null");
+    if (o->method < MI355DR_FUSE_RRF || o->method > MI355DR_FUSE_CC_DBSF) return fail(idx, MI355DR_E_INVALID, w + ": unknown method");
+    for (const int mode : {o->mode_1, o->mode_2})
+        if (mode < MI355DR_FUSE_ONE_MINUS || mode > MI355DR_FUSE_AS_IS) return fail(idx, MI355DR_E_INVALID, w + ": unknown score mode");
+    a->absent = 0.0;
+    if (o->method == MI355DR_FUSE_RRF) {
+        const int64_t far = (int64_t)o->rrf_k + (int64_t)o->fetch_k + 1;
+        if (o->rrf_k < 0 || far <= 0) return fail(idx, MI355DR_E_INVALID, w + ": rrf_k must be >= 0 and rrf_k + fetch_k + 1 > 0");
+        a->absent = 1.0 / (double)far;
+    } else {
+        if (!std::isfinite(o->weight)) return fail(idx, MI355DR_E_INVALID, w + ": weight is not finite");
+        if (o->method == MI355DR_FUSE_CC_TMM && (!std::isfinite(o->min_1) || !std::isfinite(o->min_2)))
+            return fail(idx, MI355DR_E_INVALID, w + ": tmm needs two finite minima");
+    }
+    for (int l = 0; l < 2; ++l)
+        if (io.map[l] && io.map_len[l] < 0) return fail(idx, MI355DR_E_INVALID, w + ": map_len must be >= 0");
+    if (B > 0 && (!io.vals[0] || !io.ids[0] || !io.vals[1] || !io.ids[1] || !io.out_vals || !io.out_ids))
+        return fail(idx, MI355DR_E_INVALID, w + ": null buffer");
+    if (io.w[0] > kFuseWidthMax || io.w[1] > kFuseWidthMax) return fail(idx, MI355DR_E_UNSUPPORTED, w + ": a list is wider than 1024");
+    if (k_out > kFuseMax) return fail(idx, MI355DR_E_UNSUPPORTED, w + ": k_out exceeds 2048");
+    static_assert(MI355DR_FUSE_RRF == kFuseRrf && MI355DR_FUSE_CC_MM == kFuseMm && MI355DR_FUSE_CC_TMM == kFuseTmm &&
+                      MI355DR_FUSE_CC_Z == kFuseZ && MI355DR_FUSE_CC_DBSF == kFuseDbsf && MI355DR_FUSE_ONE_MINUS == kFuseOneMinus &&
+                      MI355DR_FUSE_NEGATE == kFuseNegate && MI355DR_FUSE_AS_IS == kFuseAsIs,
+                  "k_fuse.h numbers the methods and modes as the header does");
+    a->method = o->method;
+    a->mode[0] = o->mode_1;
+    a->mode[1] = o->mode_2;
+    a->rrf_k = o->rrf_k;
+    a->weight = o->weight;
+    a->tmin[0] = o->min_1;
+    a->tmin[1] = o->min_2;
+    a->w[0] = io.w[0];
+    a->w[1] = io.w[1];
+    a->np = groups_pow2((int64_t)io.w[0] + io.w[1]);  // <= kFuseMax
+    a->k_out = k_out;
+    return MI355DR_OK;
+}
+
+// ONE launch over all B queries, `dev` being the lists on the device; asynchronous on the stream
+int launch_fuse(mi355dr_index* idx, hipStream_t s, const FuseLists& dev, int B, FuseArgs a) {
+    for (int l = 0; l < 2; ++l) {
+        a.vals[l] = dev.vals[l];
+        a.ids[l] = dev.ids[l];
+        a.map[l] = dev.map[l];
+        a.map_len[l] = dev.map[l] ? dev.map_len[l] : 0;
+    }
+    a.out_vals = dev.out_vals;
+    a.out_ids = dev.out_ids;
+    a.out_count = dev.out_count;
+    hipLaunchKernelGGL(k_fuse_lists, dim3(B), dim3(kFuseThreads), fuse_lds_bytes(a.np), s, a);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+int fuse_impl(mi355dr_index* idx, const FuseLists& io, int B, int k_out, const mi355dr_fuse_opts* opts, void* stream, bool host) {
+    FuseArgs a{};
+    Call c;
+    CHECK(begin_call(idx, "fuse_lists", stream, /*flags=*/0, c, [&]() -> int {  // (no drain: it touches no per-search state)
+        return check_fuse(idx, "fuse_lists", io, B, k_out, opts, &a);
+    }));
+    if (B == 0) return MI355DR_OK;
+    FuseLists dev = io;
+    if (host) {
+        FuseBufs& f = idx->fuse;
+        const int64_t lens[2] = {io.map[0] ? io.map_len[0] : 0, io.map[1] ? io.map_len[1] : 0};
+        HIPCHECK(idx, f.reserve(B, io.w, lens, k_out));
+        for (int l = 0; l < 2; ++l) {
+            const size_t n = (size_t)B * io.w[l];
+            HIPCHECK(idx, hipMemcpyAsync(f.vals[l].p, io.vals[l], n * sizeof(double), hipMemcpyHostToDevice, c.s));
+            HIPCHECK(idx, hipMemcpyAsync(f.ids[l].p, io.ids[l], n * sizeof(int64_t), hipMemcpyHostToDevice, c.s));
+            if (lens[l] > 0)
+                HIPCHECK(idx, hipMemcpyAsync(f.map[l].p, io.map[l], (size_t)lens[l] * sizeof(int64_t), hipMemcpyHostToDevice, c.s));
+            dev.vals[l] = f.vals[l].p;
+            dev.ids[l] = f.ids[l].p;
+            // (a map of length 0 strikes every entry out: any non-null pointer says "a map is given")
+            dev.map[l] = io.map[l] ? (lens[l] > 0 ? f.map[l].p : (const int64_t*)f.ids[l].p) : nullptr;
+        }
+        dev.out_vals = f.out_vals.p;
+        dev.out_ids = f.out_ids.p;
+        dev.out_count = io.out_count ? f.count.p : nullptr;
+    }
+    CHECK(launch_fuse(idx, c.s, dev, B, a));
+    if (host) {
+        const size_t n = (size_t)B * k_out;
+        HIPCHECK(idx, hipMemcpyAsync(io.out_vals, dev.out_vals, n * sizeof(double), hipMemcpyDeviceToHost, c.s));
+        HIPCHECK(idx, hipMemcpyAsync(io.out_ids, dev.out_ids, n * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+        if (io.out_count)
+            HIPCHECK(idx, hipMemcpyAsync(io.out_count, dev.out_count, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+    }
+    HIPCHECK(idx, hipStreamSynchronize(c.s));
+    idx->s_fuse_calls++;
+    idx->s_fuse_queries += B;
+    return MI355DR_OK;
+}
+}  // namespace
+
+int mi355dr_fuse_lists_device(mi355dr_index* idx, const double* vals1_dev, const int64_t* ids1_dev, int w1, const int64_t* map1_dev,
+                              int64_t map1_len, const double* vals2_dev, const int64_t* ids2_dev, int w2, const int64_t* map2_dev,
+                              int64_t map2_len, int B, int k_out, const mi355dr_fuse_opts* opts, double* out_vals_dev,
+                              int64_t* out_ids_dev, int32_t* out_count_dev, void* stream) {
+    const FuseLists io{{vals1_dev, vals2_dev}, {ids1_dev, ids2_dev}, {map1_dev, map2_dev}, {map1_len, map2_len}, {w1, w2},
+                       out_vals_dev, out_ids_dev, out_count_dev};
+    return fuse_impl(idx, io, B, k_out, opts, stream, /*host=*/false);
+}
+
+int mi355dr_fuse_lists(mi355dr_index* idx, const double* vals1, const int64_t* ids1, int w1, const int64_t* map1, int64_t map1_len,
+                       const double* vals2, const int64_t* ids2, int w2, const int64_t* map2, int64_t map2_len, int B, int k_out,
+                       const mi355dr_fuse_opts* opts, double* out_vals, int64_t* out_ids, int32_t* out_count) {
+    const FuseLists io{{vals1, vals2}, {ids1, ids2}, {map1, map2}, {map1_len, map2_len}, {w1, w2}, out_vals, out_ids, out_count};
+    return fuse_impl(idx, io, B, k_out, opts, nullptr, /*host=*/true);
+}
+
 // ---- range search: every row within a distance, counted on the device (csrc/k_range.h) ------------
 namespace {
 struct RangeSpan {
@@ -2896,6 +3027,8 @@ const Stat kStats[] = {
     {"group_searches", &Index::s_group_searches, true},
     {"group_subqueries", &Index::s_group_subqueries, true},
     {"groups_merged", &Index::s_groups_merged, true},
+    {"fuse_calls", &Index::s_fuse_calls, true},
+    {"fuse_queries", &Index::s_fuse_queries, true},
     {"range_searches", &Index::s_range_searches, true},
     {"range_queries", &Index::s_range_queries, true},
     {"range_in_range", &Index::s_range_in_range, true},

@@ -176,7 +176,14 @@ class _Mi355HybridBase(Mi355BaseRetrievalPipeline):
     """Two children, one fusion rule (reference HybridRetrievalPipeline, hybrid.py:289-437)."""
 
     def __init__(self, session_factory: Any, name: str, retrieval_pipeline_1: Any, retrieval_pipeline_2: Any,
-                 fetch_k_multiplier: int = 2, schema: Any | None = None, config_dir: Path | None = None, device: int = 0):
+                 fetch_k_multiplier: int = 2, schema: Any | None = None, config_dir: Path | None = None, device: int = 0,
+                 device_fusion: bool | None = None):
+        # where a page of `run()` is fused when the children are this package's dense (single mode, chunk) and BM25
+        # pipelines: None = on the device for rrf / mm / tmm (bit-identical dicts), on the host for z / dbsf (there the
+        # host's `** 0.5` and `sum` are not the library's sqrt and plain sum); True / False = device / host for all five.
+        # A constructor argument only: it is not part of the recorded config or of the config dataclasses
+        self.device_fusion = device_fusion
+        self._tables_compared: tuple | None = None   # (dense child's table, BM25 child's table, same ids in the same order)
         if isinstance(retrieval_pipeline_1, str):
             retrieval_pipeline_1 = _load_child(retrieval_pipeline_1, session_factory, schema, config_dir)
         if isinstance(retrieval_pipeline_2, str):
@@ -210,8 +217,83 @@ class _Mi355HybridBase(Mi355BaseRetrievalPipeline):
         results_2 = await self._retrieval_pipeline_2._retrieve_by_text(query_text, fetch_k)
         return self._fuse_results(results_1, results_2, top_k, fetch_k)
 
+    def _fuse_spec(self, fetch_k: int) -> dict[str, Any]:
+        """The fusion rule as Mi355Index.fuse_lists' keywords (method, rrf_k, fetch_k | weight, mins)."""
+        raise NotImplementedError
+
+    def _device_legs(self) -> tuple[Any, Any, bool] | None:
+        """(dense child, BM25 child, the dense child is list 1) when the page can be fused where the searches leave their
+        lists: this package's own single-vector chunk search and BM25 pipelines (exactly those classes: a subclass may
+        answer differently), on one GPU, without a process group, over chunk tables with the same ids in the same order
+        (compared once per pair of table exports)."""
+        from .bm25 import Mi355BM25RetrievalPipeline  # noqa: PLC0415
+        from .pipelines import Mi355VectorSearchRetrievalPipeline  # noqa: PLC0415
+
+        a, b = self._retrieval_pipeline_1, self._retrieval_pipeline_2
+        if type(a) is Mi355VectorSearchRetrievalPipeline and type(b) is Mi355BM25RetrievalPipeline:
+            dense, lex, dense_first = a, b, True
+        elif type(a) is Mi355BM25RetrievalPipeline and type(b) is Mi355VectorSearchRetrievalPipeline:
+            dense, lex, dense_first = b, a, False
+        else:
+            return None
+        if dense.search_mode != "single" or (dense.retrieval_unit or "chunk") != "chunk":
+            return None
+        s1, s2 = dense._service, lex._service
+        if s1._world is not None or s2._world is not None or self._service._world is not None or s1._device != s2._device:
+            return None
+        t1, t2 = s1._unit("chunk").table, s2._unit("chunk").table
+        seen = self._tables_compared
+        if seen is None or seen[0] is not t1 or seen[1] is not t2:
+            self._tables_compared = seen = (t1, t2, t1 is t2 or t1.ids is t2.ids or list(t1.ids) == list(t2.ids))
+        return (dense, lex, dense_first) if seen[2] else None
+
+    def _wants_device(self, method: str) -> bool:
+        """`device_fusion`, None being "where the dicts are bit-identical": at every measured page shape the device path is
+        8 to 15 times faster than the host's, so there is no size below which None prefers the host."""
+        if self.device_fusion is not None:
+            return bool(self.device_fusion)
+        return method in ("rrf", "mm", "tmm")
+
+    def _retrieve_block_device(self, query_ids: list, top_k: int, fetch_k: int) -> list[list[dict] | None] | None:
+        """The page through two searches whose lists stay on the device, one fusion launch and one [B, top_k] download; None
+        when this page has to take the host path.  A query either child would fail (no row, no embedding, no text) is None
+        alone, as on the host path."""
+        spec = self._fuse_spec(fetch_k)
+        legs = self._device_legs() if self._wants_device(spec["method"]) else None
+        if legs is None or not 0 < fetch_k <= 1024 or not 0 < top_k <= 2048 or type(spec.get("rrf_k", 0)) is not int:
+            return None
+        dense, lex, dense_first = legs
+        ids = list(query_ids)
+        ok, embeddings, texts = [], [], []
+        for qid, q1, q2 in zip(ids, dense._service.get_queries(ids), lex._service.get_queries(ids), strict=True):
+            if q1 is None or q1.embedding is None or q2 is None or q2.contents is None:
+                logger.error(f"Retrieval failed for query {qid}")
+                continue
+            ok.append(qid)
+            embeddings.append(q1.embedding)
+            texts.append(q2.contents)
+        fused: list[list[dict]] = []
+        if ok:
+            import numpy as np  # noqa: PLC0415
+
+            list_dense = dense._service.dense_lists_device(np.stack(embeddings).astype(np.float32, copy=False), fetch_k)
+            list_lex = None if list_dense is None else lex._service.bm25_lists_device(texts, fetch_k, lex.tokenizer, lex.k1, lex.b)
+            if list_dense is None or list_lex is None:
+                return None
+            first, second = (list_dense, list_lex) if dense_first else (list_lex, list_dense)
+            fused = dense._service.fuse_device_lists(first, second, dense._service._unit("chunk").table, top_k, **spec)
+        by_id = dict(zip(ok, fused))
+        return [by_id.get(qid) for qid in ids]
+
     def _retrieve_block(self, query_ids: list, top_k: int) -> list[list[dict] | None]:
         fetch_k = top_k * self.fetch_k_multiplier
+        try:
+            page = self._retrieve_block_device(query_ids, top_k, fetch_k)
+        except Exception:  # noqa: BLE001 - the device path is an optimisation: whatever stops it, the host path answers
+            logger.exception(f"hybrid pipeline {self.name!r}: fusion on the device failed, fusing this page on the host")
+            page = None
+        if page is not None:
+            return page
         page_1 = child_page(self._retrieval_pipeline_1, query_ids, fetch_k)
         page_2 = child_page(self._retrieval_pipeline_2, query_ids, fetch_k)
         return [None if a is None or b is None else self._fuse_results(a, b, top_k, fetch_k) for a, b in zip(page_1, page_2)]
@@ -221,10 +303,14 @@ class Mi355HybridRRFRetrievalPipeline(_Mi355HybridBase):
     """Reciprocal Rank Fusion of two children (reference HybridRRFRetrievalPipeline, hybrid.py:440-534)."""
 
     def __init__(self, session_factory: Any, name: str, retrieval_pipeline_1: Any, retrieval_pipeline_2: Any, rrf_k: int = 60,
-                 fetch_k_multiplier: int = 2, schema: Any | None = None, config_dir: Path | None = None, device: int = 0):
+                 fetch_k_multiplier: int = 2, schema: Any | None = None, config_dir: Path | None = None, device: int = 0,
+                 device_fusion: bool | None = None):
         self.rrf_k = rrf_k
         super().__init__(session_factory, name, retrieval_pipeline_1, retrieval_pipeline_2, fetch_k_multiplier, schema,
-                         config_dir, device)
+                         config_dir, device, device_fusion)
+
+    def _fuse_spec(self, fetch_k: int) -> dict[str, Any]:
+        return {"method": "rrf", "rrf_k": self.rrf_k, "fetch_k": fetch_k}
 
     def _get_pipeline_config(self) -> dict[str, Any]:
         return {"type": "mi355_hybrid_rrf", "retrieval_unit": self.retrieval_unit,
@@ -241,13 +327,16 @@ class Mi355HybridCCRetrievalPipeline(_Mi355HybridBase):
     def __init__(self, session_factory: Any, name: str, retrieval_pipeline_1: Any, retrieval_pipeline_2: Any,
                  weight: float = 0.5, normalize_method: NormalizationMethod = "mm", pipeline_1_min: float | None = None,
                  pipeline_2_min: float | None = None, fetch_k_multiplier: int = 2, schema: Any | None = None,
-                 config_dir: Path | None = None, device: int = 0):
+                 config_dir: Path | None = None, device: int = 0, device_fusion: bool | None = None):
         self.weight = weight
         self.normalize_method = normalize_method
         self.pipeline_1_min = pipeline_1_min
         self.pipeline_2_min = pipeline_2_min
         super().__init__(session_factory, name, retrieval_pipeline_1, retrieval_pipeline_2, fetch_k_multiplier, schema,
-                         config_dir, device)
+                         config_dir, device, device_fusion)
+
+    def _fuse_spec(self, fetch_k: int) -> dict[str, Any]:
+        return {"method": self.normalize_method, "weight": self.weight, "mins": (self.pipeline_1_min, self.pipeline_2_min)}
 
     def _get_pipeline_config(self) -> dict[str, Any]:
         config = {"type": "mi355_hybrid_cc", "retrieval_unit": self.retrieval_unit,

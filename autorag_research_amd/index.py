@@ -17,6 +17,8 @@ from ._native import NativeError, check, f32c, ptr
 METRICS = {"cosine": 0, "ip": 1}
 PATHS = {"auto": 0, "screen": 1, "scan": 2}
 SCREEN_DTYPES = {"auto": 0, "bf16": 1, "i8": 2}
+FUSE_METHODS = {"rrf": 0, "mm": 1, "tmm": 2, "z": 3, "dbsf": 4}      # MI355DR_FUSE_RRF / _CC_*
+FUSE_MODES = {"one_minus": 0, "negate": 1, "as_is": 2}               # MI355DR_FUSE_ONE_MINUS / _NEGATE / _AS_IS
 
 
 def _stream_arg(stream) -> ctypes.c_void_p:
@@ -334,6 +336,60 @@ class Mi355Index:
             for b in bufs:
                 self.dev_free(b)
         return out_v, out_r, out_c
+
+    # ---- hybrid fusion: two ranked lists per query fused into one on the device (include/mi355dr.h "hybrid fusion") ----
+    @staticmethod
+    def _fuse_opts(method: str, modes, rrf_k: int, fetch_k: int, weight: float, mins) -> "_native.FuseOpts":
+        if method not in FUSE_METHODS:
+            raise ValueError(f"method must be one of {sorted(FUSE_METHODS)}")
+        if len(modes) != 2 or any(m not in FUSE_MODES for m in modes):
+            raise ValueError(f"modes must be two of {sorted(FUSE_MODES)}")
+        if method == "tmm" and (mins is None or len(mins) != 2 or any(m is None for m in mins)):
+            raise ValueError("TMM normalization requires both minima")
+        lo = (0.0, 0.0) if mins is None or method != "tmm" else mins
+        return _native.FuseOpts(FUSE_METHODS[method], FUSE_MODES[modes[0]], FUSE_MODES[modes[1]], int(rrf_k), int(fetch_k),
+                                float(weight), float(lo[0]), float(lo[1]))
+
+    def fuse_lists_device(self, vals1_ptr: int, ids1_ptr: int, w1: int, vals2_ptr: int, ids2_ptr: int, w2: int, B: int, k: int,
+                          out_vals_ptr: int, out_ids_ptr: int, out_count_ptr: int | None = None, *, method: str,
+                          modes=("as_is", "as_is"), rrf_k: int = 60, fetch_k: int = 0, weight: float = 0.5, mins=None,
+                          map1_ptr: int | None = None, map1_len: int = 0, map2_ptr: int | None = None, map2_len: int = 0,
+                          stream: int | None = None) -> None:
+        """The fusion over device lists (float64 / int64 [B, w_l]; maps int64 [map_len_l] or None; outputs float64 / int64
+        [B, k] and int32 [B] or None).  It reads no index state: the lists may be another handle's.  Complete on return."""
+        opts = self._fuse_opts(method, modes, rrf_k, fetch_k, weight, mins)
+        vp = lambda p: ctypes.c_void_p(int(p) if p else None)  # noqa: E731
+        check(self._h, self._lib.mi355dr_fuse_lists_device(
+            self._h, vp(vals1_ptr), vp(ids1_ptr), int(w1), vp(map1_ptr), int(map1_len), vp(vals2_ptr), vp(ids2_ptr), int(w2),
+            vp(map2_ptr), int(map2_len), int(B), int(k), ctypes.byref(opts), vp(out_vals_ptr), vp(out_ids_ptr), vp(out_count_ptr),
+            _stream_arg(stream)))
+
+    def fuse_lists(self, vals1, ids1, vals2, ids2, k: int, *, method: str, modes=("as_is", "as_is"), rrf_k: int = 60,
+                   fetch_k: int = 0, weight: float = 0.5, mins=None, map1=None, map2=None):
+        """Fuse two ranked lists per query on the device: vals_l float64 [B, w_l], ids_l int64 [B, w_l] (an id < 0, a NaN
+        value, or an id its map strikes out is no entry), `modes` = how each list's values become scores ("one_minus": a
+        cosine distance, "negate": a BM25 distance, "as_is").  method "rrf" (rrf_k, fetch_k) or a convex combination "mm" |
+        "tmm" | "z" | "dbsf" (weight; mins for tmm) -- hybrid.rrf_fuse / hybrid.cc_fuse over first-seen order.  map_l: int64
+        array translating list l's ids into the common id space.  Returns (scores [B,k], ids [B,k], count int32 [B] = size of
+        each union); NaN / -1 padded."""
+        v1 = np.ascontiguousarray(vals1, dtype=np.float64)
+        i1 = np.ascontiguousarray(ids1, dtype=np.int64)
+        v2 = np.ascontiguousarray(vals2, dtype=np.float64)
+        i2 = np.ascontiguousarray(ids2, dtype=np.int64)
+        if v1.ndim != 2 or i1.shape != v1.shape or v2.ndim != 2 or i2.shape != v2.shape or v1.shape[0] != v2.shape[0]:
+            raise ValueError("vals_l and ids_l must both be [B, w_l] with one B")
+        maps = [None if m is None else np.ascontiguousarray(m, dtype=np.int64).reshape(-1) for m in (map1, map2)]
+        opts = self._fuse_opts(method, modes, rrf_k, fetch_k, weight, mins)
+        B, k = v1.shape[0], int(k)
+        out_v = np.empty((B, max(k, 0)), dtype=np.float64)
+        out_i = np.empty((B, max(k, 0)), dtype=np.int64)
+        out_c = np.empty(B, dtype=np.int32)
+        mp = lambda m: (None, 0) if m is None else (ptr(m, ctypes.c_int64), m.shape[0])  # noqa: E731
+        check(self._h, self._lib.mi355dr_fuse_lists(
+            self._h, ptr(v1, ctypes.c_double), ptr(i1, ctypes.c_int64), v1.shape[1], *mp(maps[0]), ptr(v2, ctypes.c_double),
+            ptr(i2, ctypes.c_int64), v2.shape[1], *mp(maps[1]), B, k, ctypes.byref(opts), ptr(out_v, ctypes.c_double),
+            ptr(out_i, ctypes.c_int64), ptr(out_c, ctypes.c_int32)))
+        return out_v, out_i, out_c
 
     # ---- range search: every row within a distance, counted on the device (include/mi355dr.h "range search") ----
     @staticmethod
@@ -752,6 +808,15 @@ class Mi355Index:
         a = (self._h, ptr(t, ctypes.c_int32), ptr(off, ctypes.c_int32), B, int(k), float(k1), float(b))
         return self._sparse_call(B, k, device_out, lambda d, r: self._lib.mi355dr_search_bm25(*a, d, r),
                                  lambda d, r, s: self._lib.mi355dr_search_bm25_device(*a, d, r, s))
+
+    def search_bm25_device(self, token_lists, k: int, out_dist_ptr: int, out_ids_ptr: int, k1: float = 1.2, b: float = 0.75,
+                           offsets=None, stream: int | None = None) -> None:
+        """`search_bm25` into device buffers of the caller (float64 / int64 [B, k]); the queries stay on the host.  Complete
+        on return."""
+        t, off = self._ragged_i32(token_lists, offsets, np.int32)
+        check(self._h, self._lib.mi355dr_search_bm25_device(
+            self._h, ptr(t, ctypes.c_int32), ptr(off, ctypes.c_int32), off.shape[0] - 1, int(k), float(k1), float(b),
+            ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_ids_ptr)), _stream_arg(stream)))
 
     # within a listed subset: a filter, not a view -- the statistics (N, avgdl, df) stay those of the whole store, so a listed
     # document's distance is bit for bit the unrestricted search's.  doc_ids are GLOBAL ids (local id + `row_offset`); ids

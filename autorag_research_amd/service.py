@@ -162,6 +162,52 @@ class _MultiPlan(NamedTuple):   # ... and of the multi-vector store (_UnitIndex.
     changed: np.ndarray     # positions < n_old whose documents differ
 
 
+class _DevScratch:
+    """Named device buffers of a unit that grow and are reused page after page (raw hipMalloc blocks: any open handle of
+    the device allocates and frees them)."""
+
+    def __init__(self) -> None:
+        self._bufs: dict[str, tuple[int, int]] = {}
+
+    def take(self, ix: Mi355Index, name: str, nbytes: int) -> int:
+        ptr, have = self._bufs.get(name, (0, 0))
+        if have < nbytes:
+            if ptr:
+                ix.dev_free(ptr)
+            self._bufs.pop(name, None)
+            ptr = ix.dev_alloc(nbytes)
+            self._bufs[name] = (ptr, nbytes)
+        return ptr
+
+    def drop(self, ix: Mi355Index, name: str) -> None:
+        ptr, _ = self._bufs.pop(name, (0, 0))
+        if ptr:
+            ix.dev_free(ptr)
+
+    def release(self, ix: Mi355Index | None) -> None:
+        if ix is not None:
+            for name in list(self._bufs):
+                self.drop(ix, name)
+        self._bufs.clear()
+
+
+class DeviceLists(NamedTuple):
+    """One leg's [B, width] lists where its search left them (`dense_lists_device` / `bm25_lists_device`): the handle and
+    scratch they belong to, distances float64 and ids int64 as device pointers, how a distance becomes the leg's score
+    (Mi355Index.fuse_lists `modes`), and the device map from the leg's ids to table positions (0 / 0: they are positions).
+    Valid until the same leg's next page."""
+
+    index: Mi355Index
+    scratch: _DevScratch
+    dist_ptr: int
+    ids_ptr: int
+    B: int
+    width: int
+    mode: str
+    map_ptr: int
+    map_len: int
+
+
 class _UnitIndex:
     """GPU index of one table (chunk / image_chunk): row <-> primary-key mapping + the native handle."""
 
@@ -186,6 +232,10 @@ class _UnitIndex:
         # sharded, and brought up to the table's contents when they are no longer what it was built from (`ensure_sparse`)
         self.sparse: Mi355Index | None = None
         self._sparse_of: tuple[Any, list] | None = None    # (tokenizer key, the contents list it was built from)
+        # device-side page buffers of the legs that leave their lists in HBM, and the device copy of `single_rows` they hand
+        # the fusion as its map (`single_rows_device`; dropped with the other maps in _forget_maps)
+        self.scratch = _DevScratch()
+        self._single_rows_dev: tuple[np.ndarray, int, int] | None = None   # (the single_rows array it copies, pointer, length)
 
     def _not_null_positions(self) -> np.ndarray:
         emb = self.table.embedding
@@ -290,7 +340,24 @@ class _UnitIndex:
         self.sparse, self._sparse_of = ix, (key, contents)
         return ix
 
+    def _any_handle(self) -> Mi355Index | None:
+        return next((ix for ix in (self.single, self.sparse, self.multi) if ix is not None), None)
+
+    def single_rows_device(self) -> tuple[int, int]:
+        """(device pointer, length) of `single_rows` as int64: index row -> table position, the fusion's map for the dense
+        leg.  Uploaded once per layout."""
+        ix, rows = self.ensure_single(), self.single_rows
+        if self._single_rows_dev is None or self._single_rows_dev[0] is not rows:
+            host = np.ascontiguousarray(rows, dtype=np.int64)
+            ptr = self.scratch.take(ix, "single_rows", max(host.nbytes, 8))
+            if host.nbytes:
+                ix.dev_upload(ptr, host)
+            self._single_rows_dev = (rows, ptr, host.shape[0])
+        return self._single_rows_dev[1:]
+
     def close(self) -> None:
+        self.scratch.release(self._any_handle())
+        self._single_rows_dev = None
         for ix in (self.single, self.multi, self.single_sharded, self.multi_sharded, self.sparse):
             if ix is not None:
                 ix.close()
@@ -321,6 +388,7 @@ class _UnitIndex:
 
     def _forget_maps(self) -> None:   # (the caches of pos_of_id / stored_row_of_pos: stale once the table or the layout changes)
         self._pos_of_id = self._stored_row_of_pos = None
+        self._single_rows_dev = None      # (the device copy of single_rows; its block stays in `scratch` for the next one)
 
     @property
     def slot_per_position(self) -> bool:
@@ -338,6 +406,8 @@ class _UnitIndex:
     def _relayout(self, emb: np.ndarray, null: np.ndarray, why: str) -> str:
         """`single` anew with one slot per table position: NULL rows are added as placeholders and removed at once."""
         logger.info("refresh: %s; laying it out with one slot per table position", why)
+        self.scratch.release(self.single)
+        self._single_rows_dev = None
         self.single.close()
         self.single = Mi355Index(emb.shape[1], "cosine", self.device)
         self._append_slots(emb, null, 0)
@@ -760,6 +830,72 @@ class Mi355RetrievalService:
         """BM25 top-k of a raw query text, no query row needed (reference bm25_search_by_text, :398-423).  `within`: among the
         listed chunk ids only."""
         return self._bm25_block([query_text], top_k, tokenizer, k1, b, within)[0]
+
+    # ---- hybrid fusion on the device: both legs' lists stay in HBM (include/mi355dr.h "hybrid fusion") ----
+    def dense_lists_device(self, Q: np.ndarray, top_k: int) -> DeviceLists | None:
+        """`_single_block` of the chunk table that leaves distances and rows on the device (one `search_device`).  None where
+        the lists could differ from the host path's or cannot be had: a process group, top_k above the search's 1024, a
+        query or stored row whose distance is NaN (the host path keeps such results, the fusion strikes them out)."""
+        if self._world is not None or not 0 < top_k <= 1024:
+            return None
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        norms = np.einsum("ij,ij->i", Q.astype(np.float64), Q.astype(np.float64))
+        if not (np.isfinite(norms).all() and (norms > 0).all()):
+            return None
+        u = self._unit("chunk")
+        ix = u.ensure_single()
+        if ix.stat("irregular_rows") != 0:
+            return None
+        B = Q.shape[0]
+        q_ptr = u.scratch.take(ix, "dense_q", Q.nbytes)
+        dist_ptr = u.scratch.take(ix, "dense_dist", B * top_k * 8)
+        rows_ptr = u.scratch.take(ix, "dense_rows", B * top_k * 8)
+        ix.dev_upload(q_ptr, Q)
+        ix.search_device(q_ptr, B, top_k, dist_ptr, rows_ptr)
+        map_ptr, map_len = u.single_rows_device()
+        return DeviceLists(ix, u.scratch, dist_ptr, rows_ptr, B, top_k, "one_minus", map_ptr, map_len)
+
+    def bm25_lists_device(self, texts: list[str], top_k: int, tokenizer: Any, k1: float, b: float) -> DeviceLists | None:
+        """`_bm25_block` that leaves distances and ids (= table positions) on the device (one `search_bm25_device`)."""
+        from .bm25 import get_tokenizer  # noqa: PLC0415
+
+        if self._world is not None or not 0 < top_k <= 1024:
+            return None
+        u = self._unit("chunk")
+        ix = u.ensure_sparse(tokenizer)
+        if not hasattr(ix, "search_bm25_device"):
+            return None
+        tok = get_tokenizer(tokenizer)
+        B = len(texts)
+        dist_ptr = u.scratch.take(ix, "bm25_dist", B * top_k * 8)
+        ids_ptr = u.scratch.take(ix, "bm25_ids", B * top_k * 8)
+        ix.search_bm25_device([tok(t) for t in texts], top_k, dist_ptr, ids_ptr, k1=k1, b=b)
+        return DeviceLists(ix, u.scratch, dist_ptr, ids_ptr, B, top_k, "negate", 0, 0)
+
+    @staticmethod
+    def fuse_device_lists(lists_1: DeviceLists, lists_2: DeviceLists, table: ChunkTable, top_k: int, **spec) -> list[list[dict]]:
+        """Two legs' device lists -> the dicts `hybrid.rrf_fuse` / `hybrid.cc_fuse` return ({"doc_id", "score"}, doc_id from
+        the table position): one fusion launch on the first leg's handle (the lists may be two services' handles on one GPU),
+        one [B, top_k] download.  `spec`: Mi355Index.fuse_lists' method / rrf_k / fetch_k / weight / mins."""
+        ix, B = lists_1.index, lists_1.B
+        if lists_2.B != B:
+            raise ValueError("the two legs answered different numbers of queries")
+        out_v = np.empty((B, top_k), dtype=np.float64)
+        out_i = np.empty((B, top_k), dtype=np.int64)
+        v_ptr = lists_1.scratch.take(ix, "fused_scores", max(out_v.nbytes, 8))
+        i_ptr = lists_1.scratch.take(ix, "fused_ids", max(out_i.nbytes, 8))
+        ix.fuse_lists_device(lists_1.dist_ptr, lists_1.ids_ptr, lists_1.width, lists_2.dist_ptr, lists_2.ids_ptr, lists_2.width,
+                             B, top_k, v_ptr, i_ptr, None, modes=(lists_1.mode, lists_2.mode),
+                             map1_ptr=lists_1.map_ptr or None, map1_len=lists_1.map_len,
+                             map2_ptr=lists_2.map_ptr or None, map2_len=lists_2.map_len, **spec)
+        if B == 0:
+            return []
+        ix.dev_download(v_ptr, out_v)
+        ix.dev_download(i_ptr, out_i)
+        neg = out_i < 0
+        n_valid = np.where(neg.any(axis=1), neg.argmax(axis=1), top_k).tolist()
+        pos, sc, ids = out_i.tolist(), out_v.tolist(), table.ids
+        return [[{"doc_id": ids[p], "score": s} for p, s in zip(pr[:n], sr[:n])] for pr, sr, n in zip(pos, sc, n_valid)]
 
     def _check_mmr(self, search_mode: str, mmr_fetch_k: int | None) -> None:
         """MMR is a single-vector, single-GPU selection: it scores stored rows against each other, and under row shards the

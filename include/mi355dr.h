@@ -590,7 +590,8 @@ int mi355dr_search_maxsim_subset_device(mi355dr_index* idx, const float* qtok_de
  * Views: a view has an empty sparse store and refuses mi355dr_add_sparse / _set_sparse / _remove_sparse; mi355dr_compact does
  *   not touch the sparse store.
  * Out of scope: compaction / renumbering of sparse documents (ids are table positions in the service), views over the store, a row-sharded sparse search (it needs
- *   global df / avgdl), fusion on the device, any claim of bit parity with VectorChord-BM25. */
+ *   global df / avgdl), any claim of bit parity with VectorChord-BM25.  No longer on this list: fusion on the device of a sparse
+ *   list with a dense one, which has its own section -- "hybrid fusion" below. */
 int mi355dr_add_sparse(mi355dr_index* idx, const int32_t* terms, const int64_t* offsets /* [n_docs + 1] */, int64_t n_docs); /* host */
 int64_t mi355dr_size_sparse(const mi355dr_index* idx); /* stored documents, with or without tokens */
 int mi355dr_set_sparse(mi355dr_index* idx, const int64_t* doc_ids /* HOST [n] */, const int32_t* terms,
@@ -622,6 +623,73 @@ int mi355dr_score_sparse_subset(mi355dr_index* idx, const int32_t* q_terms, cons
                                 double* out_dist /* HOST [B, m] */);
 int mi355dr_score_bm25_subset(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, double k1, double b,
                               const int64_t* doc_ids /* HOST [B, m] */, int m, double* out_dist /* HOST [B, m] */);
+
+/* ---- hybrid fusion: two ranked lists per query fused into one on the device ----
+ * The last step of a hybrid retrieval -- Reciprocal Rank Fusion, or a convex combination of normalised scores -- over the two
+ * legs' lists where the searches left them: a dense leg's (mi355dr_search_device) and a lexical leg's
+ * (mi355dr_search_bm25_device).  One launch for a page of queries; the arithmetic below is fixed operation for operation.
+ *   Inputs: two lists per query, vals_l [B, w_l] double and ids_l [B, w_l] int64 for l = 1, 2, with 1 <= w_l <= 1024.
+ *   Entries: an entry is NO entry when its id is < 0 (wherever it stands), when its value is NaN, or when a map is given for
+ *     its list and id >= map_len or map[id] < 0.  map_l: optional device int64 [map_len_l] that translates the list's ids into
+ *     the common id space, NULL = identity (a dense index's rows are not table positions once a chunk has no embedding).  The
+ *     rank of an entry is 1 + the number of entries before it in its list: struck-out slots do not count.  Within one list a
+ *     (mapped) id occurs once; if it does not, that query's line is unspecified, but the call stays memory-safe and ends.
+ *   Score of an entry, one mode per list: MI355DR_FUSE_ONE_MINUS s = 1.0 - v (a cosine distance); MI355DR_FUSE_NEGATE s = -v,
+ *     a sign flip (-0.0 for +0.0; a BM25 distance); MI355DR_FUSE_AS_IS s = v.
+ *   Union order ("first seen"): list 1's entries in list order, then list 2's entries whose id is not in list 1, in list 2's
+ *     order.  pos(d) is a document's index in that order.
+ *   Arithmetic: IEEE double, one rounding per operation, no fused multiply-add, no transcendental function; sqrt is the
+ *     correctly rounded one.
+ *   MI355DR_FUSE_RRF (rrf_k >= 0, and fetch_k with rrf_k + fetch_k + 1 > 0), for document d: f = 0.0; if d is in list 1 at rank
+ *     r1: f = f + 1.0 / (double)(rrf_k + r1); if d is in list 2 at rank r2: f = f + 1.0 / (double)(rrf_k + r2); if d is in
+ *     exactly one list: f = f + 1.0 / (double)(rrf_k + fetch_k + 1).
+ *   MI355DR_FUSE_CC_MM / _CC_TMM / _CC_Z / _CC_DBSF (weight; min_1, min_2 for TMM): column l holds the scores of the union's
+ *     documents that list l holds IN UNION ORDER (for list 2: the documents shared with list 1 first, in list 1's order).
+ *     Statistics over a column's n present scores: min, max (the first of equal values: +0.0 / -0.0);
+ *     mean = (((0.0 + s_0) + s_1) + ...) / (double)n; var = (((0.0 + (s_0 - mean) * (s_0 - mean)) + ...)) / (double)n, both
+ *     plain left-to-right sums; std = sqrt(var).  Normalised score a of a present score s:
+ *       MM    (s - min) / (max - min);   0.5 when max - min == 0
+ *       TMM   (s - min_l) / (max - min_l);   0.5 when max - min_l == 0
+ *       Z     (s - mean) / std;   0.0 when std == 0
+ *       DBSF  lo = mean - 3.0 * std, span = (mean + 3.0 * std) - lo, x = (s - lo) / span, y = x < 1.0 ? x : 1.0,
+ *             a = y > 0.0 ? y : 0.0;   0.5 when std == 0
+ *     A document absent from a list takes the floor AFTER normalisation: MM 0.0, TMM 0.0, Z -3.0, DBSF 0.0; an empty column
+ *     has no statistics and all its entries are floors.  f = (weight * a_1) + ((1.0 - weight) * a_2).
+ *   Result line: the union sorted by f descending under IEEE comparison (+0.0 and -0.0 equal; NaN, which only infinite inputs
+ *     produce, last), ties by pos ascending -- a stable descending sort over first-seen order.  The first k_out are written as
+ *     (f with its own bits, common id); behind them NaN / -1.  count[q] = the size of the union (it may exceed k_out; the
+ *     pointer may be NULL).  Two empty lists: all NaN / -1 and 0.
+ *   mi355dr_fuse_lists_device: over device lists.  Stateless like mi355dr_merge_groups_device (it reads no index state: the
+ *     lists may come from two handles on the same GPU; allowed on a view); under the handle's mutex; complete on return.
+ *   mi355dr_fuse_lists: the same with lists, maps and results on the host, staged through buffers the index owns and grows; a
+ *     failed allocation returns MI355DR_E_NOMEM with nothing changed.
+ *   MI355DR_E_INVALID: B < 0, w_l <= 0, k_out <= 0, a null pointer with work to do (lists, results, opts; a map with
+ *     map_len < 0), an unknown mode or method, rrf_k < 0 or rrf_k + fetch_k + 1 <= 0 (RRF), a non-finite weight (CC), a
+ *     non-finite minimum (TMM).  MI355DR_E_UNSUPPORTED: w_l > 1024, k_out > 2048.  B == 0 is a valid no-op.  A refused call
+ *     changes nothing.
+ *   Stats: "fuse_calls", "fuse_queries" (B, summed); both entry points.
+ *   Out of scope: more than two lists, MaxSim legs (their score has a per-query divisor), row-sharded hybrids. */
+#define MI355DR_FUSE_RRF 0
+#define MI355DR_FUSE_CC_MM 1
+#define MI355DR_FUSE_CC_TMM 2
+#define MI355DR_FUSE_CC_Z 3
+#define MI355DR_FUSE_CC_DBSF 4
+#define MI355DR_FUSE_ONE_MINUS 0
+#define MI355DR_FUSE_NEGATE 1
+#define MI355DR_FUSE_AS_IS 2
+typedef struct {
+    int method;         /* MI355DR_FUSE_RRF | _CC_MM | _CC_TMM | _CC_Z | _CC_DBSF */
+    int mode_1, mode_2; /* MI355DR_FUSE_ONE_MINUS | _NEGATE | _AS_IS */
+    int rrf_k, fetch_k; /* RRF */
+    double weight, min_1, min_2; /* CC; the minima: TMM */
+} mi355dr_fuse_opts;
+int mi355dr_fuse_lists_device(mi355dr_index* idx, const double* vals1_dev, const int64_t* ids1_dev, int w1, const int64_t* map1_dev,
+                              int64_t map1_len, const double* vals2_dev, const int64_t* ids2_dev, int w2, const int64_t* map2_dev,
+                              int64_t map2_len, int B, int k_out, const mi355dr_fuse_opts* opts, double* out_vals_dev,
+                              int64_t* out_ids_dev, int32_t* out_count_dev /* may be NULL */, void* stream);
+int mi355dr_fuse_lists(mi355dr_index* idx, const double* vals1, const int64_t* ids1, int w1, const int64_t* map1, int64_t map1_len,
+                       const double* vals2, const int64_t* ids2, int w2, const int64_t* map2, int64_t map2_len, int B, int k_out,
+                       const mi355dr_fuse_opts* opts, double* out_vals, int64_t* out_ids, int32_t* out_count /* may be NULL */); /* all host */
 
 /* ---- Guided Query Refinement of candidate pools (GQR hybrid pipeline) ----
  * Replaces the per-query numpy loops of autorag_research/pipelines/retrieval/gqr_hybrid.py: `_optimize_query_embedding`
@@ -796,6 +864,7 @@ int mi355dr_mmr_select_sharded(mi355dr_index* idx, const float* queries, int B, 
  *          "subset_rerun_queries" (mi355dr_search_subset: calls, pairs scored, queries re-run in list-sized pieces),
  *          "mmr_searches" / "mmr_queries" / "mmr_pairs_scored" (mi355dr_search_mmr* and mi355dr_mmr_select, described there),
  *          "group_searches" / "group_subqueries" / "groups_merged" (mi355dr_search_groups* and mi355dr_merge_groups_device, described there),
+ *          "fuse_calls" / "fuse_queries" (mi355dr_fuse_lists*, described there),
  *          "range_searches" / "range_queries" / "range_in_range" / "range_candidates" / "range_rescored" / "range_redo_chunks" /
  *          "range_fallback_queries" (mi355dr_search_range*, described there),
  *          "rows_searches" / "rows_queries" / "rows_skipped" (mi355dr_search_rows* and mi355dr_search_range_rows*, described there),
