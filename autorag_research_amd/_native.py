@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "mi355dr_merge_topk_packed_device", "mi355dr_comm_unique_id", "mi355dr_comm_init", "mi355dr_comm_world", "mi355dr_comm_count", "mi355dr_comm_init_custom",
     "mi355dr_search_sharded_device", "mi355dr_search_range_sharded_device", "mi355dr_search_rows_sharded_device",
     "mi355dr_search_range_rows_sharded_device", "mi355dr_search_mmr_sharded_device", "mi355dr_mmr_select_sharded",
+    "mi355dr_search_sparse_sharded_device", "mi355dr_search_bm25_sharded_device", "mi355dr_search_sparse_subset_sharded_device",
+    "mi355dr_search_bm25_subset_sharded_device", "mi355dr_score_sparse_subset_sharded", "mi355dr_score_bm25_subset_sharded",
     "mi355dr_set_option", "mi355dr_get_stat",
     "mi355dr_reset_stats", "mi355dr_timer_start", "mi355dr_timer_stop", "mi355dr_synchronize",
     "mi355dr_dev_alloc", "mi355dr_dev_free", "mi355dr_dev_upload", "mi355dr_dev_download",
@@ -270,6 +272,13 @@ def load() -> ctypes.CDLL:
     L.mi355dr_search_mmr_sharded_device.argtypes = [vp, vp, c_int, c_int, c_int, ctypes.c_double, vp, vp, vp]
     L.mi355dr_mmr_select_sharded.restype = c_int
     L.mi355dr_mmr_select_sharded.argtypes = [vp, f32p, c_int, c_int, i64p, c_int, ctypes.c_double, f64p, i64p]
+    # the row-sharded sparse forms: the argument lists of their local forms
+    for local in ("search_sparse_device", "search_bm25_device", "search_sparse_subset_device", "search_bm25_subset_device",
+                  "score_sparse_subset", "score_bm25_subset"):
+        sharded = local.replace("_device", "_sharded_device") if local.endswith("_device") else local + "_sharded"
+        fn = getattr(L, "mi355dr_" + sharded)
+        fn.restype = c_int
+        fn.argtypes = list(getattr(L, "mi355dr_" + local).argtypes)
     L.mi355dr_set_option.restype = c_int
     L.mi355dr_set_option.argtypes = [vp, ctypes.c_char_p, i64]
     L.mi355dr_get_stat.restype = c_int

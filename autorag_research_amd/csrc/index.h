@@ -426,6 +426,8 @@ struct mi355dr_index {
     int64_t s_rows_searches = 0, s_rows_queries = 0, s_rows_skipped = 0;
     // the row-sharded derived searches: calls per family, bytes this rank received through their all-gathers
     int64_t s_shard_range_searches = 0, s_shard_rows_searches = 0, s_shard_mmr_searches = 0, s_shard_gather_bytes = 0;
+    // the row-sharded sparse forms: calls of the four searches, calls of the two score forms (their gathers add to the above)
+    int64_t s_shard_sparse_searches = 0, s_shard_sparse_scores = 0;
     // mi355dr_search_sparse* / mi355dr_search_bm25*: calls, queries, postings accumulated by k_sparse_score, (query, launch)
     // candidate lists that overflowed and were run again in pieces
     int64_t s_sparse_searches = 0, s_sparse_queries = 0, s_sparse_postings_scored = 0, s_sparse_overflows = 0;
@@ -498,6 +500,12 @@ int64_t sparse_bytes(const mi355dr_index* idx);                  // mi355dr_spar
 enum { kSparseStatDocs, kSparseStatTotalLen, kSparseStatPostings, kSparseStatVocab, kSparseStatOverlayPostings, kSparseStatDeadPostings };
 int64_t sparse_stat(const mi355dr_index* idx, int which);        // mi355dr_sparse.hip: the store's own figures (0 without a store)
 int drain_searches(mi355dr_index* idx);                          // mi355dr.hip: blocks in flight finished (under the handle's mutex)
+// mi355dr.hip: mi355dr_merge_topk_packed_device for a caller that holds the handle's mutex -- the gathered packed blocks
+// [world][2][B][k] merged into [B, k] on `stream`.  merge_topk_reserve: the one allocation the merge may make (the per-search
+// state), for a caller that wants it made before its first collective
+int merge_topk_reserve(mi355dr_index* idx);
+int merge_topk_packed(mi355dr_index* idx, const int64_t* packed_all_dev, int world, int B, int k, double* out_dist_dev,
+                      int64_t* out_rows_dev, hipStream_t stream);
 void comm_destroy(mi355dr_index* idx);                           // mi355dr_comm.hip
 // one all-gather over the index's communicator (RCCL, or the host's transport): bytes_per_rank (a multiple of 8) from every
 // rank's send_dev into recv_dev, rank-major; ordered on `stream` (a host transport may instead be complete on return)

@@ -1127,6 +1127,13 @@ int rescore_host_pairs(mi355dr_index* idx, PairBufs& bufs, const float* queries,
 
 namespace mi355 {
 int drain_searches(mi355dr_index* idx) { return drain_pending(idx); }
+int merge_topk_reserve(mi355dr_index* idx) { return ensure_qstate(idx); }
+int merge_topk_packed(mi355dr_index* idx, const int64_t* packed_all_dev, int world, int B, int k, double* out_dist_dev,
+                      int64_t* out_rows_dev, hipStream_t stream) {
+    const int64_t plane = (int64_t)B * k;
+    return launch_merge(idx, (const double*)packed_all_dev, packed_all_dev + plane, 2 * plane, world, B, k, out_dist_dev, out_rows_dev,
+                        stream);
+}
 }  // namespace mi355
 
 extern "C" {
@@ -2885,8 +2892,7 @@ int mi355dr_merge_topk_packed_device(mi355dr_index* idx, const int64_t* packed_a
                                      double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
     if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
     std::lock_guard<std::mutex> g(idx->mu);
-    const int64_t plane = (int64_t)B * k;
-    return launch_merge(idx, (const double*)packed_all_dev, packed_all_dev + plane, 2 * plane, world, B, k, out_dist_dev, out_rows_dev, stream);
+    return merge_topk_packed(idx, packed_all_dev, world, B, k, out_dist_dev, out_rows_dev, (hipStream_t)stream);
 }
 
 // ---- options and stats: one table row each --------------------------------------------------------------------------------
@@ -3043,6 +3049,8 @@ const Stat kStats[] = {
     {"sharded_rows_searches", &Index::s_shard_rows_searches, true},
     {"sharded_mmr_searches", &Index::s_shard_mmr_searches, true},
     {"shard_gather_bytes", &Index::s_shard_gather_bytes, true},
+    {"sharded_sparse_searches", &Index::s_shard_sparse_searches, true},
+    {"sharded_sparse_scores", &Index::s_shard_sparse_scores, true},
     {"sparse_searches", &Index::s_sparse_searches, true},
     {"sparse_queries", &Index::s_sparse_queries, true},
     {"sparse_postings_scored", &Index::s_sparse_postings_scored, true},

@@ -10,9 +10,13 @@
 // document range in a few launches of growing size (k_sparse.h): the first cannot overflow a candidate list, every later one
 // appends only what beats the query's k-th kept entry.  Within a listed subset (the *_subset forms; sparse_subset.h) a long list
 // runs the same launches over the tiles that hold a listed document, filtered by a bitmap; a short one, and the score forms,
-// look every (query, document) pair up directly (k_sparse_pairs).
+// look every (query, document) pair up directly (k_sparse_pairs).  Over a row-sharded index (the *_sharded forms; sparse_shard.h,
+// k_sparse_shard.h) the same launches run with the statistics of ALL shards -- gathered and summed once
+// per call -- and a block's kept lists leave as a packed block for one all-gather and the world * k -> k merge.
 #include "index.h"
 #include "k_sparse.h"
+#include "k_sparse_shard.h"
+#include "sparse_shard.h"
 #include "sparse_subset.h"
 #include "subset_ids.h"
 
@@ -54,6 +58,7 @@ struct SparseStore {
     DevBuf<double> norm;
     bool norm_valid = false;
     double norm_k1 = 0.0, norm_b = 0.0;
+    uint64_t norm_avgdl = 0;        // the bits of the avgdl the norms were computed with: the store's own, or a sharded call's
     // one block's scratch
     DevBuf<int32_t> q_terms, q_off, best_doc, cand_doc;
     DevBuf<double> q_w, out_dist;
@@ -66,6 +71,8 @@ struct SparseStore {
     DevBuf<unsigned> sub_bits;
     DevBuf<int32_t> sub_tiles, sub_ids;
     DevBuf<double> pair_dist;
+    // a sharded call: this rank's payload of an all-gather, the gathered payloads of all ranks, the folded statistics row
+    DevBuf<int64_t> sh_send, sh_recv, sh_fold;
     bool lds_registered = false;
 };
 
@@ -78,7 +85,8 @@ int64_t sparse_bytes(const mi355dr_index* idx) {
     const SparseStore* s = idx->sp;
     return s ? (int64_t)(s->term_off.bytes + s->post_doc.bytes + s->post_tf.bytes + s->len_dev.bytes + s->norm.bytes +
                          s->ov_term_off.bytes + s->ov_post_doc.bytes + s->ov_post_tf.bytes + s->moved_dev.bytes +
-                         s->sub_bits.bytes + s->sub_tiles.bytes + s->sub_ids.bytes + s->pair_dist.bytes)
+                         s->sub_bits.bytes + s->sub_tiles.bytes + s->sub_ids.bytes + s->pair_dist.bytes + s->sh_send.bytes +
+                         s->sh_recv.bytes + s->sh_fold.bytes)
              : 0;
 }
 
@@ -284,9 +292,21 @@ int launch_score(mi355dr_index* idx, SparseStore* sp, hipStream_t s, const Spars
     return MI355DR_OK;
 }
 
-// the store of the handle (created when there is none), its device layout and the norms of (k1, b) brought up to date; *n: the
-// documents a search runs over (0 while no document has tokens)
-int sparse_ready(mi355dr_index* idx, double k1, double b, hipStream_t s, int64_t* n_out) {
+// the statistics a sharded call scores with in place of the store's own: the sums over every shard, passed down as a value
+struct SparseGlobal {
+    int64_t N;
+    double avgdl;  // (double)total_len / (double)N, both global
+};
+
+inline uint64_t double_bits(double x) {
+    uint64_t u;
+    memcpy(&u, &x, sizeof(u));
+    return u;
+}
+
+// the store of the handle (created when there is none), its device layout and the norms of (k1, b, avgdl) brought up to date --
+// avgdl is the store's own, or `glob`'s --; *n: the documents a search runs over (0 while no document has tokens)
+int sparse_ready(mi355dr_index* idx, double k1, double b, hipStream_t s, int64_t* n_out, const SparseGlobal* glob = nullptr) {
     if (!idx->sp) {
         idx->sp = new (std::nothrow) SparseStore();
         if (!idx->sp) return fail(idx, MI355DR_E_NOMEM, "sparse store: host memory");
@@ -305,14 +325,15 @@ int sparse_ready(mi355dr_index* idx, double k1, double b, hipStream_t s, int64_t
                                           (int)sparse_score_lds_filtered(kSparseTileMax, true, kSparseTermsMax)));
         sp->lds_registered = true;
     }
-    if (n > 0 && !(sp->norm_valid && sp->norm_k1 == k1 && sp->norm_b == b)) {
-        const double avgdl = (double)sp->total_len / (double)sp->n_live;
+    const double avgdl = glob ? glob->avgdl : (double)sp->total_len / (double)sp->n_live;
+    if (n > 0 && !(sp->norm_valid && sp->norm_k1 == k1 && sp->norm_b == b && sp->norm_avgdl == double_bits(avgdl))) {
         hipLaunchKernelGGL(k_sparse_norms, dim3((unsigned)((n + kSparseThreads - 1) / kSparseThreads)), dim3(kSparseThreads), 0, s,
                            sp->len_dev.p, n, avgdl, k1, b, sp->norm.p);
         HIPCHECK(idx, hipGetLastError());
         sp->norm_valid = true;
         sp->norm_k1 = k1;
         sp->norm_b = b;
+        sp->norm_avgdl = double_bits(avgdl);
     }
     *n_out = n;
     return MI355DR_OK;
@@ -341,6 +362,67 @@ int sparse_put_queries(mi355dr_index* idx, SparseStore* sp, const std::vector<in
     return MI355DR_OK;
 }
 
+// ---- the sharded forms' collectives (one at a time, in stream order; every rank enters each of them) -------------------------
+// the send / receive buffers for a payload of `words` int64 per rank (before the collective they serve)
+int sparse_shard_reserve(mi355dr_index* idx, SparseStore* sp, size_t words) {
+    HIPCHECK(idx, grow_each(std::max<size_t>(words, 1), sp->sh_send));
+    HIPCHECK(idx, grow_each(std::max<size_t>(words, 1) * (size_t)idx->comm_world, sp->sh_recv));
+    return MI355DR_OK;
+}
+
+// one all-gather: the payload final and visible first (a host transport reads it with copies of its own), a transport error
+// returned after the stream is drained
+int sparse_gather(mi355dr_index* idx, SparseStore* sp, hipStream_t s, size_t words) {
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    const int rc = comm_all_gather(idx, sp->sh_send.p, sp->sh_recv.p, words * sizeof(int64_t), s);
+    if (rc != MI355DR_OK) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    idx->s_shard_gather_bytes += (int64_t)idx->comm_world * (int64_t)(words * sizeof(int64_t));
+    return MI355DR_OK;
+}
+
+// a block's kept lists as this rank's packed [2, nb, k] block, one all-gather, the world * k -> k merge into od / orow [nb, k]
+int sparse_shard_block(mi355dr_index* idx, SparseStore* sp, hipStream_t s, int nb, int k, double* od, int64_t* orow) {
+    const int64_t n_best = (int64_t)nb * k;
+    hipLaunchKernelGGL(k_sparse_final_packed, dim3((unsigned)((n_best + kSparseThreads - 1) / kSparseThreads)), dim3(kSparseThreads), 0, s,
+                       sp->best_key.p, sp->best_doc.p, n_best, idx->row_offset, sp->sh_send.p);
+    HIPCHECK(idx, hipGetLastError());
+    CHECK(sparse_gather(idx, sp, s, (size_t)(2 * n_best)));
+    return merge_topk_packed(idx, sp->sh_recv.p, idx->comm_world, nb, k, od, orow, s);
+}
+
+// The statistics of a call: this rank's [2 + T] payload (n_live, total_len, df of `terms`) uploaded, gathered, summed on the
+// device by k_sparse_stats_fold and downloaded into `folded` -- the same integers on every rank.  Creates the store when the
+// handle has none (a rank that never added a document still enters the collective).
+int sparse_shard_stats(mi355dr_index* idx, hipStream_t s, const std::vector<int32_t>& terms, std::vector<int64_t>& folded) {
+    if (!idx->sp) {
+        idx->sp = new (std::nothrow) SparseStore();
+        if (!idx->sp) return fail(idx, MI355DR_E_NOMEM, "sparse store: host memory");
+    }
+    SparseStore* sp = idx->sp;
+    std::vector<int64_t> payload;
+    try {
+        shard_stats_payload(sp->n_live, sp->total_len, terms,
+                            [&](int32_t t) -> int64_t { return (int64_t)t < sp->vocab ? sp->df[(size_t)t] : 0; }, payload);
+        folded.resize(payload.size());
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, "sharded sparse search: host memory for the statistics");
+    }
+    const size_t words = payload.size();
+    CHECK(sparse_shard_reserve(idx, sp, words));
+    HIPCHECK(idx, grow_each(words, sp->sh_fold));
+    HIPCHECK(idx, hipMemcpyAsync(sp->sh_send.p, payload.data(), words * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    CHECK(sparse_gather(idx, sp, s, words));
+    hipLaunchKernelGGL(k_sparse_stats_fold, dim3((unsigned)((words + kSparseThreads - 1) / kSparseThreads)), dim3(kSparseThreads), 0, s,
+                       (const int64_t*)sp->sh_recv.p, (int64_t)words, idx->comm_world, sp->sh_fold.p);
+    HIPCHECK(idx, hipGetLastError());
+    HIPCHECK(idx, hipMemcpyAsync(folded.data(), sp->sh_fold.p, words * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    return MI355DR_OK;
+}
+
 // the lists of a call within a listed subset
 struct SparseSubsetArg {
     const int64_t* doc_ids;  // HOST, global ids
@@ -350,16 +432,19 @@ struct SparseSubsetArg {
 // Queries [0, B) as flat host arrays -- every query's terms ascending, distinct, inside [0, 2^20), at most kSparseTermsMax --
 // against the store; results to `out` ([B, k], host or device).  The handle's mutex is held.  `sub`: null, or the list the
 // search is restricted to -- its local documents run through k_sparse_pairs when they are at most "sparse_subset_pairs_max",
-// else through the launches of sparse_plan_subset with a tile list each.
+// else through the launches of sparse_plan_subset with a tile list each.  `glob`: null, or the call is a sharded one (device
+// results; the weights were computed from `glob`, the norms are) -- a block's kept lists then leave through sparse_shard_block
+// in place of k_sparse_final, and the call counts as a sharded one.
 int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, const std::vector<double>& weights,
                          const std::vector<int32_t>& offsets, int B, int k, double k1, double b, SparseOut out, hipStream_t s,
-                         const SparseSubsetArg* sub = nullptr) {
-    if (sub) idx->s_sparse_subset_searches++;
+                         const SparseSubsetArg* sub = nullptr, const SparseGlobal* glob = nullptr) {
+    if (glob) idx->s_shard_sparse_searches++;
+    else if (sub) idx->s_sparse_subset_searches++;
     else idx->s_sparse_searches++;
     idx->s_sparse_queries += B;
     if (B == 0) return MI355DR_OK;
     int64_t n = 0;
-    CHECK(sparse_ready(idx, k1, b, s, &n));
+    CHECK(sparse_ready(idx, k1, b, s, &n, glob));
     SparseStore* sp = idx->sp;
     const int cap = idx->sparse_cand_cap;
     std::vector<int32_t> listed;  // the list's local documents, ascending, each once
@@ -396,6 +481,7 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
     HIPCHECK(idx, grow_each((size_t)nb_max * (std::max(n_chunks, 1) + 1), sp->flags, sp->qlist));
     HIPCHECK(idx, grow_each(1, sp->scored));
     if (out.host) HIPCHECK(idx, grow_each((size_t)nb_max * k, sp->out_dist, sp->out_rows));
+    if (glob) CHECK(sparse_shard_reserve(idx, sp, (size_t)2 * nb_max * k));
     HIPCHECK(idx, hipMemsetAsync(sp->scored.p, 0, sizeof(unsigned long long), s));
     // (the list's device forms stay as they are for every block of the call; the host vectors until the first block's wait)
     if (pairs) HIPCHECK(idx, hipMemcpyAsync(sp->sub_ids.p, listed.data(), listed.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -464,6 +550,11 @@ int sparse_search_sorted(mi355dr_index* idx, const std::vector<int32_t>& terms, 
                         if (flags_host[q]) return fail(idx, MI355DR_E_INTERNAL, "sparse search: a piece of at most cap documents overflowed");
                 }
             }
+        }
+        if (glob) {
+            CHECK(sparse_shard_block(idx, sp, s, nb, k, out.dist + (int64_t)b0 * k, out.rows + (int64_t)b0 * k));
+            HIPCHECK(idx, hipStreamSynchronize(s));  // (the next block reuses the lists and the payload buffers)
+            continue;
         }
         double* od = out.host ? sp->out_dist.p : out.dist + (int64_t)b0 * k;
         int64_t* orow = out.host ? sp->out_rows.p : out.rows + (int64_t)b0 * k;
@@ -595,26 +686,27 @@ int search_impl(mi355dr_index* idx, bool bm25, const int32_t* q_terms, const dou
 
 constexpr int64_t kPairsLaunchMax = (int64_t)1 << 22;  // (query, document) pairs of one k_sparse_pairs launch of the score forms
 
-// mi355dr_score_sparse_subset / mi355dr_score_bm25_subset: every query against its own row of doc_ids, through k_sparse_pairs in
-// launches of whole rows (or, for a row longer than a launch, parts of one row) staged in buffers of at most kPairsLaunchMax
-int score_impl(mi355dr_index* idx, bool bm25, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B,
-               double k1, double b, const int64_t* doc_ids, int m, double* out_dist) {
-    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
-    std::unique_lock<std::mutex> lock;
-    hipStream_t s = nullptr;
-    CHECK(sparse_begin(idx, lock, nullptr, &s));
-    CHECK(check_common(idx, q_offsets, B, 1, k1, b, idx, idx));  // (no k and no result lists here: the buffers are checked below)
+// the checks of both score forms, local and sharded (no k and no result lists here)
+int check_score(mi355dr_index* idx, const int32_t* q_offsets, int B, double k1, double b, const int64_t* doc_ids, int m,
+                const double* out_dist) {
+    CHECK(check_common(idx, q_offsets, B, 1, k1, b, idx, idx));
     if (m < 0) return fail(idx, MI355DR_E_INVALID, "sparse scores: m must be >= 0");
     if (B > 0 && m > 0 && (!doc_ids || !out_dist)) return fail(idx, MI355DR_E_INVALID, "sparse scores: null buffer");
     if ((int64_t)B * m > INT32_MAX) return fail(idx, MI355DR_E_UNSUPPORTED, "sparse scores: B * m must be below 2^31");
-    SortedQueries q;
-    CHECK(bm25 ? bm25_queries(idx, q_terms, q_offsets, B, &q) : weighted_queries(idx, q_terms, q_weights, q_offsets, B, &q));
-    idx->s_sparse_subset_scores++;
-    if (B == 0 || m == 0) return MI355DR_OK;
+    return MI355DR_OK;
+}
+
+// Queries [0, B) as sparse_search_sorted takes them, B > 0, each against its own row of doc_ids [B, m > 0], through
+// k_sparse_pairs in launches of whole rows (or, for a row longer than a launch, parts of one row) staged in buffers of at most
+// kPairsLaunchMax.  `glob`: null, or the call is a sharded one -- every launch's distances (NaN where this shard does not hold
+// the document; all NaN from a shard without documents) are gathered and folded by k_sparse_fold_scores to the owner's value.
+// The launches depend on B and m alone, so every rank enters the same collectives.
+int sparse_score_sorted(mi355dr_index* idx, const SortedQueries& q, int B, double k1, double b, const int64_t* doc_ids, int m,
+                        double* out_dist, hipStream_t s, const SparseGlobal* glob = nullptr) {
     int64_t n = 0;
-    CHECK(sparse_ready(idx, k1, b, s, &n));
+    CHECK(sparse_ready(idx, k1, b, s, &n, glob));
     SparseStore* sp = idx->sp;
-    if (n == 0) {  // no document matches anything
+    if (glob ? glob->N == 0 : n == 0) {  // no document matches anything (the global N is the same on every rank)
         std::fill(out_dist, out_dist + (int64_t)B * m, std::nan(""));
         return MI355DR_OK;
     }
@@ -628,6 +720,7 @@ int score_impl(mi355dr_index* idx, bool bm25, const int32_t* q_terms, const doub
         return fail(idx, MI355DR_E_NOMEM, "sparse scores: host memory");
     }
     HIPCHECK(idx, grow_each(ids_host.size(), sp->sub_ids, sp->pair_dist));
+    if (glob) CHECK(sparse_shard_reserve(idx, sp, ids_host.size()));
     HIPCHECK(idx, grow_each((size_t)nb_max + 1, sp->q_off));
     HIPCHECK(idx, grow_each(1, sp->scored));
     HIPCHECK(idx, hipMemsetAsync(sp->scored.p, 0, sizeof(unsigned long long), s));
@@ -651,11 +744,18 @@ int score_impl(mi355dr_index* idx, bool bm25, const int32_t* q_terms, const doub
                 }
                 const size_t n_pairs = (size_t)(nq * mm);
                 HIPCHECK(idx, hipMemcpyAsync(sp->sub_ids.p, ids_host.data(), n_pairs * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                const SparsePairs pr{sp->sub_ids.p, mm, mm, sp->pair_dist.p, q0, sp->ov_active ? 1 : 0};
+                const SparsePairs pr{sp->sub_ids.p, mm, mm, glob ? (double*)sp->sh_send.p : sp->pair_dist.p, q0, sp->ov_active ? 1 : 0};
                 hipLaunchKernelGGL(k_sparse_pairs, dim3((unsigned)((mm + kSparseThreads - 1) / kSparseThreads), (unsigned)nq),
                                    dim3(kSparseThreads), 0, s, view, ov, qs, no_lists, pr, k1p1, sp->scored.p);
                 HIPCHECK(idx, hipGetLastError());
                 idx->s_sparse_subset_pairs += (int64_t)n_pairs;
+                if (glob) {
+                    CHECK(sparse_gather(idx, sp, s, n_pairs));
+                    hipLaunchKernelGGL(k_sparse_fold_scores, dim3((unsigned)((n_pairs + kSparseThreads - 1) / kSparseThreads)),
+                                       dim3(kSparseThreads), 0, s, (const int64_t*)sp->sh_recv.p, (int64_t)n_pairs, idx->comm_world,
+                                       (int64_t*)sp->pair_dist.p);
+                    HIPCHECK(idx, hipGetLastError());
+                }
                 // (rows of the launch are whole, or it is part of one row: contiguous in out_dist either way)
                 HIPCHECK(idx, hipMemcpyAsync(out_dist + (int64_t)(b0 + q0) * m + j0, sp->pair_dist.p, n_pairs * sizeof(double),
                                              hipMemcpyDeviceToHost, s));
@@ -667,6 +767,120 @@ int score_impl(mi355dr_index* idx, bool bm25, const int32_t* q_terms, const doub
     HIPCHECK(idx, hipMemcpy(&scored, sp->scored.p, sizeof(scored), hipMemcpyDeviceToHost));
     idx->s_sparse_postings_scored += (int64_t)scored;
     return MI355DR_OK;
+}
+
+// mi355dr_score_sparse_subset / mi355dr_score_bm25_subset
+int score_impl(mi355dr_index* idx, bool bm25, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets, int B,
+               double k1, double b, const int64_t* doc_ids, int m, double* out_dist) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s = nullptr;
+    CHECK(sparse_begin(idx, lock, nullptr, &s));
+    CHECK(check_score(idx, q_offsets, B, k1, b, doc_ids, m, out_dist));
+    SortedQueries q;
+    CHECK(bm25 ? bm25_queries(idx, q_terms, q_offsets, B, &q) : weighted_queries(idx, q_terms, q_weights, q_offsets, B, &q));
+    idx->s_sparse_subset_scores++;
+    if (B == 0 || m == 0) return MI355DR_OK;
+    return sparse_score_sorted(idx, q, B, k1, b, doc_ids, m, out_dist, s);
+}
+
+// ---- the six sharded forms (include/mi355dr.h, "row-sharded sparse search") -------------------------------------------------
+// What every sharded form starts with, behind the lock: a view refuses, no communicator, then -- after the local form's own
+// argument checks, run by `args_ok` -- the merge's sort limit.  Nothing has been touched and no collective entered when one
+// fails, and each depends on the arguments and `world` alone.  Behind them the merge's own state is allocated, so that a
+// failed allocation, too, comes before the first collective.
+template <class ArgCheck>
+int sparse_shard_begin(mi355dr_index* idx, const char* what, int width, ArgCheck&& args_ok) {
+    if (idx->is_view) return view_refuses(idx, what, /*ask_parent=*/true);
+    if (!idx->comm && !idx->comm_custom)
+        return fail(idx, MI355DR_E_INVALID, std::string(what) + ": mi355dr_comm_init has not been called on this index");
+    CHECK(args_ok());
+    if ((int64_t)idx->comm_world * width > kSortMax)
+        return fail(idx, MI355DR_E_UNSUPPORTED, std::string(what) + ": world*k exceeds 4096");
+    return merge_topk_reserve(idx);  // (what the merge allocates on a handle's first call: ahead of the first collective)
+}
+
+// The queries of a sharded call, before its first collective: the weighted forms' queries checked and sorted into `q`; the BM25
+// forms' raw tokens checked and their distinct in-range terms collected in `uni` (sparse_shard.h).
+int sparse_shard_check_queries(mi355dr_index* idx, bool bm25, const int32_t* q_terms, const double* q_weights,
+                               const int32_t* q_offsets, int B, SortedQueries* q, std::vector<int32_t>& uni) {
+    if (bm25) {
+        for (int i = 0; i < B; ++i)
+            if (q_offsets[i + 1] > q_offsets[i] && !q_terms) return fail(idx, MI355DR_E_INVALID, "bm25 search: null query");
+        try {
+            if (shard_query_terms(q_terms, q_offsets, B, kTermLimit, kSparseTermsMax, uni) >= 0)
+                return fail(idx, MI355DR_E_UNSUPPORTED, "bm25 search: more than 1024 distinct terms in one query");
+        } catch (const std::bad_alloc&) {
+            return fail(idx, MI355DR_E_NOMEM, "bm25 search: host memory");
+        }
+        return MI355DR_OK;
+    }
+    return weighted_queries(idx, q_terms, q_weights, q_offsets, B, q);
+}
+
+// ... and the statistics they are scored with: ONE gather -- also for a call without any term --, and for BM25 the weights
+// from the global N and df.
+int sparse_shard_queries(mi355dr_index* idx, bool bm25, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets,
+                         int B, hipStream_t s, SortedQueries* q, SparseGlobal* glob) {
+    std::vector<int32_t> uni;
+    std::vector<int64_t> folded;
+    CHECK(sparse_shard_check_queries(idx, bm25, q_terms, q_weights, q_offsets, B, q, uni));
+    CHECK(sparse_shard_stats(idx, s, uni, folded));
+    glob->N = folded[0];
+    glob->avgdl = (double)folded[1] / (double)folded[0];
+    if (bm25) {
+        try {
+            shard_split_weights(q_terms, q_offsets, B, uni, folded.data(), q->terms, q->weights, q->offsets);
+        } catch (const std::bad_alloc&) {
+            return fail(idx, MI355DR_E_NOMEM, "bm25 search: host memory");
+        }
+    }
+    return MI355DR_OK;
+}
+
+int search_sharded_impl(mi355dr_index* idx, const char* what, bool bm25, const int32_t* q_terms, const double* q_weights,
+                        const int32_t* q_offsets, int B, int k, double k1, double b, double* out_dist_dev, int64_t* out_rows_dev,
+                        void* stream, const SparseSubsetArg* sub = nullptr) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s = nullptr;
+    CHECK(sparse_begin(idx, lock, stream, &s));
+    CHECK(sparse_shard_begin(idx, what, k, [&]() -> int {
+        CHECK(check_common(idx, q_offsets, B, k, k1, b, out_dist_dev, out_rows_dev));
+        if (sub && (sub->m < 0 || (sub->m > 0 && !sub->doc_ids)))
+            return fail(idx, MI355DR_E_INVALID, "sparse search within a subset: m must be >= 0 and doc_ids not null");
+        return MI355DR_OK;
+    }));
+    SortedQueries q;
+    SparseGlobal glob{0, 0.0};
+    if (B == 0) {  // (no collective: every rank passes the same B)
+        idx->s_shard_sparse_searches++;
+        return MI355DR_OK;
+    }
+    CHECK(sparse_shard_queries(idx, bm25, q_terms, q_weights, q_offsets, B, s, &q, &glob));
+    return sparse_search_sorted(idx, q.terms, q.weights, q.offsets, B, k, k1, b, SparseOut{out_dist_dev, out_rows_dev, false}, s, sub,
+                                &glob);
+}
+
+int score_sharded_impl(mi355dr_index* idx, const char* what, bool bm25, const int32_t* q_terms, const double* q_weights,
+                       const int32_t* q_offsets, int B, double k1, double b, const int64_t* doc_ids, int m, double* out_dist) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s = nullptr;
+    CHECK(sparse_begin(idx, lock, nullptr, &s));
+    CHECK(sparse_shard_begin(idx, what, 1, [&]() -> int { return check_score(idx, q_offsets, B, k1, b, doc_ids, m, out_dist); }));
+    if (B == 0 || m == 0) {  // (a no-op like the local form's, on every rank: the queries are still checked)
+        SortedQueries unused;
+        std::vector<int32_t> uni;
+        CHECK(sparse_shard_check_queries(idx, bm25, q_terms, q_weights, q_offsets, B, &unused, uni));
+        idx->s_shard_sparse_scores++;
+        return MI355DR_OK;
+    }
+    SortedQueries q;
+    SparseGlobal glob{0, 0.0};
+    CHECK(sparse_shard_queries(idx, bm25, q_terms, q_weights, q_offsets, B, s, &q, &glob));
+    idx->s_shard_sparse_scores++;
+    return sparse_score_sorted(idx, q, B, k1, b, doc_ids, m, out_dist, s, &glob);
 }
 
 // documents [0, n) of a call as terms[offsets[j] .. offsets[j + 1]); offsets null: n documents without tokens
@@ -903,6 +1117,39 @@ int mi355dr_score_sparse_subset(mi355dr_index* idx, const int32_t* q_terms, cons
 int mi355dr_score_bm25_subset(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, double k1, double b,
                               const int64_t* doc_ids, int m, double* out_dist) {
     return score_impl(idx, true, q_tokens, nullptr, q_offsets, B, k1, b, doc_ids, m, out_dist);
+}
+
+int mi355dr_search_sparse_sharded_device(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets,
+                                         int B, int k, double k1, double b, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
+    return search_sharded_impl(idx, "search_sparse_sharded_device", false, q_terms, q_weights, q_offsets, B, k, k1, b, out_dist_dev,
+                               out_rows_dev, stream);
+}
+int mi355dr_search_bm25_sharded_device(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1,
+                                       double b, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
+    return search_sharded_impl(idx, "search_bm25_sharded_device", true, q_tokens, nullptr, q_offsets, B, k, k1, b, out_dist_dev,
+                               out_rows_dev, stream);
+}
+int mi355dr_search_sparse_subset_sharded_device(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights,
+                                                const int32_t* q_offsets, int B, int k, double k1, double b, const int64_t* doc_ids,
+                                                int64_t m, double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
+    const SparseSubsetArg sub{doc_ids, m};
+    return search_sharded_impl(idx, "search_sparse_subset_sharded_device", false, q_terms, q_weights, q_offsets, B, k, k1, b,
+                               out_dist_dev, out_rows_dev, stream, &sub);
+}
+int mi355dr_search_bm25_subset_sharded_device(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k,
+                                              double k1, double b, const int64_t* doc_ids, int64_t m, double* out_dist_dev,
+                                              int64_t* out_rows_dev, void* stream) {
+    const SparseSubsetArg sub{doc_ids, m};
+    return search_sharded_impl(idx, "search_bm25_subset_sharded_device", true, q_tokens, nullptr, q_offsets, B, k, k1, b, out_dist_dev,
+                               out_rows_dev, stream, &sub);
+}
+int mi355dr_score_sparse_subset_sharded(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets,
+                                        int B, double k1, double b, const int64_t* doc_ids, int m, double* out_dist) {
+    return score_sharded_impl(idx, "score_sparse_subset_sharded", false, q_terms, q_weights, q_offsets, B, k1, b, doc_ids, m, out_dist);
+}
+int mi355dr_score_bm25_subset_sharded(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, double k1, double b,
+                                      const int64_t* doc_ids, int m, double* out_dist) {
+    return score_sharded_impl(idx, "score_bm25_subset_sharded", true, q_tokens, nullptr, q_offsets, B, k1, b, doc_ids, m, out_dist);
 }
 
 }  // extern "C"

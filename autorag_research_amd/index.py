@@ -884,6 +884,101 @@ class Mi355Index:
                                                            ptr(out, ctypes.c_double)))
         return out
 
+    # over a row-sharded store (include/mi355dr.h "row-sharded sparse search"): this handle holds a contiguous run of the
+    # documents with `row_offset` at its first one's global id, and a communicator.  Every rank passes the same arguments and
+    # receives what ONE handle holding all shards' documents returns from the local method of the same name; N, avgdl and df
+    # are gathered on every call.  The arguments are those of the local methods
+    def _sparse_queries(self, bm25: bool, terms, weights, offsets) -> tuple[tuple, int, tuple]:
+        """The query arguments of a weighted (terms, weights, offsets) or BM25 (token lists, offsets or None) call, B, and the
+        arrays the pointers point into (the caller keeps them until the call has returned)."""
+        t, off = self._ragged_i32(terms, offsets, np.int32)
+        B = off.shape[0] - 1
+        if bm25:
+            return (ptr(t, ctypes.c_int32), ptr(off, ctypes.c_int32), B), B, (t, off)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != t.shape[0]:
+            raise ValueError("weights must have one entry per term")
+        return (ptr(t, ctypes.c_int32), ptr(w, ctypes.c_double), ptr(off, ctypes.c_int32), B), B, (t, w, off)
+
+    def _sparse_sharded_device(self, name: str, bm25: bool, terms, weights, offsets, k: int, k1: float, b: float, doc_ids,
+                               out_dist_ptr: int, out_ids_ptr: int, stream) -> None:
+        q, _B, _keep = self._sparse_queries(bm25, terms, weights, offsets)
+        tail = ()
+        if doc_ids is not None:
+            ids = self._sparse_ids(doc_ids)
+            tail = (ptr(ids, ctypes.c_int64), ids.shape[0])
+        check(self._h, getattr(self._lib, name)(self._h, *q, int(k), float(k1), float(b), *tail, ctypes.c_void_p(int(out_dist_ptr)),
+                                                ctypes.c_void_p(int(out_ids_ptr)), _stream_arg(stream)))
+
+    def search_sparse_sharded_device(self, terms, weights, offsets, k: int, out_dist_ptr: int, out_ids_ptr: int, k1: float = 1.2,
+                                     b: float = 0.75, stream: int | None = None) -> None:
+        """`search_sparse` over the shards into device buffers of the caller (float64 / int64 [B, k]); complete on return."""
+        self._sparse_sharded_device("mi355dr_search_sparse_sharded_device", False, terms, weights, offsets, k, k1, b, None,
+                                    out_dist_ptr, out_ids_ptr, stream)
+
+    def search_bm25_sharded_device(self, token_lists, k: int, out_dist_ptr: int, out_ids_ptr: int, k1: float = 1.2,
+                                   b: float = 0.75, offsets=None, stream: int | None = None) -> None:
+        """`search_bm25_device` over the shards: the idf weights come from the N and df of ALL shards."""
+        self._sparse_sharded_device("mi355dr_search_bm25_sharded_device", True, token_lists, None, offsets, k, k1, b, None,
+                                    out_dist_ptr, out_ids_ptr, stream)
+
+    def search_sparse_subset_sharded_device(self, terms, weights, offsets, k: int, doc_ids, out_dist_ptr: int, out_ids_ptr: int,
+                                            k1: float = 1.2, b: float = 0.75, stream: int | None = None) -> None:
+        """`search_sparse_subset` over the shards into device buffers; doc_ids are global ids, the same list on every rank."""
+        self._sparse_sharded_device("mi355dr_search_sparse_subset_sharded_device", False, terms, weights, offsets, k, k1, b,
+                                    doc_ids, out_dist_ptr, out_ids_ptr, stream)
+
+    def search_bm25_subset_sharded_device(self, token_lists, k: int, doc_ids, out_dist_ptr: int, out_ids_ptr: int,
+                                          k1: float = 1.2, b: float = 0.75, offsets=None, stream: int | None = None) -> None:
+        """`search_bm25_subset` over the shards into device buffers."""
+        self._sparse_sharded_device("mi355dr_search_bm25_subset_sharded_device", True, token_lists, None, offsets, k, k1, b,
+                                    doc_ids, out_dist_ptr, out_ids_ptr, stream)
+
+    def _sparse_sharded(self, device_method, B: int, k: int) -> tuple[np.ndarray, np.ndarray]:
+        return self._device_results(B, max(int(k), 0), False, lambda d, r, _c: device_method(d, r))
+
+    def search_sparse_sharded(self, terms, weights, offsets, k: int, k1: float = 1.2,
+                              b: float = 0.75) -> tuple[np.ndarray, np.ndarray]:
+        """`search_sparse` over the shards: (distance float64 [B, k], global ids int64 [B, k]), the same on every rank."""
+        B = self._ragged_i32(terms, offsets, np.int32)[1].shape[0] - 1
+        return self._sparse_sharded(lambda d, r: self.search_sparse_sharded_device(terms, weights, offsets, k, d, r, k1, b), B, k)
+
+    def search_bm25_sharded(self, token_lists, k: int, k1: float = 1.2, b: float = 0.75,
+                            offsets=None) -> tuple[np.ndarray, np.ndarray]:
+        """`search_bm25` over the shards."""
+        B = self._ragged_i32(token_lists, offsets, np.int32)[1].shape[0] - 1
+        return self._sparse_sharded(lambda d, r: self.search_bm25_sharded_device(token_lists, k, d, r, k1, b, offsets), B, k)
+
+    def search_sparse_subset_sharded(self, terms, weights, offsets, k: int, doc_ids, k1: float = 1.2,
+                                     b: float = 0.75) -> tuple[np.ndarray, np.ndarray]:
+        """`search_sparse_subset` over the shards."""
+        B = self._ragged_i32(terms, offsets, np.int32)[1].shape[0] - 1
+        return self._sparse_sharded(
+            lambda d, r: self.search_sparse_subset_sharded_device(terms, weights, offsets, k, doc_ids, d, r, k1, b), B, k)
+
+    def search_bm25_subset_sharded(self, token_lists, k: int, doc_ids, k1: float = 1.2, b: float = 0.75,
+                                   offsets=None) -> tuple[np.ndarray, np.ndarray]:
+        """`search_bm25_subset` over the shards."""
+        B = self._ragged_i32(token_lists, offsets, np.int32)[1].shape[0] - 1
+        return self._sparse_sharded(
+            lambda d, r: self.search_bm25_subset_sharded_device(token_lists, k, doc_ids, d, r, k1, b, offsets), B, k)
+
+    def _score_sharded(self, name: str, bm25: bool, terms, weights, offsets, doc_ids, k1: float, b: float) -> np.ndarray:
+        q, B, _keep = self._sparse_queries(bm25, terms, weights, offsets)
+        ids = self._sparse_pool(doc_ids, B)
+        out = np.empty(ids.shape, dtype=np.float64)
+        check(self._h, getattr(self._lib, name)(self._h, *q, float(k1), float(b), ptr(ids, ctypes.c_int64), ids.shape[1],
+                                                ptr(out, ctypes.c_double)))
+        return out
+
+    def score_sparse_subset_sharded(self, terms, weights, offsets, doc_ids, k1: float = 1.2, b: float = 0.75) -> np.ndarray:
+        """`score_sparse_subset` over the shards: each position holds its owner's value, NaN where no rank matches it."""
+        return self._score_sharded("mi355dr_score_sparse_subset_sharded", False, terms, weights, offsets, doc_ids, k1, b)
+
+    def score_bm25_subset_sharded(self, token_lists, doc_ids, k1: float = 1.2, b: float = 0.75, offsets=None) -> np.ndarray:
+        """`score_bm25_subset` over the shards, under the BM25 weights of all shards' documents."""
+        return self._score_sharded("mi355dr_score_bm25_subset_sharded", True, token_lists, None, offsets, doc_ids, k1, b)
+
     # ---- multi-vector ----
     def add_multivec(self, vecs, offsets) -> None:
         vecs = f32c(vecs)

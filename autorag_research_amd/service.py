@@ -232,6 +232,10 @@ class _UnitIndex:
         # sharded, and brought up to the table's contents when they are no longer what it was built from (`ensure_sparse`)
         self.sparse: Mi355Index | None = None
         self._sparse_of: tuple[Any, list] | None = None    # (tokenizer key, the contents list it was built from)
+        # ... unless the service was asked to shard it (`shard_sparse=True` under a _World): this rank's contiguous slice of the
+        # positions behind a ShardedSearcher, global document id = table position all the same (`sparse_searcher`)
+        self.sparse_sharded: Any | None = None
+        self._sparse_sharded_of: tuple[Any, list] | None = None
         # device-side page buffers of the legs that leave their lists in HBM, and the device copy of `single_rows` they hand
         # the fusion as its map (`single_rows_device`; dropped with the other maps in _forget_maps)
         self.scratch = _DevScratch()
@@ -340,6 +344,44 @@ class _UnitIndex:
         self.sparse, self._sparse_of = ix, (key, contents)
         return ix
 
+    def sparse_searcher(self, tokenizer: Any, world: "_World") -> Any:
+        """`ensure_sparse` under a world, row-sharded: a ShardedSearcher over this rank's `shard_bounds` slice of the table
+        positions (`row_offset` = the slice's start, the library communicator on `world.group`).  Its `search_bm25`,
+        `search_bm25_subset` and `score_bm25_subset` take what the index's methods take and answer with the statistics of ALL
+        ranks' documents.  Every rank sees the same table, so every rank takes the same branch: an equal-length table with
+        changed cells is applied as `set_local_sparse` on the owners (the others have nothing to do, and the next search gathers
+        the statistics anew); another length or another tokenizer rebuilds the store."""
+        from .bm25 import get_tokenizer, tokenizer_key  # noqa: PLC0415
+        from .sharded import ShardedSearcher, shard_bounds  # noqa: PLC0415
+
+        key, contents = tokenizer_key(tokenizer), self.table.contents
+        have, of = self.sparse_sharded, self._sparse_sharded_of
+        if have is not None and of is not None and of[0] == key:
+            if of[1] is contents:
+                return have
+            if of[1] == contents:
+                self._sparse_sharded_of = (key, contents)
+                return have
+        tok = get_tokenizer(tokenizer)
+
+        def tokens(c):
+            return [] if c is None else tok(c if isinstance(c, str) else bytes(c).decode("utf-8", "replace"))
+
+        lo, hi = shard_bounds(len(contents), world.size, world.rank)
+        if have is not None and of is not None and of[0] == key and len(of[1]) == len(contents):
+            changed = [i for i in range(lo, hi) if of[1][i] != contents[i]]
+            if changed:
+                have.set_local_sparse(changed, [tokens(contents[i]) for i in changed])
+            self._sparse_sharded_of = (key, contents)
+            return have
+        if have is not None:
+            have.close()
+            self.sparse_sharded = None
+        s = ShardedSearcher(8, "cosine", self.device, index_factory=Mi355Index, group=world.group)  # (the dense side stays empty)
+        s.add_local_sparse([tokens(c) for c in contents[lo:hi]], lo)
+        self.sparse_sharded, self._sparse_sharded_of = s, (key, contents)
+        return s
+
     def _any_handle(self) -> Mi355Index | None:
         return next((ix for ix in (self.single, self.sparse, self.multi) if ix is not None), None)
 
@@ -358,11 +400,11 @@ class _UnitIndex:
     def close(self) -> None:
         self.scratch.release(self._any_handle())
         self._single_rows_dev = None
-        for ix in (self.single, self.multi, self.single_sharded, self.multi_sharded, self.sparse):
+        for ix in (self.single, self.multi, self.single_sharded, self.multi_sharded, self.sparse, self.sparse_sharded):
             if ix is not None:
                 ix.close()
-        self.single = self.multi = self.single_sharded = self.multi_sharded = self.sparse = None
-        self._sparse_of = None
+        self.single = self.multi = self.single_sharded = self.multi_sharded = self.sparse = self.sparse_sharded = None
+        self._sparse_of = self._sparse_sharded_of = None
         self._start_over(self.table)
 
     # ---- primary key -> table position -> index row (the GQR pools and the candidate scorer name chunks by key) ----
@@ -620,8 +662,12 @@ class Mi355RetrievalService:
     """
 
     def __init__(self, session_factory: Callable[[], Any], schema: Any | None = None, device: int = 0,
-                 compact_dead_fraction: float | None = None):
+                 compact_dead_fraction: float | None = None, shard_sparse: bool = False):
         self.session_factory = session_factory
+        # True: under a _World the chunk table's sparse store (BM25) is row-sharded over the ranks like the dense index, and
+        # the lexical searches run the library's sharded forms (global N / avgdl / df, gathered per call).  False, or without a
+        # _World: every rank holds the whole store, as before
+        self._shard_sparse = bool(shard_sparse)
         # None: units never compact by themselves (compact_unit still does); else `_UnitIndex.refresh` compacts the single-vector
         # index once that share of its slots is dead, or its head is
         self._compact_dead_fraction = compact_dead_fraction
@@ -758,16 +804,24 @@ class Mi355RetrievalService:
         return self._single_block(Q, top_k, unit, within, mmr_fetch_k, mmr_lambda)
 
     # ---- BM25: the lexical leg, over the unit's sparse store (reference retrieval_pipeline.py:398-465) ----
+    def _sparse_store(self, u: _UnitIndex, tokenizer: Any) -> Any:
+        """The unit's sparse store: the whole table on this rank, or -- `shard_sparse=True` under a _World -- the row-sharded
+        searcher, whose BM25 methods take the same arguments and return the same lists on every rank."""
+        if self._shard_sparse and self._world is not None:
+            return u.sparse_searcher(tokenizer, self._world)
+        return u.ensure_sparse(tokenizer)
+
     def _bm25_block(self, texts: list[str], top_k: int, tokenizer: Any, k1: float, b: float,
                     within: list | None = None) -> list[list[dict]]:
         """A page of query texts as one block.  Under a process group every rank holds the whole sparse store and computes the
-        same lists.  score = -distance: positive, higher is better, as the reference negates the operator's (chunk.py:236).
+        same lists -- or, with `shard_sparse=True`, its slice of it, and the library's sharded search returns the same lists.
+        score = -distance: positive, higher is better, as the reference negates the operator's (chunk.py:236).
         `within`: among the listed keys only -- a filter under the whole store's statistics, as the reference's statement
         with `AND id = ANY(:ids)` behaves; unknown keys are left out."""
         from .bm25 import get_tokenizer  # noqa: PLC0415
 
         u = self._unit("chunk")
-        ix = u.ensure_sparse(tokenizer)
+        ix = self._sparse_store(u, tokenizer)
         tok = get_tokenizer(tokenizer)
         queries = [tok(t) for t in texts]
         if within is None:
@@ -801,7 +855,7 @@ class Mi355RetrievalService:
         from .bm25 import get_tokenizer  # noqa: PLC0415
 
         u = self._unit("chunk")
-        ix = u.ensure_sparse(tokenizer)
+        ix = self._sparse_store(u, tokenizer)
         pos = u.pos_of_id()
         known = [(pk, pos[pk]) for pk in doc_ids if pk in pos]
         if not known:

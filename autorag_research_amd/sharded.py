@@ -444,6 +444,70 @@ class ShardedSearcher:
         self._library_comm("mmr_select", "mmr_select_sharded")
         return self.index.mmr_select_sharded(queries, k, cand_rows, lambda_mult)
 
+    # ---- sparse store (BM25): documents sharded by rows, N / avgdl / df gathered on every call inside the library
+    # (include/mi355dr.h "row-sharded sparse search") ----
+    def add_local_sparse(self, docs, global_doc0: int) -> None:
+        """Add this rank's tokenised documents; `global_doc0` is the global id of its first document (set once).  One
+        searcher holds ONE id space (`row_offset` is one option of the handle): on a searcher that already holds rows or
+        multi-vector documents under another offset this raises ValueError -- use a searcher of its own for the sparse store."""
+        if self.index.size_sparse() == 0:
+            held = len(self.index) if hasattr(self.index, "__len__") else 0
+            if held > 0 and int(global_doc0) != self.row_offset:
+                raise ValueError(f"ShardedSearcher.add_local_sparse: the searcher holds {held} rows at row_offset {self.row_offset}; "
+                                 f"documents at {int(global_doc0)} need a searcher of their own")
+            self.row_offset = int(global_doc0)
+            self.index.set_option("row_offset", self.row_offset)
+        self.index.add_sparse(docs)
+
+    def _local_sparse_ids(self, method: str, doc_ids) -> np.ndarray:
+        """Global ids -> this shard's local ids; an id of another shard is refused (mutations are local: ask its owner)."""
+        ids = np.ascontiguousarray(doc_ids, dtype=np.int64).reshape(-1)
+        local = ids - self.row_offset
+        n = self.index.size_sparse()
+        if ((local < 0) | (local >= n)).any():
+            raise ValueError(f"ShardedSearcher.{method}: document ids outside this shard [{self.row_offset}, {self.row_offset + n})")
+        return local
+
+    def set_local_sparse(self, doc_ids, docs) -> None:
+        """Replace documents of THIS shard, named by global id; the next sharded search on every rank sees the change."""
+        self.index.set_sparse(self._local_sparse_ids("set_local_sparse", doc_ids), docs)
+
+    def remove_local_sparse(self, doc_ids) -> None:
+        """Remove documents of THIS shard, named by global id (they keep their ids and never match)."""
+        self.index.remove_sparse(self._local_sparse_ids("remove_local_sparse", doc_ids))
+
+    def _sparse(self, method: str, *args, **kw):
+        """`method` of the index at world 1, else its `_sharded` form over the library's communicator."""
+        if self.world == 1 and not self.force_pipeline:
+            return getattr(self.index, method)(*args, **kw)
+        self._library_comm(method, method + "_sharded")
+        return getattr(self.index, method + "_sharded")(*args, **kw)
+
+    def search_bm25(self, token_lists, k: int, k1: float = 1.2, b: float = 0.75):
+        """Mi355Index.search_bm25 over the row-sharded store: every rank passes the same queries and gets the same
+        (distance [B, k], global ids [B, k]) -- what one store holding every document returns, bit for bit."""
+        return self._sparse("search_bm25", token_lists, k, k1, b)
+
+    def search_sparse(self, terms, weights, offsets, k: int, k1: float = 1.2, b: float = 0.75):
+        """Mi355Index.search_sparse over the row-sharded store (the norms use the global avgdl)."""
+        return self._sparse("search_sparse", terms, weights, offsets, k, k1, b)
+
+    def search_bm25_subset(self, token_lists, k: int, doc_ids, k1: float = 1.2, b: float = 0.75):
+        """Mi355Index.search_bm25_subset over the row-sharded store: the same list of global ids on every rank."""
+        return self._sparse("search_bm25_subset", token_lists, k, doc_ids, k1, b)
+
+    def search_sparse_subset(self, terms, weights, offsets, k: int, doc_ids, k1: float = 1.2, b: float = 0.75):
+        """Mi355Index.search_sparse_subset over the row-sharded store."""
+        return self._sparse("search_sparse_subset", terms, weights, offsets, k, doc_ids, k1, b)
+
+    def score_bm25_subset(self, token_lists, doc_ids, k1: float = 1.2, b: float = 0.75):
+        """Mi355Index.score_bm25_subset over the row-sharded store: doc_ids [B, m] global ids, each scored by its owner."""
+        return self._sparse("score_bm25_subset", token_lists, doc_ids, k1, b)
+
+    def score_sparse_subset(self, terms, weights, offsets, doc_ids, k1: float = 1.2, b: float = 0.75):
+        """Mi355Index.score_sparse_subset over the row-sharded store."""
+        return self._sparse("score_sparse_subset", terms, weights, offsets, doc_ids, k1, b)
+
     # ---- multi-vector (MaxSim): docs sharded by cumulative token count, same gather + merge ----
     def add_local_multivec(self, vecs, offsets, global_doc0: int) -> None:
         """Add this rank's docs (ragged [sum_T, d] + offsets starting at 0); `global_doc0` = global index of its first doc."""

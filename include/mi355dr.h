@@ -589,9 +589,10 @@ int mi355dr_search_maxsim_subset_device(mi355dr_index* idx, const float* qtok_de
  *     The list's device buffers belong to the store and are part of "hbm_bytes_resident".
  * Views: a view has an empty sparse store and refuses mi355dr_add_sparse / _set_sparse / _remove_sparse; mi355dr_compact does
  *   not touch the sparse store.
- * Out of scope: compaction / renumbering of sparse documents (ids are table positions in the service), views over the store, a row-sharded sparse search (it needs
- *   global df / avgdl), any claim of bit parity with VectorChord-BM25.  No longer on this list: fusion on the device of a sparse
- *   list with a dense one, which has its own section -- "hybrid fusion" below. */
+ * Out of scope: compaction / renumbering of sparse documents (ids are table positions in the service), views over the store,
+ *   any claim of bit parity with VectorChord-BM25.  No longer on this list: fusion on the device of a sparse list with a dense
+ *   one, which has its own section -- "hybrid fusion" below --, and the search over a row-sharded store with global df / avgdl,
+ *   which has its own too -- "row-sharded sparse search" below. */
 int mi355dr_add_sparse(mi355dr_index* idx, const int32_t* terms, const int64_t* offsets /* [n_docs + 1] */, int64_t n_docs); /* host */
 int64_t mi355dr_size_sparse(const mi355dr_index* idx); /* stored documents, with or without tokens */
 int mi355dr_set_sparse(mi355dr_index* idx, const int64_t* doc_ids /* HOST [n] */, const int32_t* terms,
@@ -805,6 +806,61 @@ int mi355dr_search_mmr_sharded_device(mi355dr_index* idx, const float* queries_d
                                       double* out_dist_dev, int64_t* out_rows_dev, void* stream);
 int mi355dr_mmr_select_sharded(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* cand_rows /* host [B, m], global */,
                                int m, double lambda, double* out_dist, int64_t* out_rows); /* all host */
+
+/* ---- row-sharded sparse search: weighted / BM25 over shards with global statistics ----
+ * One handle is one shard on one GPU: it holds a CONTIGUOUS run of the documents, with option "row_offset" set to the global id
+ * of its first document, and a communicator (mi355dr_comm_init or mi355dr_comm_init_custom).  Arguments are those of the local
+ * entry point of the same name: the search forms take queries and lists on the HOST, write results to device memory and take a
+ * `stream`; the score forms are all host.
+ * CONTRACT.  Every rank passes the same arguments, and every rank receives what the local entry point returns on ONE handle that
+ *   was given ONE mi355dr_add_sparse of all shards' current documents in global id order: all distance bits, global ids and
+ *   NaN / -1 tails; for the score forms the NaN positions too.  A shard that scored with its own N, total_len and df would
+ *   return other bits, so the statistics are those of ALL shards:
+ *   per call every rank contributes int64 [2 + T] -- its N (documents with tokens), its total_len, and its df of each of the T
+ *   distinct in-range terms of the call's queries, ascending (BM25 forms; T = 0 for the weighted forms, whose weights are the
+ *   caller's) --, one all-gather, and the rows are SUMMED on the device.  They are integers, so the sums are exact and the same
+ *   on every rank.  Each rank then drops the terms with global df = 0 and computes avgdl, norm_i and w_t by the formulas of the
+ *   sparse store above from the global N, total_len and df.  Weights are not exchanged: every rank calls log() on the same
+ *   integers, and RANKS ARE ASSUMED TO RUN THE SAME libm (one that differs in the last bit of log breaks the parity, nothing
+ *   else).
+ *   search forms: per block of at most 1024 queries the shard is searched by the local machinery (a listed id outside the shard
+ *   is skipped by the subset rule, so the shared list filters itself), the kept lists leave as the packed [2, nb, k] block of
+ *   mi355dr_pack_topk_device, one all-gather, one world * k -> k merge (mi355dr_merge_topk_packed_device).  The store's keys and
+ *   the merge sort under the same order -- distance ascending (-0.0 before +0.0), then id ascending --, so the merged list is
+ *   the one handle's list.
+ *   score forms: each rank writes its [B, m] distances, NaN for a pair it does not own or that does not match; one all-gather
+ *   per launch; per position the value of the lowest rank whose value is not NaN -- at most one rank owns a document.
+ * Rules.  Without a communicator: MI355DR_E_INVALID.  A view refuses (ask the parent).  world * k > 4096 (the merge's sort):
+ *   MI355DR_E_UNSUPPORTED.  Otherwise the local form's rules.  Every check runs before the first collective and depends on the
+ *   arguments and `world` alone, so all ranks refuse alike; a refused call changes nothing.  A rank whose shard has no document
+ *   with tokens -- one that never called mi355dr_add_sparse included -- still enters every collective.  Global N = 0: every
+ *   result line is NaN / -1 (every score NaN).  B == 0 (and m == 0 for the score forms) is a no-op without a collective.  Calls
+ *   are complete on return; B above 1024 runs in internal blocks.  A transport error returns MI355DR_E_HIP after the stream has
+ *   been drained.
+ * Mutations (mi355dr_add_sparse / _set_sparse / _remove_sparse) on any rank are local, and the next sharded call sees them: the
+ *   statistics are gathered on every call.  The local entry points on the same handle keep answering with the shard's own
+ *   statistics; the norms are cached per (k1, b, avgdl), so the two kinds of call recompute them only when they alternate.
+ * Stats: "sharded_sparse_searches" (calls of the four search forms), "sharded_sparse_scores" (calls of the two score forms);
+ *   the gathered bytes add to "shard_gather_bytes".  The local "sparse_*" counters move as the inner work moves them
+ *   ("sparse_queries", "sparse_postings_scored", "sparse_overflows", "sparse_subset_pairs", "sparse_subset_tiles", the builds);
+ *   the call counters of the local entry points stay.  The payload buffers belong to the store ("hbm_bytes_resident").
+ * Out of scope: fusing a sharded lexical list with a sharded dense one on the device (the hybrid fusion above stays one handle's). */
+int mi355dr_search_sparse_sharded_device(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets,
+                                         int B, int k, double k1, double b, double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+int mi355dr_search_bm25_sharded_device(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k, double k1,
+                                       double b, double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+int mi355dr_search_sparse_subset_sharded_device(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights,
+                                                const int32_t* q_offsets, int B, int k, double k1, double b,
+                                                const int64_t* doc_ids /* HOST [m], global */, int64_t m, double* out_dist_dev,
+                                                int64_t* out_rows_dev, void* stream);
+int mi355dr_search_bm25_subset_sharded_device(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, int k,
+                                              double k1, double b, const int64_t* doc_ids /* HOST [m], global */, int64_t m,
+                                              double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+int mi355dr_score_sparse_subset_sharded(mi355dr_index* idx, const int32_t* q_terms, const double* q_weights, const int32_t* q_offsets,
+                                        int B, double k1, double b, const int64_t* doc_ids /* HOST [B, m], global */, int m,
+                                        double* out_dist /* HOST [B, m] */);
+int mi355dr_score_bm25_subset_sharded(mi355dr_index* idx, const int32_t* q_tokens, const int32_t* q_offsets, int B, double k1, double b,
+                                      const int64_t* doc_ids /* HOST [B, m], global */, int m, double* out_dist /* HOST [B, m] */);
 
 /* ---- options / stats / timing ----
  * options: "path" (MI355DR_PATH_*), "screen_dtype" (MI355DR_SCREEN_*), "row_offset", "profile" (0/1: HIP-event
