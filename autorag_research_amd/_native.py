@@ -37,6 +37,8 @@ ABI_SYMBOLS = [
     "mi355dr_search_range_rows_sharded_device", "mi355dr_search_mmr_sharded_device", "mi355dr_mmr_select_sharded",
     "mi355dr_search_sparse_sharded_device", "mi355dr_search_bm25_sharded_device", "mi355dr_search_sparse_subset_sharded_device",
     "mi355dr_search_bm25_subset_sharded_device", "mi355dr_score_sparse_subset_sharded", "mi355dr_score_bm25_subset_sharded",
+    "mi355dr_collapse_lists", "mi355dr_collapse_lists_device", "mi355dr_search_collapsed", "mi355dr_search_collapsed_device",
+    "mi355dr_search_collapsed_sharded_device",
     "mi355dr_set_option", "mi355dr_get_stat",
     "mi355dr_reset_stats", "mi355dr_timer_start", "mi355dr_timer_stop", "mi355dr_synchronize",
     "mi355dr_dev_alloc", "mi355dr_dev_free", "mi355dr_dev_upload", "mi355dr_dev_download",
@@ -166,6 +168,16 @@ def load() -> ctypes.CDLL:
     L.mi355dr_fuse_lists_device.argtypes = [vp, vp, vp, c_int, vp, i64, vp, vp, c_int, vp, i64, c_int, c_int, fuse_p, vp, vp, vp, vp]
     L.mi355dr_fuse_lists.restype = c_int
     L.mi355dr_fuse_lists.argtypes = [vp, f64p, i64p, c_int, i64p, i64, f64p, i64p, c_int, i64p, i64, c_int, c_int, fuse_p, f64p, i64p, i32p]
+    L.mi355dr_collapse_lists_device.restype = c_int
+    L.mi355dr_collapse_lists_device.argtypes = [vp, vp, vp, c_int, c_int, vp, i64, c_int, c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.mi355dr_collapse_lists.restype = c_int
+    L.mi355dr_collapse_lists.argtypes = [vp, f64p, i64p, c_int, c_int, i64p, i64, c_int, c_int, f64p, i64p, i64p, i32p, i32p, i32p]
+    L.mi355dr_search_collapsed.restype = c_int
+    L.mi355dr_search_collapsed.argtypes = [vp, f32p, c_int, c_int, c_int, i64p, i64, c_int, c_int, f64p, i64p, i64p, i32p, i32p]
+    L.mi355dr_search_collapsed_device.restype = c_int
+    L.mi355dr_search_collapsed_device.argtypes = [vp, vp, c_int, c_int, c_int, vp, i64, c_int, c_int, vp, vp, vp, vp, vp, vp]
+    L.mi355dr_search_collapsed_sharded_device.restype = c_int
+    L.mi355dr_search_collapsed_sharded_device.argtypes = list(L.mi355dr_search_collapsed_device.argtypes)
     L.mi355dr_search_range.restype = c_int
     L.mi355dr_search_range.argtypes = [vp, f32p, c_int, f64p, c_int, f64p, i64p, i64p]
     L.mi355dr_search_range_device.restype = c_int

@@ -170,6 +170,38 @@ struct FuseBufs {
         return e;
     }
 };
+// source-capped lists and search (mi355dr_collapse_lists* / mi355dr_search_collapsed*).  The host list
+// form's staging: the lists [B, w], the key table, the results [B, k_out] / [B] (B unbounded: not block-shaped, so it grows
+// here).  The search forms' block state: the candidate lists [nb, max_fetch], the host form's copy of the block's queries (a
+// fix-up of the inner search overwrites qdev), the gathered queries of a re-search, their slot-to-line list, the kernel's
+// (kept, entries), and the host form's key table and its staging of the results' keys
+struct CollapseBufs {
+    DevBuf<double> vals, out_vals, cand_dist;
+    DevBuf<int64_t> ids, keys, out_ids, out_keys, cand_rows;
+    DevBuf<int32_t> out_pos, count, entries, lines, kept;
+    DevBuf<float> q_all, q_sub;
+    hipError_t reserve_lists(size_t B, size_t w, size_t keys_len, size_t k_out) {
+        hipError_t e = grow_each(B * w, vals, ids);
+        if (!e) e = grow_each(keys_len, keys);
+        if (!e) e = grow_each(B * k_out, out_vals, out_ids, out_keys, out_pos);
+        if (!e) e = grow_each(B, count, entries);
+        return e;
+    }
+    hipError_t reserve_search(size_t nb, size_t max_fetch, size_t k, size_t dim, size_t host_keys_len, bool host) {
+        hipError_t e = grow_each(nb * max_fetch, cand_dist, cand_rows);
+        if (!e) e = grow_each(nb * dim, q_sub);
+        if (!e) e = grow_each(nb, lines, kept, entries);
+        if (!e && host) e = grow_each(nb * dim, q_all);
+        if (!e && host) e = grow_each(host_keys_len, keys);
+        if (!e && host) e = grow_each(nb * k, out_keys);
+        return e;
+    }
+    size_t bytes() const {
+        return vals.bytes + out_vals.bytes + cand_dist.bytes + ids.bytes + keys.bytes + out_ids.bytes + out_keys.bytes +
+               cand_rows.bytes + out_pos.bytes + count.bytes + entries.bytes + lines.bytes + kept.bytes + q_all.bytes +
+               q_sub.bytes;
+    }
+};
 // range search (mi355dr_search_range*): one block's result buffers [nb, R slots] with their per-query
 // words, the radii, the redo list of `pairs` pairs, the two device counters and the sub-block of the queries the ordinary
 // search serves (fb_*: map, gathered queries, lists [nb, m])
@@ -281,6 +313,7 @@ struct mi355dr_index {
     mi355::MmrBufs mmr;      // per-family scratch of the derived searches (above): grown by each family's reserve()
     mi355::GroupBufs grp;
     mi355::FuseBufs fuse;
+    mi355::CollapseBufs clp;
     mi355::RangeBufs rng;
     mi355::RowQueryBufs rowq;
     mi355::ShardBufs shd;
@@ -418,6 +451,9 @@ struct mi355dr_index {
     int64_t s_group_searches = 0, s_group_subqueries = 0, s_groups_merged = 0;
     // mi355dr_fuse_lists*: calls, queries
     int64_t s_fuse_calls = 0, s_fuse_queries = 0;
+    // mi355dr_collapse_lists* / mi355dr_search_collapsed*: list calls; search calls, their queries, (query, round) re-searches,
+    // queries returned truncated
+    int64_t s_collapse_calls = 0, s_collapse_searches = 0, s_collapse_queries = 0, s_collapse_researched = 0, s_collapse_truncated = 0;
     // mi355dr_search_range*: calls, queries, rows in range (the counts, summed); screen path: candidates taken from the screens
     // and of them re-scored; (query, chunk) pairs run again on the exact path; queries whose list the ordinary search served
     int64_t s_range_searches = 0, s_range_queries = 0, s_range_in_range = 0, s_range_candidates = 0, s_range_rescored = 0,

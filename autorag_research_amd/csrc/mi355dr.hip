@@ -25,9 +25,13 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "mmr_order.h"
 #include "k_groups.h"
 #include "k_fuse.h"
+#include "k_collapse.h"
+#include "collapse_plan.h"
 #include "k_range.h"
 #include "k_rows.h"
 #include "k_shard.h"
+
+#include <functional>
 
 using namespace mi355;
 
@@ -183,6 +187,8 @@ int ensure_qstate(mi355dr_index* idx) {
                                       (int)mmr_lds_bytes(idx->dim, kMmrMax)));
     HIPCHECK(idx, hipFuncSetAttribute((const void*)k_merge_groups, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)groups_lds_bytes(kSortMax)));
+    HIPCHECK(idx, hipFuncSetAttribute((const void*)k_collapse_lists, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)collapse_lds_bytes(kSortMax)));
     idx->qstate_ready = true;  // (behind the last step that can fail)
     return MI355DR_OK;
 }
@@ -2176,6 +2182,240 @@ int mi355dr_fuse_lists(mi355dr_index* idx, const double* vals1, const int64_t* i
     return fuse_impl(idx, io, B, k_out, opts, nullptr, /*host=*/true);
 }
 
+// ---- source-capped lists and search: at most `cap` entries per source (csrc/k_collapse.h) ----------
+namespace {
+struct CollapseLists {  // one call's inputs and outputs, all on the device or all on the host
+    const double* vals;
+    const int64_t* ids;
+    const int64_t* keys;
+    int64_t keys_len;
+    double* out_vals;
+    int64_t* out_ids;
+    int64_t* out_keys;
+    int32_t* out_pos;
+    int32_t* out_count;
+    int32_t* out_entries;
+};
+
+// the key table's own rules, shared by the list and the search forms
+int check_collapse_keys(mi355dr_index* idx, const std::string& w, const int64_t* keys, int64_t keys_len, int cap) {
+    if (cap <= 0) return fail(idx, MI355DR_E_INVALID, w + ": cap must be > 0");
+    if (keys_len < 0) return fail(idx, MI355DR_E_INVALID, w + ": keys_len must be >= 0");
+    if (keys && keys_len == 0) return fail(idx, MI355DR_E_INVALID, w + ": a key table of length 0 (pass NULL for no keys)");
+    if (!keys && keys_len > 0) return fail(idx, MI355DR_E_INVALID, w + ": keys is null");
+    return MI355DR_OK;
+}
+
+// `n` lists [n, w] -> the lines `lines` names (null: line s for list s); asynchronous on the stream
+int launch_collapse(mi355dr_index* idx, hipStream_t s, int n, int w, const int32_t* lines, const CollapseLists& dev, int cap,
+                    int k_out) {
+    const int np = collapse_pow2(w);
+    hipLaunchKernelGGL(k_collapse_lists, dim3(n), dim3(kCollapseThreads), collapse_lds_bytes(np), s, (const uint64_t*)dev.vals,
+                       dev.ids, w, np, lines, dev.keys, dev.keys ? dev.keys_len : 0, cap, k_out, (uint64_t*)dev.out_vals,
+                       dev.out_ids, dev.out_keys, dev.out_pos, dev.out_count, dev.out_entries);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+int collapse_lists_impl(mi355dr_index* idx, const CollapseLists& io, int w, int B, int cap, int k_out, void* stream, bool host) {
+    Call c;
+    CHECK(begin_call(idx, "collapse_lists", stream, /*flags=*/0, c, [&]() -> int {  // (no drain: it touches no per-search state)
+        const std::string what("collapse_lists");
+        if (B < 0) return fail(idx, MI355DR_E_INVALID, what + ": B must be >= 0");
+        if (w <= 0 || k_out <= 0) return fail(idx, MI355DR_E_INVALID, what + ": the list width and k_out must be > 0");
+        CHECK(check_collapse_keys(idx, what, io.keys, io.keys_len, cap));
+        if (B > 0 && (!io.vals || !io.ids || !io.out_vals || !io.out_ids)) return fail(idx, MI355DR_E_INVALID, what + ": null buffer");
+        if (w > kSortMax) return fail(idx, MI355DR_E_UNSUPPORTED, what + ": a list is wider than 4096");
+        if (k_out > kSortMax) return fail(idx, MI355DR_E_UNSUPPORTED, what + ": k_out exceeds 4096");
+        return MI355DR_OK;
+    }));
+    if (B == 0) return MI355DR_OK;
+    CollapseLists dev = io;
+    if (host) {
+        CollapseBufs& b = idx->clp;
+        HIPCHECK(idx, b.reserve_lists(B, w, io.keys ? io.keys_len : 0, k_out));
+        const size_t n = (size_t)B * w;
+        HIPCHECK(idx, hipMemcpyAsync(b.vals.p, io.vals, n * sizeof(double), hipMemcpyHostToDevice, c.s));
+        HIPCHECK(idx, hipMemcpyAsync(b.ids.p, io.ids, n * sizeof(int64_t), hipMemcpyHostToDevice, c.s));
+        if (io.keys) HIPCHECK(idx, hipMemcpyAsync(b.keys.p, io.keys, (size_t)io.keys_len * sizeof(int64_t), hipMemcpyHostToDevice, c.s));
+        dev = CollapseLists{b.vals.p, b.ids.p, io.keys ? b.keys.p : nullptr, io.keys_len, b.out_vals.p, b.out_ids.p,
+                            io.out_keys ? b.out_keys.p : nullptr, io.out_pos ? b.out_pos.p : nullptr,
+                            io.out_count ? b.count.p : nullptr, io.out_entries ? b.entries.p : nullptr};
+    }
+    CHECK(launch_collapse(idx, c.s, B, w, nullptr, dev, cap, k_out));
+    if (host) {
+        const size_t n = (size_t)B * k_out;
+        HIPCHECK(idx, hipMemcpyAsync(io.out_vals, dev.out_vals, n * sizeof(double), hipMemcpyDeviceToHost, c.s));
+        HIPCHECK(idx, hipMemcpyAsync(io.out_ids, dev.out_ids, n * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+        if (io.out_keys) HIPCHECK(idx, hipMemcpyAsync(io.out_keys, dev.out_keys, n * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+        if (io.out_pos) HIPCHECK(idx, hipMemcpyAsync(io.out_pos, dev.out_pos, n * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (io.out_count)
+            HIPCHECK(idx, hipMemcpyAsync(io.out_count, dev.out_count, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+        if (io.out_entries)
+            HIPCHECK(idx, hipMemcpyAsync(io.out_entries, dev.out_entries, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+    }
+    HIPCHECK(idx, hipStreamSynchronize(c.s));
+    idx->s_collapse_calls++;
+    return MI355DR_OK;
+}
+
+// what one call of the search forms carries besides its inner search
+struct CollapseSearch {
+    const char* what;
+    const float* queries;
+    int B, k, cap;
+    const int64_t* keys;
+    int64_t keys_len;
+    int fetch_k, max_fetch;
+    double* out_dist;
+    int64_t* out_rows;
+    int64_t* out_keys;
+    int32_t* out_count;
+    int32_t* out_state;
+    void* stream;
+    bool host;
+};
+
+// Both search forms and the sharded one.  `topk(s, q_dev, n, w, od, orow)`: the ordinary search of n device queries at width w
+// into [n, w] device lists, screened and with its fix-ups completed (search_block; shard_topk_block over a communicator).
+// `more_checks`: the form's own argument rules, behind the common ones.  `reserve_inner(nb_max)`: whatever `topk` may need for
+// ANY round of a block of nb_max queries -- up to nb_max lists of max_fetch entries -- taken before the first search, so that no
+// later round allocates (over a communicator: no rank can fail an allocation between two collectives of a call).
+// (std::function parameters, not a template: the entry points below stand inside the file's extern "C" block.)
+using CollapseTopK = std::function<int(hipStream_t, const float*, int, int, double*, int64_t*)>;
+int search_collapsed_impl(mi355dr_index* idx, const CollapseSearch& a, unsigned flags, const std::function<int()>& more_checks,
+                          const std::function<int(int)>& reserve_inner, const CollapseTopK& topk) {
+    Call c;
+    CHECK(begin_call(idx, a.what, a.stream, flags, c, [&]() -> int {
+        const std::string what(a.what);
+        CHECK(check_search_args(idx, a.queries, a.B, a.k, a.out_dist, a.out_rows));
+        CHECK(check_collapse_keys(idx, what, a.keys, a.keys_len, a.cap));
+        if (a.fetch_k < a.k) return fail(idx, MI355DR_E_INVALID, what + ": fetch_k must be >= k");
+        if (a.max_fetch < a.fetch_k) return fail(idx, MI355DR_E_INVALID, what + ": max_fetch must be >= fetch_k");
+        if (a.max_fetch > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, what + ": max_fetch exceeds 1024");
+        return more_checks();
+    }));
+    const int B = a.B, k = a.k;
+    if (B == 0) return MI355DR_OK;
+    CollapseBufs& cb = idx->clp;
+    const int nb_max = std::min(B, kQBlockMax);
+    HIPCHECK(idx, cb.reserve_search(nb_max, a.max_fetch, k, idx->dim, a.host && a.keys ? a.keys_len : 0, a.host));
+    CHECK(reserve_inner(nb_max));
+    std::vector<int32_t> kept, entries, count, state;
+    CollapsePlan plan;
+    try {
+        kept.resize(nb_max);
+        entries.resize(nb_max);
+        count.resize(nb_max);
+        state.resize(nb_max);
+        plan.lines.reserve(nb_max);
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, std::string(a.what) + ": out of host memory for the schedule");
+    }
+    const int64_t* keys_dev = a.keys;
+    if (a.host && a.keys) {
+        HIPCHECK(idx, hipMemcpyAsync(cb.keys.p, a.keys, (size_t)a.keys_len * sizeof(int64_t), hipMemcpyHostToDevice, c.s));
+        keys_dev = cb.keys.p;
+    }
+    int64_t researched = 0, truncated = 0;
+    const CallIO<> io{a.host, c.s, a.queries, {a.out_dist, a.out_rows, nullptr}, k};
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        // the block's queries where they stay readable through every round: not block_queries' qdev, which the inner search's
+        // fix-ups overwrite -- the host form keeps a copy of its own
+        const float* q = a.queries + (int64_t)b0 * idx->dim;
+        if (a.host) {
+            HIPCHECK(idx, hipMemcpyAsync(cb.q_all.p, q, (size_t)nb * idx->dim * sizeof(float), hipMemcpyHostToDevice, c.s));
+            q = cb.q_all.p;
+        }
+        const BlockOut<int64_t> o = block_outputs(idx, io, b0);
+        CollapseLists dev{cb.cand_dist.p, cb.cand_rows.p, keys_dev, a.keys_len, o.dist, o.rows, nullptr, nullptr, cb.kept.p, cb.entries.p};
+        if (a.out_keys) dev.out_keys = a.host ? cb.out_keys.p : a.out_keys + (int64_t)b0 * k;
+        plan.begin(nb, k, a.fetch_k, a.max_fetch);
+        const float* q_round = q;
+        const int32_t* lines = nullptr;
+        for (int n = nb;;) {
+            // the ordinary search of the round's queries at f, the cap over their lists, (kept, entries) back
+            CHECK(topk(c.s, q_round, n, plan.f, cb.cand_dist.p, cb.cand_rows.p));
+            CHECK(launch_collapse(idx, c.s, n, plan.f, lines, dev, a.cap, k));
+            HIPCHECK(idx, hipMemcpyAsync(kept.data(), cb.kept.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+            HIPCHECK(idx, hipMemcpyAsync(entries.data(), cb.entries.p, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+            HIPCHECK(idx, hipStreamSynchronize(c.s));
+            if (!plan.advance(kept.data(), entries.data())) break;
+            // the unfinished queries, and only they, side by side for the next round; their lists write their own lines
+            n = (int)plan.lines.size();
+            HIPCHECK(idx, hipMemcpyAsync(cb.lines.p, plan.lines.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c.s));
+            hipLaunchKernelGGL(k_gather_queries, dim3(n), dim3(128), 0, c.s, q, (const int*)cb.lines.p, idx->dim, cb.q_sub.p);
+            HIPCHECK(idx, hipGetLastError());
+            HIPCHECK(idx, hipStreamSynchronize(c.s));  // `plan.lines` (pageable) was read by the copy
+            q_round = cb.q_sub.p;
+            lines = cb.lines.p;
+        }
+        researched += plan.researched;
+        for (int i = 0; i < nb; ++i) {
+            count[i] = collapse_count(kept[i], k);
+            state[i] = collapse_state(kept[i], entries[i], k, a.max_fetch);
+            truncated += state[i] & kCollapseTruncated ? 1 : 0;
+        }
+        // distances and rows as every host form returns them; the keys behind them; count and state are the host's own words
+        CHECK(block_return(idx, io, b0, nb, o));
+        if (a.host) {
+            if (a.out_keys)
+                HIPCHECK(idx, hipMemcpyAsync(a.out_keys + (int64_t)b0 * k, dev.out_keys, (size_t)nb * k * sizeof(int64_t), hipMemcpyDeviceToHost, c.s));
+            if (a.out_count) memcpy(a.out_count + b0, count.data(), (size_t)nb * sizeof(int32_t));
+            if (a.out_state) memcpy(a.out_state + b0, state.data(), (size_t)nb * sizeof(int32_t));
+        } else {
+            if (a.out_count) HIPCHECK(idx, hipMemcpyAsync(a.out_count + b0, count.data(), (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice, c.s));
+            if (a.out_state) HIPCHECK(idx, hipMemcpyAsync(a.out_state + b0, state.data(), (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice, c.s));
+        }
+        HIPCHECK(idx, hipStreamSynchronize(c.s));  // (the next block reuses the staging, the lists and the host words)
+    }
+    idx->s_collapse_searches++;
+    idx->s_collapse_queries += B;
+    idx->s_collapse_researched += researched;
+    idx->s_collapse_truncated += truncated;
+    return MI355DR_OK;
+}
+
+int search_collapsed_local(mi355dr_index* idx, const CollapseSearch& a) {
+    return search_collapsed_impl(idx, a, kCallDrain, [] { return MI355DR_OK; }, [](int) { return MI355DR_OK; },
+                                 [&](hipStream_t s, const float* q, int n, int w, double* od, int64_t* orow) {
+                                     return search_block(idx, s, q, n, w, od, orow);
+                                 });
+}
+}  // namespace
+
+int mi355dr_collapse_lists_device(mi355dr_index* idx, const double* vals_dev, const int64_t* ids_dev, int w, int B,
+                                  const int64_t* keys_dev, int64_t keys_len, int cap, int k_out, double* out_vals_dev,
+                                  int64_t* out_ids_dev, int64_t* out_keys_dev, int32_t* out_pos_dev, int32_t* out_count_dev,
+                                  int32_t* out_entries_dev, void* stream) {
+    const CollapseLists io{vals_dev, ids_dev, keys_dev, keys_len, out_vals_dev, out_ids_dev, out_keys_dev, out_pos_dev,
+                           out_count_dev, out_entries_dev};
+    return collapse_lists_impl(idx, io, w, B, cap, k_out, stream, /*host=*/false);
+}
+
+int mi355dr_collapse_lists(mi355dr_index* idx, const double* vals, const int64_t* ids, int w, int B, const int64_t* keys,
+                           int64_t keys_len, int cap, int k_out, double* out_vals, int64_t* out_ids, int64_t* out_keys,
+                           int32_t* out_pos, int32_t* out_count, int32_t* out_entries) {
+    const CollapseLists io{vals, ids, keys, keys_len, out_vals, out_ids, out_keys, out_pos, out_count, out_entries};
+    return collapse_lists_impl(idx, io, w, B, cap, k_out, nullptr, /*host=*/true);
+}
+
+int mi355dr_search_collapsed(mi355dr_index* idx, const float* queries, int B, int k, int cap, const int64_t* keys, int64_t keys_len,
+                             int fetch_k, int max_fetch, double* out_dist, int64_t* out_rows, int64_t* out_keys,
+                             int32_t* out_count, int32_t* out_state) {
+    return search_collapsed_local(idx, CollapseSearch{"search_collapsed", queries, B, k, cap, keys, keys_len, fetch_k, max_fetch,
+                                                      out_dist, out_rows, out_keys, out_count, out_state, nullptr, /*host=*/true});
+}
+
+int mi355dr_search_collapsed_device(mi355dr_index* idx, const float* queries_dev, int B, int k, int cap, const int64_t* keys_dev,
+                                    int64_t keys_len, int fetch_k, int max_fetch, double* out_dist_dev, int64_t* out_rows_dev,
+                                    int64_t* out_keys_dev, int32_t* out_count_dev, int32_t* out_state_dev, void* stream) {
+    return search_collapsed_local(idx, CollapseSearch{"search_collapsed_device", queries_dev, B, k, cap, keys_dev, keys_len, fetch_k,
+                                                      max_fetch, out_dist_dev, out_rows_dev, out_keys_dev, out_count_dev,
+                                                      out_state_dev, stream, /*host=*/false});
+}
+
 // ---- range search: every row within a distance, counted on the device (csrc/k_range.h) ------------
 namespace {
 struct RangeSpan {
@@ -2773,6 +3013,28 @@ int mi355dr_search_mmr_sharded_device(mi355dr_index* idx, const float* queries_d
     return shard_mmr_finish(idx, B);
 }
 
+// the source-capped search over the shards (section 4.8m): every rank sees the same merged lists, so it takes the same
+// decisions and enters the same collectives, round by round
+int mi355dr_search_collapsed_sharded_device(mi355dr_index* idx, const float* queries_dev, int B, int k, int cap,
+                                            const int64_t* keys_dev, int64_t keys_len, int fetch_k, int max_fetch,
+                                            double* out_dist_dev, int64_t* out_rows_dev, int64_t* out_keys_dev,
+                                            int32_t* out_count_dev, int32_t* out_state_dev, void* stream) {
+    const char* what = "search_collapsed_sharded_device";
+    const CollapseSearch a{what, queries_dev, B, k, cap, keys_dev, keys_len, fetch_k, max_fetch, out_dist_dev, out_rows_dev,
+                           out_keys_dev, out_count_dev, out_state_dev, stream, /*host=*/false};
+    return search_collapsed_impl(
+        idx, a, kCallNoView | kCallDrain,
+        [&]() -> int {
+            CHECK(check_comm(idx));
+            return check_shard_width(idx, what, max_fetch);
+        },
+        // the packed [2, n, f] block of the widest round there can be: a later round (1 x 512 after 5 x 16) never grows it
+        [&](int nb_max) { return shard_reserve_words(idx, 2 * (size_t)nb_max * (size_t)max_fetch); },
+        [&](hipStream_t s, const float* q, int n, int w, double* od, int64_t* orow) {
+            return shard_topk_block(idx, s, q, n, w, od, orow);
+        });
+}
+
 int mi355dr_mmr_select_sharded(mi355dr_index* idx, const float* queries, int B, int k, const int64_t* cand_rows, int m, double lambda,
                                double* out_dist, int64_t* out_rows) {
     Call c;
@@ -3035,6 +3297,11 @@ const Stat kStats[] = {
     {"groups_merged", &Index::s_groups_merged, true},
     {"fuse_calls", &Index::s_fuse_calls, true},
     {"fuse_queries", &Index::s_fuse_queries, true},
+    {"collapse_calls", &Index::s_collapse_calls, true},
+    {"collapse_searches", &Index::s_collapse_searches, true},
+    {"collapse_queries", &Index::s_collapse_queries, true},
+    {"collapse_researched", &Index::s_collapse_researched, true},
+    {"collapse_truncated", &Index::s_collapse_truncated, true},
     {"range_searches", &Index::s_range_searches, true},
     {"range_queries", &Index::s_range_queries, true},
     {"range_in_range", &Index::s_range_in_range, true},
@@ -3083,7 +3350,7 @@ const Stat kStats[] = {
          return x->cap_rows * ((int64_t)x->dim * 4 + (int64_t)x->dpad * 2 + (int64_t)x->dpad8 + 5) +
                 x->cap_rows / kI8GroupRows * (int64_t)sizeof(I8Group) + multivec_bytes(x) +
                 (int64_t)(x->view_row_map.bytes + x->view_doc_map.bytes) +  // (a view's two id maps; none on a parent)
-                sparse_bytes(x);
+                sparse_bytes(x) + (int64_t)x->clp.bytes();  // (the source-capped forms' staging and block state, as grown)
      }},
 };
 }  // namespace

@@ -8,6 +8,7 @@ answers exact top-k.  Rows are dense indices in insertion order; id mapping live
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 
@@ -19,6 +20,74 @@ PATHS = {"auto": 0, "screen": 1, "scan": 2}
 SCREEN_DTYPES = {"auto": 0, "bf16": 1, "i8": 2}
 FUSE_METHODS = {"rrf": 0, "mm": 1, "tmm": 2, "z": 3, "dbsf": 4}      # MI355DR_FUSE_RRF / _CC_*
 FUSE_MODES = {"one_minus": 0, "negate": 1, "as_is": 2}               # MI355DR_FUSE_ONE_MINUS / _NEGATE / _AS_IS
+
+
+COLLAPSE_TRUNCATED = 1   # MI355DR_COLLAPSE_TRUNCATED: fewer than k kept although the ranking was cut at max_fetch
+# search_collapsed's first round is searched at COLLAPSE_FETCH_MULT * k unless the caller says otherwise.  The rule
+# (profiles/collapse_timing.txt): the multiple of k that is cheapest where every source holds 8
+# near-copies AND costs a corpus whose cap almost never bites no more than the table's box-to-box noise over fetch_k = k.
+# Measured at 1 M x 768, 1024 queries, k = 10: 2 k costs the Gaussian corpus 1.13 ms against 1.03 (+9 %) where two boxes differ
+# by under 4 %, so no multiple above 1 qualifies.  A corpus of near-copies is served best by a caller's fetch_k of about 4 k
+# (6.5 ms against 12.4).
+COLLAPSE_FETCH_MULT = 1
+
+
+class CollapsedLists(NamedTuple):
+    """`Mi355Index.collapse_lists`: the kept entries of each list; a field the call switched off is None."""
+
+    vals: np.ndarray
+    ids: np.ndarray
+    keys: np.ndarray | None
+    pos: np.ndarray | None
+    count: np.ndarray | None
+    entries: np.ndarray | None
+
+
+class CollapsedSearch(NamedTuple):
+    """`Mi355Index.search_collapsed*`: at most `cap` rows per source."""
+
+    dist: np.ndarray
+    rows: np.ndarray
+    keys: np.ndarray
+    count: np.ndarray
+    state: np.ndarray
+
+
+class DeviceKeys:
+    """A key table on an index's device (`Mi355Index.upload_keys`): int64 [length] at `ptr`, 0 / 0 for an empty table."""
+
+    def __init__(self, index: "Mi355Index", keys):
+        t = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        self._index = index
+        self.length = int(t.shape[0])
+        self.ptr = 0
+        if self.length:
+            self.ptr = index.dev_alloc(t.nbytes)
+            try:
+                index.dev_upload(self.ptr, t)
+            except Exception:
+                self.close()
+                raise
+
+    @classmethod
+    def borrowed(cls, ptr: int, length: int) -> "DeviceKeys":
+        """A table that lives in a device buffer of the caller's (int64 [length] at `ptr`): close() leaves it alone."""
+        self = cls.__new__(cls)
+        self._index, self.ptr, self.length = None, int(ptr), int(length)
+        return self
+
+    def close(self) -> None:
+        if self.ptr:
+            p, self.ptr = self.ptr, 0
+            if self._index is not None:
+                self._index.dev_free(p)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+        return False
 
 
 def _stream_arg(stream) -> ctypes.c_void_p:
@@ -390,6 +459,192 @@ class Mi355Index:
             ptr(i2, ctypes.c_int64), v2.shape[1], *mp(maps[1]), B, k, ctypes.byref(opts), ptr(out_v, ctypes.c_double),
             ptr(out_i, ctypes.c_int64), ptr(out_c, ctypes.c_int32)))
         return out_v, out_i, out_c
+
+    # ---- source-capped lists and search: at most `cap` results per source (include/mi355dr.h "source-capped lists and search") ----
+    def upload_keys(self, keys) -> "DeviceKeys":
+        """A key table (int64 [keys_len], keys[id] = the source of id, negative = none) uploaded ONCE, for any number of
+        `collapse_lists` / `search_collapsed*` calls; close it (or use it as a context manager) when done.  A numpy table
+        passed per call takes the host form instead, which uploads it every time."""
+        return DeviceKeys(self, keys)
+
+    @staticmethod
+    def _host_keys(keys) -> np.ndarray | None:
+        if keys is None:
+            return None
+        t = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        return t if t.shape[0] else None   # (an empty table gives no entry a key: the C ABI's NULL / 0)
+
+    def collapse_lists_device(self, vals_ptr: int, ids_ptr: int, w: int, B: int, cap: int, k: int, out_vals_ptr: int,
+                              out_ids_ptr: int, out_keys_ptr: int | None = None, out_pos_ptr: int | None = None,
+                              out_count_ptr: int | None = None, out_entries_ptr: int | None = None, *,
+                              keys_ptr: int | None = None, keys_len: int = 0, stream: int | None = None) -> None:
+        """The cap over device lists (float64 / int64 [B, w]; table int64 [keys_len] or None; outputs float64 / int64 [B, k],
+        and each of int64 [B, k] keys, int32 [B, k] positions, int32 [B] kept, int32 [B] entries or None).  It reads no
+        index state: the lists may be another handle's.  Complete on return."""
+        vp = lambda p: ctypes.c_void_p(int(p) if p else None)  # noqa: E731
+        check(self._h, self._lib.mi355dr_collapse_lists_device(
+            self._h, vp(vals_ptr), vp(ids_ptr), int(w), int(B), vp(keys_ptr), int(keys_len), int(cap), int(k), vp(out_vals_ptr),
+            vp(out_ids_ptr), vp(out_keys_ptr), vp(out_pos_ptr), vp(out_count_ptr), vp(out_entries_ptr), _stream_arg(stream)))
+
+    def collapse_lists(self, vals, ids, keys, cap: int, k: int | None = None, *, with_keys: bool = True, with_pos: bool = True,
+                       with_count: bool = True, with_entries: bool = True) -> "CollapsedLists":
+        """At most `cap` entries per source in each ranked list: vals float64 [B, w], ids int64 [B, w] in ranking order (an
+        id < 0 is no entry; a NaN value with an id is one).  `keys`: None, an int64 array (the host form) or a `DeviceKeys`
+        (`upload_keys`: the device form).  An entry is kept iff it has no key or fewer than `cap` earlier entries of its list
+        have its key; the first `k` (default w) kept entries come back in list order with the bits they came with, NaN / -1
+        behind them.  Returns CollapsedLists(vals [B,k], ids [B,k], keys [B,k] (-1: none), pos int32 [B,k] (slot in the
+        input), count int32 [B] (kept in the whole list), entries int32 [B]); a field switched off is None."""
+        v = np.ascontiguousarray(vals, dtype=np.float64)
+        i = np.ascontiguousarray(ids, dtype=np.int64)
+        if v.ndim != 2 or i.shape != v.shape:
+            raise ValueError("vals and ids must both be [B, w]")
+        B, w = v.shape
+        k = int(w if k is None else k)
+        out_v = np.empty((B, max(k, 0)), dtype=np.float64)
+        out_i = np.empty((B, max(k, 0)), dtype=np.int64)
+        out_k = np.empty((B, max(k, 0)), dtype=np.int64) if with_keys else None
+        out_p = np.empty((B, max(k, 0)), dtype=np.int32) if with_pos else None
+        out_c = np.empty(B, dtype=np.int32) if with_count else None
+        out_e = np.empty(B, dtype=np.int32) if with_entries else None
+        outs = (out_v, out_i, out_k, out_p, out_c, out_e)
+        if isinstance(keys, DeviceKeys):
+            bufs = []
+            try:
+                for a in (v, i, *outs):
+                    bufs.append(None if a is None else self.dev_alloc(max(a.nbytes, 8)))
+                if v.size:
+                    self.dev_upload(bufs[0], v)
+                    self.dev_upload(bufs[1], i)
+                self.collapse_lists_device(bufs[0], bufs[1], w, B, cap, k, *bufs[2:], keys_ptr=keys.ptr, keys_len=keys.length)
+                for a, b in zip(outs, bufs[2:]):
+                    if a is not None and a.size:
+                        self.dev_download(b, a)
+            finally:
+                for b in bufs:
+                    if b is not None:
+                        self.dev_free(b)
+            return CollapsedLists(*outs)
+        t = self._host_keys(keys)
+        opt = lambda a, ct: None if a is None else ptr(a, ct)  # noqa: E731
+        check(self._h, self._lib.mi355dr_collapse_lists(
+            self._h, ptr(v, ctypes.c_double), ptr(i, ctypes.c_int64), int(w), B, opt(t, ctypes.c_int64),
+            0 if t is None else t.shape[0], int(cap), k, ptr(out_v, ctypes.c_double), ptr(out_i, ctypes.c_int64),
+            opt(out_k, ctypes.c_int64), opt(out_p, ctypes.c_int32), opt(out_c, ctypes.c_int32), opt(out_e, ctypes.c_int32)))
+        return CollapsedLists(*outs)
+
+    @staticmethod
+    def collapse_fetch_k(k: int, fetch_k: int | None, max_fetch: int) -> int:
+        """The first round's width of `search_collapsed*`: `fetch_k`, or COLLAPSE_FETCH_MULT * k within [k, max_fetch]."""
+        if fetch_k is not None:
+            return int(fetch_k)
+        return max(int(k), min(COLLAPSE_FETCH_MULT * int(k), int(max_fetch)))
+
+    def _search_collapsed_device_form(self, fn, q_ptr: int, B: int, k: int, cap: int, keys_ptr, keys_len: int, fetch_k: int,
+                                      max_fetch: int, out_dist_ptr: int, out_rows_ptr: int, out_keys_ptr, out_count_ptr,
+                                      out_state_ptr, stream) -> None:
+        vp = lambda p: ctypes.c_void_p(int(p) if p else None)  # noqa: E731
+        check(self._h, fn(self._h, vp(q_ptr), int(B), int(k), int(cap), vp(keys_ptr), int(keys_len), int(fetch_k), int(max_fetch),
+                          vp(out_dist_ptr), vp(out_rows_ptr), vp(out_keys_ptr), vp(out_count_ptr), vp(out_state_ptr),
+                          _stream_arg(stream)))
+
+    def search_collapsed_device(self, q_ptr: int, B: int, k: int, cap: int, fetch_k: int, max_fetch: int, out_dist_ptr: int,
+                                out_rows_ptr: int, out_keys_ptr: int | None = None, out_count_ptr: int | None = None,
+                                out_state_ptr: int | None = None, *, keys_ptr: int | None = None, keys_len: int = 0,
+                                stream: int | None = None) -> None:
+        """`search_collapsed` with queries, table and outputs (float64 / int64 / int64 [B, k], int32 [B] count and state) in
+        device memory; complete on return."""
+        self._search_collapsed_device_form(self._lib.mi355dr_search_collapsed_device, q_ptr, B, k, cap, keys_ptr, keys_len,
+                                           fetch_k, max_fetch, out_dist_ptr, out_rows_ptr, out_keys_ptr, out_count_ptr,
+                                           out_state_ptr, stream)
+
+    def search_collapsed_sharded_device(self, q_ptr: int, B: int, k: int, cap: int, fetch_k: int, max_fetch: int,
+                                        out_dist_ptr: int, out_rows_ptr: int, out_keys_ptr: int | None = None,
+                                        out_count_ptr: int | None = None, out_state_ptr: int | None = None, *,
+                                        keys_ptr: int | None = None, keys_len: int = 0, stream: int | None = None) -> None:
+        """The same over the communicator: every rank passes the same arguments (the table is indexed by GLOBAL rows) and
+        receives what one index holding all rows would return."""
+        self._search_collapsed_device_form(self._lib.mi355dr_search_collapsed_sharded_device, q_ptr, B, k, cap, keys_ptr,
+                                           keys_len, fetch_k, max_fetch, out_dist_ptr, out_rows_ptr, out_keys_ptr,
+                                           out_count_ptr, out_state_ptr, stream)
+
+    def _search_collapsed_buffers(self, device_form, queries, k: int, cap: int, keys, fetch_k: int,
+                                  max_fetch: int) -> "CollapsedSearch":
+        """One call of a _device form over buffers of this call: the queries uploaded, the five results downloaded; a numpy
+        table is uploaded for the call, a DeviceKeys is used in place."""
+        q, qp = self._device_queries(queries)
+        B, k = q.shape[0], int(k)
+        outs = (np.empty((B, max(k, 0)), dtype=np.float64), np.empty((B, max(k, 0)), dtype=np.int64),
+                np.empty((B, max(k, 0)), dtype=np.int64), np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32))
+        own = None if keys is None or isinstance(keys, DeviceKeys) else DeviceKeys(self, keys)
+        table = own if own is not None else keys
+        bufs = []
+        try:
+            for a in outs:
+                bufs.append(self.dev_alloc(max(a.nbytes, 8)))
+            device_form(qp, B, k, cap, fetch_k, max_fetch, *bufs, keys_ptr=table.ptr if table is not None else None,
+                        keys_len=table.length if table is not None else 0)
+            for a, b in zip(outs, bufs):
+                if a.size:
+                    self.dev_download(b, a)
+        finally:
+            for b in bufs:
+                self.dev_free(b)
+            self.dev_free(qp)
+            if own is not None:
+                own.close()
+        return CollapsedSearch(*outs)
+
+    def search_collapsed(self, queries, k: int, cap: int, keys, fetch_k: int | None = None,
+                         max_fetch: int = 1024) -> "CollapsedSearch":
+        """The best `k`, at most `cap` per source: `search` whose ranking is walked under the cap.  keys: int64 [keys_len]
+        indexed by the rows `search` returns (negative or beyond the table: no source, never capped), a `DeviceKeys`, or None
+        (the bits of `search(queries, k)`).  The block is searched at `fetch_k` and only the queries whose cap bit deeper
+        are searched again, at twice the width, up to `max_fetch` <= 1024: the result is that of one pass at `max_fetch`
+        whatever `fetch_k` is (default: `collapse_fetch_k`).  Returns CollapsedSearch(dist float64 [B,k], rows int64 [B,k],
+        keys int64 [B,k] (-1: none), count int32 [B] (lines written), state int32 [B] (COLLAPSE_TRUNCATED: fewer than k
+        although the ranking was cut at max_fetch)); NaN / -1 padded."""
+        f = self.collapse_fetch_k(k, fetch_k, max_fetch)
+        if isinstance(keys, DeviceKeys):
+            return self._search_collapsed_buffers(self.search_collapsed_device, queries, k, cap, keys, f, max_fetch)
+        q = self._queries_2d(queries)
+        t = self._host_keys(keys)
+        B, k = q.shape[0], int(k)
+        dist = np.empty((B, max(k, 0)), dtype=np.float64)
+        rows = np.empty((B, max(k, 0)), dtype=np.int64)
+        okeys = np.empty((B, max(k, 0)), dtype=np.int64)
+        count = np.empty(B, dtype=np.int32)
+        state = np.empty(B, dtype=np.int32)
+        check(self._h, self._lib.mi355dr_search_collapsed(
+            self._h, ptr(q, ctypes.c_float), B, k, int(cap), None if t is None else ptr(t, ctypes.c_int64),
+            0 if t is None else t.shape[0], f, int(max_fetch), ptr(dist, ctypes.c_double), ptr(rows, ctypes.c_int64),
+            ptr(okeys, ctypes.c_int64), ptr(count, ctypes.c_int32), ptr(state, ctypes.c_int32)))
+        return CollapsedSearch(dist, rows, okeys, count, state)
+
+    def search_collapsed_sharded(self, queries, k: int, cap: int, keys, fetch_k: int | None = None,
+                                 max_fetch: int = 1024) -> "CollapsedSearch":
+        """`search_collapsed` over the shards; `keys` is indexed by global rows and is the same on every rank."""
+        f = self.collapse_fetch_k(k, fetch_k, max_fetch)
+        return self._search_collapsed_buffers(self.search_collapsed_sharded_device, queries, k, cap, keys, f, max_fetch)
+
+    def search_maxsim_collapsed(self, qtok, q_offsets, k: int, cap: int, keys, fetch_k: int):
+        """`search_maxsim` at `fetch_k`, then the cap over its lists (`collapse_lists`): at most `cap` documents per source
+        among the first `fetch_k`.  The fp32 distances are taken from the search's own list through the kept entries'
+        positions, so their bits are the search's.  Returns (distance float32 [B,k], docs int64 [B,k], keys int64 [B,k],
+        count int32 [B] = kept among the fetch_k)."""
+        dist, docs = self.search_maxsim(qtok, q_offsets, int(fetch_k))
+        got = self.collapse_lists(dist.astype(np.float64), docs, keys, cap, k, with_entries=False)
+        out = np.full(got.pos.shape, np.nan, dtype=np.float32)
+        b, s = np.nonzero(got.pos >= 0)
+        out[b, s] = dist[b, got.pos[b, s]]
+        return out, got.ids, got.keys, got.count
+
+    def search_bm25_collapsed(self, token_lists, k: int, cap: int, keys, fetch_k: int, k1: float = 1.2, b: float = 0.75,
+                              offsets=None):
+        """`search_bm25` at `fetch_k`, then the cap over its lists: at most `cap` documents per source among the first
+        `fetch_k`.  Returns (distance float64 [B,k] = -score, ids int64 [B,k], keys int64 [B,k], count int32 [B])."""
+        dist, ids = self.search_bm25(token_lists, int(fetch_k), k1, b, offsets=offsets)
+        got = self.collapse_lists(dist, ids, keys, cap, k, with_pos=False, with_entries=False)
+        return got.vals, got.ids, got.keys, got.count
 
     # ---- range search: every row within a distance, counted on the device (include/mi355dr.h "range search") ----
     @staticmethod

@@ -190,6 +190,40 @@ class _DevScratch:
                 self.drop(ix, name)
         self._bufs.clear()
 
+    def holds(self, name: str, ptr: int) -> bool:
+        """`name` is still the block at `ptr` (it has not been dropped, released or regrown since)."""
+        return bool(ptr) and self._bufs.get(name, (0, 0))[0] == ptr
+
+
+# The default depth of a `per_source` search over a leg that cannot deepen (`within`, MaxSim, BM25), as a multiple of top_k.
+# Not measured for these legs: 4 is the depth at which the search form needed the fewest extra rounds on sources of 8
+# near-copies (DESIGN.md section 4.8m), taken over as a starting point.  A caller who knows its sources passes source_fetch_k.
+LIST_SOURCE_FETCH_MULT = 4
+
+
+def source_key_table(ids: list, source_of: Any, pos_of_row: np.ndarray | None = None) -> np.ndarray:
+    """The key table of a `per_source` search (include/mi355dr.h "source-capped lists and search") in the id space of one leg:
+    int64, entry j = the source of the chunk the leg returns as id j, -1 where it has none.  `source_of`: primary key -> source
+    (any hashable; a missing key or None = no source, never capped); the sources are numbered in first-seen table order.
+    `pos_of_row`: the leg's id -> table position (`single_rows` of a dense index, whose rows are not table positions once a
+    chunk has no embedding; None: the ids are positions, as the sparse store's and a multi-vector store's are)."""
+    codes: dict = {}
+    by_pos = np.full(len(ids), -1, dtype=np.int64)
+    for p, pk in enumerate(ids):
+        src = source_of.get(pk)
+        if src is not None:
+            by_pos[p] = codes.setdefault(src, len(codes))
+    return by_pos if pos_of_row is None else by_pos[np.asarray(pos_of_row, dtype=np.int64)]
+
+
+class _SourceKeys(NamedTuple):   # one leg's key table on the device, and what it was built from (_UnitIndex.source_keys)
+    source_of: Any
+    table: ChunkTable
+    rows: np.ndarray | None
+    handle: Any          # the index whose device the block was taken on (under a _World: the sharded searcher's)
+    ptr: int
+    length: int
+
 
 class DeviceLists(NamedTuple):
     """One leg's [B, width] lists where its search left them (`dense_lists_device` / `bm25_lists_device`): the handle and
@@ -240,6 +274,9 @@ class _UnitIndex:
         # the fusion as its map (`single_rows_device`; dropped with the other maps in _forget_maps)
         self.scratch = _DevScratch()
         self._single_rows_dev: tuple[np.ndarray, int, int] | None = None   # (the single_rows array it copies, pointer, length)
+        # the `per_source` key tables, one per leg ("single" / "multi" / "sparse"), kept on the device while the mapping, the
+        # table and the leg's layout are the objects they were built from (`source_keys`)
+        self._source_keys: dict[str, _SourceKeys] = {}
 
     def _not_null_positions(self) -> np.ndarray:
         emb = self.table.embedding
@@ -385,6 +422,25 @@ class _UnitIndex:
     def _any_handle(self) -> Mi355Index | None:
         return next((ix for ix in (self.single, self.sparse, self.multi) if ix is not None), None)
 
+    def source_keys(self, leg: str, source_of: Any, handle: Mi355Index) -> Any:
+        """The device key table of a `per_source` search over one leg ("single": indexed by index rows through `single_rows`;
+        "multi" / "sparse": by table position), built by `source_key_table` and uploaded ONCE per mapping: it is reused while
+        `source_of` is the same object, the table and the layout are what it was built from and its block is still held.  A
+        mapping changed in place is a stale one: pass a new object.  Returns a DeviceKeys that owns nothing."""
+        from .index import DeviceKeys  # noqa: PLC0415
+
+        rows = self.single_rows if leg == "single" else None
+        name = "source_keys:" + leg
+        have = self._source_keys.get(leg)
+        if (have is None or have.source_of is not source_of or have.table is not self.table or have.rows is not rows
+                or not self.scratch.holds(name, have.ptr)):
+            host = np.ascontiguousarray(source_key_table(self.table.ids, source_of, rows))
+            ptr = self.scratch.take(handle, name, max(host.nbytes, 8))
+            if host.nbytes:
+                handle.dev_upload(ptr, host)
+            have = self._source_keys[leg] = _SourceKeys(source_of, self.table, rows, handle, ptr, host.shape[0])
+        return DeviceKeys.borrowed(have.ptr if have.length else 0, have.length)
+
     def single_rows_device(self) -> tuple[int, int]:
         """(device pointer, length) of `single_rows` as int64: index row -> table position, the fusion's map for the dense
         leg.  Uploaded once per layout."""
@@ -398,6 +454,10 @@ class _UnitIndex:
         return self._single_rows_dev[1:]
 
     def close(self) -> None:
+        for leg, have in self._source_keys.items():   # (through the handle that took them: under a _World there is no local one)
+            if self.scratch.holds("source_keys:" + leg, have.ptr):
+                self.scratch.drop(have.handle, "source_keys:" + leg)
+        self._source_keys.clear()
         self.scratch.release(self._any_handle())
         self._single_rows_dev = None
         for ix in (self.single, self.multi, self.single_sharded, self.multi_sharded, self.sparse, self.sparse_sharded):
@@ -777,14 +837,23 @@ class Mi355RetrievalService:
     def vector_search(self, query_ids: list[int | str], top_k: int = 10,
                       search_mode: Literal["single", "multi"] = "single", unit: str = "chunk",
                       within: list | None = None, mmr_fetch_k: int | None = None,
-                      mmr_lambda: float = 0.5) -> list[list[dict]]:
+                      mmr_lambda: float = 0.5, per_source: int | None = None, source_of: Any = None,
+                      source_fetch_k: int | None = None) -> list[list[dict]]:
         """Top-k for every query id, scored as one block.  Raises ValueError exactly like the reference.
         `within` (not in the reference's signature; None = today's behaviour): primary keys the search is restricted to --
         the statement with `AND id = ANY(:within)`.  Keys unknown to the table or without a stored embedding are left out.
         `mmr_fetch_k` (None = today's behaviour; single mode only): diversify -- the top_k results are picked from the
         mmr_fetch_k nearest by Maximal Marginal Relevance with weight `mmr_lambda` on the query similarity
-        (Mi355Index.search_mmr), and come in selection order."""
+        (Mi355Index.search_mmr), and come in selection order.
+        `per_source` (None = today's behaviour): at most that many results per source -- `source_of` maps a primary key to
+        its source (a document, a page, a duplicate cluster; a missing key has none and is never capped).  Single mode
+        without `within`: Mi355Index.search_collapsed, which deepens only the queries whose cap bites (first round at
+        `source_fetch_k`, default `Mi355Index.collapse_fetch_k`) and so returns top_k results wherever the first 1024 of the
+        ranking hold them; with `within` and in multi mode: ONE search at `source_fetch_k` (default LIST_SOURCE_FETCH_MULT *
+        top_k, at most 1024), then the cap over its lists -- nothing deepens there, so a query whose cap strikes more than
+        that depth can refill gets fewer than top_k results.  Not together with `mmr_fetch_k`."""
         self._check_mmr(search_mode, mmr_fetch_k)
+        self._check_per_source(top_k, per_source, source_of, source_fetch_k, mmr_fetch_k)
         queries = []
         for qid, q in zip(query_ids, self.get_queries(list(query_ids)), strict=True):
             if q is None:
@@ -799,9 +868,10 @@ class Mi355RetrievalService:
         if not queries:
             return []
         if search_mode == "multi":
-            return self.maxsim_search_by_embeddings([q.embeddings for q in queries], top_k, unit, within=within)
+            return self.maxsim_search_by_embeddings([q.embeddings for q in queries], top_k, unit, within=within,
+                                                    per_source=per_source, source_of=source_of, source_fetch_k=source_fetch_k)
         Q = np.stack([q.embedding for q in queries]).astype(np.float32, copy=False)
-        return self._single_block(Q, top_k, unit, within, mmr_fetch_k, mmr_lambda)
+        return self._single_block(Q, top_k, unit, within, mmr_fetch_k, mmr_lambda, per_source, source_of, source_fetch_k)
 
     # ---- BM25: the lexical leg, over the unit's sparse store (reference retrieval_pipeline.py:398-465) ----
     def _sparse_store(self, u: _UnitIndex, tokenizer: Any) -> Any:
@@ -812,22 +882,29 @@ class Mi355RetrievalService:
         return u.ensure_sparse(tokenizer)
 
     def _bm25_block(self, texts: list[str], top_k: int, tokenizer: Any, k1: float, b: float,
-                    within: list | None = None) -> list[list[dict]]:
+                    within: list | None = None, per_source: int | None = None, source_of: Any = None,
+                    source_fetch_k: int | None = None) -> list[list[dict]]:
         """A page of query texts as one block.  Under a process group every rank holds the whole sparse store and computes the
         same lists -- or, with `shard_sparse=True`, its slice of it, and the library's sharded search returns the same lists.
         score = -distance: positive, higher is better, as the reference negates the operator's (chunk.py:236).
         `within`: among the listed keys only -- a filter under the whole store's statistics, as the reference's statement
-        with `AND id = ANY(:ids)` behaves; unknown keys are left out."""
+        with `AND id = ANY(:ids)` behaves; unknown keys are left out.  `per_source`: ONE search at `source_fetch_k` (default
+        LIST_SOURCE_FETCH_MULT * top_k), then at most that many per source: nothing deepens, a list can come back shorter
+        than top_k (`vector_search`)."""
         from .bm25 import get_tokenizer  # noqa: PLC0415
 
+        self._check_per_source(top_k, per_source, source_of, source_fetch_k, None)
         u = self._unit("chunk")
         ix = self._sparse_store(u, tokenizer)
         tok = get_tokenizer(tokenizer)
         queries = [tok(t) for t in texts]
+        depth = top_k if per_source is None else self._source_depth(top_k, source_fetch_k)
         if within is None:
-            dist, rows = ix.search_bm25(queries, top_k, k1=k1, b=b)
+            dist, rows = ix.search_bm25(queries, depth, k1=k1, b=b)
         else:
-            dist, rows = self._bm25_within(u, ix, queries, top_k, k1, b, within)
+            dist, rows = self._bm25_within(u, ix, queries, depth, k1, b, within)
+        if per_source is not None:
+            dist, rows = self._cap_lists(u, "sparse", ix, dist, rows, per_source, source_of, top_k)
         return self._results_from_block(u.table, np.arange(len(u.table.ids)), rows, -dist, True)
 
     @staticmethod
@@ -866,9 +943,12 @@ class Mi355RetrievalService:
 
     def bm25_search(self, query_ids: list[int | str], top_k: int = 10, tokenizer: Any = "simple",
                     index_name: str = "idx_chunk_bm25", k1: float = 1.2, b: float = 0.75,
+                    per_source: int | None = None, source_of: Any = None, source_fetch_k: int | None = None,
                     within: list | None = None) -> list[list[dict]]:
         """BM25 top-k for every query id, scored as one block (reference bm25_search, :425-465; `index_name` is recorded by the
-        pipeline and unused here).  Raises ValueError exactly like the reference.  `within`: among the listed chunk ids only."""
+        pipeline and unused here).  Raises ValueError exactly like the reference.  `within`: among the listed chunk ids only.
+        `per_source` / `source_of` / `source_fetch_k`: at most that many results per source, as in `vector_search`'s list-capped
+        legs.  They stand BEFORE `within` in the signature: pass `within` by keyword."""
         texts = []
         for qid, q in zip(query_ids, self.get_queries(list(query_ids)), strict=True):
             if q is None:
@@ -876,14 +956,16 @@ class Mi355RetrievalService:
             texts.append(q.contents or "")
         if not texts:
             return []
-        return self._bm25_block(texts, top_k, tokenizer, k1, b, within)
+        return self._bm25_block(texts, top_k, tokenizer, k1, b, within, per_source, source_of, source_fetch_k)
 
     def bm25_search_by_text(self, query_text: str, top_k: int = 10, tokenizer: Any = "simple",
                             index_name: str = "idx_chunk_bm25", k1: float = 1.2, b: float = 0.75,
+                            per_source: int | None = None, source_of: Any = None, source_fetch_k: int | None = None,
                             within: list | None = None) -> list[dict]:
         """BM25 top-k of a raw query text, no query row needed (reference bm25_search_by_text, :398-423).  `within`: among the
-        listed chunk ids only."""
-        return self._bm25_block([query_text], top_k, tokenizer, k1, b, within)[0]
+        listed chunk ids only.  `per_source` / `source_of` / `source_fetch_k`: as in `bm25_search` (before `within`: pass
+        `within` by keyword)."""
+        return self._bm25_block([query_text], top_k, tokenizer, k1, b, within, per_source, source_of, source_fetch_k)[0]
 
     # ---- hybrid fusion on the device: both legs' lists stay in HBM (include/mi355dr.h "hybrid fusion") ----
     def dense_lists_device(self, Q: np.ndarray, top_k: int) -> DeviceLists | None:
@@ -962,6 +1044,46 @@ class Mi355RetrievalService:
             raise NotImplementedError("MMR under a process group: the candidates' vectors lie on different GPUs")
 
     @staticmethod
+    def _check_per_source(top_k: int, per_source: int | None, source_of: Any, source_fetch_k: int | None,
+                          mmr_fetch_k: int | None) -> None:
+        """The `per_source` arguments of every search method, checked before anything is searched (on every rank alike)."""
+        if per_source is None:
+            return
+        if isinstance(per_source, bool) or not isinstance(per_source, (int, np.integer)) or per_source < 1:
+            raise ValueError("per_source must be an integer >= 1")  # noqa: TRY003
+        if source_of is None or not hasattr(source_of, "get"):
+            raise ValueError("per_source needs source_of, a mapping from primary key to source")  # noqa: TRY003
+        if mmr_fetch_k is not None:
+            raise ValueError("per_source and mmr_fetch_k are two selections over one list: pass one of them")  # noqa: TRY003
+        if source_fetch_k is not None and not top_k <= source_fetch_k <= 1024:
+            raise ValueError("source_fetch_k must lie in [top_k, 1024]")  # noqa: TRY003
+
+    @staticmethod
+    def _source_depth(top_k: int, source_fetch_k: int | None) -> int:
+        """The depth the LIST-capped legs (`within`, MaxSim, BM25) search at: `source_fetch_k`, or LIST_SOURCE_FETCH_MULT *
+        top_k within [top_k, 1024].  These legs search once and cap that list: nothing deepens, so a list whose cap strikes more
+        than depth - top_k entries comes back shorter than top_k.  (Not Mi355Index.collapse_fetch_k: its default, top_k, was
+        chosen for the search form, which refills what the cap strikes; here it could only ever shorten the plain top-k.)"""
+        if source_fetch_k is not None:
+            return int(source_fetch_k)
+        return max(int(top_k), min(LIST_SOURCE_FETCH_MULT * int(top_k), 1024))
+
+    @staticmethod
+    def _cap_lists(u: _UnitIndex, leg: str, ix: Any, dist: np.ndarray, rows: np.ndarray, per_source: int, source_of: Any,
+                   top_k: int) -> tuple[np.ndarray, np.ndarray]:
+        """At most `per_source` entries per source in the lists a leg's search returned (Mi355Index.collapse_lists over the
+        leg's device key table): [B, top_k] in the lists' order.  The distances are taken from `dist` through the kept
+        entries' positions, so a MaxSim leg's fp32 values keep their bits."""
+        handle = ix if hasattr(ix, "collapse_lists") else ix.index   # (a ShardedSearcher's lists are global on every rank)
+        got = handle.collapse_lists(np.asarray(dist, dtype=np.float64), np.asarray(rows, dtype=np.int64),
+                                    u.source_keys(leg, source_of, handle), per_source, top_k, with_keys=False,
+                                    with_count=False, with_entries=False)
+        out = np.full(got.pos.shape, np.nan, dtype=np.asarray(dist).dtype)
+        b, s = np.nonzero(got.pos >= 0)
+        out[b, s] = np.asarray(dist)[b, got.pos[b, s]]
+        return out, got.ids
+
+    @staticmethod
     def _results_from_block(table: ChunkTable, pos_of_row: np.ndarray, rows: np.ndarray, scores: np.ndarray,
                             with_content: bool) -> list[list[dict]]:
         """[B,k] index rows (-1 padded at the tail) + float64 scores -> the reference's list of result dicts per query.
@@ -989,11 +1111,21 @@ class Mi355RetrievalService:
         return list(known), np.fromiter(known.values(), dtype=np.int64, count=len(known))
 
     def _single_block(self, Q: np.ndarray, top_k: int, unit: str, within: list | None = None,
-                      mmr_fetch_k: int | None = None, mmr_lambda: float = 0.5) -> list[list[dict]]:
+                      mmr_fetch_k: int | None = None, mmr_lambda: float = 0.5, per_source: int | None = None,
+                      source_of: Any = None, source_fetch_k: int | None = None) -> list[list[dict]]:
         u = self._unit(unit)
         # (one process per GPU, every rank: local top-k of its rows, all-gather, merge -> the same global lists)
         searcher = u.single_searcher(self._world)
-        if mmr_fetch_k is not None:
+        if per_source is not None:
+            handle = searcher if hasattr(searcher, "collapse_lists") else searcher.index
+            if within is None:   # only the queries whose cap bites are searched deeper (under a _World: on every rank alike)
+                got = searcher.search_collapsed(Q, top_k, per_source, u.source_keys("single", source_of, handle), source_fetch_k)
+                dist, rows = got.dist, got.rows
+            else:
+                depth = self._source_depth(top_k, source_fetch_k)
+                dist, rows = searcher.search_subset(Q, depth, self._single_rows_of(u, within)[1])
+                dist, rows = self._cap_lists(u, "single", searcher, dist, rows, per_source, source_of, top_k)
+        elif mmr_fetch_k is not None:
             if within is None:
                 dist, rows = searcher.search_mmr(Q, top_k, mmr_fetch_k, mmr_lambda)
             else:   # the mmr_fetch_k nearest of the listed rows are each query's pool (-1 padding is skipped by the library)
@@ -1010,11 +1142,14 @@ class Mi355RetrievalService:
 
     def vector_search_by_embedding(self, embedding: list[float], top_k: int = 10, unit: str = "chunk",
                                    within: list | None = None, mmr_fetch_k: int | None = None,
-                                   mmr_lambda: float = 0.5) -> list[dict]:
+                                   mmr_lambda: float = 0.5, per_source: int | None = None, source_of: Any = None,
+                                   source_fetch_k: int | None = None) -> list[dict]:
         self._check_mmr("single", mmr_fetch_k)
+        self._check_per_source(top_k, per_source, source_of, source_fetch_k, mmr_fetch_k)
         if len(embedding) == 0:  # reference: `if not query_vector: return []` (base.py:403-404)
             return []
-        return self._single_block(np.asarray(embedding, dtype=np.float32)[None, :], top_k, unit, within, mmr_fetch_k, mmr_lambda)[0]
+        return self._single_block(np.asarray(embedding, dtype=np.float32)[None, :], top_k, unit, within, mmr_fetch_k, mmr_lambda,
+                                  per_source, source_of, source_fetch_k)[0]
 
     # ---- range search: everything within a distance, and how many (not in the reference's service) ----
     def _range_block(self, Q: np.ndarray, max_distance, limit: int, unit: str) -> list[tuple[list[dict], int]]:
@@ -1146,7 +1281,12 @@ class Mi355RetrievalService:
         return {pk: 1.0 - float(dv) for pk, dv in zip(known, dist)}
 
     def maxsim_search_by_embeddings(self, query_vectors: list, top_k: int, unit: str = "chunk",
-                                    within: list | None = None) -> list[list[dict]]:
+                                    within: list | None = None, per_source: int | None = None, source_of: Any = None,
+                                    source_fetch_k: int | None = None) -> list[list[dict]]:
+        """`per_source` / `source_of` / `source_fetch_k` (None = today's behaviour): ONE MaxSim search at `source_fetch_k`
+        (default LIST_SOURCE_FETCH_MULT * top_k), then at most `per_source` results per source: nothing deepens, a list can
+        come back shorter than top_k (`vector_search`)."""
+        self._check_per_source(top_k, per_source, source_of, source_fetch_k, None)
         u = self._unit(unit)
         ix = u.multi_searcher(self._world)
         dim = u.table.mv_tokens.shape[1]
@@ -1158,10 +1298,13 @@ class Mi355RetrievalService:
             return out
         qtok = np.concatenate([mats[i] for i in live], axis=0)
         qoff = np.concatenate([[0], np.cumsum([lens[i] for i in live])]).astype(np.int32)
+        depth = top_k if per_source is None else self._source_depth(top_k, source_fetch_k)
         if within is None:
-            dist, rows = ix.search_maxsim(qtok, qoff, top_k)
+            dist, rows = ix.search_maxsim(qtok, qoff, depth)
         else:
-            dist, rows = self._maxsim_within(u, ix, qtok, qoff, top_k, within)
+            dist, rows = self._maxsim_within(u, ix, qtok, qoff, depth, within)
+        if per_source is not None:
+            dist, rows = self._cap_lists(u, "multi", ix, dist, rows, per_source, source_of, top_k)
         # reference: score = -distance / n_query_vectors (retrieval_pipeline.py:511-514): float(f32) negated, divided
         n_q = np.maximum(1, np.asarray([lens[i] for i in live], dtype=np.int64))[:, None]
         scores = -dist.astype(np.float64) / n_q

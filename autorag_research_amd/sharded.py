@@ -437,6 +437,14 @@ class ShardedSearcher:
         self._library_comm("search_mmr", "search_mmr_sharded")
         return self.index.search_mmr_sharded(queries, k, fetch_k, lambda_mult)
 
+    def search_collapsed(self, queries, k: int, cap: int, keys, fetch_k: int | None = None, max_fetch: int = 1024):
+        """Mi355Index.search_collapsed over the row-sharded corpus: at most `cap` rows per source, the table indexed by GLOBAL
+        rows and the same on every rank; only the queries whose cap bites deeper are searched again, on every rank alike."""
+        if self.world == 1 and not self.force_pipeline:
+            return self.index.search_collapsed(queries, k, cap, keys, fetch_k, max_fetch)
+        self._library_comm("search_collapsed", "search_collapsed_sharded")
+        return self.index.search_collapsed_sharded(queries, k, cap, keys, fetch_k, max_fetch)
+
     def mmr_select(self, queries, k: int, cand_rows, lambda_mult: float = 0.5):
         """Mi355Index.mmr_select over the row-sharded corpus: the same pools (global rows) on every rank."""
         if self.world == 1 and not self.force_pipeline:

@@ -692,6 +692,69 @@ int mi355dr_fuse_lists(mi355dr_index* idx, const double* vals1, const int64_t* i
                        const double* vals2, const int64_t* ids2, int w2, const int64_t* map2, int64_t map2_len, int B, int k_out,
                        const mi355dr_fuse_opts* opts, double* out_vals, int64_t* out_ids, int32_t* out_count /* may be NULL */); /* all host */
 
+/* ---- source-capped lists and search: at most c results per source, on the device ----
+ * Every retrieval unit has a source -- a chunk its document, an image chunk its page, a near-duplicate its cluster -- and a top-k
+ * often spends most of k on one of them.  These entry points answer "the best k, at most cap per source" (Elasticsearch's
+ * collapse, Qdrant's and Milvus' group search) over lists where the searches leave them, and as a search that deepens only the
+ * queries that need it.
+ *   Key table: keys int64 [keys_len], indexed by the id exactly as a list carries it -- the global id as the searches return it
+ *     (the parent's ids on a view, global rows under a communicator, the common id space after a fusion).  An entry HAS a key
+ *     when 0 <= id < keys_len and keys[id] >= 0; otherwise it has none (a NULL table with keys_len == 0: no entry has one).
+ *     Every non-negative int64, INT64_MAX included, is a real key: "no key" travels as a bit of its own, not as a value.
+ *   The walk, over one list of w (value, id) entries IN THE ORDER GIVEN (the list order is the ranking; nothing is re-sorted by
+ *     value): a slot with id < 0 is no entry; a slot with an id and a NaN value is one (an irregular row's result).  An entry is
+ *     KEPT iff it has no key, or fewer than cap earlier entries of the same list have its key; an id listed twice is two
+ *     entries.  Output: the first k_out kept entries in list order -- the value with the bits it came with (+0.0, -0.0, +-inf
+ *     and NaN payloads untouched), the id as given -- and NaN / -1 behind them.  Optional outputs (NULL skips one):
+ *     out_keys [B, k_out] int64, the key, -1 for no key and for tail slots; out_pos [B, k_out] int32, the entry's slot in the
+ *     input list, -1 for tail slots; out_count [B] int32, kept entries of the WHOLE list (it may exceed k_out); out_entries [B]
+ *     int32, entries of the list.
+ *   mi355dr_collapse_lists_device: over device lists.  Stateless like mi355dr_merge_groups_device (it reads no index state: the
+ *     lists may be another handle's; allowed on a view); under the handle's mutex; complete on return.
+ *   mi355dr_collapse_lists: the same with lists, table and results on the host, staged through buffers the index owns and grows
+ *     (they count in "hbm_bytes_resident"); a failed allocation returns MI355DR_E_NOMEM with nothing changed.
+ *   MI355DR_E_INVALID: B < 0, w <= 0, cap <= 0, k_out <= 0, keys_len < 0, a null pointer with work to do (lists, results, a
+ *     null table with keys_len > 0), a non-null table with keys_len == 0.  MI355DR_E_UNSUPPORTED: w > 4096, k_out > 4096.
+ *     B == 0 is a valid no-op.  A refused call changes nothing.
+ *   mi355dr_search_collapsed / _device: the result of query q is the walk over q's ranking -- the ordinary search's total order
+ *     -- cut to its first max_fetch entries, at k_out = k.  out_count[q]: lines written, at most k.  out_state[q] has
+ *     MI355DR_COLLAPSE_TRUNCATED iff fewer than k were kept ALTHOUGH the ranking was cut (it had max_fetch entries).  out_keys,
+ *     out_count and out_state may be NULL.  keys: HOST in the host form, device in the _device form; keys == NULL returns the
+ *     bits of mi355dr_search at k.  1 <= k <= fetch_k <= max_fetch <= 1024, else MI355DR_E_INVALID (above 1024:
+ *     MI355DR_E_UNSUPPORTED); cap and the table under the rules above.
+ *   Schedule: the result does not depend on fetch_k, only the cost does.  The block is searched at f = fetch_k (screened, fix-ups
+ *     completed) and collapsed; a query is finished when it kept k, when its ranking ended (entries < f), or when f ==
+ *     max_fetch.  The unfinished queries, and only they, are gathered and searched again at min(2 f, max_fetch), their lists
+ *     collapsed into their own result lines; and so on.  Exact, because under the total order the top-f list is a prefix of the
+ *     top-2f list and the verdict on an entry depends on the entries before it alone.
+ *   B above 1024 runs in internal blocks; the call first completes whatever search is in flight and is complete on return; it
+ *     works on a view (it takes no global ids as input: the table is indexed by the parent's ids the view returns).
+ *   mi355dr_search_collapsed_sharded_device: the same over the communicator (the sharded block search in the local one's
+ *     place): mi355dr_comm_init first, a view refuses, world * max_fetch <= 4096 (else MI355DR_E_UNSUPPORTED).  Every rank
+ *     passes the same arguments, sees the same merged lists, takes the same decisions and makes the same collective calls.
+ *   Stats: "collapse_calls" (the list forms), "collapse_searches" (the search forms), "collapse_queries" (their B, summed),
+ *     "collapse_researched" ((query, round) re-searches, summed), "collapse_truncated" (queries returned truncated). */
+#define MI355DR_COLLAPSE_TRUNCATED 1
+int mi355dr_collapse_lists_device(mi355dr_index* idx, const double* vals_dev, const int64_t* ids_dev, int w, int B,
+                                  const int64_t* keys_dev /* may be NULL */, int64_t keys_len, int cap, int k_out,
+                                  double* out_vals_dev, int64_t* out_ids_dev, int64_t* out_keys_dev /* may be NULL */,
+                                  int32_t* out_pos_dev /* may be NULL */, int32_t* out_count_dev /* may be NULL */,
+                                  int32_t* out_entries_dev /* may be NULL */, void* stream);
+int mi355dr_collapse_lists(mi355dr_index* idx, const double* vals, const int64_t* ids, int w, int B, const int64_t* keys,
+                           int64_t keys_len, int cap, int k_out, double* out_vals, int64_t* out_ids, int64_t* out_keys,
+                           int32_t* out_pos, int32_t* out_count, int32_t* out_entries); /* all host */
+int mi355dr_search_collapsed(mi355dr_index* idx, const float* queries, int B, int k, int cap, const int64_t* keys /* HOST */,
+                             int64_t keys_len, int fetch_k, int max_fetch, double* out_dist, int64_t* out_rows,
+                             int64_t* out_keys /* may be NULL */, int32_t* out_count /* may be NULL */,
+                             int32_t* out_state /* may be NULL */);
+int mi355dr_search_collapsed_device(mi355dr_index* idx, const float* queries_dev, int B, int k, int cap, const int64_t* keys_dev,
+                                    int64_t keys_len, int fetch_k, int max_fetch, double* out_dist_dev, int64_t* out_rows_dev,
+                                    int64_t* out_keys_dev, int32_t* out_count_dev, int32_t* out_state_dev, void* stream);
+int mi355dr_search_collapsed_sharded_device(mi355dr_index* idx, const float* queries_dev, int B, int k, int cap,
+                                            const int64_t* keys_dev, int64_t keys_len, int fetch_k, int max_fetch,
+                                            double* out_dist_dev, int64_t* out_rows_dev, int64_t* out_keys_dev,
+                                            int32_t* out_count_dev, int32_t* out_state_dev, void* stream);
+
 /* ---- Guided Query Refinement of candidate pools (GQR hybrid pipeline) ----
  * Replaces the per-query numpy loops of autorag_research/pipelines/retrieval/gqr_hybrid.py: `_optimize_query_embedding`
  * (:321-340), `_optimize_query_multi_embedding` (:342-362), `_optimize_in_score_space` (:306-319).  Float64 throughout
@@ -921,6 +984,8 @@ int mi355dr_score_bm25_subset_sharded(mi355dr_index* idx, const int32_t* q_token
  *          "mmr_searches" / "mmr_queries" / "mmr_pairs_scored" (mi355dr_search_mmr* and mi355dr_mmr_select, described there),
  *          "group_searches" / "group_subqueries" / "groups_merged" (mi355dr_search_groups* and mi355dr_merge_groups_device, described there),
  *          "fuse_calls" / "fuse_queries" (mi355dr_fuse_lists*, described there),
+ *          "collapse_calls" / "collapse_searches" / "collapse_queries" / "collapse_researched" / "collapse_truncated"
+ *          (mi355dr_collapse_lists* and mi355dr_search_collapsed*, described there),
  *          "range_searches" / "range_queries" / "range_in_range" / "range_candidates" / "range_rescored" / "range_redo_chunks" /
  *          "range_fallback_queries" (mi355dr_search_range*, described there),
  *          "rows_searches" / "rows_queries" / "rows_skipped" (mi355dr_search_rows* and mi355dr_search_range_rows*, described there),
@@ -928,7 +993,8 @@ int mi355dr_score_bm25_subset_sharded(mi355dr_index* idx, const int32_t* q_token
  *          "maxsim_subset_fallbacks" (mi355dr_search_maxsim_subset, described there),
  *          "view" / "view_rows" / "view_docs" (mi355dr_view_create: 1 on a view / the rows / the documents it holds),
  *          "hbm_bytes_resident" (the single-vector corpus with its shadows at its capacity + the multi-vector store's two
- *          images, offset table and granule-packed copy as allocated now). */
+ *          images, offset table and granule-packed copy as allocated now + the staging and block state of the source-capped
+ *          forms as grown so far). */
 int mi355dr_set_option(mi355dr_index* idx, const char* key, int64_t value);
 int mi355dr_get_stat(mi355dr_index* idx, const char* key, int64_t* out);
 int mi355dr_reset_stats(mi355dr_index* idx);
