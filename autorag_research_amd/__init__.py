@@ -8,7 +8,7 @@ store.py / service.py / pipelines.py (host-side mirror of the reference's reposi
 pipeline interfaces for this path), heaven.py (HEAVEN two-stage caller: cosine top-N then candidate MaxSim),
 gqr.py (Guided Query Refinement caller: candidate-pool refinement loops on the GPU), hybrid.py (RRF / convex-combination
 fusion of two child pipelines), bm25.py (BM25 over the chunk contents: tokenizers, the pipeline; scored by the library's
-sparse store), hyde.py (hypothetical-document retrieval), decompose.py (question-decomposition retrieval: the
+sparse store), hyde.py (hypothetical-document retrieval), feedback.py (Rocchio pseudo-relevance feedback retrieval), decompose.py (question-decomposition retrieval: the
 sub-questions' searches fused in one grouped call on the GPU),
 metrics.py (retrieval metrics), embeddings.py (embedding interfaces), shards.py (fp32 shard files: memory-mapped,
 chunked load), sharded.py (row-sharded multi-GPU search).

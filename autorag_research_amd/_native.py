@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "mi355dr_search_bm25_subset_sharded_device", "mi355dr_score_sparse_subset_sharded", "mi355dr_score_bm25_subset_sharded",
     "mi355dr_collapse_lists", "mi355dr_collapse_lists_device", "mi355dr_search_collapsed", "mi355dr_search_collapsed_device",
     "mi355dr_search_collapsed_sharded_device",
+    "mi355dr_combine_rows", "mi355dr_combine_rows_device", "mi355dr_search_examples", "mi355dr_search_examples_device",
+    "mi355dr_search_feedback", "mi355dr_search_feedback_device",
     "mi355dr_set_option", "mi355dr_get_stat",
     "mi355dr_reset_stats", "mi355dr_timer_start", "mi355dr_timer_stop", "mi355dr_synchronize",
     "mi355dr_dev_alloc", "mi355dr_dev_free", "mi355dr_dev_upload", "mi355dr_dev_download",
@@ -190,6 +192,19 @@ def load() -> ctypes.CDLL:
     L.mi355dr_search_range_rows.argtypes = [vp, i64p, c_int, f64p, c_int, c_int, f64p, i64p, i64p]
     L.mi355dr_search_range_rows_device.restype = c_int
     L.mi355dr_search_range_rows_device.argtypes = [vp, i64p, c_int, f64p, c_int, c_int, vp, vp, vp, vp]
+    dbl = ctypes.c_double
+    L.mi355dr_combine_rows.restype = c_int
+    L.mi355dr_combine_rows.argtypes = [vp, f32p, c_int, i64p, c_int, i64p, c_int, dbl, dbl, dbl, f32p, i32p]
+    L.mi355dr_combine_rows_device.restype = c_int
+    L.mi355dr_combine_rows_device.argtypes = [vp, vp, c_int, i64p, c_int, i64p, c_int, dbl, dbl, dbl, vp, vp, vp]
+    L.mi355dr_search_examples.restype = c_int
+    L.mi355dr_search_examples.argtypes = [vp, f32p, c_int, i64p, c_int, i64p, c_int, dbl, dbl, dbl, c_int, c_int, f64p, i64p]
+    L.mi355dr_search_examples_device.restype = c_int
+    L.mi355dr_search_examples_device.argtypes = [vp, vp, c_int, i64p, c_int, i64p, c_int, dbl, dbl, dbl, c_int, c_int, vp, vp, vp]
+    L.mi355dr_search_feedback.restype = c_int
+    L.mi355dr_search_feedback.argtypes = [vp, f32p, c_int, c_int, c_int, dbl, dbl, f64p, i64p]
+    L.mi355dr_search_feedback_device.restype = c_int
+    L.mi355dr_search_feedback_device.argtypes = [vp, vp, c_int, c_int, c_int, dbl, dbl, vp, vp, vp]
     L.mi355dr_view_create.restype = c_int
     L.mi355dr_view_create.argtypes = [vp, i64p, i64, i64p, i64, ctypes.POINTER(vp)]
     L.mi355dr_add_multivec.restype = c_int

@@ -243,6 +243,27 @@ struct RowQueryBufs {
         return e;
     }
 };
+// search by examples / feedback (mi355dr_combine_rows* / mi355dr_search_examples* / mi355dr_search_feedback*; DESIGN.md
+// section 4.8n): one block's listed ids [nb, mp] / [nb, mn], the combined query vectors [nb, dim] and validity words, the inner
+// passes' lists [nb, stride], the feedback host form's copy of the block's queries (a fix-up of pass 1 overwrites qdev) and
+// the two counters of k_combine_rows (skipped positions, invalid slots)
+struct ExampleBufs {
+    DevBuf<int64_t> pos, neg, cand_rows;
+    DevBuf<float> q, base;
+    DevBuf<int> valid;
+    DevBuf<double> cand_dist;
+    DevBuf<unsigned long long> counters;
+    hipError_t reserve(size_t nb, size_t mp, size_t mn, size_t stride, size_t dim, bool own_base) {
+        hipError_t e = grow_each(nb * mp, pos);
+        if (!e) e = grow_each(nb * mn, neg);
+        if (!e) e = grow_each(nb, valid);
+        if (!e) e = grow_each(nb * dim, q);
+        if (!e) e = grow_each(nb * stride, cand_dist, cand_rows);
+        if (!e) e = grow_each(2, counters);
+        if (!e && own_base) e = grow_each(nb * dim, base);
+        return e;
+    }
+};
 // row-sharded derived searches (mi355dr_search_*_sharded_device / mi355dr_mmr_select_sharded): this
 // rank's payload of an all-gather and the gathered payloads of all ranks (packed lists, query rows, host candidate lists: one
 // collective at a time, in stream order), the MMR candidate stage and its gathered form, the counter k_rows_gather's own
@@ -316,6 +337,7 @@ struct mi355dr_index {
     mi355::CollapseBufs clp;
     mi355::RangeBufs rng;
     mi355::RowQueryBufs rowq;
+    mi355::ExampleBufs exq;
     mi355::ShardBufs shd;
     // a view (mi355dr_view_create; DESIGN.md "Views"): a read-only index built from listed rows / documents of a parent.  The
     // maps are null on every other index: the result-writing kernels then add row_offset instead
@@ -460,6 +482,10 @@ struct mi355dr_index {
             s_range_redo_chunks = 0, s_range_fallback_queries = 0;
     // mi355dr_search_rows* / mi355dr_search_range_rows*: calls, slots, slots whose id was outside the shard or a removed row
     int64_t s_rows_searches = 0, s_rows_queries = 0, s_rows_skipped = 0;
+    // mi355dr_combine_rows* / mi355dr_search_examples* / mi355dr_search_feedback*: calls of the three, their slots, example
+    // positions skipped, slots answered NaN / -1; of the calls, the feedback ones
+    int64_t s_examples_searches = 0, s_examples_queries = 0, s_examples_skipped = 0, s_examples_skipped_slots = 0,
+            s_feedback_searches = 0;
     // the row-sharded derived searches: calls per family, bytes this rank received through their all-gathers
     int64_t s_shard_range_searches = 0, s_shard_rows_searches = 0, s_shard_mmr_searches = 0, s_shard_gather_bytes = 0;
     // the row-sharded sparse forms: calls of the four searches, calls of the two score forms (their gathers add to the above)

@@ -29,6 +29,7 @@ inline bool screen_rq_has(int ksteps) { return ksteps >= 1 && ksteps <= 6; }
 #include "collapse_plan.h"
 #include "k_range.h"
 #include "k_rows.h"
+#include "k_combine.h"
 #include "k_shard.h"
 
 #include <functional>
@@ -2746,6 +2747,191 @@ int mi355dr_search_range_rows_device(mi355dr_index* idx, const int64_t* row_ids,
                             out_count_dev, stream, /*host=*/false);
 }
 
+// ---- search by examples / Rocchio feedback: queries built on the device (csrc/k_combine.h) ---------
+namespace {
+enum ExamplesForm { kExCombine, kExSearch, kExFeedback };
+struct ExamplesArgs {
+    const char* what;
+    ExamplesForm form;
+    const float* queries;  // the base vectors [B, dim] or null (feedback: the queries)
+    int B;
+    const int64_t* pos_ids;  // HOST [B, mp]
+    int mp;
+    const int64_t* neg_ids;  // HOST [B, mn]
+    int mn;
+    double alpha, beta, gamma;
+    int k, fb_k, flags;
+    float* out_vectors;  // kExCombine: [B, dim]
+    int32_t* out_valid;  // kExCombine: [B]
+    double* out_dist;    // the searches: [B, k]
+    int64_t* out_rows;
+    void* stream;
+    bool host;
+};
+
+inline bool weight_ok(double w) { return std::isfinite(w) && w >= 0.0; }
+
+int launch_combine(mi355dr_index* idx, hipStream_t s, const float* q, int nb, const int64_t* pos, int mp, const int64_t* neg,
+                   int mn, const double* pos_dist, const ExamplesArgs& a, float* q_out, int* valid) {
+    hipLaunchKernelGGL(k_combine_rows, dim3(nb), dim3(kCombineThreads), 0, s, q, pos, mp, neg, mn, pos_dist, idx->row_offset,
+                       idx->n, (const float*)idx->rows.p, (const float*)idx->nrm2.p, idx->dim, idx->metric, a.alpha, a.beta,
+                       a.gamma, q_out, valid, idx->exq.counters.p);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+int launch_strike(mi355dr_index* idx, hipStream_t s, int nb, int stride, int mp, int mn, bool strike, int k, double* od,
+                  int64_t* orow) {
+    hipLaunchKernelGGL(k_examples_strike, dim3(nb), dim3(kCombineThreads), 0, s, (const double*)idx->exq.cand_dist.p,
+                       (const int64_t*)idx->exq.cand_rows.p, stride, (const int64_t*)idx->exq.pos.p, mp,
+                       (const int64_t*)idx->exq.neg.p, mn, strike ? 1 : 0, (const int*)idx->exq.valid.p, idx->n > 0 ? 0 : 1, k,
+                       od, orow);
+    HIPCHECK(idx, hipGetLastError());
+    return MI355DR_OK;
+}
+
+int examples_impl(mi355dr_index* idx, const ExamplesArgs& a) {
+    const bool keep = (a.flags & MI355DR_EXAMPLES_KEEP) != 0;
+    const bool strike = a.form == kExSearch && !keep;
+    const int B = a.B, d = idx ? idx->dim : 0;
+    // the width of the inner pass's lists: room for every listed row (feedback: both passes share the lists)
+    const int64_t stride = a.form == kExSearch ? (int64_t)a.k + (strike ? (int64_t)a.mp + a.mn : 0)
+                                               : a.form == kExFeedback ? std::max(a.k, a.fb_k) : 0;
+    Call c;
+    CHECK(begin_call(idx, a.what, a.stream, kCallNoView | kCallDrain, c, [&]() -> int {
+        const std::string w(a.what);
+        if (B < 0) return fail(idx, MI355DR_E_INVALID, w + ": B must be >= 0");
+        if (a.mp < 0 || a.mn < 0) return fail(idx, MI355DR_E_INVALID, w + ": mp and mn must be >= 0");
+        if (a.form != kExCombine && a.k <= 0) return fail(idx, MI355DR_E_INVALID, w + ": k must be > 0");
+        if (a.form == kExFeedback && a.fb_k <= 0) return fail(idx, MI355DR_E_INVALID, w + ": fb_k must be > 0");
+        if (!weight_ok(a.alpha) || !weight_ok(a.beta) || !weight_ok(a.gamma))
+            return fail(idx, MI355DR_E_INVALID, w + ": alpha, beta and gamma must be finite and >= 0");
+        if (a.flags & ~MI355DR_EXAMPLES_KEEP) return fail(idx, MI355DR_E_INVALID, w + ": unknown flag bits");
+        if (a.form != kExFeedback && !a.queries && a.mp == 0)
+            return fail(idx, MI355DR_E_INVALID, w + ": neither a base vector nor a positive example");
+        if (B > 0) {
+            const bool outs = a.form == kExCombine ? a.out_vectors && a.out_valid : a.out_dist && a.out_rows;
+            if (!outs || (a.mp > 0 && !a.pos_ids) || (a.mn > 0 && !a.neg_ids) || (a.form == kExFeedback && !a.queries))
+                return fail(idx, MI355DR_E_INVALID, w + ": null buffer");
+        }
+        if (a.form == kExFeedback) {
+            if (a.fb_k > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, w + ": fb_k exceeds 1024");
+            if (a.k > kKMax) return fail(idx, MI355DR_E_UNSUPPORTED, w + ": k exceeds 1024");
+        } else {
+            if ((int64_t)a.mp + a.mn > kCombineMaxExamples) return fail(idx, MI355DR_E_UNSUPPORTED, w + ": mp + mn exceeds 1024");
+            if (stride > kKMax)
+                return fail(idx, MI355DR_E_UNSUPPORTED, w + (strike ? ": k + mp + mn (room for every listed row)" : ": k") + " exceeds 1024");
+        }
+        return MI355DR_OK;
+    }));
+    if (B == 0) return MI355DR_OK;
+    hipStream_t s = c.s;
+    const int nb_max = std::min(B, kQBlockMax);
+    const int mp = a.form == kExFeedback ? a.fb_k : a.mp, mn = a.form == kExFeedback ? 0 : a.mn;
+    const bool own_base = a.form == kExFeedback && a.host;
+    // (every allocation before any work; the feedback form's positives are pass 1's own rows: no id buffer)
+    HIPCHECK(idx, idx->exq.reserve(nb_max, a.form == kExFeedback ? 0 : mp, mn, (size_t)stride, d, own_base));
+    HIPCHECK(idx, hipMemsetAsync(idx->exq.counters.p, 0, 2 * sizeof(unsigned long long), s));
+    const CallIO<> io{a.host, s, a.queries, {a.out_dist, a.out_rows, nullptr}, a.k};
+    for (int b0 = 0; b0 < B; b0 += kQBlockMax) {
+        const int nb = std::min(kQBlockMax, B - b0);
+        const float* q = nullptr;
+        if (a.queries) CHECK(block_queries(idx, io, b0, nb, &q));
+        if (a.form != kExFeedback) {
+            // (the ids are pageable: HIP stages such a copy before the call returns, as for the id lists of mutate_rows_impl)
+            if (mp > 0)
+                HIPCHECK(idx, hipMemcpyAsync(idx->exq.pos.p, a.pos_ids + (int64_t)b0 * mp, (size_t)nb * mp * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            if (mn > 0)
+                HIPCHECK(idx, hipMemcpyAsync(idx->exq.neg.p, a.neg_ids + (int64_t)b0 * mn, (size_t)nb * mn * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        }
+        if (a.form == kExCombine) {
+            float* qv = a.host ? idx->exq.q.p : a.out_vectors + (int64_t)b0 * d;
+            int* vv = a.host ? idx->exq.valid.p : (int*)a.out_valid + b0;
+            CHECK(launch_combine(idx, s, q, nb, idx->exq.pos.p, mp, idx->exq.neg.p, mn, nullptr, a, qv, vv));
+            if (a.host) {
+                HIPCHECK(idx, hipMemcpyAsync(a.out_vectors + (int64_t)b0 * d, qv, (size_t)nb * d * sizeof(float), hipMemcpyDeviceToHost, s));
+                HIPCHECK(idx, hipMemcpyAsync(a.out_valid + b0, vv, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, s));
+            }
+            HIPCHECK(idx, hipStreamSynchronize(s));  // (the next block reuses the id and query buffers)
+            continue;
+        }
+        const BlockOut<int64_t> o = block_outputs(idx, io, b0);
+        if (a.form == kExSearch) {
+            CHECK(launch_combine(idx, s, q, nb, idx->exq.pos.p, mp, idx->exq.neg.p, mn, nullptr, a, idx->exq.q.p, idx->exq.valid.p));
+            // the ordinary search of the combined block (screened, fix-ups completed); an empty index: the lists are not read
+            if (idx->n > 0) CHECK(search_block(idx, s, idx->exq.q.p, nb, (int)stride, idx->exq.cand_dist.p, idx->exq.cand_rows.p));
+            CHECK(launch_strike(idx, s, nb, (int)stride, mp, mn, strike, a.k, o.dist, o.rows));
+        } else {
+            if (own_base) {  // (a fix-up of pass 1 overwrites qdev, where block_queries staged the block)
+                HIPCHECK(idx, hipMemcpyAsync(idx->exq.base.p, q, (size_t)nb * d * sizeof(float), hipMemcpyDeviceToDevice, s));
+                q = idx->exq.base.p;
+            }
+            if (idx->n > 0) {
+                // pass 1 at fb_k; its lists are the positives, read where they lie
+                CHECK(search_block(idx, s, q, nb, a.fb_k, idx->exq.cand_dist.p, idx->exq.cand_rows.p));
+            } else {
+                HIPCHECK(idx, hipMemsetAsync(idx->exq.cand_rows.p, 0xFF, (size_t)nb * a.fb_k * sizeof(int64_t), s));  // (-1: no positives)
+                HIPCHECK(idx, hipMemsetAsync(idx->exq.cand_dist.p, 0xFF, (size_t)nb * a.fb_k * sizeof(double), s));   // (NaN)
+            }
+            CHECK(launch_combine(idx, s, q, nb, idx->exq.cand_rows.p, a.fb_k, nullptr, 0, idx->exq.cand_dist.p, a, idx->exq.q.p,
+                                 idx->exq.valid.p));
+            // pass 2 at k over the same lists (the combination has been read: stream order), nothing struck
+            if (idx->n > 0) CHECK(search_block(idx, s, idx->exq.q.p, nb, a.k, idx->exq.cand_dist.p, idx->exq.cand_rows.p));
+            CHECK(launch_strike(idx, s, nb, a.k, 0, 0, false, a.k, o.dist, o.rows));
+        }
+        CHECK(block_return(idx, io, b0, nb, o));
+        HIPCHECK(idx, hipStreamSynchronize(s));  // (the next block reuses the id, query and list buffers)
+    }
+    unsigned long long counters[2] = {0, 0};
+    HIPCHECK(idx, hipMemcpy(counters, idx->exq.counters.p, sizeof(counters), hipMemcpyDeviceToHost));
+    idx->s_examples_searches++;
+    idx->s_examples_queries += B;
+    idx->s_examples_skipped += (int64_t)counters[0];
+    idx->s_examples_skipped_slots += (int64_t)counters[1];
+    if (a.form == kExFeedback) idx->s_feedback_searches++;
+    return MI355DR_OK;
+}
+}  // namespace
+
+int mi355dr_combine_rows(mi355dr_index* idx, const float* queries, int B, const int64_t* pos_ids, int mp, const int64_t* neg_ids,
+                         int mn, double alpha, double beta, double gamma, float* out_vectors, int32_t* out_valid) {
+    return examples_impl(idx, ExamplesArgs{"combine_rows", kExCombine, queries, B, pos_ids, mp, neg_ids, mn, alpha, beta, gamma, 0, 0,
+                                           0, out_vectors, out_valid, nullptr, nullptr, nullptr, /*host=*/true});
+}
+
+int mi355dr_combine_rows_device(mi355dr_index* idx, const float* queries_dev, int B, const int64_t* pos_ids, int mp,
+                                const int64_t* neg_ids, int mn, double alpha, double beta, double gamma, float* out_vectors_dev,
+                                int32_t* out_valid_dev, void* stream) {
+    return examples_impl(idx, ExamplesArgs{"combine_rows", kExCombine, queries_dev, B, pos_ids, mp, neg_ids, mn, alpha, beta, gamma,
+                                           0, 0, 0, out_vectors_dev, out_valid_dev, nullptr, nullptr, stream, /*host=*/false});
+}
+
+int mi355dr_search_examples(mi355dr_index* idx, const float* queries, int B, const int64_t* pos_ids, int mp, const int64_t* neg_ids,
+                            int mn, double alpha, double beta, double gamma, int k, int flags, double* out_dist,
+                            int64_t* out_rows) {
+    return examples_impl(idx, ExamplesArgs{"search_examples", kExSearch, queries, B, pos_ids, mp, neg_ids, mn, alpha, beta, gamma, k,
+                                           0, flags, nullptr, nullptr, out_dist, out_rows, nullptr, /*host=*/true});
+}
+
+int mi355dr_search_examples_device(mi355dr_index* idx, const float* queries_dev, int B, const int64_t* pos_ids, int mp,
+                                   const int64_t* neg_ids, int mn, double alpha, double beta, double gamma, int k, int flags,
+                                   double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
+    return examples_impl(idx, ExamplesArgs{"search_examples", kExSearch, queries_dev, B, pos_ids, mp, neg_ids, mn, alpha, beta,
+                                           gamma, k, 0, flags, nullptr, nullptr, out_dist_dev, out_rows_dev, stream, /*host=*/false});
+}
+
+int mi355dr_search_feedback(mi355dr_index* idx, const float* queries, int B, int k, int fb_k, double alpha, double beta,
+                            double* out_dist, int64_t* out_rows) {
+    return examples_impl(idx, ExamplesArgs{"search_feedback", kExFeedback, queries, B, nullptr, 0, nullptr, 0, alpha, beta, 0.0, k,
+                                           fb_k, 0, nullptr, nullptr, out_dist, out_rows, nullptr, /*host=*/true});
+}
+
+int mi355dr_search_feedback_device(mi355dr_index* idx, const float* queries_dev, int B, int k, int fb_k, double alpha, double beta,
+                                   double* out_dist_dev, int64_t* out_rows_dev, void* stream) {
+    return examples_impl(idx, ExamplesArgs{"search_feedback", kExFeedback, queries_dev, B, nullptr, 0, nullptr, 0, alpha, beta, 0.0,
+                                           k, fb_k, 0, nullptr, nullptr, out_dist_dev, out_rows_dev, stream, /*host=*/false});
+}
+
 // ---- the derived searches over a row-sharded index (csrc/k_shard.h) ---------------------------------
 // One frame (begin_call) per call, so nothing below may call a public entry point: the inner "sharded block at width w" is
 // search_block straight into the packed planes, comm_all_gather, launch_merge with the rank stride.  Every rank enters every
@@ -3312,6 +3498,11 @@ const Stat kStats[] = {
     {"rows_searches", &Index::s_rows_searches, true},
     {"rows_queries", &Index::s_rows_queries, true},
     {"rows_skipped", &Index::s_rows_skipped, true},
+    {"examples_searches", &Index::s_examples_searches, true},
+    {"examples_queries", &Index::s_examples_queries, true},
+    {"examples_skipped", &Index::s_examples_skipped, true},
+    {"examples_skipped_slots", &Index::s_examples_skipped_slots, true},
+    {"feedback_searches", &Index::s_feedback_searches, true},
     {"sharded_range_searches", &Index::s_shard_range_searches, true},
     {"sharded_rows_searches", &Index::s_shard_rows_searches, true},
     {"sharded_mmr_searches", &Index::s_shard_mmr_searches, true},

@@ -732,6 +732,112 @@ class Mi355Index:
             1 if include_self else 0, ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)),
             ctypes.c_void_p(int(out_count_ptr)), _stream_arg(stream)))
 
+    # ---- search by examples / feedback: queries built on the device (include/mi355dr.h "search by examples / feedback") ----
+    @staticmethod
+    def _example_lists(lists, B: int | None) -> np.ndarray:
+        """Example ids -> int64 [B, m], -1 padded.  None: no examples; a flat sequence of ids: one slot; a sequence of
+        sequences (ragged allowed): one list per slot."""
+        if lists is None:
+            return np.full((B or 0, 0), -1, dtype=np.int64)
+        if isinstance(lists, np.ndarray):
+            a = np.ascontiguousarray(lists, dtype=np.int64)
+            if a.ndim == 1:
+                a = a[None, :]
+        else:
+            lists = list(lists)
+            if not lists:
+                return np.full((B or 0, 0), -1, dtype=np.int64)
+            if all(np.ndim(x) == 0 for x in lists):
+                lists = [lists]
+            m = max((len(x) for x in lists), default=0)
+            a = np.full((len(lists), m), -1, dtype=np.int64)
+            for b, x in enumerate(lists):
+                a[b, :len(x)] = np.asarray(x, dtype=np.int64)
+        if a.ndim != 2 or (B is not None and a.shape[0] != B):
+            raise ValueError(f"example ids must be [B, m] with B = {B}, got shape {a.shape}")
+        return a
+
+    def _example_args(self, queries, pos_ids, neg_ids):
+        q = None if queries is None else self._queries_2d(queries)
+        pos = self._example_lists(pos_ids, None if q is None else q.shape[0])
+        B = pos.shape[0] if q is None else q.shape[0]
+        neg = self._example_lists(neg_ids, B)
+        return q, B, pos, neg
+
+    @staticmethod
+    def _ids_arg(a: np.ndarray):
+        return ptr(a, ctypes.c_int64) if a.size else None
+
+    def combine_rows(self, pos_ids, neg_ids=None, queries=None, alpha: float = 1.0, beta: float = 1.0,
+                     gamma: float = 1.0) -> tuple[np.ndarray, np.ndarray]:
+        """Per slot alpha * base + beta * mean(positives) - gamma * mean(negatives) over stored rows (global ids, ragged lists
+        are padded with -1), unit-normalised terms on a cosine index, formed on the device under the fixed double arithmetic
+        of the header.  `queries`: the base vectors [B, dim] or None.  Returns (vectors float32 [B, dim], valid int32 [B]);
+        beta = 1 without a base and without negatives is the centroid of the listed rows."""
+        q, B, pos, neg = self._example_args(queries, pos_ids, neg_ids)
+        vec = np.empty((B, self.dim), dtype=np.float32)
+        valid = np.empty(B, dtype=np.int32)
+        check(self._h, self._lib.mi355dr_combine_rows(
+            self._h, None if q is None else ptr(q, ctypes.c_float), B, self._ids_arg(pos), pos.shape[1], self._ids_arg(neg),
+            neg.shape[1], float(alpha), float(beta), float(gamma), ptr(vec, ctypes.c_float), ptr(valid, ctypes.c_int32)))
+        return vec, valid
+
+    def combine_rows_device(self, pos_ids, neg_ids, q_ptr: int | None, out_vectors_ptr: int, out_valid_ptr: int,
+                            alpha: float = 1.0, beta: float = 1.0, gamma: float = 1.0, stream: int | None = None) -> None:
+        """The same with the base vectors (or None) and both outputs in device memory; the ids stay on the host."""
+        pos = self._example_lists(pos_ids, None)
+        neg = self._example_lists(neg_ids, pos.shape[0])
+        check(self._h, self._lib.mi355dr_combine_rows_device(
+            self._h, ctypes.c_void_p(int(q_ptr)) if q_ptr else None, pos.shape[0], self._ids_arg(pos), pos.shape[1],
+            self._ids_arg(neg), neg.shape[1], float(alpha), float(beta), float(gamma), ctypes.c_void_p(int(out_vectors_ptr)),
+            ctypes.c_void_p(int(out_valid_ptr)), _stream_arg(stream)))
+
+    def search_examples(self, pos_ids, k: int, neg_ids=None, queries=None, alpha: float = 1.0, beta: float = 1.0,
+                        gamma: float = 1.0, keep: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """"More like these, less like those": `search(combine_rows(...), k)` with every listed row left out of the answer
+        (keep=True: nothing is left out), in one call on the device.  Returns (distance float64 [B,k], rows int64 [B,k]); an
+        invalid slot (`combine_rows`) gives a NaN / -1 line."""
+        q, B, pos, neg = self._example_args(queries, pos_ids, neg_ids)
+        dist = np.empty((B, max(int(k), 0)), dtype=np.float64)
+        rows = np.empty((B, max(int(k), 0)), dtype=np.int64)
+        check(self._h, self._lib.mi355dr_search_examples(
+            self._h, None if q is None else ptr(q, ctypes.c_float), B, self._ids_arg(pos), pos.shape[1], self._ids_arg(neg),
+            neg.shape[1], float(alpha), float(beta), float(gamma), int(k), 1 if keep else 0, ptr(dist, ctypes.c_double),
+            ptr(rows, ctypes.c_int64)))
+        return dist, rows
+
+    def search_examples_device(self, pos_ids, neg_ids, q_ptr: int | None, k: int, out_dist_ptr: int, out_rows_ptr: int,
+                               alpha: float = 1.0, beta: float = 1.0, gamma: float = 1.0, keep: bool = False,
+                               stream: int | None = None) -> None:
+        """The same with the base vectors (or None) and the outputs (float64 / int64 [B,k]) in device memory; the ids stay on
+        the host.  Complete on return."""
+        pos = self._example_lists(pos_ids, None)
+        neg = self._example_lists(neg_ids, pos.shape[0])
+        check(self._h, self._lib.mi355dr_search_examples_device(
+            self._h, ctypes.c_void_p(int(q_ptr)) if q_ptr else None, pos.shape[0], self._ids_arg(pos), pos.shape[1],
+            self._ids_arg(neg), neg.shape[1], float(alpha), float(beta), float(gamma), int(k), 1 if keep else 0,
+            ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)), _stream_arg(stream)))
+
+    def search_feedback(self, queries, k: int, fb_k: int = 10, alpha: float = 1.0,
+                        beta: float = 0.75) -> tuple[np.ndarray, np.ndarray]:
+        """Rocchio pseudo-relevance feedback: `search` at `fb_k`, the query moved towards the mean of those rows
+        (alpha * query + beta * mean, `combine_rows`), `search` of the moved query at `k`.  The first pass's lists never
+        leave the device.  Returns (distance float64 [B,k], rows int64 [B,k])."""
+        q = self._queries_2d(queries)
+        B = q.shape[0]
+        dist = np.empty((B, max(int(k), 0)), dtype=np.float64)
+        rows = np.empty((B, max(int(k), 0)), dtype=np.int64)
+        check(self._h, self._lib.mi355dr_search_feedback(self._h, ptr(q, ctypes.c_float), B, int(k), int(fb_k), float(alpha),
+                                                         float(beta), ptr(dist, ctypes.c_double), ptr(rows, ctypes.c_int64)))
+        return dist, rows
+
+    def search_feedback_device(self, q_ptr: int, B: int, k: int, fb_k: int, out_dist_ptr: int, out_rows_ptr: int,
+                               alpha: float = 1.0, beta: float = 0.75, stream: int | None = None) -> None:
+        """The same with queries and outputs in device memory; complete on return."""
+        check(self._h, self._lib.mi355dr_search_feedback_device(
+            self._h, ctypes.c_void_p(int(q_ptr)), int(B), int(k), int(fb_k), float(alpha), float(beta),
+            ctypes.c_void_p(int(out_dist_ptr)), ctypes.c_void_p(int(out_rows_ptr)), _stream_arg(stream)))
+
     def _row_span(self, row0: int, row1: int | None, block: int) -> tuple[int, int, int]:
         row0, row1, block = int(row0), len(self) if row1 is None else int(row1), int(block)
         if row1 < row0 or block < 1:

@@ -1217,6 +1217,77 @@ class Mi355RetrievalService:
         block = self._results_from_block(u.table, u.single_rows, rows, 1.0 - dist, unit == "chunk")
         return [(res, int(c)) for res, c in zip(block, count.tolist())]
 
+    # ---- search by examples and Rocchio feedback: queries built on the device (not in the reference's service) ----
+    def _example_rows(self, u: _UnitIndex, doc_ids: list, unit: str) -> np.ndarray:
+        """the index rows of the listed keys, in list order; ValueError for an unknown key or one without an embedding"""
+        row_of = dict(zip(*self._single_rows_of(u, doc_ids)))
+        pos = u.pos_of_id()
+        for pk in doc_ids:
+            if pk not in pos:
+                raise ValueError(f"Chunk {pk} not found")  # noqa: TRY003
+            if pk not in row_of:
+                msg = f"Chunk {pk} has no embedding" if unit == "chunk" else f"Chunk {pk} has no single-vector embedding"
+                raise ValueError(msg)
+        return np.fromiter((row_of[pk] for pk in doc_ids), dtype=np.int64, count=len(doc_ids))
+
+    def similar_to_examples(self, positive_ids: list, negative_ids: list = (), top_k: int = 10, unit: str = "chunk",
+                            embedding: list[float] | None = None, alpha: float = 1.0, beta: float = 1.0,
+                            gamma: float = 1.0, keep: bool = False) -> list[dict]:
+        """"More like these, less like those": the `top_k` chunks nearest to alpha * embedding + beta * mean(positives) -
+        gamma * mean(negatives) (unit-normalised terms; `embedding` optional), the listed chunks themselves absent unless
+        `keep`.  The stored vectors are combined and searched on the device (Mi355Index.search_examples).  Result dicts and
+        scores as `vector_search_by_embedding`.  Raises ValueError for a key unknown to the table or without a stored
+        embedding, NotImplementedError under a process group."""
+        if self._world is not None:  # (every rank alike, before any collective)
+            raise NotImplementedError("similar_to_examples under a process group: the examples live on different shards")
+        positive_ids, negative_ids = list(positive_ids), list(negative_ids)
+        if not positive_ids and (embedding is None or len(embedding) == 0):
+            return []
+        u = self._unit(unit)
+        pos = self._example_rows(u, positive_ids, unit)
+        neg = self._example_rows(u, negative_ids, unit)
+        base = None if embedding is None or len(embedding) == 0 else np.asarray(embedding, dtype=np.float32)[None, :]
+        dist, rows = u.single_searcher(None).search_examples(pos[None, :], top_k, neg_ids=neg[None, :], queries=base,
+                                                             alpha=alpha, beta=beta, gamma=gamma, keep=keep)
+        return self._results_from_block(u.table, u.single_rows, rows, 1.0 - dist, unit == "chunk")[0]
+
+    def _feedback_block(self, Q: np.ndarray, top_k: int, fb_k: int, alpha: float, beta: float, unit: str) -> list[list[dict]]:
+        if self._world is not None:  # (every rank alike, before any collective)
+            raise NotImplementedError("feedback search under a process group: the first pass's rows live on different shards")
+        u = self._unit(unit)
+        dist, rows = u.single_searcher(None).search_feedback(Q, top_k, fb_k, alpha, beta)
+        return self._results_from_block(u.table, u.single_rows, rows, 1.0 - dist, unit == "chunk")
+
+    def vector_search_feedback(self, query_ids: list[int | str], top_k: int = 10, fb_k: int = 10, alpha: float = 1.0,
+                               beta: float = 0.75, unit: str = "chunk") -> list[list[dict]]:
+        """`vector_search` with one round of Rocchio pseudo-relevance feedback, scored as one block: every query is searched
+        at `fb_k`, moved to alpha * query + beta * mean(those chunks) (unit-normalised terms) and searched again at `top_k`
+        (Mi355Index.search_feedback; the first pass's lists stay on the device).  Raises ValueError for an unknown query or
+        one without an embedding, like `vector_search`; NotImplementedError under a process group."""
+        if self._world is not None:
+            raise NotImplementedError("feedback search under a process group: the first pass's rows live on different shards")
+        queries = []
+        for qid, q in zip(query_ids, self.get_queries(list(query_ids)), strict=True):
+            if q is None:
+                raise ValueError(f"Query {qid} not found")  # noqa: TRY003
+            if q.embedding is None:
+                msg = f"Query {qid} has no embedding" if unit == "chunk" else f"Query {qid} has no single-vector embedding"
+                raise ValueError(msg)
+            queries.append(q)
+        if not queries:
+            return []
+        Q = np.stack([q.embedding for q in queries]).astype(np.float32, copy=False)
+        return self._feedback_block(Q, top_k, fb_k, alpha, beta, unit)
+
+    def vector_search_feedback_by_embedding(self, embedding: list[float], top_k: int = 10, fb_k: int = 10, alpha: float = 1.0,
+                                            beta: float = 0.75, unit: str = "chunk") -> list[dict]:
+        """`vector_search_feedback` for one embedding."""
+        if self._world is not None:
+            raise NotImplementedError("feedback search under a process group: the first pass's rows live on different shards")
+        if len(embedding) == 0:  # (as `vector_search_by_embedding`)
+            return []
+        return self._feedback_block(np.asarray(embedding, dtype=np.float32)[None, :], top_k, fb_k, alpha, beta, unit)[0]
+
     def vector_search_groups(self, embeddings_per_query: list, top_k: int, fetch_k: int | None = None, unit: str = "chunk",
                              search_mode: Literal["single", "multi"] = "single") -> list[list[dict]]:
         """Several searches per question, fused on the device (not in the reference's service: its callers loop in Python,

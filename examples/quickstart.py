@@ -50,6 +50,13 @@ with amd.Mi355Index(d, "cosine") as idx:
         vdist, vrows = tenant.search(queries[:4], k=3)
         print("the same through a view of the pool:", len(tenant), "rows, identical =",
               bool(np.array_equal(vrows, srows) and np.array_equal(vdist, sdist)))
+    # "more like rows 0 and 1, less like row 2": the query is combined from the stored rows on the device and the listed rows
+    # are left out of the answer
+    print("more like rows [0, 1], less like [2]:", idx.search_examples([[0, 1]], k=3, neg_ids=[[2]])[1][0].tolist())
+    # Rocchio feedback: search at fb_k, move every query towards the mean of its own first results, search again -- one call
+    fdist, frows = idx.search_feedback(queries, k=10, fb_k=5)
+    print("feedback (fb_k = 5): planted neighbour still first for", int((frows[:, 0] == np.arange(64)).sum()), "of 64 queries,",
+          int((frows != rows).any(axis=1).sum()), "lists changed behind it")
 
 # ---- 2. multi vectors (late interaction) ---------------------------------------------------------------------------------
 n_docs, dm = 5_000, 128

@@ -356,6 +356,78 @@ int mi355dr_search_range_rows_device(mi355dr_index* idx, const int64_t* row_ids 
                                      const double* radius /* HOST [B] */, int max_results, int flags, double* out_dist_dev,
                                      int64_t* out_rows_dev, int64_t* out_count_dev, void* stream);
 
+/* ---- search by examples / feedback: queries built on the device from stored rows ----
+ * "More like these, less like those" (the `recommend` of vector stores) and Rocchio pseudo-relevance feedback: the query is a
+ * combination of stored rows, optionally with a vector of the caller's.  The rows are read where they lie; neither they nor
+ * the first pass's lists of the feedback form leave the device.
+ *   Inputs of slot b: an optional base vector q_b (fp32 [dim]; absent when `queries` is NULL), positives pos_ids[b, 0..mp) and
+ *     negatives neg_ids[b, 0..mn) -- GLOBAL row ids, HOST arrays, -1-padded; a repeat counts once per position --, and per call
+ *     the doubles alpha, beta, gamma, each finite and >= 0.
+ *   A listed position is VALID iff its id lies in the shard (the rule of mi355dr_search_subset: [row_offset, row_offset +
+ *     mi355dr_size)), the row is not removed, and the row's stored squared norm -- the k-ascending fp32 chain -- is finite and
+ *     > 0; the same under both metrics.  Every other position (-1 padding included) is skipped and counted in stat
+ *     "examples_skipped".  A base vector is valid iff its squared norm under the same chain is finite and > 0.
+ *   A slot is INVALID if it has an invalid base, or no valid term at all (no base, no valid positive, no valid negative): its
+ *     combined vector is all zeros, valid[b] = 0, its result line NaN / -1, and it is counted in "examples_skipped_slots".
+ *   The arithmetic: IEEE double, one rounding per operation, nothing fused; sqrt and / as in the cosine distance.
+ *       s(v) = 1.0 / sqrt((double)nrm2(v))   (cosine index)        s(v) = 1.0   (inner-product index)
+ *       cp = beta / (double)(valid positives)     cn = gamma / (double)(valid negatives)     (none: no such term)
+ *       per coordinate i:  acc = base present ? alpha * (s(q) * (double)q_i) : +0.0
+ *                          each valid positive j, in list position order:  acc = acc + cp * (s_j * (double)c_ji)
+ *                          each valid negative j, in list position order:  acc = acc - cn * (s_j * (double)c_ji)
+ *                          q'_i = (float)acc   (round to nearest even)
+ *     Whatever q' comes out is searched as mi355dr_search would search it -- a vector that cancelled to zero or overflowed
+ *     included; nothing is special-cased beyond the validity rules.
+ *   mi355dr_combine_rows: the combination alone -- out_vectors [B, dim] fp32, out_valid [B] int32.  Also a centroid of stored
+ *     rows without a mi355dr_get_rows per id.  mp + mn <= 1024.
+ *   mi355dr_search_examples: the mi355dr_search ranking of q'_b over the live rows, cut to k, after every id listed in the slot
+ *     -- positive or negative, valid or not -- has been struck out.  The inner pass runs at k + mp + mn: at most that many rows
+ *     can be struck, so the first k survivors are the exact answer (a duplicate of a listed row under another id stays).
+ *     flags: 0, or MI355DR_EXAMPLES_KEEP: nothing is struck, the inner pass runs at k.
+ *   mi355dr_search_feedback: pass 1 is mi355dr_search of `queries` at fb_k (1 <= fb_k <= 1024).  The positives of slot b are the
+ *     entries of its pass-1 list with row >= 0 and a non-NaN distance, in list order (the other entries are no positions at
+ *     all: not counted); there are no negatives; q' is built as above from alpha, beta and the caller's vector as base; pass 2
+ *     is mi355dr_search of q' at k, nothing struck.  By construction: mi355dr_search at fb_k, then mi355dr_search_examples with
+ *     those rows and KEEP.
+ *   MI355DR_E_INVALID, before anything is touched: B < 0; k <= 0, fb_k <= 0, negative mp / mn; a NaN, infinite or negative
+ *     weight; unknown flag bits; a null buffer with work to do; queries == NULL together with mp == 0; and all six on a view
+ *     (they take global ids: ask the parent).  MI355DR_E_UNSUPPORTED: a depth above 1024 -- k + mp + mn without KEEP; k, or
+ *     mp + mn, with it; mp + mn of mi355dr_combine_rows; k or fb_k of the feedback.  B == 0 is a valid no-op.  An empty index
+ *     gives all NaN / -1.
+ *   Each call runs under the handle's mutex, first completes whatever search is in flight and is complete on return (the
+ *     _device forms too: `stream`, or the index's own when NULL, is synchronised).  B above 1024 runs in internal blocks.  Per
+ *     block: the ids are uploaded, k_combine_rows writes q' into a buffer the index owns, the ordinary search of the block
+ *     runs into lists the index owns, and k_examples_strike writes the outputs.  Options and paths apply as in mi355dr_search.
+ *   Known cost: an inner pass at k + mp + mn may be served by the next k class of the search (<= 32 | 33 ... 128 | above).
+ *   Stats: "examples_searches" (calls of the six), "examples_queries" (their slots), "examples_skipped",
+ *     "examples_skipped_slots", "feedback_searches" (of the calls, the feedback ones); the ordinary stats move as the inner
+ *     passes move them.
+ *   Not served: views (above); a row-sharded form (the examples of a slot live on different shards, and the fixed summation
+ *     order does not survive a reduction across ranks); MaxSim and the sparse store; more than one feedback round per call (a
+ *     caller can loop). */
+#define MI355DR_EXAMPLES_KEEP 1 /* flags: the listed rows stay in the result (default 0: they are struck out) */
+int mi355dr_combine_rows(mi355dr_index* idx, const float* queries /* [B, dim] or NULL */, int B,
+                         const int64_t* pos_ids /* HOST [B, mp], global */, int mp, const int64_t* neg_ids /* HOST [B, mn] */, int mn,
+                         double alpha, double beta, double gamma, float* out_vectors /* [B, dim] */,
+                         int32_t* out_valid /* [B] */); /* queries and outputs on the host */
+/* queries_dev (or NULL), out_vectors_dev [B, dim], out_valid_dev [B] on the index's device; the ids stay on the HOST */
+int mi355dr_combine_rows_device(mi355dr_index* idx, const float* queries_dev, int B, const int64_t* pos_ids /* HOST */, int mp,
+                                const int64_t* neg_ids /* HOST */, int mn, double alpha, double beta, double gamma,
+                                float* out_vectors_dev, int32_t* out_valid_dev, void* stream);
+int mi355dr_search_examples(mi355dr_index* idx, const float* queries /* [B, dim] or NULL */, int B,
+                            const int64_t* pos_ids /* HOST [B, mp] */, int mp, const int64_t* neg_ids /* HOST [B, mn] */, int mn,
+                            double alpha, double beta, double gamma, int k, int flags, double* out_dist /* [B, k] */,
+                            int64_t* out_rows /* [B, k] */); /* queries and outputs on the host */
+/* queries_dev (or NULL), out_dist_dev / out_rows_dev [B, k] on the index's device; the ids stay on the HOST */
+int mi355dr_search_examples_device(mi355dr_index* idx, const float* queries_dev, int B, const int64_t* pos_ids /* HOST */, int mp,
+                                   const int64_t* neg_ids /* HOST */, int mn, double alpha, double beta, double gamma, int k,
+                                   int flags, double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+int mi355dr_search_feedback(mi355dr_index* idx, const float* queries /* [B, dim] */, int B, int k, int fb_k, double alpha,
+                            double beta, double* out_dist /* [B, k] */, int64_t* out_rows /* [B, k] */); /* all host */
+/* queries_dev [B, dim], out_dist_dev / out_rows_dev [B, k] on the index's device */
+int mi355dr_search_feedback_device(mi355dr_index* idx, const float* queries_dev, int B, int k, int fb_k, double alpha, double beta,
+                                   double* out_dist_dev, int64_t* out_rows_dev, void* stream);
+
 /* ---- views: a listed subset of rows / documents as an index of its own ----
  * For a list that is searched again and again -- one tenant, one document collection, one PDF's pages: the key filter of the
  * statement above, fixed for many query blocks.  mi355dr_search_subset scans the list exactly on every call (cost ~ m x B, no
@@ -385,7 +457,7 @@ int mi355dr_search_range_rows_device(mi355dr_index* idx, const int64_t* row_ids 
  *   Read-only: mi355dr_add_rows*, _update_rows*, _remove_rows, _compact, _reserve, _add_multivec*, _set_multivec* and option
  *     "row_offset" return MI355DR_E_INVALID on a view and change nothing.  So does every entry point that takes global ids or a
  *     communicator, with an error text that refers the caller to the parent: mi355dr_search_subset*, _score_subset, _search_mmr*, _mmr_select,
- *     _search_rows*, _search_range_rows*, _maxsim_subset*, _search_maxsim_subset*, _gqr_refine, _gqr_refine_maxsim, _comm_init*, _search_sharded_device, and mi355dr_view_create itself (no
+ *     _search_rows*, _search_range_rows*, _combine_rows*, _search_examples*, _search_feedback*, _maxsim_subset*, _search_maxsim_subset*, _gqr_refine, _gqr_refine_maxsim, _comm_init*, _search_sharded_device, and mi355dr_view_create itself (no
  *     views of views).  The stateless ones stay usable: mi355dr_merge_topk*, _pack_topk_device, _gqr_refine_scores, _merge_groups_device.
  *   The call takes the parent's mutex, first completes whatever search is in flight there, and is complete on return;
  *     afterwards the two handles are independent.  The parent is only read.  On any error *out_view is NULL, everything
@@ -989,6 +1061,8 @@ int mi355dr_score_bm25_subset_sharded(mi355dr_index* idx, const int32_t* q_token
  *          "range_searches" / "range_queries" / "range_in_range" / "range_candidates" / "range_rescored" / "range_redo_chunks" /
  *          "range_fallback_queries" (mi355dr_search_range*, described there),
  *          "rows_searches" / "rows_queries" / "rows_skipped" (mi355dr_search_rows* and mi355dr_search_range_rows*, described there),
+ *          "examples_searches" / "examples_queries" / "examples_skipped" / "examples_skipped_slots" / "feedback_searches" (search by
+ *          examples / feedback, described there),
  *          "maxsim_subset_searches" / "maxsim_subset_docs" / "maxsim_subset_screened" / "maxsim_subset_exact" /
  *          "maxsim_subset_fallbacks" (mi355dr_search_maxsim_subset, described there),
  *          "view" / "view_rows" / "view_docs" (mi355dr_view_create: 1 on a view / the rows / the documents it holds),
