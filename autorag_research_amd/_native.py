@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "mi355dr_search", "mi355dr_search_device", "mi355dr_search_device_async", "mi355dr_search_wait",
     "mi355dr_search_subset", "mi355dr_search_subset_device", "mi355dr_score_subset", "mi355dr_search_mmr", "mi355dr_search_mmr_device", "mi355dr_mmr_select", "mi355dr_merge_groups_device", "mi355dr_search_groups", "mi355dr_search_groups_device", "mi355dr_fuse_lists", "mi355dr_fuse_lists_device", "mi355dr_search_range", "mi355dr_search_range_device",
     "mi355dr_search_rows", "mi355dr_search_rows_device", "mi355dr_search_range_rows", "mi355dr_search_range_rows_device", "mi355dr_view_create", "mi355dr_add_multivec", "mi355dr_size_multivec",
-    "mi355dr_search_maxsim", "mi355dr_search_maxsim_device", "mi355dr_search_maxsim_subset", "mi355dr_search_maxsim_subset_device", "mi355dr_maxsim_subset", "mi355dr_maxsim_subset_ex", "mi355dr_add_multivec_device", "mi355dr_gqr_refine", "mi355dr_gqr_refine_maxsim",
+    "mi355dr_search_maxsim", "mi355dr_search_maxsim_device", "mi355dr_search_maxsim_subset", "mi355dr_search_maxsim_subset_device", "mi355dr_maxsim_subset", "mi355dr_maxsim_subset_ex", "mi355dr_multivec_token_counts", "mi355dr_maxsim_align", "mi355dr_maxsim_map", "mi355dr_add_multivec_device", "mi355dr_gqr_refine", "mi355dr_gqr_refine_maxsim",
     "mi355dr_set_multivec", "mi355dr_set_multivec_device", "mi355dr_live_multivec",
     "mi355dr_add_sparse", "mi355dr_size_sparse", "mi355dr_sparse_df", "mi355dr_search_sparse", "mi355dr_search_sparse_device",
     "mi355dr_search_bm25", "mi355dr_search_bm25_device", "mi355dr_set_sparse", "mi355dr_remove_sparse", "mi355dr_live_sparse",
@@ -223,6 +223,12 @@ def load() -> ctypes.CDLL:
     L.mi355dr_maxsim_subset.argtypes = [vp, f32p, i32p, c_int, i64p, c_int, f32p]
     L.mi355dr_maxsim_subset_ex.restype = c_int
     L.mi355dr_maxsim_subset_ex.argtypes = [vp, f32p, i32p, c_int, i64p, c_int, c_int, f32p]
+    L.mi355dr_multivec_token_counts.restype = c_int
+    L.mi355dr_multivec_token_counts.argtypes = [vp, i64p, i64, i32p]
+    L.mi355dr_maxsim_align.restype = c_int
+    L.mi355dr_maxsim_align.argtypes = [vp, f32p, i32p, c_int, i64p, c_int, c_int, f32p, i32p, f32p]
+    L.mi355dr_maxsim_map.restype = c_int
+    L.mi355dr_maxsim_map.argtypes = [vp, f32p, i32p, c_int, i32p, i64p, i64, i64p, f32p]
     L.mi355dr_add_multivec_device.restype = c_int
     L.mi355dr_add_multivec_device.argtypes = [vp, vp, i64p, i64]
     L.mi355dr_set_multivec.restype = c_int

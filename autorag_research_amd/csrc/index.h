@@ -467,6 +467,8 @@ struct mi355dr_index {
     // mi355dr_search_maxsim_subset: calls, listed documents with vectors, queries served by the list screen / by the exact list
     // path (fallbacks included), queries whose candidate list overflowed
     int64_t s_mss_searches = 0, s_mss_docs = 0, s_mss_screened = 0, s_mss_exact = 0, s_mss_fallbacks = 0;
+    // mi355dr_maxsim_align: calls, (query, document) pairs scored; mi355dr_maxsim_map: calls, floats written
+    int64_t s_msa_calls = 0, s_msa_pairs = 0, s_msm_calls = 0, s_msm_values = 0;
     // mi355dr_search_mmr* / mi355dr_mmr_select: calls, queries, (picked row, unselected candidate) dots of k_mmr_select
     int64_t s_mmr_searches = 0, s_mmr_queries = 0, s_mmr_pairs = 0;
     // mi355dr_search_groups*: calls, sub-queries; groups merged by them and by mi355dr_merge_groups_device

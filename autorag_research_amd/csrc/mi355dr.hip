@@ -3475,6 +3475,10 @@ const Stat kStats[] = {
     {"maxsim_subset_screened", &Index::s_mss_screened, true},
     {"maxsim_subset_exact", &Index::s_mss_exact, true},
     {"maxsim_subset_fallbacks", &Index::s_mss_fallbacks, true},
+    {"maxsim_align_calls", &Index::s_msa_calls, true},
+    {"maxsim_align_pairs", &Index::s_msa_pairs, true},
+    {"maxsim_map_calls", &Index::s_msm_calls, true},
+    {"maxsim_map_values", &Index::s_msm_values, true},
     {"mmr_searches", &Index::s_mmr_searches, true},
     {"mmr_queries", &Index::s_mmr_queries, true},
     {"mmr_pairs_scored", &Index::s_mmr_pairs, true},

@@ -1,6 +1,6 @@
 // mi355dr_maxsim.hip -- multi-vector (late interaction) store and exact MaxSim top-k: the host side.
-// Kernels: k_maxsim_exact.h (k_maxsim), k_maxsim_select.h (selection), k_maxsim_build.h (store images); the bf16 screens live in
-// mi355dr_maxsim_screen.hip.
+// Kernels: k_maxsim_exact.h (k_maxsim), k_maxsim_align.h (the terms of its sum: alignment and maps), k_maxsim_select.h (selection),
+// k_maxsim_build.h (store images); the bf16 screens live in mi355dr_maxsim_screen.hip.
 //
 // Replaces VectorChord's `embeddings @# ARRAY[q_1..q_n]` + ORDER BY distance LIMIT k
 // (reference autorag_research/orm/repository/base.py:487-535, :537-571):
@@ -34,6 +34,7 @@
 
 #include "k_maxsim_build.h"
 #include "k_maxsim_exact.h"
+#include "k_maxsim_align.h"
 #include "k_maxsim_select.h"
 
 using namespace mi355;
@@ -1313,6 +1314,206 @@ int maxsim_subset_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_o
     return MI355DR_OK;
 }
 
+// ---- MaxSim explained: the terms of the sum (k_maxsim_align.h) ----
+
+// token vectors of local document v; -1: not a document of this store
+inline int32_t ms_token_count(const MultiVecStore* m, int64_t v) {
+    return (m && v >= 0 && v < m->n_docs) ? m->tok_cnt_host[(size_t)v] : -1;
+}
+
+int multivec_token_counts_impl(mi355dr_index* idx, const int64_t* doc_ids, int64_t n, int32_t* out_counts) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "multivec_token_counts", /*ask_parent=*/true);
+    if (n < 0 || (n > 0 && (!doc_ids || !out_counts))) return fail(idx, MI355DR_E_INVALID, "bad multivec_token_counts arguments");
+    for (int64_t j = 0; j < n; ++j) out_counts[j] = ms_token_count(idx->mv, doc_ids[j] - idx->row_offset);
+    return MI355DR_OK;
+}
+
+// what both calls share on the device: every query vector packed in the store's column order, and the tile table
+struct MsAlignScratch {
+    DevBuf<float> q_dev;
+    DevBuf<MsAlignTile> tiles_dev;
+    std::vector<float> qimg;
+    std::vector<MsAlignTile> tiles;
+};
+
+// dim bound and the kernels' dynamic LDS; *cols = query vectors per tile
+int ms_align_prepare(mi355dr_index* idx, const MultiVecStore* m, int* cols, size_t* lds) {
+    *cols = ms_cols_for(m->dpad);
+    if (*cols < 32) return fail(idx, MI355DR_E_UNSUPPORTED, "dim too large for the MaxSim kernel's LDS budget (dim <= 1272)");
+    *lds = (size_t)*cols * (m->dpad + 4) * sizeof(float);
+    HIPCHECK(idx, hipSetDevice(idx->device));
+    HIPCHECK(idx, hipFuncSetAttribute((const void*)k_maxsim_align, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds));
+    HIPCHECK(idx, hipFuncSetAttribute((const void*)k_maxsim_map, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds));
+    return MI355DR_OK;
+}
+
+// allocate, then upload (nothing is launched before every buffer of the call is there: the caller grows its own first)
+int ms_align_upload(mi355dr_index* idx, MsAlignScratch& w, hipStream_t s) {
+    HIPCHECK(idx, hipMemcpyAsync(w.q_dev.p, w.qimg.data(), w.qimg.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHECK(idx, hipMemcpyAsync(w.tiles_dev.p, w.tiles.data(), w.tiles.size() * sizeof(MsAlignTile), hipMemcpyHostToDevice, s));
+    return MI355DR_OK;
+}
+
+void ms_align_pack_queries(const MultiVecStore* m, int d, const float* qtok, const int32_t* q_offsets, int B, std::vector<float>& qimg) {
+    const int64_t V = q_offsets[B] - q_offsets[0];
+    qimg.resize((size_t)V * m->dpad);
+    for (int64_t g = 0; g < V; ++g)
+        multivec_pack_query_row(qtok + (q_offsets[0] + g) * d, d, m->dpad, &qimg[(size_t)g * m->dpad]);
+}
+
+int maxsim_align_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, const int64_t* doc_ids, int m_ids,
+                      int flags, float* out_val, int32_t* out_tok, float* out_dist) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "maxsim_align", /*ask_parent=*/true);
+    if (flags & ~MI355DR_MAXSIM_CLAMP0) return fail(idx, MI355DR_E_INVALID, "unknown maxsim flag");
+    if (B < 0 || m_ids < 0 || (B > 0 && !q_offsets)) return fail(idx, MI355DR_E_INVALID, "bad maxsim_align arguments");
+    for (int b = 0; b < B; ++b)
+        if (q_offsets[b + 1] < q_offsets[b]) return fail(idx, MI355DR_E_INVALID, "q_offsets must be non-decreasing");
+    const int64_t V = B > 0 ? (int64_t)q_offsets[B] - q_offsets[0] : 0;
+    const int64_t mm = m_ids, n_val = V * mm, n_dist = (int64_t)B * mm;
+    if ((n_val > 0 && (!qtok || !out_val || !out_tok)) || (n_dist > 0 && !doc_ids))
+        return fail(idx, MI355DR_E_INVALID, "maxsim_align: null pointer");
+    for (int64_t i = 0; i < n_val; ++i) {
+        out_val[i] = NAN;
+        out_tok[i] = -1;
+    }
+    if (out_dist)
+        for (int64_t i = 0; i < n_dist; ++i) out_dist[i] = NAN;
+    idx->s_msa_calls++;
+    MultiVecStore* m = idx->mv;
+    if (n_val == 0 || !m || m->n_docs == 0) return MI355DR_OK;
+    int cols = 0;
+    size_t lds = 0;
+    CHECK(ms_align_prepare(idx, m, &cols, &lds));
+    hipStream_t s = idx->stream;
+    MsAlignScratch w;
+    std::vector<int32_t> list;
+    int64_t pairs = 0;
+    try {
+        list.resize((size_t)n_dist);
+        for (int b = 0; b < B; ++b) {
+            const int nq = q_offsets[b + 1] - q_offsets[b];
+            for (int64_t p = 0; p < mm; ++p) {
+                const int64_t v = doc_ids[b * mm + p] - idx->row_offset;  // ids are global rows, like the search results
+                const bool mine = v >= 0 && v < m->n_docs;
+                list[(size_t)(b * mm + p)] = mine ? (int32_t)v : -1;
+                if (mine && nq > 0 && m->tok_cnt_host[(size_t)v] > 0) ++pairs;
+            }
+            for (int t0 = 0; t0 < nq; t0 += cols)
+                w.tiles.push_back(MsAlignTile{q_offsets[b] - q_offsets[0] + t0, std::min(cols, nq - t0), b, 0, 0, 0, 0});
+        }
+        ms_align_pack_queries(m, idx->dim, qtok, q_offsets, B, w.qimg);
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, "maxsim_align: out of host memory");
+    }
+    DevBuf<int32_t> list_dev, tok_dev, qoff_dev;
+    DevBuf<float> val_dev, dist_dev;
+    HIPCHECK(idx, w.q_dev.grow(w.qimg.size() * sizeof(float)));
+    HIPCHECK(idx, w.tiles_dev.grow(w.tiles.size() * sizeof(MsAlignTile)));
+    HIPCHECK(idx, list_dev.grow(list.size() * sizeof(int32_t)));
+    HIPCHECK(idx, val_dev.grow((size_t)n_val * sizeof(float)));
+    HIPCHECK(idx, tok_dev.grow((size_t)n_val * sizeof(int32_t)));
+    if (out_dist) {
+        HIPCHECK(idx, dist_dev.grow((size_t)n_dist * sizeof(float)));
+        HIPCHECK(idx, qoff_dev.grow((size_t)(B + 1) * sizeof(int32_t)));
+    }
+    CHECK(ms_align_upload(idx, w, s));
+    HIPCHECK(idx, hipMemcpyAsync(list_dev.p, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    std::vector<int32_t> qoff((size_t)B + 1);
+    for (int b = 0; b <= B; ++b) qoff[(size_t)b] = q_offsets[b] - q_offsets[0];
+    if (out_dist) HIPCHECK(idx, hipMemcpyAsync(qoff_dev.p, qoff.data(), qoff.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    MsAlignArgs a{};
+    a.tok = m->tok.p;
+    a.blk_off = m->blk_off.p;
+    a.qtok = w.q_dev.p;
+    a.doc_list = list_dev.p;
+    a.out_val = val_dev.p;
+    a.out_tok = tok_dev.p;
+    a.m = mm;
+    a.n_docs = m->n_docs;
+    a.dpad = m->dpad;
+    a.clamp0 = (flags & MI355DR_MAXSIM_CLAMP0) ? 1 : 0;
+    const unsigned gx = (unsigned)std::min<int64_t>((mm + 3) / 4, kMsListGrid);
+    for (size_t t0 = 0; t0 < w.tiles.size(); t0 += 65535) {  // one workgroup row per tile; every vector owns its output row
+        a.tiles = w.tiles_dev.p + t0;
+        hipLaunchKernelGGL(k_maxsim_align, dim3(gx, (unsigned)std::min<size_t>(65535, w.tiles.size() - t0)), dim3(kMsThreads), lds, s, a);
+        HIPCHECK(idx, hipGetLastError());
+    }
+    if (out_dist) {
+        hipLaunchKernelGGL(k_maxsim_align_dist, dim3((unsigned)((n_dist + 255) / 256)), dim3(256), 0, s, val_dev.p, qoff_dev.p, B, mm,
+                           dist_dev.p);
+        HIPCHECK(idx, hipGetLastError());
+        HIPCHECK(idx, hipMemcpyAsync(out_dist, dist_dev.p, (size_t)n_dist * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(idx, hipMemcpyAsync(out_val, val_dev.p, (size_t)n_val * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipMemcpyAsync(out_tok, tok_dev.p, (size_t)n_val * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    idx->s_msa_pairs += pairs;
+    return MI355DR_OK;
+}
+
+int maxsim_map_impl(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, const int32_t* pair_query,
+                    const int64_t* pair_doc, int64_t P, const int64_t* out_offsets, float* out) {
+    if (!idx) return fail(nullptr, MI355DR_E_INVALID, "null index");
+    std::lock_guard<std::mutex> g(idx->mu);
+    if (idx->is_view) return view_refuses(idx, "maxsim_map", /*ask_parent=*/true);
+    if (B < 0 || P < 0 || (B > 0 && !q_offsets) || (P > 0 && (!pair_query || !pair_doc || !out_offsets)))
+        return fail(idx, MI355DR_E_INVALID, "bad maxsim_map arguments");
+    for (int b = 0; b < B; ++b)
+        if (q_offsets[b + 1] < q_offsets[b]) return fail(idx, MI355DR_E_INVALID, "q_offsets must be non-decreasing");
+    MultiVecStore* m = idx->mv;
+    int cols = 32;
+    size_t lds = 0;
+    if (P > 0 && m && m->n_docs > 0) CHECK(ms_align_prepare(idx, m, &cols, &lds));
+    MsAlignScratch w;
+    try {
+        for (int64_t p = 0; p < P; ++p) {
+            if (pair_query[p] < 0 || pair_query[p] >= B) return fail(idx, MI355DR_E_INVALID, "maxsim_map: pair_query out of range");
+            const int b = pair_query[p];
+            const int64_t v = pair_doc[p] - idx->row_offset;
+            const int nq = q_offsets[b + 1] - q_offsets[b];
+            const int64_t T = std::max<int64_t>(ms_token_count(m, v), 0);
+            if (out_offsets[p + 1] - out_offsets[p] != nq * T)
+                return fail(idx, MI355DR_E_INVALID, "maxsim_map: a slot must hold exactly nq * T floats (mi355dr_multivec_token_counts)");
+            if (nq * T == 0) continue;
+            for (int t0 = 0; t0 < nq; t0 += cols)
+                w.tiles.push_back(MsAlignTile{q_offsets[b] - q_offsets[0] + t0, std::min(cols, nq - t0), b, (int)v, (int)T, 0,
+                                              out_offsets[p] - out_offsets[0] + t0 * T});
+        }
+        const int64_t total = P > 0 ? out_offsets[P] - out_offsets[0] : 0;
+        if (total > 0 && (!out || !qtok)) return fail(idx, MI355DR_E_INVALID, "maxsim_map: null pointer");
+        idx->s_msm_calls++;
+        if (total == 0) return MI355DR_OK;
+        ms_align_pack_queries(m, idx->dim, qtok, q_offsets, B, w.qimg);
+    } catch (const std::bad_alloc&) {
+        return fail(idx, MI355DR_E_NOMEM, "maxsim_map: out of host memory");
+    }
+    const int64_t total = out_offsets[P] - out_offsets[0];
+    hipStream_t s = idx->stream;
+    DevBuf<float> out_dev;
+    HIPCHECK(idx, w.q_dev.grow(w.qimg.size() * sizeof(float)));
+    HIPCHECK(idx, w.tiles_dev.grow(w.tiles.size() * sizeof(MsAlignTile)));
+    HIPCHECK(idx, out_dev.grow((size_t)total * sizeof(float)));
+    CHECK(ms_align_upload(idx, w, s));
+    MsAlignArgs a{};
+    a.tok = m->tok.p;
+    a.blk_off = m->blk_off.p;
+    a.qtok = w.q_dev.p;
+    a.tiles = w.tiles_dev.p;
+    a.out_val = out_dev.p;
+    a.n_docs = m->n_docs;
+    a.dpad = m->dpad;
+    hipLaunchKernelGGL(k_maxsim_map, dim3((unsigned)w.tiles.size()), dim3(kMsThreads), lds, s, a);
+    HIPCHECK(idx, hipGetLastError());
+    HIPCHECK(idx, hipMemcpyAsync(out + out_offsets[0], out_dev.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHECK(idx, hipStreamSynchronize(s));
+    idx->s_msm_values += total;
+    return MI355DR_OK;
+}
+
 // ---- test hook: one pass of the search above, observed (mi355dr_debug_maxsim_pass, include/mi355dr.h) ----
 // what a pass counts and the one option the hook switches off for its own pass, put back on every way out
 struct MsDebugKeep {
@@ -1512,6 +1713,20 @@ int mi355dr_maxsim_subset_ex(mi355dr_index* idx, const float* qtok, const int32_
                              int m_ids, int flags, float* out_dist) {
     if (flags & ~MI355DR_MAXSIM_CLAMP0) return fail(idx, MI355DR_E_INVALID, "unknown maxsim flag");
     return maxsim_subset_impl(idx, qtok, q_offsets, B, doc_ids, m_ids, (flags & MI355DR_MAXSIM_CLAMP0) ? 1 : 0, out_dist);
+}
+
+int mi355dr_multivec_token_counts(mi355dr_index* idx, const int64_t* doc_ids, int64_t n, int32_t* out_counts) {
+    return multivec_token_counts_impl(idx, doc_ids, n, out_counts);
+}
+
+int mi355dr_maxsim_align(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, const int64_t* doc_ids, int m,
+                         int flags, float* out_val, int32_t* out_tok, float* out_dist) {
+    return maxsim_align_impl(idx, qtok, q_offsets, B, doc_ids, m, flags, out_val, out_tok, out_dist);
+}
+
+int mi355dr_maxsim_map(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, const int32_t* pair_query,
+                       const int64_t* pair_doc, int64_t P, const int64_t* out_offsets, float* out) {
+    return maxsim_map_impl(idx, qtok, q_offsets, B, pair_query, pair_doc, P, out_offsets, out);
 }
 
 int mi355dr_debug_maxsim_pass(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, int k, const int64_t* doc_ids,

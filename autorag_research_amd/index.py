@@ -53,6 +53,14 @@ class CollapsedSearch(NamedTuple):
     state: np.ndarray
 
 
+class MaxSimAlignment(NamedTuple):
+    """`Mi355Index.maxsim_align`: per query vector (V in all, in query order) and candidate position the matched token."""
+
+    values: np.ndarray        # [V, m] float32: max_j <q_i, d_j> (clamp0: max(0, .)); NaN = candidate skipped
+    tokens: np.ndarray        # [V, m] int32: the lowest token index that reaches the unclamped maximum; -1 = none
+    dist: np.ndarray | None   # [B, m] float32: the bits of `maxsim_subset`; None when not asked for
+
+
 class DeviceKeys:
     """A key table on an index's device (`Mi355Index.upload_keys`): int64 [length] at `ptr`, 0 / 0 for an empty table."""
 
@@ -1465,6 +1473,57 @@ class Mi355Index:
                                                           B, ptr(ids, ctypes.c_int64), ids.shape[1], 1 if clamp0 else 0,
                                                           ptr(out, ctypes.c_float)))
         return out
+
+    # ---- MaxSim explained: the terms of the sum (include/mi355dr.h) ----
+    def multivec_token_counts(self, doc_ids) -> np.ndarray:
+        """Token vectors of the listed GLOBAL documents: int32 [n]; 0 = a document without vectors, -1 = not in this index."""
+        ids = np.ascontiguousarray(doc_ids, dtype=np.int64).reshape(-1)
+        out = np.empty(ids.shape[0], dtype=np.int32)
+        check(self._h, self._lib.mi355dr_multivec_token_counts(self._h, ptr(ids, ctypes.c_int64), ids.shape[0],
+                                                               ptr(out, ctypes.c_int32)))
+        return out
+
+    def maxsim_align(self, qtok, q_offsets, doc_ids, clamp0: bool = False, want_dist: bool = True) -> MaxSimAlignment:
+        """Token alignment of each query with its own list of docs (doc_ids [B, m], the shapes of `maxsim_subset`): for every
+        query vector the best dot over the document's tokens and the lowest token index that reaches it.  `dist` is bit for
+        bit `maxsim_subset(qtok, q_offsets, doc_ids, clamp0)`."""
+        qtok = f32c(qtok).reshape(-1, self.dim)
+        q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int32)
+        ids = np.ascontiguousarray(doc_ids, dtype=np.int64)
+        B = q_offsets.shape[0] - 1
+        if ids.ndim != 2 or ids.shape[0] != B:
+            raise ValueError("doc_ids must be [B, m]")
+        V, m = int(q_offsets[B] - q_offsets[0]) if B > 0 else 0, ids.shape[1]
+        values = np.empty((V, m), dtype=np.float32)
+        tokens = np.empty((V, m), dtype=np.int32)
+        dist = np.empty((B, m), dtype=np.float32) if want_dist else None
+        check(self._h, self._lib.mi355dr_maxsim_align(
+            self._h, ptr(qtok, ctypes.c_float), ptr(q_offsets, ctypes.c_int32), B, ptr(ids, ctypes.c_int64), m,
+            1 if clamp0 else 0, ptr(values, ctypes.c_float), ptr(tokens, ctypes.c_int32),
+            ptr(dist, ctypes.c_float) if want_dist else None))
+        return MaxSimAlignment(values, tokens, dist)
+
+    def maxsim_map(self, qtok, q_offsets, pair_query, pair_doc) -> list[np.ndarray]:
+        """Similarity maps of the listed (query, GLOBAL document) pairs: one float32 [nq_p, T_p] array per pair, element
+        [i, j] = <q_i, d_j>; T_p = 0 for a document without vectors or outside this index."""
+        qtok = f32c(qtok).reshape(-1, self.dim)
+        q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int32)
+        pq = np.ascontiguousarray(pair_query, dtype=np.int32).reshape(-1)
+        pd = np.ascontiguousarray(pair_doc, dtype=np.int64).reshape(-1)
+        B, P = q_offsets.shape[0] - 1, pq.shape[0]
+        if pd.shape[0] != P:
+            raise ValueError("pair_query and pair_doc must have one entry per pair")
+        if P and (pq.min() < 0 or pq.max() >= B):
+            raise ValueError("pair_query out of range")
+        T = np.maximum(self.multivec_token_counts(pd), 0).astype(np.int64)
+        nq = (q_offsets[1:] - q_offsets[:-1]).astype(np.int64)[pq] if P else np.zeros(0, np.int64)
+        off = np.zeros(P + 1, dtype=np.int64)
+        np.cumsum(nq * T, out=off[1:])
+        out = np.empty(max(int(off[P]), 1), dtype=np.float32)
+        check(self._h, self._lib.mi355dr_maxsim_map(
+            self._h, ptr(qtok, ctypes.c_float), ptr(q_offsets, ctypes.c_int32), B, ptr(pq, ctypes.c_int32),
+            ptr(pd, ctypes.c_int64), P, ptr(off, ctypes.c_int64), ptr(out, ctypes.c_float)))
+        return [out[off[p]:off[p + 1]].reshape(int(nq[p]), int(T[p])).copy() for p in range(P)]
 
     # ---- Guided Query Refinement of candidate pools (reference gqr_hybrid.py:306-362) ----
     @staticmethod

@@ -1425,6 +1425,36 @@ class Mi355RetrievalService:
         dist = u.multi_searcher(self._world).maxsim_subset(q, np.array([0, q.shape[0]], dtype=np.int32), rows)[0]
         return {pk: -float(dv) / q.shape[0] for (pk, _), dv in zip(known, dist) if dv == dv}
 
+    def maxsim_explain(self, query_vectors, doc_ids: list, unit: str = "chunk", clamp0: bool = False) -> dict:
+        """The terms of `maxsim_score_candidates`: {doc_id: {"score", "token_scores": [n_q], "token_matches": [n_q]}} -- per
+        query vector its best dot over the document's tokens and the index of the token that gave it (the lowest on a tie;
+        ColBERT's token alignment).  Id hygiene and `score` are those of `maxsim_score_candidates` (with `clamp0` every
+        vector contributes max(0, .), the ColBERT reranker's form); no query vectors -> {}."""
+        u = self._unit(unit)
+        pos, off = u.pos_of_id(), u.table.mv_offsets
+        known = [(pk, pos[pk]) for pk in doc_ids if pk in pos and off is not None and off[pos[pk] + 1] > off[pos[pk]]]
+        q = np.asarray(query_vectors, dtype=np.float32)
+        if not known or q.size == 0:
+            return {}
+        q = q.reshape(-1, u.table.mv_tokens.shape[1])
+        rows = np.array([[p for _, p in known]], dtype=np.int64)
+        al = u.multi_searcher(self._world).maxsim_align(q, np.array([0, q.shape[0]], dtype=np.int32), rows, clamp0=clamp0)
+        return {pk: {"score": -float(al.dist[0, j]) / q.shape[0],
+                     "token_scores": np.asarray(al.values[:, j], dtype=np.float32).copy(),
+                     "token_matches": np.asarray(al.tokens[:, j], dtype=np.int32).copy()}
+                for j, (pk, _) in enumerate(known) if al.dist[0, j] == al.dist[0, j]}
+
+    def maxsim_similarity_map(self, query_vectors, doc_id, unit: str = "chunk") -> np.ndarray | None:
+        """Every dot of the query's vectors with the document's tokens: float32 [n_q, T] (ColPali's heat-map over the patches of
+        a page).  None for an id unknown to the table or without multi-vector embeddings, and for no query vectors."""
+        u = self._unit(unit)
+        pos, off = u.pos_of_id(), u.table.mv_offsets
+        q = np.asarray(query_vectors, dtype=np.float32)
+        if doc_id not in pos or off is None or off[pos[doc_id] + 1] <= off[pos[doc_id]] or q.size == 0:
+            return None
+        q = q.reshape(-1, u.table.mv_tokens.shape[1])
+        return u.multi_searcher(self._world).maxsim_map(q, np.array([0, q.shape[0]], dtype=np.int32), [0], [pos[doc_id]])[0]
+
     # ---- Guided Query Refinement support (reference retrieval_pipeline.py:573-641 + gqr_hybrid.py:306-362) ----
     def get_query_embedding(self, query_id) -> np.ndarray | None:
         """Stored single-vector query embedding as float64, None when the query or its embedding is missing (:573-587)."""

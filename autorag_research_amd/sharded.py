@@ -624,6 +624,77 @@ class ShardedSearcher:
             out = np.where(np.isnan(out), g[r], out)
         return out
 
+    # ---- MaxSim explained over a token-sharded store: the pattern of `maxsim_subset`, one all-gather per output ----
+    def _gather_host(self, local: np.ndarray) -> np.ndarray:
+        """[world, *local.shape]: every rank's block of the same shape and dtype (4-byte elements), rank-major."""
+        import torch
+
+        dev = torch.device("cuda", self.device) if self.backend == "nccl" else torch.device("cpu")
+        mine = torch.from_numpy(np.ascontiguousarray(local).reshape(-1).view(np.int32)).to(dev)
+        gathered = torch.empty((self.world * mine.numel(),), dtype=torch.int32, device=dev)
+        self._dist.all_gather_into_tensor(gathered, mine, group=self.group)
+        return gathered.cpu().numpy().view(local.dtype).reshape((self.world,) + tuple(local.shape))
+
+    def multivec_token_counts(self, doc_ids) -> np.ndarray:
+        """Token vectors of the listed GLOBAL documents over all shards: the owner's count; -1 = no rank holds the id."""
+        local = np.ascontiguousarray(self.index.multivec_token_counts(doc_ids), dtype=np.int32)
+        if self.world == 1 and not self.force_pipeline:
+            return local
+        g = self._gather_host(local)
+        out = g[0].copy()
+        for r in range(1, self.world):   # -1 = "not mine"
+            out = np.where(out < 0, g[r], out)
+        return out
+
+    def maxsim_align(self, qtok, q_offsets, doc_ids, clamp0: bool = False, want_dist: bool = True):
+        """`Mi355Index.maxsim_align` over a token-sharded store.  Every rank passes the same arguments and aligns the candidates
+        it owns; one all-gather per output; the first rank whose value is not NaN wins and the token follows it.  The result on
+        every rank is what one store holding every document returns."""
+        from .index import MaxSimAlignment
+
+        ids = np.ascontiguousarray(doc_ids, dtype=np.int64)
+        if ids.ndim == 1:
+            ids = ids[None, :]
+        loc = self.index.maxsim_align(qtok, q_offsets, ids, clamp0=clamp0, want_dist=want_dist)
+        if self.world == 1 and not self.force_pipeline:
+            return loc
+        gv = self._gather_host(np.ascontiguousarray(loc.values, dtype=np.float32))
+        gt = self._gather_host(np.ascontiguousarray(loc.tokens, dtype=np.int32))
+        val, tok = gv[0].copy(), gt[0].copy()
+        for r in range(1, self.world):
+            take = np.isnan(val)
+            val, tok = np.where(take, gv[r], val), np.where(take, gt[r], tok)
+        dist = None
+        if want_dist:
+            gd = self._gather_host(np.ascontiguousarray(loc.dist, dtype=np.float32))
+            dist = gd[0].copy()
+            for r in range(1, self.world):
+                dist = np.where(np.isnan(dist), gd[r], dist)
+        return MaxSimAlignment(val, tok, dist)
+
+    def maxsim_map(self, qtok, q_offsets, pair_query, pair_doc) -> list[np.ndarray]:
+        """`Mi355Index.maxsim_map` over a token-sharded store: the counts are gathered first, then every rank's maps as one
+        NaN-filled block of the same size; a pair's map comes from the rank that owns its document."""
+        pq = np.ascontiguousarray(pair_query, dtype=np.int32).reshape(-1)
+        pd = np.ascontiguousarray(pair_doc, dtype=np.int64).reshape(-1)
+        local = self.index.maxsim_map(qtok, q_offsets, pq, pd)
+        if self.world == 1 and not self.force_pipeline:
+            return local
+        own = np.ascontiguousarray(self.index.multivec_token_counts(pd), dtype=np.int32)
+        g_cnt = self._gather_host(own)                       # [world, P]
+        T = np.maximum(g_cnt.max(axis=0), 0).astype(np.int64) if pd.size else np.zeros(0, np.int64)
+        owner = np.argmax(g_cnt >= 0, axis=0) if pd.size else np.zeros(0, np.int64)   # the first rank that knows the id
+        qo = np.ascontiguousarray(q_offsets, dtype=np.int64)
+        nq = (qo[1:] - qo[:-1])[pq] if pd.size else np.zeros(0, np.int64)
+        off = np.zeros(pd.size + 1, dtype=np.int64)
+        np.cumsum(nq * T, out=off[1:])
+        block = np.full(max(int(off[-1]), 1), np.nan, dtype=np.float32)
+        for p, a in enumerate(local):
+            if a.size:
+                block[off[p]:off[p] + a.size] = a.reshape(-1)
+        g = self._gather_host(block)
+        return [g[int(owner[p]), off[p]:off[p + 1]].reshape(int(nq[p]), int(T[p])).copy() for p in range(pd.size)]
+
     # ---- views: the same lists on every rank, each keeps what falls in its shard ----
     def view(self, row_ids=None, doc_ids=None) -> "ShardedSearcher":
         """A searcher over the listed GLOBAL rows / documents only (Mi355Index.view).  Every rank passes the same lists; each

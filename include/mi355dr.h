@@ -539,6 +539,54 @@ int mi355dr_maxsim_subset(mi355dr_index* idx, const float* qtok, const int32_t* 
 int mi355dr_maxsim_subset_ex(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, const int64_t* doc_ids,
                              int m, int flags, float* out_dist);
 
+/* ---- MaxSim explained: the terms of the sum ----
+ * Every entry point above answers with one number per (query, document), -sum_i max_j <q_i, d_j>.  These three give the terms:
+ * ColBERT's token alignment (per query vector the matched document token and its dot) and ColPali's similarity map (per query
+ * vector the dot with every token of a page).  The token vectors never leave the device.
+ * The rule (tests/maxsim_align_ref.py restates it):
+ *   - every dot is the exact kernel's k-ascending fp32 fmaf chain from 0.0f (oracle.c orc_dot), the chain mi355dr_search_maxsim
+ *     and mi355dr_maxsim_subset promise;
+ *   - the maximum is fmaxf from -inf over the document's tokens; a NaN dot is ignored;
+ *   - out_tok is the LOWEST token index j with dot_j == maximum under float equality.  The store pads a document's last
+ *     32-token block with copies of its last token; a copy is never reported: the answer is < T.  If every dot of a query
+ *     vector is NaN, the maximum is -inf: out_val = -inf, out_tok = -1;
+ *   - a candidate whose id is skipped (outside the shard, negative, -1 padding) or whose document has no vectors gets
+ *     out_val = NaN, out_tok = -1 and out_dist = NaN;
+ *   - a query without vectors owns no rows of out_val / out_tok, its out_dist row is NaN, and no pair of mi355dr_maxsim_map may
+ *     name it with a non-empty slot.
+ * Consequence: out_dist is bit for bit what mi355dr_maxsim_subset_ex returns for the same arguments and flags, NaN cells at the
+ * same places; -out_val summed in fp32 in vector order gives the same bits; every element of a map is the orc_dot of its two
+ * vectors, a map's row maxima are the unclamped out_val and their first argmax is out_tok.
+ * All three run under the handle's mutex and are complete on return; a view refuses them (ask the parent).  MI355DR_E_INVALID:
+ * an unknown flag, B < 0, m < 0, P < 0, n < 0, a null pointer with work to do, a decreasing q_offsets, a pair_query outside
+ * [0, B), a slot of the wrong size.  MI355DR_E_UNSUPPORTED: dim > 1272 (the exact kernel's LDS bound).  Every allocation
+ * precedes the first launch: MI355DR_E_NOMEM changes nothing.  B = 0, m = 0 or P = 0 is a no-op that still fills what it owns
+ * with NaN / -1.  A query of more than 128 vectors (d = 768: 32) is scored in tiles of its vectors; the tiles are independent.
+ * Stats: "maxsim_align_calls", "maxsim_align_pairs" ((query, document) pairs scored), "maxsim_map_calls", "maxsim_map_values"
+ * (floats written).  No other stat moves. */
+
+/* tokens of stored documents.  doc_ids: HOST [n] GLOBAL ids under the rule of mi355dr_maxsim_subset (local + "row_offset").
+ * out_counts[j] = number of token vectors; 0 = a document without vectors (never given any, or removed);
+ * -1 = an id outside this shard.  Read from the host table, no device work. */
+int mi355dr_multivec_token_counts(mi355dr_index* idx, const int64_t* doc_ids, int64_t n, int32_t* out_counts);
+
+/* alignment of every query with its own row of candidates (the shapes of mi355dr_maxsim_subset_ex: doc_ids HOST [B, m]).
+ *   V = q_offsets[B] query vectors in all; for global query vector g = q_offsets[b] + i and candidate position p:
+ *   out_val[g*m + p]  fp32: that vector's term of the sum, v = max_j <q_i, d_j> (with MI355DR_MAXSIM_CLAMP0: max(0, v)).
+ *   out_tok[g*m + p]  int32: the LOWEST token index j of the document whose dot equals the unclamped maximum;
+ *                     -1 where there is none (see the rule).
+ *   out_dist[b*m + p] fp32, optional (NULL: not wanted): acc = 0.0f; acc = acc + (-out_val) over i ascending. */
+int mi355dr_maxsim_align(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, const int64_t* doc_ids, int m,
+                         int flags, float* out_val, int32_t* out_tok, float* out_dist);          /* all host */
+
+/* full similarity maps of listed (query, document) pairs.  pair_query HOST [P] in [0, B); pair_doc HOST [P] global ids;
+ * out_offsets HOST [P+1], non-decreasing element offsets into out.
+ * Slot p must hold exactly nq_p * max(T_p, 0) floats, T_p as mi355dr_multivec_token_counts reports it;
+ * any other size is MI355DR_E_INVALID and nothing is written.
+ * out[out_offsets[p] + i*T_p + j] = <q_i, d_j>. */
+int mi355dr_maxsim_map(mi355dr_index* idx, const float* qtok, const int32_t* q_offsets, int B, const int32_t* pair_query,
+                       const int64_t* pair_doc, int64_t P, const int64_t* out_offsets, float* out); /* all host */
+
 /* ---- MaxSim search within a listed subset of documents ----
  * `embeddings @# q ... WHERE embeddings IS NOT NULL AND id = ANY(:ids) ORDER BY distance LIMIT k`: maxsim_search
  * (orm/repository/base.py:487-535) with a key filter -- one tenant's pages, one PDF's passages.  The multi-vector sibling of
@@ -1065,6 +1113,8 @@ int mi355dr_score_bm25_subset_sharded(mi355dr_index* idx, const int32_t* q_token
  *          examples / feedback, described there),
  *          "maxsim_subset_searches" / "maxsim_subset_docs" / "maxsim_subset_screened" / "maxsim_subset_exact" /
  *          "maxsim_subset_fallbacks" (mi355dr_search_maxsim_subset, described there),
+ *          "maxsim_align_calls" / "maxsim_align_pairs" / "maxsim_map_calls" / "maxsim_map_values" (MaxSim explained, described
+ *          there),
  *          "view" / "view_rows" / "view_docs" (mi355dr_view_create: 1 on a view / the rows / the documents it holds),
  *          "hbm_bytes_resident" (the single-vector corpus with its shadows at its capacity + the multi-vector store's two
  *          images, offset table and granule-packed copy as allocated now + the staging and block state of the source-capped
